@@ -7,6 +7,8 @@ states already resident in HBM.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
   python bench.py --gpus 2 --dry-launch                 (CPU: the whole multi-rank protocol over gloo with a stub controller)
+  python bench.py ... --dump-outputs DIR                (also writes the last timed step's outputs as DIR/<name>.npy: seeded
+                                                         inputs, so two builds run with the same arguments compare output for output)
 
 Rank 0 prints ONE JSON line.  Extra objects: "roofline" (dominant kernel, hipEvent-timed over
 the timed region, algorithmic bytes from DESIGN.md section 5) and, at N=1, "cpu_baseline" (the float64
@@ -33,6 +35,8 @@ import torch
 BATCH_PER_GPU = 4096
 HORIZON = 10
 EVENT_STRIDE = 4   # per-kernel HIP events are recorded on every 4th step of the timed region
+PROFILE_MAX_TICKS = 100000   # rg_mpc_profile_begin's limit: the first 400000 timed steps carry events, later ones none
+DUMP_BUDGET_BYTES = 60 << 20   # --dump-outputs: array data in all, under 64 MB with the .npy headers
 RING = 50          # state slabs in the input ring = ticks of one 0.5 s trot cycle (measured contacts stay gait-consistent)
 PROFILE_TAG = "r6"
 # algorithmic HBM bytes per controller step (kin_mode 0, all optional outputs off): inputs 320, persistent
@@ -96,6 +100,21 @@ def make_input_ring(cfg, B, seed, device, ring, amp, fixed_cmd=None, gait=None, 
             dev["contact_sched"] = torch.from_numpy(synthetic.contact_schedule(cfg, t_off + 0.01 * j, gait, dropout=0.1, seed=seed, tick=j)).to(device)
         slabs.append(dev)
     return state, cmd, t_off, slabs
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, as <out_dir>/<name>.npy (float32 or
+    float64).  Over DUMP_BUDGET_BYTES in all, every array keeps the same fixed, seeded sample of rows (in row order), so that
+    two builds run with the same arguments are compared row for row."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {n: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)) for n, a in arrays.items()}
+    arrays = {n: (a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)) for n, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, a.shape[0] * DUMP_BUDGET_BYTES // total)
+            a = a[np.sort(np.random.default_rng(seed).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def compiled_sources(read=None):
@@ -547,7 +566,11 @@ def main():
     ap.add_argument("--jitter", type=float, default=0.1, help="amplitude of the per-tick input variation")
     ap.add_argument("--no-extras", action="store_true", help="skip the static-input and PCIe-inclusive side measurements")
     ap.add_argument("--sustain-s", type=float, default=5.0, help="seconds of back-to-back ticks behind config.sustained_steps_per_s (0 = skip; part of the extras)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, rank 0 writes what the last one returned as DIR/<name>.npy: "
+                    "action [B, 60] float32, and action_allgathered [robots, 60] when the all-gather is inside the timed step (at most 64 MB, a seeded row sample beyond)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.random_schedule:
         args.lookahead = True
     ring = 1 if args.static_inputs else max(1, args.ring)
@@ -629,6 +652,8 @@ def main():
         from robot_gym_amd.core.sharding import GatherBuffers
         gather_bufs = GatherBuffers(args.total_batch, world, 60, torch.float32, device)
 
+    last_outputs = {}   # what the last step of the latest run() returned to its caller (device tensors)
+
     def run(slab_list, steps, warmup, events, cfg_run=None, allgather=None, clock_probe=None):
         """`warmup` untimed then `steps` timed ticks on a fresh controller; returns (seconds, handle-side profile, stats).
         allgather: "ring" / "direct" -- every step also all-gathers the [B, 60] action slab over the process group (RCCL over
@@ -640,11 +665,13 @@ def main():
         ctl.reset_at(-t_off)
         ctl.update_controller_params(torch.from_numpy(cmd.T.copy()).to(device))
         nslab = len(slab_list)
+        last_outputs.clear()
 
         def one_step(k):
             act = ctl.get_action(0.01 * k, slab_list[k % nslab])
+            last_outputs["action"] = act
             if allgather:
-                all_gather_actions(act, out=gathered, schedule=allgather, total=(args.total_batch if args.total_batch is not None else None), buffers=gather_bufs)
+                last_outputs["action_allgathered"] = all_gather_actions(act, out=gathered, schedule=allgather, total=(args.total_batch if args.total_batch is not None else None), buffers=gather_bufs)
 
         for k in range(warmup):
             one_step(k)
@@ -655,7 +682,7 @@ def main():
         if events:
             # per-kernel HIP events on every 4th step of the timed region (an event record costs ~4-5 us of stream time)
             ctl._handle.profile_stride(EVENT_STRIDE)
-            ctl._handle.profile_begin(steps)
+            ctl._handle.profile_begin(min(-(-steps // EVENT_STRIDE), PROFILE_MAX_TICKS))   # the ticks that record events
         t0 = time.perf_counter()
         for k in range(steps):
             one_step(warmup + k)
@@ -681,6 +708,8 @@ def main():
 
     use_ag = bool(args.allgather and dist is not None)
     elapsed, (nprof, kms, robots), stats, wn, ctl = run(slabs, args.steps, args.warmup, not args.no_kernel_events, allgather=(args.allgather_schedule if use_ag else None))
+    if args.dump_outputs and rank == 0:   # before any further pass reuses the controller's buffers
+        dump_outputs(args.dump_outputs, last_outputs)
     elapsed = max_over_ranks(elapsed)
     # SURVEY.md 8e asks for both rates -- without the all-gather and with it -- and the exchange has two schedules (ring /
     # direct, core/sharding.py): further timed passes of the same steps, only when there is a process group to gather over

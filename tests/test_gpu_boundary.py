@@ -452,7 +452,7 @@ def test_bench_under_torchrun_world_size_1(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29531", os.path.join(root, "bench.py"), "--gpus", "1", "--allgather", "--steps", "3", "--warmup", "1",
-           "--batch", "512", "--no-cpu-baseline"]
+           "--batch", "512", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out")]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     line = [l for l in res.stdout.splitlines() if l.startswith("{") and '"metric"' in l][-1]
@@ -460,6 +460,10 @@ def test_bench_under_torchrun_world_size_1(tmp_path):
     assert out["n_gpus"] == 1 and out["steps"] == 3 and out["scaling"] == "weak" and out["value"] > 0
     assert out["config"]["allgather"] is True and out["config"]["admm_iterations"]["failures"] == 0
     assert out["roofline"]["kernel"] == "rg_qp_fused_kernel" and out["roofline"]["avg_launch_ms"] > 0
+    # --dump-outputs: the last timed step's action slab, and the all-gathered one (the same rows at world size 1)
+    act, gathered = np.load(tmp_path / "out" / "action.npy"), np.load(tmp_path / "out" / "action_allgathered.npy")
+    assert act.dtype == np.float32 and act.shape == (512, 60) and np.isfinite(act).all() and np.abs(act).max() > 0
+    assert np.array_equal(gathered, act)
 
 
 def test_bench_self_launch_one_rank(tmp_path):

@@ -84,23 +84,27 @@ def test_all_gather_actions_on_a_subgroup_world_size_3_gloo(tmp_path):
     assert [open(tmp_path / f"r{r}").read() for r in range(3)] == ["ok", "ok", "ok"]
 
 
-def test_bench_launches_its_own_ranks_dry_run_world_size_2():
+def test_bench_launches_its_own_ranks_dry_run_world_size_2(tmp_path):
     """`python bench.py --gpus 2` without RANK in the environment must start its own ranks (the driver's form for the
     scaling runs): a fresh torch.distributed.run child with two processes.  --dry-launch runs the whole protocol on CPU over
     gloo with a stub controller: rendezvous on 127.0.0.1, barriers, MAX-over-ranks timing, both all-gather variants, the
-    per-rank kernel-time gather and the JSON contract."""
+    per-rank kernel-time gather and the JSON contract.  --dump-outputs writes the timed pass's last action slab: the stub
+    adds one to every entry per call, so it also counts the warm-up and timed steps that ran."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-launch", "--batch", "64", "--steps", "3",
-                          "--warmup", "1", "--ring", "4"], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+                          "--warmup", "1", "--ring", "4", "--dump-outputs", str(tmp_path / "out")], cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines                      # rank 0's JSON line and nothing else on stdout
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["warmup"] == 1 and out["scaling"] == "weak" and out["value"] > 0
+    assert sorted(os.listdir(tmp_path / "out")) == ["action.npy"]
+    act = np.load(tmp_path / "out" / "action.npy")
+    assert act.dtype == np.float32 and act.shape == (64, 60) and (act == 1 + 3).all()
     c = out["config"]
     assert c["dry_launch"] is True and c["rccl_ranks"] == 2 and c["backend"] == "gloo" and len(c["kernel_ms_per_rank"]) == 2
     assert c["with_allgather_steps_per_s"] > 0 and c["without_allgather_steps_per_s"] == out["value"]
@@ -133,6 +137,24 @@ def test_bench_dry_run_world_size_8_uneven_shards():
     assert c["with_allgather_steps_per_s"] > 0 and c["with_allgather_direct_steps_per_s"] > 0
     assert c["sharding"].startswith("517 robots over 8 ranks")
     assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 517) < 1e-6 * 517        # value = all robots of all ranks per step time
+
+
+def test_bench_dump_outputs_stays_under_its_budget_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 / float64 .npy files; over the byte budget every array keeps the same seeded row sample."""
+    import bench
+    act = torch.arange(1000 * 60, dtype=torch.float32).view(1000, 60)
+    legs = np.arange(1000 * 4, dtype=np.int32).reshape(1000, 4)
+    bench.dump_outputs(tmp_path / "full", {"action": act, "legs": legs})
+    assert np.array_equal(np.load(tmp_path / "full" / "action.npy"), act.numpy())
+    assert np.load(tmp_path / "full" / "legs.npy").dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 100_000)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, {"action": act, "legs": legs})
+    a, l = np.load(tmp_path / "a" / "action.npy"), np.load(tmp_path / "a" / "legs.npy")
+    assert a.nbytes + l.nbytes <= 100_000 and 0 < a.shape[0] == l.shape[0] < 1000
+    rows = a[:, 0].astype(np.int64) // 60
+    assert (np.diff(rows) > 0).all() and np.array_equal(l[:, 0], 4 * rows)   # the same rows of both arrays, in order
+    assert np.array_equal(np.load(tmp_path / "b" / "action.npy"), a)
 
 
 def test_synthetic_states_are_deterministic_and_shaped():
