@@ -34,9 +34,13 @@
 #include <vector>
 
 #include "rg_front_kernel.inc"
+// QP kernels: shared helpers, the register-tile primitives, the symmetric 6 x 6-block sweep, then one file per body (the
+// schedule body and the exact wrench-space body reuse WrenchLane / wrench_admm_vote of the wrench-space ADMM body), then
+// the launches
 #include "rg_qp_common.inc"
-#include "rg_qp_tile_kernel.inc"
+#include "rg_qp_tile.inc"
 #include "rg_qp_sym6.inc"
+#include "rg_qp_tile_kernel.inc"
 #include "rg_qp_wrench_kernel.inc"
 #include "rg_qp_exact_kernel.inc"
 #include "rg_qp_sched_kernel.inc"

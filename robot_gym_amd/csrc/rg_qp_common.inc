@@ -3,16 +3,6 @@
 // Included by rg_mpc.hip (single translation unit); not a stand-alone header.
 #pragma once
 
-// Pin C row registers (see pin_row in rg_qp_tile_kernel.inc): ten per empty asm statement.
-template <int C>
-__device__ __forceinline__ void pin_array(double (&t)[C]) {
-#pragma unroll
-  for (int i = 0; i + 9 < C; i += 10)
-    asm volatile("" : "+v"(t[i]), "+v"(t[i + 1]), "+v"(t[i + 2]), "+v"(t[i + 3]), "+v"(t[i + 4]), "+v"(t[i + 5]), "+v"(t[i + 6]), "+v"(t[i + 7]), "+v"(t[i + 8]), "+v"(t[i + 9]));
-#pragma unroll
-  for (int i = (C / 10) * 10; i < C; i++) asm volatile("" : "+v"(t[i]));
-}
-
 // index of the k-th set bit of a 4-bit contact mask (k-th stance leg) without a scratch array
 __device__ __forceinline__ int nth_leg(int mask, int k) {
   int l0 = __builtin_ctz(mask | 16);
@@ -277,143 +267,10 @@ __device__ __forceinline__ void qp_write_outputs(const DevCfg *__restrict__ c, c
 #endif
 }
 
-// Lane grid per horizon: at one horizon every ADMM body runs on the same (1 << LG) x (1 << LG) lanes -- H = 10: one 64-lane
-// wave (8 x 8), H = 20: 256 lanes (16 x 16) -- so that one launch can switch body per work item.  T1: tile size of the one-leg body.
-template <int H> struct FusedShape;
-template <> struct FusedShape<10> { static constexpr int LG = 3, T1 = 4; };   // one leg: 30 -> 32 = 4 x 8
-template <> struct FusedShape<20> { static constexpr int LG = 4, T1 = 4; };   // one leg: 60 -> 64 = 4 x 16
 constexpr size_t cmax(size_t a, size_t b) { return a > b ? a : b; }
 
 // workgroup preamble shared by all QP kernels: 2 N_ab and 2 S_ab into LDS
 template <int H>
 __device__ __forceinline__ void load_horizon_tables(const DevCfg *__restrict__ c, double *tabN, double *tabS, const int tid, const int nt) {
   for (int e = tid; e < H * H; e += nt) { tabN[e] = 2.0 * c->Ntab[e]; tabS[e] = 2.0 * c->Stab[e]; }
-}
-
-
-// ---- branch-free build of an 8 x 8 register tile of  N (x) U + S (x) V + diag  for 6-wide blocks ----
-// The matrix is 2 (N (x) G_U + S (x) G_V) with 6 x 6 blocks (two stance legs in force space, or any leg count in
-// wrench space).  A tile row/column range of 8 straddles at most two blocks, always at an even offset, so a lane
-// needs four N and four S table values in all, and its 8 x 8 window of the PERIODIC extensions EU, EV of the two
-// 6 x 6 matrices ([14][18] doubles in LDS, written by put_periodic6) as 16-byte reads.  ~430 instructions and 72
-// LDS reads per lane, no branches; the per-entry version (index divisions, four 8-byte reads and a branch per
-// entry) was 1240 instructions and 256 reads -- 10 % of a trot robot's time under load.
-#define RG_E6_ROWS 14
-#define RG_E6_LD 18
-#define RG_E6_DOUBLES (RG_E6_ROWS * RG_E6_LD)
-__device__ __forceinline__ void put_periodic6(double *E, const int i, const int j, const double v) {
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int q = 0; q < 3; q++)
-      if (i + 6 * r < RG_E6_ROWS) E[(i + 6 * r) * RG_E6_LD + j + 6 * q] = v;
-}
-template <int H>
-__device__ __forceinline__ void build_tile_kron6(double (&tile)[8][8], const double *tabN, const double *tabS, const double *EU, const double *EV,
-                                                 const int lr, const int lc, const int nreal, const double diag_real) {
-  const int r0 = 8 * lr, c0 = 8 * lc;
-  const int a0r = r0 / 6, i0 = r0 - 6 * a0r, b0r = c0 / 6, j0 = c0 - 6 * b0r;   // i0, j0 in {0, 2, 4}
-  const int a0 = a0r < H ? a0r : H - 1, a1 = a0r + 1 < H ? a0r + 1 : H - 1;
-  const int b0 = b0r < H ? b0r : H - 1, b1 = b0r + 1 < H ? b0r + 1 : H - 1;
-  const double n00 = tabN[a0 * H + b0], n01 = tabN[a0 * H + b1], n10 = tabN[a1 * H + b0], n11 = tabN[a1 * H + b1];
-  const double s00 = tabS[a0 * H + b0], s01 = tabS[a0 * H + b1], s10 = tabS[a1 * H + b0], s11 = tabS[a1 * H + b1];
-  // Table factor per column pair, for a row in the low / high block.  Column pair p is in the high block iff
-  // j0 + 2 p >= 6: never for p = 0, always for p = 3, lane-dependent only for p = 1, 2.
-  double nlo[4], nhi[4], slo[4], shi[4];
-#pragma unroll
-  for (int p = 0; p < 4; p++) {
-    if (p == 0) { nlo[p] = n00; nhi[p] = n10; slo[p] = s00; shi[p] = s10; }
-    else if (p == 3) { nlo[p] = n01; nhi[p] = n11; slo[p] = s01; shi[p] = s11; }
-    else {
-      const bool chi = j0 + 2 * p >= 6;
-      nlo[p] = chi ? n01 : n00; nhi[p] = chi ? n11 : n10; slo[p] = chi ? s01 : s00; shi[p] = chi ? s11 : s10;
-    }
-  }
-  const double dlane = (lr == lc) ? diag_real : 0.0;
-#pragma unroll
-  for (int ta = 0; ta < 8; ta++) {
-    // row ta is in the high block iff i0 + ta >= 6: never for ta < 2, always for ta >= 6
-    const bool rhi = i0 + ta >= 6;
-    const double *eu = EU + (i0 + ta) * RG_E6_LD + j0, *ev = EV + (i0 + ta) * RG_E6_LD + j0;
-#pragma unroll
-    for (int p = 0; p < 4; p++) {
-      const double2 u = *reinterpret_cast<const double2 *>(eu + 2 * p), v = *reinterpret_cast<const double2 *>(ev + 2 * p);
-      const double np = ta < 2 ? nlo[p] : (ta >= 6 ? nhi[p] : (rhi ? nhi[p] : nlo[p]));
-      const double sp = ta < 2 ? slo[p] : (ta >= 6 ? shi[p] : (rhi ? shi[p] : slo[p]));
-      tile[ta][2 * p] = fma(np, u.x, sp * v.x);
-      tile[ta][2 * p + 1] = fma(np, u.y, sp * v.y);
-    }
-    tile[ta][ta] += dlane;
-    __builtin_amdgcn_sched_barrier(0);   // one tile row at a time: bounds the LDS loads in flight (VGPR pressure)
-  }
-  // padding (only the last lane-row / lane-column has any): zero, with 1 on the diagonal
-  if (c0 + 8 > nreal) {
-#pragma unroll
-    for (int tb = 0; tb < 8; tb++)
-      if (c0 + tb >= nreal) {
-#pragma unroll
-        for (int ta = 0; ta < 8; ta++) tile[ta][tb] = 0.0;
-      }
-  }
-  if (r0 + 8 > nreal) {
-#pragma unroll
-    for (int ta = 0; ta < 8; ta++)
-      if (r0 + ta >= nreal) {
-#pragma unroll
-        for (int tb = 0; tb < 8; tb++) tile[ta][tb] = (ta == tb && lr == lc) ? 1.0 : 0.0;
-      }
-  }
-}
-
-// ---- force-space set-up shared by the ADMM body (qp_tile_robot) and the exact body (qp_exact_robot) ----
-// From the front->QP record (LDS): B_w = Iw^-1 [r]x per stance-leg force component, T B_w (rpy-rate map), the Gram blocks
-// G_U = U' W U, G_V = V' W V (m3 x m3; their periodic extensions when the tile is built by build_tile_kron6) and the two
-// per-variable coefficient tables of the linear term: q_(a,i) = 2 sum_{k >= a} [ c1(k,i) + (k - a + 1/2) c2(k,i) ].
-// cmask: contact mask whose set bits are the NC stance legs, in order.  Ends with a workgroup barrier.
-template <int NC, int H, int NT, bool KRON6>
-__device__ __forceinline__ void force_space_tables(const DevCfg *__restrict__ c, const double *rec, const int cmask, const int tid, double *Bw, double *TBw,
-                                                   double *GU, double *GV, double *EU, double *EV, double *c1, double *c2) {
-  constexpr int m3 = 3 * NC, N = m3 * H;
-  const double dt = c->dt;
-  if (tid < m3) {
-    int l = nth_leg(cmask, tid / 3), d = tid % 3;
-    const double *rr = &rec[REC_FEETW + 3 * l];
-    double s0 = (d == 0) ? 0.0 : (d == 1 ? -rr[2] : rr[1]);
-    double s1 = (d == 0) ? rr[2] : (d == 1 ? 0.0 : -rr[0]);
-    double s2 = (d == 0) ? -rr[1] : (d == 1 ? rr[0] : 0.0);
-    const double *Iw = &rec[REC_IWINV];
-    double b0 = Iw[0] * s0 + Iw[1] * s1 + Iw[2] * s2;
-    double b1 = Iw[3] * s0 + Iw[4] * s1 + Iw[5] * s2;
-    double b2 = Iw[6] * s0 + Iw[7] * s1 + Iw[8] * s2;
-    Bw[tid] = b0; Bw[m3 + tid] = b1; Bw[2 * m3 + tid] = b2;
-    TBw[tid] = rec[REC_INVCP] * b0; TBw[m3 + tid] = b1; TBw[2 * m3 + tid] = rec[REC_TANP] * b0 + b2;
-  }
-  __syncthreads();
-  for (int e = tid; e < m3 * m3; e += NT) {
-    int i = e / m3, j = e % m3;
-    double gu = c->w[6] * Bw[i] * Bw[j] + c->w[7] * Bw[m3 + i] * Bw[m3 + j] + c->w[8] * Bw[2 * m3 + i] * Bw[2 * m3 + j];
-    double gv = c->w[0] * TBw[i] * TBw[j] + c->w[1] * TBw[m3 + i] * TBw[m3 + j] + c->w[2] * TBw[2 * m3 + i] * TBw[2 * m3 + j];
-    if (i % 3 == j % 3) { gu += c->w[9 + i % 3] * c->inv_mass * c->inv_mass; gv += c->w[3 + i % 3] * c->inv_mass * c->inv_mass; }
-    GU[e] = gu * dt * dt;
-    GV[e] = gv * dt * dt * dt * dt;
-    if constexpr (KRON6) { put_periodic6(EU, i, j, GU[e]); put_periodic6(EV, i, j, GV[e]); }
-  }
-  for (int e = tid; e < N; e += NT) {
-    int a = e / m3, i = e % m3;
-    double kd = (double)(a + 1) * dt;
-    const double *om = &rec[REC_OMEGA], *vb = &rec[REC_VBODY], *cm = &rec[REC_CMD];
-    double e_r = rec[REC_ROLL] + kd * rec[REC_INVCP] * om[0];
-    double e_p = rec[REC_PITCH] + kd * om[1];
-    double e_y = kd * (rec[REC_TANP] * om[0] + om[2]) - kd * cm[2];
-    double e_x = kd * vb[0] - kd * cm[0];
-    double e_yy = kd * vb[1] - kd * cm[1];
-    double e_z = rec[REC_COMZ] + kd * vb[2] - 0.5 * kd * kd * c->g - c->body_height;
-    double e_w0 = om[0], e_w1 = om[1], e_w2 = om[2] - cm[2];
-    double e_v0 = vb[0] - cm[0], e_v1 = vb[1] - cm[1], e_v2 = vb[2] - kd * c->g;
-    int d = i % 3;
-    double ev = (d == 0) ? c->w[9] * e_v0 : (d == 1 ? c->w[10] * e_v1 : c->w[11] * e_v2);
-    double ep = (d == 0) ? c->w[3] * e_x : (d == 1 ? c->w[4] * e_yy : c->w[5] * e_z);
-    c1[e] = dt * (Bw[i] * c->w[6] * e_w0 + Bw[m3 + i] * c->w[7] * e_w1 + Bw[2 * m3 + i] * c->w[8] * e_w2 + c->inv_mass * ev);
-    c2[e] = dt * dt * (TBw[i] * c->w[0] * e_r + TBw[m3 + i] * c->w[1] * e_p + TBw[2 * m3 + i] * c->w[2] * e_y + c->inv_mass * ep);
-  }
 }

@@ -331,10 +331,10 @@ struct ExactLds {
   static constexpr int m3 = 3 * NC, N = m3 * H, LC = 1 << LG, NT = LC * LC, NP = T * LC, TS = TileShape<T>::TS, NPAD = TS * LC, NPB = NPAD + 2, NB = N / 3;
   // 8 x 8 tiles (one wave at horizon 10, 256 lanes at horizon 20): the matrix is swept with every 6 x 6 block held once
   // (rg_qp_sym6.inc) and moved into the tiles through a staging area that covers everything from `vv` on (nothing there is
-  // live at that moment)
-  static constexpr bool SYM6 = (T == 8 && N % 6 == 0 && ((LG == 3 && N <= 60) || (LG == 4 && N <= 120)));
+  // live at that moment); 4 x 4 tiles (256 lanes at horizon 10) go through tile_sweep
+  static constexpr bool SYM6 = T == 8;
+  static_assert(T == 4 || (N % 6 == 0 && ((LG == 3 && N <= 60) || (LG == 4 && N <= 120))), "8 x 8 tiles: the symmetric 6 x 6-block sweep covers the matrix");
   static constexpr int NBS = N / 6;                // block rows of the symmetric sweep
-  static constexpr bool KRON6 = (m3 == 6 && T == 8 && !SYM6);
   static constexpr int LAMC = (6 * NB + 63) / 64 * 64 < 128 ? 128 : (6 * NB + 63) / 64 * 64;
   // live through the solve
   static constexpr int rec = 0;                    // RG_REC_N
@@ -352,10 +352,12 @@ struct ExactLds {
   static constexpr int pbuf = Tm;                  // the sweep's ping-pong pivot buffers
   static constexpr int PBUF = SYM6 ? 2 * Sym6<SYM6 ? NBS : 1>::PB : 2 * NPB;
   static constexpr int GU = pbuf + PBUF, GV = GU + m3 * m3, c1 = GV + m3 * m3, c2 = c1 + N, Bw = c2 + N, TBw = Bw + 3 * m3;
-  static constexpr int EU = (TBw + 3 * m3 + 1) & ~1, EV = EU + (KRON6 ? RG_E6_DOUBLES : 0);
-  static constexpr int setup_end = EV + (KRON6 ? RG_E6_DOUBLES : 0);
+  static constexpr int setup_end = TBw + 3 * m3;
   static constexpr int stage_end = SYM6 ? vv + Sym6<SYM6 ? NBS : 1>::STG : 0;   // staging area of sym6_to_tile8: from vv on
   template <bool PACKED> static constexpr int total = cmax(cmax((size_t)(Tm + ExactT<Q, PACKED>::doubles), (size_t)setup_end), (size_t)stage_end);
+  // what stays live through sym6_to_tile8 ends where the staging area starts, and the staging area fits the layout
+  static_assert(!SYM6 || (rec + RG_REC_N <= vv && grf + 24 <= vv && lamc + LAMC <= vv && sc + (NT > 64 ? 8 : 0) <= vv), "sym6_to_tile8 stages over live LDS");
+  static_assert(!SYM6 || (stage_end <= total<false> && stage_end <= total<true>), "the staging area of sym6_to_tile8 fits the layout");
 };
 template <int NC, int H, int Q, bool PACKED = false, int LG = 3, int T = 8>
 constexpr size_t qp_exact_lds_doubles() { return (size_t)ExactLds<NC, H, Q, LG, T>::template total<PACKED>; }
@@ -376,11 +378,10 @@ __device__ __forceinline__ void qp_exact_robot(const DevCfg *__restrict__ c, con
   using LY = ExactLds<NC, H, Q, LG, T>;
   using TSH = TileShape<T>;
   constexpr int LC = LY::LC, NT = LY::NT, m3 = LY::m3, N = LY::N, NB = LY::NB, NP = LY::NP;
-  constexpr bool KRON6 = LY::KRON6;
   static_assert(N <= NP && NP <= 128 && NB <= 64 && Q <= 64 && Q % 8 == 0 && 6 * NB <= LY::LAMC, "a working-set slot and a force block per lane of the solver wave; rows of T in groups of 8");
   double *vv = lds + LY::vv, *qv = lds + LY::x0, *xv = lds + LY::x, *dv = lds + LY::d, *lamc = lds + LY::lamc, *rec = lds + LY::rec, *grf = lds + LY::grf;
   double *Tm = lds + LY::Tm, *svv = lds + LY::sv, *rvv = lds + LY::rv, *pbuf = lds + LY::pbuf, *GU = lds + LY::GU, *GV = lds + LY::GV, *c1 = lds + LY::c1, *c2 = lds + LY::c2;
-  double *Bw = lds + LY::Bw, *TBw = lds + LY::TBw, *EU = lds + LY::EU, *EV = lds + LY::EV, *sc = lds + LY::sc;
+  double *Bw = lds + LY::Bw, *TBw = lds + LY::TBw, *sc = lds + LY::sc;
   int cmask;
   double tile[T][T];
   double qi = 0.0;
@@ -392,7 +393,7 @@ __device__ __forceinline__ void qp_exact_robot(const DevCfg *__restrict__ c, con
     for (int e = tid; e < LY::LAMC; e += NT) lamc[e] = 0.0;
     __syncthreads();
     cmask = (int)rec[REC_CONTACT];
-    force_space_tables<NC, H, NT, KRON6>(c, rec, cmask, tid, Bw, TBw, GU, GV, EU, EV, c1, c2);
+    force_space_tables<NC, H, NT, false>(c, rec, cmask, tid, Bw, TBw, GU, GV, nullptr, nullptr, c1, c2);
     __syncthreads();
     // ---- my T x T tile of P = 2 (N (x) G_U + S (x) G_V) + alpha I (identity in the padding), and q of the row I own ----
     int lrv = tid >> LG, lcv = tid & (LC - 1);
@@ -422,13 +423,12 @@ __device__ __forceinline__ void qp_exact_robot(const DevCfg *__restrict__ c, con
       stamp_phase(2);
       sym6_to_tile8<NBS, NBS, LG, NT>(X, sbr, sbc, son, tile, lds + LY::vv, tid);
     } else {
-    if constexpr (KRON6) build_tile_kron6<H>(tile, tabN, tabS, EU, EV, lrv, lcv, N, c->alpha);
-    else build_tile_entries<T, H, m3>(tile, tabN, tabS, GU, GV, lrv, lcv, N, c->alpha);
+    build_tile_entries<T, H, m3>(tile, tabN, tabS, GU, GV, lrv, lcv, N, c->alpha);
     // ---- symmetric sweep: tile <- -(P^-1) (+2 on the diagonal, removed once), rows reordered for the reduce-scatter ----
     stamp_phase(1);
     tile_sweep<T, LG, N>(tile, pbuf, lrv, lcv);
     stamp_phase(2);
-    finish_swept_tile<T>(tile, lrv, lcv);
+    finish_swept_tile4(tile, lrv, lcv);
     }
     // the set-up arrays are dead: their LDS becomes T (zero outside the working set's q x q block)
     __syncthreads();

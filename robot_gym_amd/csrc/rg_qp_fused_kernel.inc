@@ -8,7 +8,7 @@
 // work item (block-uniform branch).  This removes three launch gaps and, more important, the tail of each
 // per-count launch: at H = 10, 835 four-leg robots alone fill 40 % of the chip's 2048 wave slots, 3261
 // two-leg robots 1.6 rounds of them; together they are 2.0 rounds.
-// (FusedShape<H>: lane grid per horizon, defined in rg_qp_common.inc)
+// (FusedShape<H>: lane grid per horizon, defined in rg_qp_tile.inc)
 
 // EX (horizon 10) selects the bodies: 0 -- ADMM for every stance-leg count; 1 -- one- and two-leg robots run the exact
 // active-set body (qp_exact_robot), three and four legs keep the wrench-space ADMM body: the RG_SOLVER_HYBRID plan; 2 -- every
@@ -111,9 +111,11 @@ static hipError_t launch_qp_fused(const DevCfg *dcfg, const DevState &st, const 
   constexpr int QX = H == 20 ? RG_EXACT_Q20 : RG_EXACT_Q;
   constexpr size_t body12 = EX ? cmax(qp_exact_lds_doubles<2, H, QX, false, LG, TT>(), qp_exact_lds_doubles<1, H, QX, false, LG, TT>())
                                : cmax(qp_tile_lds_doubles<2, H, 8, LG>(), qp_tile_lds_doubles<1, H, T1, LG>());
-  constexpr size_t body34 = H == 20 ? qp_sched_lds_doubles<H, LG, false>()
-                            : (EX == 2 ? cmax(qp_exact_wrench_lds_doubles<4, 10, RG_EXACT_QW>(), qp_exact_wrench_lds_doubles<3, 10, RG_EXACT_QW>())
-                                       : cmax(qp_wrench_lds_doubles<4, H, LG, TT>(), qp_wrench_lds_doubles<3, H, LG, TT>()));
+  constexpr size_t body34 = [] {   // (if constexpr: the wrench-space ADMM layout exists at horizon 10 only)
+    if constexpr (H == 20) return qp_sched_lds_doubles<H, LG, false>();
+    else if constexpr (EX == 2) return cmax(qp_exact_wrench_lds_doubles<4, 10, RG_EXACT_QW>(), qp_exact_wrench_lds_doubles<3, 10, RG_EXACT_QW>());
+    else return cmax(qp_wrench_lds_doubles<4, H, LG, TT>(), qp_wrench_lds_doubles<3, H, LG, TT>());
+  }();
   constexpr size_t body = cmax(body34, body12);
   const size_t lds = sizeof(double) * (body + 2 * H * H);
   // horizon 10: eight one-wave workgroups per CU (20 KB each); horizon 20: two 256-lane workgroups per CU (80 KB each)

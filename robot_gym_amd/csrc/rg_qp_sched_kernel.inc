@@ -172,13 +172,17 @@ struct SchedLds {
   static constexpr int as_x = as0, as_g = as_x + NV, as_z = as_g + NV, as_w = as_z + NV, as_lam = as_w + NV, as_sv = as_lam + QMAX, as_r = as_sv + QMAX,
                        as_v0 = as_r + QMAX, as_v1 = as_v0 + QMAX, as_T = as_v1 + QMAX, as_int = as_T + QLDS * (QLDS + 1) / 2,
                        as_sc = as_int + (3 * QMAX + 4 * H + 1) / 2 + 1, total = AS ? as_sc + 8 : as0;
+  // what stays live through sym6_to_tile8 ends where the staging area starts, and the staging area fits the layout
+  static_assert(!SYM6 || (rec + RG_REC_N <= stage && grf + 24 <= stage && qh + NW <= stage && Lk + 36 * H <= stage && Lik + 7 * H <= stage &&
+                          Cm + 72 <= stage && sum3 + 16 <= stage), "sym6_to_tile8 stages over live LDS");
+  static_assert(!SYM6 || stage + Sym6<NBS>::STG <= total, "the staging area of sym6_to_tile8 fits the layout");
 };
 
 template <int H, int LG, bool AS>
 constexpr size_t qp_sched_lds_doubles() { return (size_t)SchedLds<H, LG, AS>::total; }
 
 // Exact dual active-set method of the schedule body (range-space form) on G = P^-1 = I / alpha + X M X', see qp_sched_robot.
-// Same method and constraint numbering as the force-space solver in rg_qp_tile_kernel.inc (id = 6 * block + type), with block =
+// Same method and constraint numbering as the force-space solver in rg_qp_exact_kernel.inc (id = 6 * block + type), with block =
 // (step, leg) lane index 4 k + j and variable index 3 * block + axis.  apply_G(in, out, in_is_qh): out = G in on the enabled
 // block lanes (G is applied, never formed); the state lives in the AS part of the body's LDS (SchedLds).  Leaves the optimum in
 // as_x (LDS); returns false on a breakdown (iteration cap, more than QMAX active constraints); `it` counts constraint additions.
@@ -478,7 +482,8 @@ __device__ __forceinline__ void qp_sched_robot(const DevCfg *__restrict__ c, con
   // after admm_switch iterations rho2 (larger).  With a randomised schedule the iteration count is bimodal: nine robots
   // in ten converge in ~70 iterations at rho = 1e-4, the rest -- many constraints active in stiff directions -- take 300
   // to 1500 there but ~100 more at 4e-4 (where the easy ones would need 170).  The iterate carries over; the scaled
-  // multiplier y = lambda / rho is rescaled.  Between stages z and y are parked in LDS (not in registers across the sweep).
+  // multiplier y = lambda / rho is rescaled.  Between stages z stays in zb and y is parked in ypark, both in registers (the
+  // staging area of the next sweep goes over the vote state in LDS).
   double rho = AS ? 0.0 : c->rho * c->rho_sched_scale;   // first stage: admm_rho x admm_rho_sched_scale (the wrench-space iteration likes a lower rho, see qp_wrench_robot)
   int it_limit = (!AS && c->rho2 > 0.0 && c->admm_abs_tol > 0.0 && c->admm_switch < c->admm_iters) ? c->admm_switch : c->admm_iters;
   int next_chk = c->admm_check;
@@ -668,7 +673,7 @@ __device__ __forceinline__ void qp_sched_robot(const DevCfg *__restrict__ c, con
     }
   } else {
     // ================= exact dual active-set method (range-space form) on G = P^-1 = I / alpha + X M X' =================
-    // Same method and constraint numbering as the force-space body in rg_qp_tile_kernel.inc (id = 6 * block + type), with
+    // Same method and constraint numbering as the force-space body in rg_qp_exact_kernel.inc (id = 6 * block + type), with
     // block = (step, leg) lane index 4 k + j and variable index 3 * block + axis.  G is applied, never formed:
     //   G w = w / alpha + X [ (alpha I + K')^-1 - I / alpha ] X' w   -- the ADMM iteration's linear algebra with rho = 0.
     double *as_x = lds + LY::as_x;   // the solver's state lives in the AS part of this body's LDS (SchedLds); it leaves the optimum here

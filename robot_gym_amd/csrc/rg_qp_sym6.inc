@@ -6,7 +6,7 @@
 // ------------------------------------------------------------------------------------
 // Every QP body starts by inverting a symmetric positive definite 6 NB x 6 NB matrix whose natural unit is a 6 x 6 block
 // (force space, two stance legs: P, block = a pair of horizon steps; wrench space: a I + K').  tile_sweep
-// (rg_qp_tile_kernel.inc) holds it as LC x LC lanes x 8 x 8 register tiles, i.e. BOTH triangles: lanes (r, c) and (c, r)
+// (rg_qp_tile.inc) holds it as LC x LC lanes x 8 x 8 register tiles, i.e. BOTH triangles: lanes (r, c) and (c, r)
 // compute the same 64 numbers -- 64 FMAs, 8 coefficient products and 16 doubles from LDS per lane and pivot, and the sweep
 // was 45 % of the wave-slot time of the headline launch (profiles/r5_launch_schedule.txt).
 //

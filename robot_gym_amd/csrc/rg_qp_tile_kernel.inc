@@ -1,196 +1,8 @@
-// rg_qp_tile_kernel.inc -- force-space ADMM QP body on 2-D register tiles (one and two stance legs), the in-register sweep and
-// the tile helpers every QP body shares.  (The exact active-set bodies are in rg_qp_exact_kernel.inc / rg_qp_sched_kernel.inc.)
+// rg_qp_tile_kernel.inc -- force-space ADMM QP body on 2-D register tiles (one and two stance legs) and its LDS layout.  (The
+// tile primitives it shares with the other bodies are in rg_qp_tile.inc; the exact active-set bodies are in
+// rg_qp_exact_kernel.inc / rg_qp_sched_kernel.inc.)
 // Included by rg_mpc.hip (single translation unit); not a stand-alone header.
 #pragma once
-
-// ------------------------------------------------------------------------------------
-// A row-per-lane layout is bound by the LDS instruction pipe (rocprof: SQ_ACTIVE_INST_LDS ~ 88 % of kernel
-// time in the round-1 experiment): every f64 FMA needs half a 16-B broadcast read.  Here the lanes of a robot form an LC x LC grid and lane (lr, lc) keeps the T x T tile
-// rows lr*T.., cols lc*T.. of the (padded, NP = T*LC) symmetric matrix in VGPRs, so every value
-// read from LDS feeds T FMAs:
-//   sweep step kp: 2T values (pivot-row entries of my columns and, by symmetry, of my rows)
-//                  for T*T FMAs; the LC lanes of lane-row kp/T publish the row in parallel.
-//   ADMM mat-vec : T values of the rhs for T*T FMAs, then a reduce-scatter over the LC lanes
-//                  of a lane-row (cross-lane, no LDS data) leaves one finished entry per lane.
-// ------------------------------------------------------------------------------------
-// Opaque "use + redefine" of one tile row: no instruction is emitted, but the optimiser can no longer
-// defer this row's updates past this point.  (Left alone, hipcc turns the unrolled pivot steps into
-// a look-ahead schedule that keeps every step's pivot-row values live: > 380 VGPRs, spills in the loop.)
-template <int T>
-__device__ __forceinline__ void pin_row(double (&t)[T]) {
-  if constexpr (T == 8) asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]));
-  else if constexpr (T == 6) asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]));
-  else if constexpr (T == 4) asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
-  else {
-#pragma unroll
-    for (int i = 0; i < T; i++) asm volatile("" : "+v"(t[i]));
-  }
-}
-
-// The reduce-scatter that finishes an 8 x 8-tile mat-vec keeps a different half of the partial sums on
-// each lane (selected by lane-column bits 2 and 0): 24 v_cndmask per mat-vec.  Reordering the tile ROWS of
-// each lane once (rows h <-> h+4 where bit 2 is set, then h <-> h+2 where bit 0 is set) makes "keep the low
-// half, send the high half" right for every lane, so the selects disappear from the iteration loop.
-__device__ __forceinline__ void permute_tile_rows_for_reduce(double (&tile)[8][8], const int lc) {
-  const bool s4 = (lc >> 2) & 1, s2 = lc & 1;
-#pragma unroll
-  for (int h = 0; h < 4; h++)
-#pragma unroll
-    for (int tb = 0; tb < 8; tb++) { const double a = tile[h][tb], b = tile[h + 4][tb]; tile[h][tb] = s4 ? b : a; tile[h + 4][tb] = s4 ? a : b; }
-#pragma unroll
-  for (int h = 0; h < 8; h++) {
-    if (h & 2) continue;
-#pragma unroll
-    for (int tb = 0; tb < 8; tb++) { const double a = tile[h][tb], b = tile[h + 2][tb]; tile[h][tb] = s2 ? b : a; tile[h + 2][tb] = s2 ? a : b; }
-  }
-}
-// row sums of a row-permuted tile's mat-vec partials -> the lane's own row (4 b2 + 2 b0 + b1 of its lane-row)
-template <int LG>
-__device__ __forceinline__ double reduce_scatter8_permuted(double (&acc)[8], const int lc) {
-#pragma unroll
-  for (int h2 = 0; h2 < 4; h2++) acc[h2] += dpp_f64<0x141>(acc[4 + (h2 ^ 2)]);   // 7 - i inside 8 lanes: that lane's bit 0 differs too, hence ^ 2
-#pragma unroll
-  for (int h2 = 0; h2 < 2; h2++) acc[h2] += dpp_f64<0xB1>(acc[2 + h2]);    // lane ^ 1
-  const bool up = (lc >> 1) & 1;
-  const double keep = up ? acc[1] : acc[0], send = up ? acc[0] : acc[1];
-  double tot = keep + dpp_f64<0x4E>(send);                                  // lane ^ 2
-  if constexpr (LG >= 4) tot += dpp_f64<0x128>(tot);
-#pragma unroll
-  for (int kx = 4; kx < LG; kx++) tot += __shfl_xor(tot, 1 << kx);
-  return tot;
-}
-
-// ---- the same for 4 x 4 tiles on a 16 x 16 lane grid (horizon 10 on 256 lanes: the small-batch lane grid) ----
-// Two reduce-scatter steps (lane ^ 1, lane ^ 2) leave one row sum per lane, then two all-reduce steps over the four lane
-// groups of a lane-row (row_ror:4, row_ror:8); the rows of each lane's tile are reordered once so that every lane keeps its
-// low half.  Kept row: 2 b0 + b1 of the lane-row's four rows.
-__device__ __forceinline__ void permute_tile_rows_for_reduce4(double (&tile)[4][4], const int lc) {
-  const bool s2 = lc & 1, s1 = (lc >> 1) & 1;
-#pragma unroll
-  for (int h = 0; h < 2; h++)
-#pragma unroll
-    for (int tb = 0; tb < 4; tb++) { const double a = tile[h][tb], b = tile[h + 2][tb]; tile[h][tb] = s2 ? b : a; tile[h + 2][tb] = s2 ? a : b; }
-#pragma unroll
-  for (int h = 0; h < 4; h += 2)   // both halves: the half a lane sends in the first step must be in its partner's order
-#pragma unroll
-    for (int tb = 0; tb < 4; tb++) { const double a = tile[h][tb], b = tile[h + 1][tb]; tile[h][tb] = s1 ? b : a; tile[h + 1][tb] = s1 ? a : b; }
-}
-__device__ __forceinline__ double reduce_scatter4_permuted(double (&acc)[4]) {
-#pragma unroll
-  for (int h2 = 0; h2 < 2; h2++) acc[h2] += dpp_f64<0xB1>(acc[2 + h2]);   // lane ^ 1 (that lane sends its other half: its rows are swapped)
-  double tot = acc[0] + dpp_f64<0x4E>(acc[1]);                             // lane ^ 2
-  tot += dpp_f64<0x124>(tot);                                              // row_ror:4
-  tot += dpp_f64<0x128>(tot);                                              // row_ror:8
-  return tot;
-}
-
-// Tile-size traits shared by the bodies that run on more than one lane grid: padded group stride of the LDS vectors that are
-// read as T-wide groups, the position of row r in such a vector, and the row of its lane-row a lane owns after the reduce.
-template <int T> struct TileShape {
-  static constexpr int TS = (T == 8) ? 10 : T;
-  static __device__ __forceinline__ int pad(const int r) { return (int)(((unsigned)r / (unsigned)T) * (unsigned)TS + ((unsigned)r % (unsigned)T)); }
-  static __device__ __forceinline__ int own_a(const int lc) {
-    if constexpr (T == 8) return 4 * ((lc >> 2) & 1) + 2 * (lc & 1) + ((lc >> 1) & 1);
-    else { static_assert(T == 4, "tile sizes with a DPP reduce-scatter: 8 and 4"); return 2 * (lc & 1) + ((lc >> 1) & 1); }
-  }
-};
-
-template <int LT>
-__device__ __forceinline__ int bitrev_lt(int x) {
-  int r = 0;
-#pragma unroll
-  for (int i = 0; i < LT; i++) r |= ((x >> i) & 1) << (LT - 1 - i);
-  return r;
-}
-
-// Symmetric in-register sweep of a T x T-tiled SPD matrix on an LC x LC lane grid: on return tile = -(M^-1) with +2 on every
-// diagonal entry (the caller removes it once).  NREAL: rows / columns of M; the rest of the T LC grid is identity padding,
-// whose pivot steps change nothing (d = 1, every coefficient 0) and are skipped.  Per pivot the pivot row goes through the
-// LDS ping-pong buffer pbuf (2 x (TS LC + 2) doubles, groups of T padded to TS) with entry kp replaced by d - 1, so that one
-// unconditional FMA per entry is right for every row (no branches, no dynamic register indexing).  Look-ahead: inside step kp
-// the tile row that holds pivot row kp + 1 is updated FIRST and published immediately, so its LDS write -> read latency hides
-// behind the other T - 1 row updates.
-template <int T, int LG, int NREAL>
-__device__ __forceinline__ void tile_sweep(double (&tile)[T][T], double *pbuf, const int lr, const int lc) {
-  constexpr int TS = (T == 8) ? 10 : T, LC = 1 << LG, NPAD = TS * LC, NPB = NPAD + 2;
-  auto publish = [&](int tr, int kb, double *pb) {   // lanes of lane-row kb publish tile row tr (tr static after unrolling)
-    if (lr == kb) {
-      const bool diag = (lc == kb);
-#pragma unroll
-      for (int tb = 0; tb < T; tb += 2) {
-        double v0 = tile[tr][tb], v1 = tile[tr][tb + 1];
-        if (tb == tr) v0 = diag ? v0 - 1.0 : v0;
-        if (tb + 1 == tr) v1 = diag ? v1 - 1.0 : v1;
-        *reinterpret_cast<double2 *>(&pb[lc * TS + tb]) = make_double2(v0, v1);
-      }
-      if (diag) pb[NPAD] = tile[tr][tr];
-    }
-  };
-  publish(0, 0, pbuf);
-  __syncthreads();
-  for (int kb = 0; kb < LC; kb++) {
-#pragma unroll
-    for (int tr = 0; tr < T; tr++) {
-      const int kp = kb * T + tr;
-      if (kp >= NREAL) continue;
-      double *pb = pbuf + (kp & 1) * NPB;
-      const double invd = fast_rcp(pb[NPAD]);
-      double prow[T], pcol[T];
-#pragma unroll
-      for (int t2 = 0; t2 < T; t2 += 2) {
-        double2 a2 = *reinterpret_cast<const double2 *>(&pb[lr * TS + t2]);
-        double2 b2 = *reinterpret_cast<const double2 *>(&pb[lc * TS + t2]);
-        prow[t2] = a2.x; prow[t2 + 1] = a2.y; pcol[t2] = b2.x; pcol[t2 + 1] = b2.y;
-      }
-      const int tn = (tr + 1) % T;                // tile row of the next pivot (static)
-      const int kbn = (tr + 1 < T) ? kb : kb + 1;  // its lane-row
-      {
-        const double ncc = -prow[tn] * invd;
-#pragma unroll
-        for (int tb = 0; tb < T; tb++) tile[tn][tb] = fma(ncc, pcol[tb], tile[tn][tb]);
-      }
-      if (kp + 1 < NREAL) publish(tn, kbn, pbuf + ((kp + 1) & 1) * NPB);
-#pragma unroll
-      for (int ta = 0; ta < T; ta++) {
-        if (ta == tn) continue;
-        // (pivot row itself, ta == tr on lane-row kb: its prow entry is the published d - 1, so -prow/d = 1/d - 1 as required)
-        const double ncc = -prow[ta] * invd;
-#pragma unroll
-        for (int tb = 0; tb < T; tb++) tile[ta][tb] = fma(ncc, pcol[tb], tile[ta][tb]);
-      }
-#pragma unroll
-      for (int ta = 0; ta < T; ta++) pin_row<T>(tile[ta]);
-      __syncthreads();
-    }
-  }
-}
-
-// Per-entry build of a T x T register tile of  N (x) GU + S (x) GV + diag I  (m3 x m3 blocks GU / GV in LDS, identity in the
-// padding): index divisions and four 8-byte reads per entry -- the build for the lane grids without a branch-free table
-// version (build_tile_kron6 covers 8 x 8 tiles of 6 x 6 blocks); with 4 x 4 tiles it is 16 entries per lane.
-template <int T, int H, int m3>
-__device__ __forceinline__ void build_tile_entries(double (&tile)[T][T], const double *tabN, const double *tabS, const double *GU, const double *GV,
-                                                   const int lr, const int lc, const int nreal, const double diag_real) {
-#pragma unroll
-  for (int ta = 0; ta < T; ta++) {
-    const int row = lr * T + ta;
-    const int a = row / m3, i = row - a * m3;
-    const bool rreal = row < nreal;
-    const double *tN = tabN + (rreal ? a : 0) * H, *tS = tabS + (rreal ? a : 0) * H, *gu = GU + (rreal ? i : 0), *gv = GV + (rreal ? i : 0);
-#pragma unroll
-    for (int tb = 0; tb < T; tb++) {
-      const int col = lc * T + tb;
-      const int bb = col / m3, j = col - bb * m3;
-      double v;
-      if (rreal && col < nreal) {
-        v = tN[bb] * gu[j * m3] + tS[bb] * gv[j * m3];
-        if (col == row) v += diag_real;
-      } else v = (col == row) ? 1.0 : 0.0;
-      tile[ta][tb] = v;
-    }
-    __builtin_amdgcn_sched_barrier(0);   // one tile row at a time: bounds the LDS loads in flight (VGPR pressure)
-  }
-}
 
 // One robot's QP on the LC x LC lanes of the calling workgroup.  tabN / tabS: 2 N_ab, 2 S_ab in LDS
 // (loaded by the caller once per workgroup); lds: this body's scratch, qp_tile_lds_doubles() long.
@@ -202,9 +14,8 @@ __device__ __forceinline__ void qp_tile_robot(const DevCfg *__restrict__ c, cons
   constexpr int LC = 1 << LG;        // lanes per side
   constexpr int NP = T * LC;         // padded size
   constexpr int NT = LC * LC;
-  constexpr bool TPOW2 = (T & (T - 1)) == 0;
-  constexpr int LT = (T == 2) ? 1 : (T == 4) ? 2 : (T == 8) ? 3 : (T == 16) ? 4 : 0;
-  static_assert(NP >= N && T % 2 == 0 && T <= LC, "tile/grid must cover the problem");
+  static_assert(T == 4 || T == 8, "tile sizes with a reduce-scatter below: 8 and 4");
+  static_assert(NP >= N && T <= LC, "tile/grid must cover the problem");
   // opaque copy: the lane-role integers below are recomputed per robot instead of being hoisted out of the
   // caller's work loop for all bodies at once and spilled (43 scratch stores in the fused kernel's preamble)
   const int tid = wg_lane<NT>();
@@ -237,8 +48,8 @@ __device__ __forceinline__ void qp_tile_robot(const DevCfg *__restrict__ c, cons
   const double relax = c->relax, lo = c->fz_min, hi = c->fz_max;
   // the one matrix row whose scalar ADMM state this lane owns after the reduce-scatter
   const bool owner = lc < T;
-  // T == 8: the reduce-scatter below pairs lanes as (7-i), (i^1), (i^2) -> kept row 4*b2 + 2*b0 + b1
-  const int own_a = (T == 8) ? (4 * ((lc >> 2) & 1) + 2 * (lc & 1) + ((lc >> 1) & 1)) : (TPOW2 ? bitrev_lt<LT>(lc & (T - 1)) : (lc < T ? lc : 0));
+  // T == 8: the reduce-scatter below pairs lanes as (7-i), (i^1), (i^2) -> kept row 4*b2 + 2*b0 + b1; T == 4: 2*b0 + b1
+  const int own_a = TileShape<T>::own_a(lc);
   const int io = lr * T + own_a;
   const bool own_real = owner && io < N;
   const int iov_pad = lr * TS + own_a;   // position of row io in the padded vectors
@@ -273,6 +84,7 @@ __device__ __forceinline__ void qp_tile_robot(const DevCfg *__restrict__ c, cons
         for (int kq = a; kq < H; kq++) qi += c1[kq * m3 + i] + ((double)(kq - a) + 0.5) * c2[kq * m3 + i];
         qi *= 2.0;
       }
+      // (one leg: the loop of build_tile_entries, written out -- called, it compiles to different code in the fused kernels)
       if constexpr (KRON6) build_tile_kron6<H>(tile, tabN, tabS, EU, EV, lrv, lcv, N, c->alpha + rho);
       else
 #pragma unroll
@@ -363,8 +175,9 @@ __device__ __forceinline__ void qp_tile_robot(const DevCfg *__restrict__ c, cons
         // i <-> 7-i (row_half_mirror), step 2 i^1, step 3 i^2; the tile rows were reordered after the sweep
         // so every lane keeps its low half.  Lane-rows of 16/32 lanes finish with all-reduce steps.
         tot = reduce_scatter8_permuted<LG>(acc, lc);
-      } else if constexpr (TPOW2) {
+      } else {
         // reduce-scatter: after step k (xor 2^k) a lane keeps the half selected by bit k of lc
+        constexpr int LT = 2;   // log2 T
 #pragma unroll
         for (int k = 0; k < LT; k++) {
           const int half = T >> (k + 1);
@@ -379,15 +192,6 @@ __device__ __forceinline__ void qp_tile_robot(const DevCfg *__restrict__ c, cons
         tot = acc[0];
 #pragma unroll
         for (int k = LT; k < LG; k++) tot += __shfl_xor(tot, 1 << k);
-      } else {
-#pragma unroll
-        for (int ta = 0; ta < T; ta++) {
-#pragma unroll
-          for (int k = 0; k < LG; k++) acc[ta] += __shfl_xor(acc[ta], 1 << k);
-        }
-        tot = acc[0];
-#pragma unroll
-        for (int ta = 1; ta < T; ta++) tot = (own_a == ta) ? acc[ta] : tot;
       }
       const double u = -tot;
       const double w = relax * u + (1.0 - relax) * z + y;

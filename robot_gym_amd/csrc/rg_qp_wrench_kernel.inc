@@ -1,5 +1,6 @@
 // rg_qp_wrench_kernel.inc -- ADMM QP body for 3 and 4 stance legs (contacts held over the horizon), solved in wrench coordinates.
-// (Per-step contact schedules use the generalisation in rg_qp_sched_kernel.inc, which also reuses the tile helpers below.)
+// (Per-step contact schedules use the generalisation in rg_qp_sched_kernel.inc, which also reuses WrenchLane and
+// wrench_admm_vote below; the tile primitives are in rg_qp_tile.inc.)
 // Included by rg_mpc.hip (single translation unit); not a stand-alone header.
 #pragma once
 
@@ -23,48 +24,6 @@
 // Per iteration: 18 FMAs + quad reduce (DPP) -> LDS -> 64 FMAs + reduce-scatter (DPP) -> LDS -> 18 FMAs
 // + projection.
 // ------------------------------------------------------------------------------------
-
-// (M^-1 v)_io on the owner lanes (tile = -M^-1, rows reordered by permute_tile_rows_for_reduce): tile mat-vec, then the DPP reduce-scatter over the lanes of a lane-row
-template <int LG>
-__device__ __forceinline__ double tile8_matvec(const double (&tile)[8][8], const double *vin_pad, const int lr, const int lc) {
-  constexpr int T = 8, TS = 10;
-  double acc[T], vloc[T];
-#pragma unroll
-  for (int t2 = 0; t2 < T; t2 += 2) {
-    double2 v2 = *reinterpret_cast<const double2 *>(&vin_pad[lc * TS + t2]);
-    vloc[t2] = v2.x; vloc[t2 + 1] = v2.y;
-  }
-#pragma unroll
-  for (int ta = 0; ta < T; ta++) {
-    double a0 = 0.0;
-#pragma unroll
-    for (int tb = 0; tb < T; tb++) a0 = fma(tile[ta][tb], vloc[tb], a0);
-    acc[ta] = a0;
-  }
-  return -reduce_scatter8_permuted<LG>(acc, lc);
-}
-
-// ... and for either tile size: T = 8 on 8 x 8 or 16 x 16 lanes, T = 4 on 16 x 16 lanes (rows reordered by the matching permute)
-template <int T, int LG>
-__device__ __forceinline__ double tile_matvec(const double (&tile)[T][T], const double *vin_pad, const int lr, const int lc) {
-  if constexpr (T == 8) return tile8_matvec<LG>(tile, vin_pad, lr, lc);
-  else {
-    static_assert(T == 4 && LG == 4, "4 x 4 tiles run on the 16 x 16 lane grid");
-    const double2 a = *reinterpret_cast<const double2 *>(&vin_pad[lc * 4]), b = *reinterpret_cast<const double2 *>(&vin_pad[lc * 4 + 2]);
-    double acc[4];
-#pragma unroll
-    for (int ta = 0; ta < 4; ta++) acc[ta] = fma(tile[ta][3], b.y, fma(tile[ta][2], b.x, fma(tile[ta][1], a.y, tile[ta][0] * a.x)));
-    return -reduce_scatter4_permuted(acc);
-  }
-}
-template <int T>
-__device__ __forceinline__ void finish_swept_tile(double (&tile)[T][T], const int lr, const int lc) {
-  if (lr == lc) {   // remove the sweep's +2 diagonal offset: tile = -M^-1
-#pragma unroll
-    for (int ta = 0; ta < T; ta++) tile[ta][ta] -= 2.0;
-  }
-  if constexpr (T == 8) permute_tile_rows_for_reduce(tile, lc); else permute_tile_rows_for_reduce4(tile, lc);
-}
 
 // Roles of one lane in the ADMM iteration of the wrench-space bodies (see the header comment), derived from its index in
 // the workgroup.  The bodies derive them AFTER the sweep, from a fresh opaque lane index (wg_lane), and once more in the
@@ -150,8 +109,9 @@ __device__ __forceinline__ bool wrench_admm_vote(const DevCfg *__restrict__ c, c
 // second stage stays in registers across the sweep).
 template <int NC, int H, int LG, int T>
 struct WrenchLds {
+  static_assert(H == 10 && ((LG == 3 && T == 8) || (LG == 4 && T == 4)), "the wrench-space ADMM body runs at horizon 10, on 8 x 8 lanes with 8 x 8 tiles or 16 x 16 lanes with 4 x 4 tiles");
   static constexpr int m3 = 3 * NC, NW = 6 * H, LC = 1 << LG, NP = T * LC, NT = LC * LC, TS = TileShape<T>::TS, NPAD = TS * LC, NPB = NPAD + 2;
-  static constexpr bool SYM6 = (LG == 3 && T == 8 && NW == 60);
+  static constexpr bool SYM6 = T == 8;   // the one-wave grid
   static constexpr int rec = 0;                   // RG_REC_N
   static constexpr int grf = rec + RG_REC_N;      // 24
   static constexpr int Ch = grf + 24;             // 6 * m3  L^-1 C
@@ -172,10 +132,12 @@ struct WrenchLds {
   static constexpr int yst = zck + 3 * NT;        // 3 * NT  movement of the forces over the window before
   static constexpr int yck = yst + 3 * NT;        // 3 * NT  multipliers at the previous convergence vote
   static constexpr int dyq = yck + 3 * NT;        // 3 * NT  their movement over the window before (extrapolation test)
-  static constexpr int EU = dyq + 3 * NT;         // RG_E6_DOUBLES periodic extension of AU (build_tile_kron6; not on the one-wave grid)
-  static constexpr int EV = EU + ((T == 8 && !SYM6) ? RG_E6_DOUBLES : 0);
-  static constexpr int end = EV + ((T == 8 && !SYM6) ? RG_E6_DOUBLES : 0);
+  static constexpr int end = dyq + 3 * NT;
   static constexpr int total = (SYM6 && stage + Sym6<10>::STG > end) ? stage + Sym6<10>::STG : end;
+  // what stays live through sym6_to_tile8 ends where the staging area starts, and the staging area fits the layout
+  static_assert(!SYM6 || (rec + RG_REC_N <= stage && grf + 24 <= stage && Ch + 6 * m3 <= stage && AU + 36 <= stage && AV + 36 <= stage &&
+                          qh + NW <= stage && sum3 + 16 <= stage), "sym6_to_tile8 stages over live LDS");
+  static_assert(!SYM6 || stage + Sym6<10>::STG <= total, "the staging area of sym6_to_tile8 fits the layout");
 };
 
 // Lane grids (LG, T): (3, 8) one wave (horizon 10), (4, 4) 256 lanes with 4 x 4 tiles (horizon 10, small batches: a quarter of
@@ -194,7 +156,7 @@ __device__ __forceinline__ void qp_wrench_robot(const DevCfg *__restrict__ c, co
   constexpr bool SYM6 = LY::SYM6;
   double *rec = lds + LY::rec, *grf = lds + LY::grf, *Ch = lds + LY::Ch, *AU = lds + LY::AU, *AV = lds + LY::AV, *qh = lds + LY::qh, *sum3 = lds + LY::sum3;
   double *pbuf = lds + LY::pbuf, *vv = lds + LY::vv, *uv = lds + LY::uv, *Cm = lds + LY::Cm, *Qm = lds + LY::Qm, *Lm = lds + LY::Lm, *qw = lds + LY::qw;
-  double *zck = lds + LY::zck, *yst = lds + LY::yst, *yck = lds + LY::yck, *dyq = lds + LY::dyq, *EU = lds + LY::EU, *EV = lds + LY::EV;
+  double *zck = lds + LY::zck, *yst = lds + LY::yst, *yck = lds + LY::yck, *dyq = lds + LY::dyq;
   // first-stage rho of this body: admm_rho x admm_rho34_scale (the wrench-space iteration converges in fewer iterations at a
   // lower rho than the force-space one, at every percentile of the population); second ADMM stage: c->rho2 (stage loop below)
   double rho = c->rho * c->rho34_scale;
@@ -316,7 +278,6 @@ __device__ __forceinline__ void qp_wrench_robot(const DevCfg *__restrict__ c, co
       }
       AU[tid] = su * dt * dt;
       AV[tid] = sv * dt * dt * dt * dt;
-      if constexpr (T == 8 && !SYM6) { put_periodic6(EU, i, j, AU[tid]); put_periodic6(EV, i, j, AV[tid]); }
     }
     for (int e = tid; e < NW; e += NT) {   // qh = L' q_w per step
       const int a = e / 6, cc = e % 6;
@@ -326,8 +287,8 @@ __device__ __forceinline__ void qp_wrench_robot(const DevCfg *__restrict__ c, co
     }
     __syncthreads();
     // Up to two ADMM stages with their own factorisation (rho, then rho2 for the robots still moving after admm_switch
-    // iterations), as in qp_tile_robot; z and y are parked across the second sweep (in LDS; in registers on the one-wave grid,
-    // whose sweep leaves the room and whose staging area takes the LDS).
+    // iterations), as in qp_tile_robot; z and y are parked across the second sweep: the 256-lane grid parks them in LDS, the
+    // one-wave grid -- whose sweep leaves the room and whose staging area takes the LDS -- keeps them in registers.
     double ypark[3] = {0.0, 0.0, 0.0};
     int it = 0, stage = 0;
     int it_limit = (c->rho2 > 0.0 && c->admm_abs_tol > 0.0 && c->admm_switch < c->admm_iters) ? c->admm_switch : c->admm_iters;
@@ -336,11 +297,10 @@ __device__ __forceinline__ void qp_wrench_robot(const DevCfg *__restrict__ c, co
     for (bool again = true; again;) {
     again = false;
     const double aa = uniform_f64(c->alpha + rho), inv_aa = uniform_f64(1.0 / aa), rho_aa = uniform_f64(rho * inv_aa);
-    // ---- my 8 x 8 tile of a I + K' (identity in the padding) ----
+    // ---- my T x T tile of a I + K' (identity in the padding) ----
     double tile[T][T];
     {   // on its own copy of the lane index: (lr, lc) are not kept across the ADMM loop of the stage before
       const int ts = wg_lane<NT>();
-      const int lr = ts >> LG, lc = ts & (LC - 1);
       if (stage == 0) stamp_phase(0);
       if constexpr (SYM6) {
         // every 6 x 6 block of a I + K' once: build (a lane below the block diagonal starts with the mirror image of its block),
@@ -357,18 +317,12 @@ __device__ __forceinline__ void qp_wrench_robot(const DevCfg *__restrict__ c, co
         __syncthreads();
         if (ts >= NW && ts < NP) vv[TileShape<T>::pad(ts)] = 0.0;   // padding of the mat-vec input (the staging area went over it): must not hold NaN bits
       } else {
-      if constexpr (T == 8) build_tile_kron6<H>(tile, tabN, tabS, EU, EV, lr, lc, NW, aa);
-      else build_tile_entries<T, H, 6>(tile, tabN, tabS, AU, AV, lr, lc, NW, aa);
-      if (stage == 0) stamp_phase(1);
-      tile_sweep<T, LG, NW>(tile, pbuf, lr, lc);
-      if (stage == 0) stamp_phase(2);
-      if constexpr (T == 8) {   // (spelled out: through finish_swept_tile the one-wave fused kernel spilled 84 values instead of 20, two of them in the iteration loop)
-      if (lr == lc) {   // remove the sweep's +2 diagonal offset: tile = -(a I + K')^-1
-#pragma unroll
-        for (int ta = 0; ta < T; ta++) tile[ta][ta] -= 2.0;
-      }
-      permute_tile_rows_for_reduce(tile, lc);
-      } else finish_swept_tile<T>(tile, lr, lc);
+        const int lr = ts >> LG, lc = ts & (LC - 1);
+        build_tile_entries<T, H, 6>(tile, tabN, tabS, AU, AV, lr, lc, NW, aa);
+        if (stage == 0) stamp_phase(1);
+        tile_sweep<T, LG, NW>(tile, pbuf, lr, lc);
+        if (stage == 0) stamp_phase(2);
+        finish_swept_tile4(tile, lr, lc);
       }
     }
     // lane roles of the iteration, from a fresh lane index (WrenchLane)

@@ -15,8 +15,7 @@
 #include <vector>
 #include <algorithm>
 #include "rg_qp_common.inc"
-#include "rg_qp_tile_kernel.inc"
-#include "rg_qp_wrench_kernel.inc"
+#include "rg_qp_tile.inc"
 #include "rg_qp_sym6.inc"
 #include "sweep_variants.inc"
 
