@@ -242,6 +242,24 @@ int rg_mpc_set_command(rg_mpc_handle *h, const float *cmd, void *stream);
 int rg_mpc_set_gait(rg_mpc_handle *h, const double *stance_duration, const double *duty_factor, const double *init_phase,
                     const int32_t *init_state, void *stream);
 
+/* Per-robot single-rigid-body model: what _setup_controller takes from each robot's constants (mpc_controller.py:28-66: mass,
+ * inertia, body height, hip positions) plus the friction coefficients, one row per robot instead of one per handle -- a batch
+ * that mixes robots, or randomises the planner model per env.
+ * HOST arrays (float64), component-major [k][n] over the n robots idx_host[0..n) (idx_host NULL: robots 0..n-1, n == batch):
+ * mass [n], inertia [9][n] (row-major body inertia), body_height [n], mu [4][n] (per leg, FR FL RR RL; per cone row under
+ * conv_friction_rows), hip [12][n] ([leg][xyz]).  Any of them may be NULL: that field keeps its current per-robot value (the
+ * config's until first set).  rg_mpc_set_body(h, NULL, 0, NULL, NULL, NULL, NULL, NULL, s) returns every robot to the config.
+ * Validated before anything is copied -- mass > 0, inertia symmetric positive definite, body_height > 0, 0 < mu <= 100, all
+ * finite -- else RG_MPC_ERR_INVALID naming the first bad robot, and the handle's rows are untouched.  With conv_friction_rows = 1
+ * mu rows need solver = RG_SOLVER_ACTIVE_SET (as unequal config coefficients do).
+ * The host derives 1 / m, the normal-force bounds fz_min / fz_max = scale * m * g and the inverse inertia, and uploads the whole
+ * table in one copy on `stream`; the call waits for it (the host rows are its staging buffer).  admm_tol keeps its config-wide
+ * scale admm_tol * m * g.  While rows are set the step runs the per-leg-friction ("per_leg") kernel instantiations, which read
+ * the robot's body from its front->QP record; the audit lane's re-solves read the copy of that record taken at the tick they
+ * audit, so a change of rows never shows up as a false over_tol.  Takes effect from the next rg_mpc_step. */
+int rg_mpc_set_body(rg_mpc_handle *h, const int32_t *idx_host, int32_t n, const double *mass, const double *inertia,
+                    const double *body_height, const double *mu, const double *hip, void *stream);
+
 /* MPCController.get_action (mpc_controller.py:102-106) for all B robots at clock value t. */
 int rg_mpc_step(rg_mpc_handle *h, double t, const rg_mpc_state_ptrs *in, const rg_mpc_out_ptrs *out, void *stream);
 
@@ -325,7 +343,8 @@ const char *rg_mpc_profile_window_names(const rg_mpc_handle *h);
 
 /* What rg_mpc_create chose for this handle, as one line of space-separated key=value pairs (keys: solver, horizon, batch,
  * lanes -- lanes per robot in the QP launch: 64 or 256, see lane_grid --, exact12 -- one / two stance legs on the exact body --,
- * mu -- "uniform" or "per_leg" kernel instantiations --, schedule, audit, direct).  For logs and tests; valid until destroy. */
+ * mu -- "uniform" or "per_leg" kernel instantiations (per_leg while per-robot body rows are set) --, schedule, audit, direct,
+ * body -- "config" or "per_robot": rg_mpc_set_body rows).  For logs and tests; valid until the handle's next call. */
 const char *rg_mpc_plan_description(const rg_mpc_handle *h);
 
 /* Names of the kernels launched by rg_mpc_step, for matching rocprof rows. */

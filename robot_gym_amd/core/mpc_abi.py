@@ -52,7 +52,7 @@ class COutPtrs(C.Structure):
     _fields_ = [(n, fp) for n in ("action", "grf", "tau_stance", "leg_state", "desired_state", "phase", "foot_target", "v_body")]
 
 
-EXPORTS = ("rg_mpc_create", "rg_mpc_reset", "rg_mpc_reset_at", "rg_mpc_set_command", "rg_mpc_set_gait", "rg_mpc_step", "rg_mpc_step_host", "rg_mpc_hybrid_to_torque",
+EXPORTS = ("rg_mpc_create", "rg_mpc_reset", "rg_mpc_reset_at", "rg_mpc_set_command", "rg_mpc_set_gait", "rg_mpc_set_body", "rg_mpc_step", "rg_mpc_step_host", "rg_mpc_hybrid_to_torque",
            "rg_mpc_hybrid_to_torque_substeps",
            "rg_mpc_last_bin_counts", "rg_mpc_last_solver_stats", "rg_mpc_last_iterations", "rg_mpc_audit_stats", "rg_mpc_last_direct_count", "rg_mpc_profile_begin", "rg_mpc_profile_stride", "rg_mpc_profile_end", "rg_mpc_kernel_names", "rg_mpc_plan_description", "rg_mpc_profile_window_names", "rg_mpc_debug_poison_lds", "rg_mpc_destroy", "rg_mpc_last_error",
            "rg_mpc_abi_version", "rg_mpc_config_size")
@@ -88,6 +88,8 @@ def load_library(path=None):
     L.rg_mpc_hybrid_to_torque_substeps.restype = i32
     L.rg_mpc_set_gait.argtypes = [fp, fp, fp, fp, fp, fp]
     L.rg_mpc_set_gait.restype = i32
+    L.rg_mpc_set_body.argtypes = [fp, C.POINTER(i32), i32, fp, fp, fp, fp, fp, fp]
+    L.rg_mpc_set_body.restype = i32
     L.rg_mpc_last_bin_counts.argtypes = [fp, C.POINTER(i32 * 5), fp]
     L.rg_mpc_last_bin_counts.restype = i32
     L.rg_mpc_last_solver_stats.argtypes = [fp, C.POINTER(C.c_int64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), fp]
@@ -191,6 +193,21 @@ class MpcHandle:
     def set_gait(self, stance_ptr, duty_ptr, phase_ptr, init_state_ptr=None, stream=None):
         self._check(self._lib.rg_mpc_set_gait(self._h, stance_ptr, duty_ptr, phase_ptr, init_state_ptr, stream))
 
+    def set_body(self, idx=None, n=0, mass=None, inertia=None, body_height=None, mu=None, hip=None, stream=None):
+        """rg_mpc_set_body: host float64 arrays, component-major [k][n] (contiguous numpy), or None to keep a field.  All None
+        with idx None and n 0 returns every robot to the config."""
+        import numpy as np
+        keep = []
+
+        def ptr(a):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            keep.append(a)
+            return a.ctypes.data
+        ia = None if idx is None else (i32 * len(idx))(*[int(i) for i in idx])
+        self._check(self._lib.rg_mpc_set_body(self._h, ia, int(n), ptr(mass), ptr(inertia), ptr(body_height), ptr(mu), ptr(hip), stream))
+
     def hybrid_to_torque(self, action_ptr, q_ptr, qd_ptr, tau_ptr, stream=None, substeps=None):
         if substeps is None:
             self._check(self._lib.rg_mpc_hybrid_to_torque(self._h, action_ptr, q_ptr, qd_ptr, tau_ptr, stream))
@@ -253,7 +270,8 @@ class MpcHandle:
         return self._lib.rg_mpc_profile_window_names(self._h).decode().split(",")
 
     def plan(self):
-        """rg_mpc_plan_description as a dict: what create chose (solver, horizon, batch, lanes, exact12, mu, schedule, audit, direct)."""
+        """rg_mpc_plan_description as a dict: what create chose (solver, horizon, batch, lanes, exact12, mu, schedule, audit, direct) and
+        whether per-robot body rows are set (body: config / per_robot)."""
         return dict(kv.split("=", 1) for kv in self._lib.rg_mpc_plan_description(self._h).decode().split())
 
     def kernel_names(self):

@@ -133,9 +133,15 @@ rg_front_kernel(const DevCfg *__restrict__ c, DevState st, DevIn in, DevOut out,
   const int hard_prev = st.hard[b], ncs_prev = st.ncs[b], it_prev = st.iters[b], ws_cnt_raw = (st.ws_cnt ? st.ws_cnt : st.ncs)[b];   // (work lists, below)
   const double t_rob_raw = (in.t_robot ? in.t_robot : st.reset_time)[b];
   const int sched_raw = (in.contact_sched ? in.contact_sched : in.contact)[leg * B + b];   // caller's contact schedule (contact_lookahead)
+  // hip positions: the robot's body row (rg_mpc_set_body), else the config's
   double hip[3];
+  if (c->body) {
 #pragma unroll
-  for (int a = 0; a < 3; a++) hip[a] = c->hip[3 * leg + a];
+    for (int a = 0; a < 3; a++) hip[a] = c->body[(size_t)b * RG_BODY_N + BODY_HIP + 3 * leg + a];
+  } else {
+#pragma unroll
+    for (int a = 0; a < 3; a++) hip[a] = c->hip[3 * leg + a];
+  }
   const LegGait gt = load_leg_gait(c, st, leg, b, B);
   double foot[3], jac[9];
   {
@@ -274,7 +280,9 @@ rg_front_kernel(const DevCfg *__restrict__ c, DevState st, DevIn in, DevOut out,
   if (do_swing) {
     double tw[3] = {-hip[1], hip[0], 0.0};
     double cv[3] = {vb[0], vb[1], 0.0}, dv[3] = {cmd[0], cmd[1], 0.0};
-    double dh[3] = {0.0, 0.0, c->body_height - c->foot_clearance};
+    // (the robot's own body height is loaded here, behind the work-list atomic: only handles with body rows pay that wait)
+    const double body_h = c->body ? c->body[(size_t)b * RG_BODY_N + BODY_HEIGHT] : c->body_height;
+    double dh[3] = {0.0, 0.0, body_h - c->foot_clearance};
     double target[3], start[3];
 #pragma unroll
     for (int a = 0; a < 3; a++) {
@@ -340,6 +348,11 @@ rg_front_kernel(const DevCfg *__restrict__ c, DevState st, DevIn in, DevOut out,
 #pragma unroll
   for (int i = 0; i < 9; i++) rec[REC_JAC + 9 * leg + i] = jac[i];
   rec[REC_SCHED + leg] = (double)sched;
+  if (c->body_rec) {   // the body block of the record (REC_BODY), for the MU4 QP instantiations: two doubles per leg lane
+    static_assert(RG_BODY_REC == 8 && REC_BODY + RG_BODY_REC <= REC_EMIT, "four lanes copy two doubles each into the record's body block");
+    const double *br = c->body ? c->body + (size_t)b * RG_BODY_N : c->body_cfg;
+    rec[REC_BODY + 2 * leg] = br[2 * leg]; rec[REC_BODY + 2 * leg + 1] = br[2 * leg + 1];
+  }
   if (leg == 0) {
     rec[REC_ROLL] = rpy[0]; rec[REC_PITCH] = rpy[1];
     rec[REC_COMZ] = nc > 0 ? fabs(hz / nc) : 0.0;
@@ -347,12 +360,20 @@ rg_front_kernel(const DevCfg *__restrict__ c, DevState st, DevIn in, DevOut out,
     for (int i = 0; i < 3; i++) { rec[REC_OMEGA + i] = rate[i]; rec[REC_VBODY + i] = vb[i]; rec[REC_CMD + i] = cmd[i]; }
     // body rotation for the inertia: Ry(pitch) Rx(roll)
     double Rb[9] = {cp, sp * sr, sp * cr_, 0, cr_, -sr, -sp, cp * sr, cp * cr_};
-    double T1[9], Rt[9], Iw[9];
+    double T1[9], Rt[9], Iw[9], Ii[9];
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
       for (int j = 0; j < 3; j++) Rt[3 * i + j] = Rb[3 * j + i];
-    m3mul(Rb, c->Iinv, T1);
+    // body-frame inverse inertia: the robot's row (loaded here, by the leg-0 lanes only), or the config's (scalar loads)
+    if (c->body) {
+#pragma unroll
+      for (int i = 0; i < 9; i++) Ii[i] = c->body[(size_t)b * RG_BODY_N + BODY_IINV + i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 9; i++) Ii[i] = c->Iinv[i];
+    }
+    m3mul(Rb, Ii, T1);
     m3mul(T1, Rt, Iw);
 #pragma unroll
     for (int i = 0; i < 9; i++) rec[REC_IWINV + i] = Iw[i];

@@ -108,6 +108,10 @@ struct rg_mpc_handle {
   bool exact12 = false;             // ... in which one- and two-leg robots run the exact active-set body (RG_SOLVER_HYBRID / RG_SOLVER_ACTIVE_SET, constant contacts)
   bool wide = false;                // ... on 256 lanes per robot instead of one wave (horizon 10, hybrid plan: rg_mpc_config.lane_grid)
   bool mu4 = false;                 // the four legs' friction coefficients differ: the kernel instantiations with a per-lane coefficient (leg_mu)
+  bool body_on = false;             // per-robot body rows are set (rg_mpc_set_body): the MU4 instantiations, which read the body from the record
+  double *body_dev = nullptr;       // [B][RG_BODY_N] per-robot body rows (DevCfg::body while body_on)
+  std::vector<double> body_host;    // host copy of the rows: a partial update rewrites its robots here and uploads the whole table
+  bool kmu4() const { return mu4 || body_on; }   // which QP kernel instantiations the step launches
   int *counts2 = nullptr;           // [2][RG_NCOUNTS] double-buffered work-list counters
   bool auto_retry = false;          // RG_SOLVER_AUTO: robots ADMM left unconverged are re-solved exactly
   int retry_max_nc = 0;             // ... for robots with up to this many stance legs
@@ -263,11 +267,17 @@ static int build_devcfg(const rg_mpc_config *c, DevCfg *d, std::string &err) {
     d->Iinv[3] = c01 * inv; d->Iinv[4] = (I[0] * I[8] - I[2] * I[6]) * inv; d->Iinv[5] = (I[2] * I[3] - I[0] * I[5]) * inv;
     d->Iinv[6] = c02 * inv; d->Iinv[7] = (I[1] * I[6] - I[0] * I[7]) * inv; d->Iinv[8] = (I[0] * I[4] - I[1] * I[3]) * inv;
   }
+  // the config's body model as one row (the front kernel reads the robot's row or this one; the MU4 bodies read its copy in the record)
+  d->body = nullptr;
+  d->body_cfg[BODY_INV_MASS] = d->inv_mass; d->body_cfg[BODY_HEIGHT] = d->body_height; d->body_cfg[BODY_FZ_MIN] = d->fz_min; d->body_cfg[BODY_FZ_MAX] = d->fz_max;
+  for (int i = 0; i < 4; i++) d->body_cfg[BODY_MU + i] = d->mu4[i];
+  for (int i = 0; i < 9; i++) d->body_cfg[BODY_IINV + i] = d->Iinv[i];
   memcpy(d->w, c->weights, sizeof(d->w));
   for (int i = 0; i < 4; i++) { d->stance_dur[i] = c->stance_duration[i]; d->duty[i] = c->duty_factor[i]; d->init_phase[i] = c->init_phase[i]; d->init_state[i] = c->init_state[i]; }
   d->contact_thresh = c->contact_phase_thresh; d->foot_clearance = c->foot_clearance; d->max_clearance = c->max_clearance;
   memcpy(d->swing_kp, c->swing_kp, sizeof(d->swing_kp));
   memcpy(d->hip, c->hip, sizeof(d->hip));
+  for (int i = 0; i < 12; i++) d->body_cfg[BODY_HIP + i] = c->hip[i];
   memcpy(d->kp, c->motor_kp, sizeof(d->kp)); memcpy(d->kd, c->motor_kd, sizeof(d->kd));
   memcpy(d->mdir, c->motor_dir, sizeof(d->mdir)); memcpy(d->moff, c->motor_off, sizeof(d->moff));
   memcpy(d->jxyz, c->jxyz, sizeof(d->jxyz));
@@ -293,6 +303,18 @@ static int build_devcfg(const rg_mpc_config *c, DevCfg *d, std::string &err) {
       d->Stab[a * H + b] = s;
     }
   return RG_MPC_OK;
+}
+
+// rg_mpc_plan_description (mu: the kernel instantiations the step launches -- per-robot body rows run the per_leg ones)
+static void describe_plan(rg_mpc_handle *h) {
+  static const char *solver_name[] = {"admm", "active_set", "auto", "hybrid"};
+  const rg_mpc_config *cfg = &h->cfg;
+  char buf[256];
+  const int lanes = (cfg->horizon == 20 || h->wide) ? 256 : 64;
+  snprintf(buf, sizeof(buf), "solver=%s horizon=%d batch=%d lanes=%d exact12=%d mu=%s schedule=%d audit=%d direct=%d body=%s", solver_name[cfg->solver], cfg->horizon, h->B, lanes,
+           h->exact12 ? 1 : 0, h->kmu4() ? "per_leg" : "uniform", cfg->contact_lookahead ? 1 : 0, h->audit_on ? 1 : 0, h->direct_on ? 1 : 0,
+           h->body_on ? "per_robot" : "config");
+  h->plan = buf;
 }
 
 template <typename T>
@@ -344,6 +366,7 @@ int rg_mpc_create(const rg_mpc_config *cfg, int32_t batch, int32_t device, rg_mp
   int rc = build_devcfg(cfg, &h->hcfg, h->err);
   h->hcfg.plan = h->fused ? 1 : 0;
   h->hcfg.exact12 = h->exact12 ? (cfg->solver == RG_SOLVER_ACTIVE_SET ? 2 : 1) : 0;
+  h->hcfg.body_rec = h->mu4 ? 1 : 0;
   if (rc) { g_create_err = h->err; delete h; return rc; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_err = "no HIP device available"; delete h; return RG_MPC_ERR_NO_DEVICE; }
@@ -402,14 +425,7 @@ int rg_mpc_create(const rg_mpc_config *cfg, int32_t batch, int32_t device, rg_mp
   }
 #undef CR
 #undef AL
-  {
-    static const char *solver_name[] = {"admm", "active_set", "auto", "hybrid"};
-    char buf[256];
-    const int lanes = (cfg->horizon == 20 || h->wide) ? 256 : 64;
-    snprintf(buf, sizeof(buf), "solver=%s horizon=%d batch=%d lanes=%d exact12=%d mu=%s schedule=%d audit=%d direct=%d", solver_name[cfg->solver], cfg->horizon, batch, lanes,
-             h->exact12 ? 1 : 0, h->mu4 ? "per_leg" : "uniform", cfg->contact_lookahead ? 1 : 0, h->audit_on ? 1 : 0, h->direct_on ? 1 : 0);
-    h->plan = buf;
-  }
+  describe_plan(h);
   *out = h;
   int r = rg_mpc_reset(h, nullptr, batch, 0.0, nullptr);
   if (r) { g_create_err = h->err; rg_mpc_destroy(h); *out = nullptr; return r; }
@@ -504,6 +520,102 @@ int rg_mpc_set_gait(rg_mpc_handle *h, const double *stance_duration, const doubl
   return RG_MPC_OK;
 }
 
+// Per-robot body rows.  Everything is validated and packed on the host (1 / mass, normal-force bounds, inverse inertia), the
+// whole [B][RG_BODY_N] table goes up in one copy on `stream`, and the front kernel reads it from the next tick on.  The QP bodies
+// read the robot's body from its record, where the front kernel put it: the audit lane's re-solves of an earlier tick, still in
+// flight on the side stream, read their own copies of those records and so the body of the tick they audit.
+int rg_mpc_set_body(rg_mpc_handle *h, const int32_t *idx_host, int32_t n, const double *mass, const double *inertia,
+                    const double *body_height, const double *mu, const double *hip, void *stream) {
+  if (!h) return RG_MPC_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  DeviceScope dev_(h->device); HIPCHK(h, dev_.err);
+  const int B = h->B;
+  const bool any = mass || inertia || body_height || mu || hip;
+  if (!any) {
+    if (idx_host || n != 0) { h->err = "set_body: no field given (n = 0 and a null index list return every robot to the config)"; return RG_MPC_ERR_INVALID; }
+    if (h->body_on) {   // back to the config: the front kernel reads DevCfg::body_cfg again (ordered behind the ticks already enqueued)
+      h->hcfg.body = nullptr;
+      h->hcfg.body_rec = h->mu4 ? 1 : 0;
+      h->hcfg.mu_rows = (h->cfg.conv_friction_rows && h->mu4) ? 1 : 0;
+      HIPCHK(h, hipMemcpyAsync(h->dcfg, &h->hcfg, sizeof(DevCfg), hipMemcpyHostToDevice, s));
+      HIPCHK(h, hipStreamSynchronize(s));
+      h->body_on = false;
+      describe_plan(h);
+    }
+    return RG_MPC_OK;
+  }
+  if (idx_host ? (n < 1 || n > B) : n != B) { h->err = "set_body: n must be the batch without an index list, 1..batch with one"; return RG_MPC_ERR_INVALID; }
+  if (mu && h->cfg.conv_friction_rows && h->cfg.solver != RG_SOLVER_ACTIVE_SET) {
+    h->err = "set_body: friction rows with conv_friction_rows = 1 (one coefficient per cone row: an asymmetric pyramid) need solver = RG_SOLVER_ACTIVE_SET";
+    return RG_MPC_ERR_INVALID;
+  }
+  char msg[256];
+  auto bad = [&](int k, const char *what) {
+    snprintf(msg, sizeof(msg), "set_body: robot %d (entry %d): %s", idx_host ? idx_host[k] : k, k, what);
+    h->err = msg;
+    return RG_MPC_ERR_INVALID;
+  };
+  // validate every entry before anything is copied: a refused call leaves the handle's rows as they were
+  for (int k = 0; k < n; k++) {
+    if (idx_host && (idx_host[k] < 0 || idx_host[k] >= B)) return bad(k, "index out of range");
+    if (mass && !(mass[k] > 0 && mass[k] <= 1e300)) return bad(k, "mass must be positive and finite");
+    if (body_height && !(body_height[k] > 0 && body_height[k] <= 1e300)) return bad(k, "body_height must be positive and finite");
+    if (mu) for (int l = 0; l < 4; l++) if (!(mu[l * n + k] > 0 && mu[l * n + k] <= 100.0)) return bad(k, "friction coefficients must be in (0, 100]");
+    if (hip) for (int i = 0; i < 12; i++) if (!(fabs(hip[i * n + k]) <= 1e300)) return bad(k, "hip positions must be finite");
+    if (inertia) {
+      double I[9], mx = 0.0;
+      for (int i = 0; i < 9; i++) { I[i] = inertia[i * n + k]; if (!(fabs(I[i]) <= 1e300)) return bad(k, "inertia must be finite"); mx = fmax(mx, fabs(I[i])); }
+      for (int i = 0; i < 3; i++)
+        for (int j = 0; j < i; j++) if (fabs(I[3 * i + j] - I[3 * j + i]) > 1e-12 * mx) return bad(k, "inertia must be symmetric");
+      const double m2 = I[0] * I[4] - I[1] * I[3];
+      const double det = I[0] * (I[4] * I[8] - I[5] * I[7]) - I[1] * (I[3] * I[8] - I[5] * I[6]) + I[2] * (I[3] * I[7] - I[4] * I[6]);
+      if (!(I[0] > 0 && m2 > 0 && det > 0)) return bad(k, "inertia must be positive definite");
+    }
+  }
+  if (!h->body_dev) {
+    int r_ = dev_alloc(h, &h->body_dev, (size_t)B * RG_BODY_N); if (r_) return r_;
+  }
+  if (!h->body_on) {   // every robot starts from the config's row
+    h->body_host.resize((size_t)B * RG_BODY_N);
+    for (int b = 0; b < B; b++) memcpy(&h->body_host[(size_t)b * RG_BODY_N], h->hcfg.body_cfg, sizeof(h->hcfg.body_cfg));
+  }
+  const rg_mpc_config &c = h->cfg;
+  for (int k = 0; k < n; k++) {
+    double *r = &h->body_host[(size_t)(idx_host ? idx_host[k] : k) * RG_BODY_N];
+    if (mass) {   // as build_devcfg: 1 / m, fz bounds = scale * m * g
+      r[BODY_INV_MASS] = 1.0 / mass[k];
+      r[BODY_FZ_MIN] = mass[k] * c.gravity * c.fz_min_scale; r[BODY_FZ_MAX] = mass[k] * c.gravity * c.fz_max_scale;
+    }
+    if (body_height) r[BODY_HEIGHT] = body_height[k];
+    if (mu) for (int l = 0; l < 4; l++) r[BODY_MU + l] = mu[l * n + k];
+    if (hip) for (int i = 0; i < 12; i++) r[BODY_HIP + i] = hip[i * n + k];
+    if (inertia) {   // the same cofactor inverse as build_devcfg
+      double I[9];
+      for (int i = 0; i < 9; i++) I[i] = inertia[i * n + k];
+      const double c00 = I[4] * I[8] - I[5] * I[7], c01 = I[5] * I[6] - I[3] * I[8], c02 = I[3] * I[7] - I[4] * I[6];
+      const double inv = 1.0 / (I[0] * c00 + I[1] * c01 + I[2] * c02);
+      double *Ii = r + BODY_IINV;
+      Ii[0] = c00 * inv; Ii[1] = (I[2] * I[7] - I[1] * I[8]) * inv; Ii[2] = (I[1] * I[5] - I[2] * I[4]) * inv;
+      Ii[3] = c01 * inv; Ii[4] = (I[0] * I[8] - I[2] * I[6]) * inv; Ii[5] = (I[2] * I[3] - I[0] * I[5]) * inv;
+      Ii[6] = c02 * inv; Ii[7] = (I[1] * I[6] - I[0] * I[7]) * inv; Ii[8] = (I[0] * I[4] - I[1] * I[3]) * inv;
+    }
+  }
+  // one copy of the table on the caller's stream (behind the ticks already enqueued, which read the previous rows), then the
+  // pointer in the device config; the host copy is the staging buffer, so the call waits for the copies
+  HIPCHK(h, hipMemcpyAsync(h->body_dev, h->body_host.data(), sizeof(double) * h->body_host.size(), hipMemcpyHostToDevice, s));
+  if (!h->body_on || mu) {
+    h->hcfg.body = h->body_dev;
+    h->hcfg.body_rec = 1;
+    // conv_friction_rows (solver = RG_SOLVER_ACTIVE_SET): per-robot coefficients belong to the cone rows as the config's would
+    if (mu && c.conv_friction_rows) h->hcfg.mu_rows = 1;
+    HIPCHK(h, hipMemcpyAsync(h->dcfg, &h->hcfg, sizeof(DevCfg), hipMemcpyHostToDevice, s));
+  }
+  HIPCHK(h, hipStreamSynchronize(s));
+  h->body_on = true;
+  describe_plan(h);
+  return RG_MPC_OK;
+}
+
 int rg_mpc_step(rg_mpc_handle *h, double t, const rg_mpc_state_ptrs *in, const rg_mpc_out_ptrs *out, void *stream) {
   if (!h || !in || !out) { if (h) h->err = "step: null argument"; return RG_MPC_ERR_INVALID; }
   if (!in->rpy || !in->rpy_rate || !in->v_world || !in->quat || !in->q || !in->contact) { h->err = "step: missing required state pointer"; return RG_MPC_ERR_INVALID; }
@@ -545,7 +657,7 @@ int rg_mpc_step(rg_mpc_handle *h, double t, const rg_mpc_state_ptrs *in, const r
   if (direct_now) {
     HIPCHK(h, hipEventRecord(h->front_done, s));
     HIPCHK(h, hipStreamWaitEvent(h->direct_stream, h->front_done, 0));
-    HIPCHK(h, launch_qp_resolve_h10(h->mu4, h->dcfg, h->st, dout, B, h->cu_count, h->direct_stream, RETRY_DIRECT));
+    HIPCHK(h, launch_qp_resolve_h10(h->kmu4(), h->dcfg, h->st, dout, B, h->cu_count, h->direct_stream, RETRY_DIRECT));
     HIPCHK(h, hipEventRecord(h->direct_done, h->direct_stream));
     h->direct_launches++;
   }
@@ -554,8 +666,8 @@ int rg_mpc_step(rg_mpc_handle *h, double t, const rg_mpc_state_ptrs *in, const r
   // (a contact schedule puts every robot on the schedule body: its own launch, same work lists; the exact solver with a
   // contact schedule has no QP launch of its own: the front kernel's stance-leg bins are the re-solve launch's direct lists)
   if (h->fused) {
-    if (h->cfg.contact_lookahead) HIPCHK(h, launch_qp_sched_any(H, h->mu4, h->dcfg, h->st, dout, B, s));
-    else HIPCHK(h, launch_qp_fused_any(H, h->exact12 ? (h->cfg.solver == RG_SOLVER_ACTIVE_SET ? 2 : 1) : 0, h->wide, h->mu4, h->dcfg, h->st, dout, B, s));
+    if (h->cfg.contact_lookahead) HIPCHK(h, launch_qp_sched_any(H, h->kmu4(), h->dcfg, h->st, dout, B, s));
+    else HIPCHK(h, launch_qp_fused_any(H, h->exact12 ? (h->cfg.solver == RG_SOLVER_ACTIVE_SET ? 2 : 1) : 0, h->wide, h->kmu4(), h->dcfg, h->st, dout, B, s));
   } else {   // no QP launch to carry the swing IK lanes: a launch of their own
     hipLaunchKernelGGL(rg_swing_ik_kernel, dim3((4 * B + 63) / 64), dim3(64), 0, s, h->dcfg, h->st, dout, B);
     HIPCHK(h, hipGetLastError());
@@ -563,14 +675,14 @@ int rg_mpc_step(rg_mpc_handle *h, double t, const rg_mpc_state_ptrs *in, const r
   if (pev) HIPCHK(h, hipEventRecord(pev[3], s));
   if (ring >= 0) HIPCHK(h, hipEventRecord(h->audit_fused[ring], s));
   if (direct_now) HIPCHK(h, hipStreamWaitEvent(s, h->direct_done, 0));   // the direct robots' actions are part of this tick
-  if (h->auto_retry && H == 10) HIPCHK(h, launch_qp_resolve_h10(h->mu4, h->dcfg, h->st, dout, B, h->cu_count, s, head ? RETRY_AFTER_HEAD : (direct_now ? RETRY_LISTS : RETRY_ALL)));
-  else if (h->auto_retry) HIPCHK(h, launch_qp_sched_retry_h20(h->mu4, h->dcfg, h->st, dout, B, h->cu_count, s, 0));
+  if (h->auto_retry && H == 10) HIPCHK(h, launch_qp_resolve_h10(h->kmu4(), h->dcfg, h->st, dout, B, h->cu_count, s, head ? RETRY_AFTER_HEAD : (direct_now ? RETRY_LISTS : RETRY_ALL)));
+  else if (h->auto_retry) HIPCHK(h, launch_qp_sched_retry_h20(h->kmu4(), h->dcfg, h->st, dout, B, h->cu_count, s, 0));
   if (pev) { HIPCHK(h, hipEventRecord(pev[5], s)); h->prof_n++; }
   if (ring >= 0) {
     // the same exact body, in audit mode, over the captured records: side stream, ordered after the ADMM launch only
     HIPCHK(h, hipStreamWaitEvent(h->audit_stream, h->audit_fused[ring], 0));
-    if (H == 10) HIPCHK(h, launch_qp_resolve_h10(h->mu4, h->dcfg, h->st, dout, B, h->cu_count, h->audit_stream, RETRY_AUDIT));
-    else HIPCHK(h, launch_qp_sched_retry_h20(h->mu4, h->dcfg, h->st, dout, B, h->cu_count, h->audit_stream, 1));
+    if (H == 10) HIPCHK(h, launch_qp_resolve_h10(h->kmu4(), h->dcfg, h->st, dout, B, h->cu_count, h->audit_stream, RETRY_AUDIT));
+    else HIPCHK(h, launch_qp_sched_retry_h20(h->kmu4(), h->dcfg, h->st, dout, B, h->cu_count, h->audit_stream, 1));
     HIPCHK(h, hipEventRecord(h->audit_done[ring], h->audit_stream));
     h->audit_inflight[ring] = true;
   }

@@ -29,10 +29,22 @@
 #define REC_INVCP 33
 #define REC_TANP 34
 #define REC_JAC 35
-#define REC_SWINGQ 71
+#define REC_BODY 71     // 8 doubles: the robot's planner body model, copied by the front kernel from its row (BODY_INV_MASS .. BODY_MU + 3):
+                        // the MU4 kernel instantiations read it from here, and the audit lane's copy of the record is its snapshot
 #define REC_EMIT 83
 #define REC_CONTACT 84
 #define REC_SCHED 88    // 4 doubles: per leg, bit k = in contact at horizon step k (look-ahead extension)
+
+// Per-robot single-rigid-body rows (rg_mpc_set_body), [B][RG_BODY_N] doubles, and DevCfg::body_cfg: the config's own row
+#define BODY_INV_MASS 0
+#define BODY_HEIGHT 1
+#define BODY_FZ_MIN 2
+#define BODY_FZ_MAX 3
+#define BODY_MU 4       // 4: per leg (FR, FL, RR, RL), or per cone row under DevCfg::mu_rows
+#define BODY_IINV 8     // 9: body-frame inverse inertia, row-major
+#define BODY_HIP 17     // 12: hip positions [leg][xyz]
+#define RG_BODY_N 32
+#define RG_BODY_REC 8   // BODY_INV_MASS .. BODY_MU + 3 travel in the record (REC_BODY)
 
 struct DevCfg {
   int H, window, kin_mode, ik_iters, admm_iters;
@@ -75,6 +87,9 @@ struct DevCfg {
   double *as_spill;          // horizon-20 re-solve: per-workgroup slabs of global memory for the rows of the packed (C_A G C_A')^-1 beyond the LDS part (SchedLds::SPILL doubles each); null: none
   int as_spill_audit_base;   // first slab of the audit launch's workgroups (the re-solve launch uses 0 .. its grid - 1)
   int mu_rows;               // rg_mpc_config.conv_friction_rows with unequal coefficients: mu4[t] belongs to cone row t (-x, +x, -y, +y) of EVERY block, not to leg t
+  const double *body;        // [B][RG_BODY_N] per-robot body rows (rg_mpc_set_body); null: every robot has body_cfg
+  double body_cfg[RG_BODY_N]; // the config's body model as one row
+  int body_rec;              // 1: the front kernel fills the record's body block (REC_BODY) -- the step runs the MU4 instantiations
 };
 
 struct DevState {
@@ -269,15 +284,18 @@ __device__ inline void leg_ik(const DevCfg *c, int leg, const double target[3], 
 // Friction coefficient of a leg.  MU4 = false (the four coefficients are equal: every shipped robot, reference 0.45 x 4
 // [UPSTREAM-RECALL, SURVEY 8a-18]): one wave-uniform value that stays in SGPRs across the solver loops.  MU4 = true: the
 // leg's own, a per-lane value -- its own kernel instantiations, so that the uniform case pays no register for it.
+// The MU4 instantiations also carry the robot's own body model: friction, 1 / mass, body height and the normal-force bounds
+// come from the robot's record (REC_BODY, staged in LDS with the rest of it; the front kernel filled it from the robot's row of
+// rg_mpc_set_body, or from the config's), so that they serve per-robot bodies as well as per-leg friction coefficients.
 template <bool MU4>
-__device__ __forceinline__ double leg_mu(const DevCfg *__restrict__ c, const int leg) {
-  if constexpr (MU4) return c->mu4[leg & 3]; else return c->mu;
+__device__ __forceinline__ double leg_mu(const DevCfg *__restrict__ c, const double *rec, const int leg) {
+  if constexpr (MU4) return rec[REC_BODY + BODY_MU + (leg & 3)]; else return c->mu;
 }
 // ... of cone row `ty` (0: -fx, 1: +fx, 2: -fy, 3: +fy) of a block of leg `leg`: the exact bodies ask per constraint, so that
 // they can also follow the other recalled reading of upstream's four coefficients (conv_friction_rows: one per cone ROW)
 template <bool MU4>
-__device__ __forceinline__ double row_mu(const DevCfg *__restrict__ c, const int leg, const int ty) {
-  if constexpr (MU4) return c->mu4[(c->mu_rows ? ty : leg) & 3]; else return c->mu;
+__device__ __forceinline__ double row_mu(const DevCfg *__restrict__ c, const double *rec, const int leg, const int ty) {
+  if constexpr (MU4) return rec[REC_BODY + BODY_MU + ((c->mu_rows ? ty : leg) & 3)]; else return c->mu;
 }
 
 // Euclidean projection onto { |x| <= mu z, |y| <= mu z, lo <= z <= hi }.
@@ -369,4 +387,11 @@ __device__ __forceinline__ void neumaier_add(double &sum, double &corr, double v
   double ns = sum + v;
   if (fabs(sum) >= fabs(v)) corr += (sum - ns) + v; else corr += (v - ns) + sum;
   sum = ns;
+}
+
+// 1 / mass, body height, normal-force bounds: the config's (scalar loads) or, MU4, the robot's record (pinned to SGPRs)
+template <bool MU4>
+__device__ __forceinline__ double body_val(const DevCfg *__restrict__ c, const double *rec, const int k) {
+  if constexpr (MU4) return uniform_f64(rec[REC_BODY + k]);
+  else return k == BODY_INV_MASS ? c->inv_mass : (k == BODY_HEIGHT ? c->body_height : (k == BODY_FZ_MIN ? c->fz_min : c->fz_max));
 }

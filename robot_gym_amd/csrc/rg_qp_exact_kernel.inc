@@ -137,12 +137,22 @@ __device__ __forceinline__ void solver_sync() {
   else __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
 }
 // mu_of(block, row): friction coefficient of cone row `row` of a force block (row_mu: one scalar; under MU4 the leg's own, or the row's).
+// The MU4 bodies pass it wrapped with the robot's record (WithBody): the normal-force bounds are then the robot's as well.
+template <class F, bool UNI = false> struct WithBody {
+  F f;
+  const double *rec;
+  __device__ __forceinline__ double operator()(const int blk, const int ty) const { return f(blk, ty); }
+};
+template <class T> struct WithBody_of { static constexpr bool value = false; };
+template <class F, bool U> struct WithBody_of<WithBody<F, U>> { static constexpr bool value = true; static constexpr bool uni = U; };
+template <class T> struct WithBody_of<T &> : WithBody_of<T> {};
 template <int NB, int Q, bool PACKED, bool DEFER, int NT, class ColumnOfG, class RecomputeX, class MuOf>
 __device__ __forceinline__ bool exact_active_set(const DevCfg *__restrict__ c, const DevState &st, const int b, const int cmask, const int lane, const bool blk_on,
                                                  double *Tm, double *svv, double *rvv, double *lamc, const double *x0, const double *xv, const double *dv,
                                                  ColumnOfG &&column_of_G, RecomputeX &&recompute_x, MuOf &&mu_of, int &q, int &cid, int &its) {
   using TS_ = ExactT<Q, PACKED>;
-  const double lo = c->fz_min, hi = c->fz_max;
+  double lo = c->fz_min, hi = c->fz_max;
+  if constexpr (WithBody_of<MuOf>::value) { lo = mu_of.rec[REC_BODY + BODY_FZ_MIN]; hi = mu_of.rec[REC_BODY + BODY_FZ_MAX]; if constexpr (WithBody_of<MuOf>::uni) { lo = uniform_f64(lo); hi = uniform_f64(hi); } }   // MU4: the robot's (LDS)
   const double vtol = 1e-9 * (1.0 + hi * 1e-3);
   int am = blk_on ? 0 : 0x3F;   // active-type mask of this lane's block (a block that is no variable has nothing to search)
   double clam = 0.0, cs0 = 0.0;   // slot k on lane k: multiplier; DEFER: c_k'x0 - b_k
@@ -393,7 +403,7 @@ __device__ __forceinline__ void qp_exact_robot(const DevCfg *__restrict__ c, con
     for (int e = tid; e < LY::LAMC; e += NT) lamc[e] = 0.0;
     __syncthreads();
     cmask = (int)rec[REC_CONTACT];
-    force_space_tables<NC, H, NT, false>(c, rec, cmask, tid, Bw, TBw, GU, GV, nullptr, nullptr, c1, c2);
+    force_space_tables<NC, H, NT, false, MU4>(c, rec, cmask, tid, Bw, TBw, GU, GV, nullptr, nullptr, c1, c2);
     __syncthreads();
     // ---- my T x T tile of P = 2 (N (x) G_U + S (x) G_V) + alpha I (identity in the padding), and q of the row I own ----
     int lrv = tid >> LG, lcv = tid & (LC - 1);
@@ -446,7 +456,8 @@ __device__ __forceinline__ void qp_exact_robot(const DevCfg *__restrict__ c, con
   bool solved = false;
   const int wave = NT > 64 ? __builtin_amdgcn_readfirstlane(lane >> 6) : 0;   // (scalar: the barriers below sit in wave-uniform control flow)
   if (wave == 0) {
-    auto mu_of = [&](const int blk, const int ty) -> double { return row_mu<MU4>(c, MU4 ? nth_leg(cmask, blk % NC) : 0, ty); };   // block = step * NC + stance-leg slot
+    auto mu_of = [&](const int blk, const int ty) -> double { if constexpr (MU4) return row_mu<MU4>(c, rec, nth_leg(cmask, blk % NC), ty);
+                                                         else return row_mu<MU4>(c, nullptr, MU4 ? nth_leg(cmask, blk % NC) : 0, ty); };   // block = step * NC + stance-leg slot (rec: captured by the MU4 lambda only)
     // dst = G vv on the owner lanes (tile = -G): every lane of the workgroup takes part, between two barriers
     auto apply_G = [&](const int cmd) {
       if constexpr (NT > 64) { if (lane == 0) sc[0] = (double)cmd; }
@@ -479,7 +490,8 @@ __device__ __forceinline__ void qp_exact_robot(const DevCfg *__restrict__ c, con
       for (int r = N + lane; r < NP; r += 64) vv[TSH::pad(r)] = 0.0;
       apply_G(RG_EXACT_CMD_X);
     };
-    solved = exact_active_set<NB, Q, PACKED, true, NT>(c, st, mode == RG_QP_AUDIT ? -1 : b, cmask, lane, lane < NB, Tm, svv, rvv, lamc, qv, xv, dv, column_of_G, recompute_x, mu_of, q, cid, its);
+    if constexpr (MU4) solved = exact_active_set<NB, Q, PACKED, true, NT>(c, st, mode == RG_QP_AUDIT ? -1 : b, cmask, lane, lane < NB, Tm, svv, rvv, lamc, qv, xv, dv, column_of_G, recompute_x, WithBody<decltype(mu_of)>{mu_of, rec}, q, cid, its);
+    else solved = exact_active_set<NB, Q, PACKED, true, NT>(c, st, mode == RG_QP_AUDIT ? -1 : b, cmask, lane, lane < NB, Tm, svv, rvv, lamc, qv, xv, dv, column_of_G, recompute_x, mu_of, q, cid, its);
     if constexpr (NT > 64) {   // the helper waves leave their loop; the outcome goes to every wave
       if (lane == 0) { sc[0] = (double)RG_EXACT_CMD_DONE; sc[1] = solved ? 1.0 : 0.0; sc[2] = (double)q; sc[3] = (double)its; }
       __syncthreads();
@@ -634,10 +646,10 @@ __device__ __forceinline__ void qp_exact_wrench_robot(const DevCfg *__restrict__
       if (cc == 0) { p0 = c->w[6] * om[0]; r0 = icp * c->w[0] * rec[REC_ROLL]; r1 = icp * c->w[0] * icp * om[0] + tnp * c->w[2] * yawr; }
       else if (cc == 1) { p0 = c->w[7] * om[1]; r0 = c->w[1] * rec[REC_PITCH]; r1 = c->w[1] * om[1]; }
       else if (cc == 2) { p0 = c->w[8] * (om[2] - cm[2]); r1 = c->w[2] * yawr; }
-      else if (cc < 5) { const double ev = vb[cc - 3] - cm[cc - 3]; p0 = c->w[9 + cc - 3] * ev * c->inv_mass; r1 = c->w[3 + cc - 3] * ev * c->inv_mass; }
+      else if (cc < 5) { const double ev = vb[cc - 3] - cm[cc - 3]; p0 = c->w[9 + cc - 3] * ev * body_val<MU4>(c, rec, BODY_INV_MASS); r1 = c->w[3 + cc - 3] * ev * body_val<MU4>(c, rec, BODY_INV_MASS); }
       else {
-        p0 = c->w[11] * vb[2] * c->inv_mass; p1 = -c->w[11] * c->g * c->inv_mass;
-        r0 = c->w[5] * (rec[REC_COMZ] - c->body_height) * c->inv_mass; r1 = c->w[5] * vb[2] * c->inv_mass; r2 = -0.5 * c->w[5] * c->g * c->inv_mass;
+        p0 = c->w[11] * vb[2] * body_val<MU4>(c, rec, BODY_INV_MASS); p1 = -c->w[11] * c->g * body_val<MU4>(c, rec, BODY_INV_MASS);
+        r0 = c->w[5] * (rec[REC_COMZ] - body_val<MU4>(c, rec, BODY_HEIGHT)) * body_val<MU4>(c, rec, BODY_INV_MASS); r1 = c->w[5] * vb[2] * body_val<MU4>(c, rec, BODY_INV_MASS); r2 = -0.5 * c->w[5] * c->g * body_val<MU4>(c, rec, BODY_INV_MASS);
       }
       double acc = 0.0;
       for (int k = a; k < H; k++) {
@@ -650,7 +662,7 @@ __device__ __forceinline__ void qp_exact_wrench_robot(const DevCfg *__restrict__
     __syncthreads();
     if (tid < 36) {
       const int i = tid / 6, j = tid % 6;
-      const double im2 = c->inv_mass * c->inv_mass;
+      const double im2 = body_val<MU4>(c, rec, BODY_INV_MASS) * body_val<MU4>(c, rec, BODY_INV_MASS);
       double su = 0.0, sv_ = 0.0;
 #pragma unroll
       for (int r = 0; r < 6; r++) {
@@ -739,7 +751,8 @@ __device__ __forceinline__ void qp_exact_wrench_robot(const DevCfg *__restrict__
       o0 = x3[0]; o1 = x3[1]; o2 = x3[2];
     }
   };
-  auto mu_of = [&](const int blk, const int ty) -> double { return row_mu<MU4>(c, MU4 ? nth_leg(cmask, blk & 3) : 0, ty); };   // block = lane 4 k + stance-leg slot
+  auto mu_of = [&](const int blk, const int ty) -> double { if constexpr (MU4) return row_mu<MU4>(c, rec, nth_leg(cmask, blk & 3), ty);
+                                                         else return row_mu<MU4>(c, nullptr, MU4 ? nth_leg(cmask, blk & 3) : 0, ty); };   // block = lane 4 k + stance-leg slot (rec: captured by the MU4 lambda only)
   // d = G c_p -> dv, returns sigma = c_p' G c_p
   auto column_of_G = [&](const ExactCon &p, double *) -> double {
     const int pb = p.i1 / 3;   // the constraint's block = its lane
@@ -777,7 +790,8 @@ __device__ __forceinline__ void qp_exact_wrench_robot(const DevCfg *__restrict__
   __syncthreads();
   int q = 0, cid = -1, its = 1;
   bool solved = false;
-  if (!degenerate) solved = exact_active_set<NB, Q, true, false, 64>(c, st, mode == RG_QP_AUDIT ? -1 : b, cmask, lane, blk_real, Tm, svv, rvv, lamc, x0, xv, dv, column_of_G, recompute_x, mu_of, q, cid, its);
+  if constexpr (MU4) { if (!degenerate) solved = exact_active_set<NB, Q, true, false, 64>(c, st, mode == RG_QP_AUDIT ? -1 : b, cmask, lane, blk_real, Tm, svv, rvv, lamc, x0, xv, dv, column_of_G, recompute_x, WithBody<decltype(mu_of), true>{mu_of, rec}, q, cid, its); }
+  else if (!degenerate) solved = exact_active_set<NB, Q, true, false, 64>(c, st, mode == RG_QP_AUDIT ? -1 : b, cmask, lane, blk_real, Tm, svv, rvv, lamc, x0, xv, dv, column_of_G, recompute_x, mu_of, q, cid, its);
   const int te = wg_lane<NT>();
   if (!exact_epilogue<NC>(c, solved, te, b, cmask, q, cid, its, mode, role)) return;
   if (te < NC) { const int leg = nth_leg(cmask, te); grf[3 * leg] = -xv[3 * te]; grf[3 * leg + 1] = -xv[3 * te + 1]; grf[3 * leg + 2] = -xv[3 * te + 2]; }

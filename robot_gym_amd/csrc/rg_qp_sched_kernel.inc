@@ -414,10 +414,10 @@ __device__ __forceinline__ void qp_sched_robot(const DevCfg *__restrict__ c, con
     if (cc == 0) { p0 = c->w[6] * om[0]; r0 = icp * c->w[0] * rec[REC_ROLL]; r1 = icp * c->w[0] * icp * om[0] + tnp * c->w[2] * yawr; }
     else if (cc == 1) { p0 = c->w[7] * om[1]; r0 = c->w[1] * rec[REC_PITCH]; r1 = c->w[1] * om[1]; }
     else if (cc == 2) { p0 = c->w[8] * (om[2] - cm[2]); r1 = c->w[2] * yawr; }
-    else if (cc < 5) { const double ev = vb[cc - 3] - cm[cc - 3]; p0 = c->w[9 + cc - 3] * ev * c->inv_mass; r1 = c->w[3 + cc - 3] * ev * c->inv_mass; }
+    else if (cc < 5) { const double ev = vb[cc - 3] - cm[cc - 3]; p0 = c->w[9 + cc - 3] * ev * (MU4 ? rec[REC_BODY + BODY_INV_MASS] : c->inv_mass); r1 = c->w[3 + cc - 3] * ev * (MU4 ? rec[REC_BODY + BODY_INV_MASS] : c->inv_mass); }
     else {
-      p0 = c->w[11] * vb[2] * c->inv_mass; p1 = -c->w[11] * c->g * c->inv_mass;
-      r0 = c->w[5] * (rec[REC_COMZ] - c->body_height) * c->inv_mass; r1 = c->w[5] * vb[2] * c->inv_mass; r2 = -0.5 * c->w[5] * c->g * c->inv_mass;
+      p0 = c->w[11] * vb[2] * (MU4 ? rec[REC_BODY + BODY_INV_MASS] : c->inv_mass); p1 = -c->w[11] * c->g * (MU4 ? rec[REC_BODY + BODY_INV_MASS] : c->inv_mass);
+      r0 = c->w[5] * (rec[REC_COMZ] - (MU4 ? rec[REC_BODY + BODY_HEIGHT] : c->body_height)) * (MU4 ? rec[REC_BODY + BODY_INV_MASS] : c->inv_mass); r1 = c->w[5] * vb[2] * (MU4 ? rec[REC_BODY + BODY_INV_MASS] : c->inv_mass); r2 = -0.5 * c->w[5] * c->g * (MU4 ? rec[REC_BODY + BODY_INV_MASS] : c->inv_mass);
     }
     double acc = 0.0;
     for (int k = a; k < H; k++) {
@@ -476,7 +476,8 @@ __device__ __forceinline__ void qp_sched_robot(const DevCfg *__restrict__ c, con
     qh[e] = s;
   }
   const QpKernArgsP ka = reread_kernel_args();
-  double zb[3] = {0.0, 0.0, lane_enabled(tid) ? c->fz_min : 0.0};
+  // (the robot's bounds for the ADMM iteration; the active-set form solves in the config's force units, see below)
+  double zb[3] = {0.0, 0.0, lane_enabled(tid) ? ((MU4 && !AS) ? rec[REC_BODY + BODY_FZ_MIN] : c->fz_min) : 0.0};
   int it = 0;
   // ADMM runs in up to two stages with their own factorisation: rho first, and for the robots that have not converged
   // after admm_switch iterations rho2 (larger).  With a randomised schedule the iteration count is bimodal: nine robots
@@ -502,7 +503,7 @@ __device__ __forceinline__ void qp_sched_robot(const DevCfg *__restrict__ c, con
     const int r = e / NP, ki = e - r * NP;
     if (ki >= NW) { LUr[e] = 0.0; MVr[e] = 0.0; continue; }   // padding read by the tile build (the region is reused below, so every stage clears it)
     const int k = ki / 6, i = ki - 6 * k;
-    const double im = c->inv_mass;
+    const double im = (MU4 ? rec[REC_BODY + BODY_INV_MASS] : c->inv_mass);   // (MU4: plain LDS reads in this set-up -- as SGPR pairs they were kept across the solve)
     const double wu = r == 0 ? c->w[6] : r == 1 ? c->w[7] : r == 2 ? c->w[8] : r == 3 ? c->w[9] : r == 4 ? c->w[10] : c->w[11];
     const double wv = r == 0 ? c->w[0] : r == 1 ? c->w[1] : r == 2 ? c->w[2] : r == 3 ? c->w[3] : r == 4 ? c->w[4] : c->w[5];
     const double sc = r < 3 ? dt : im * dt;
@@ -545,8 +546,8 @@ __device__ __forceinline__ void qp_sched_robot(const DevCfg *__restrict__ c, con
   const int ubase0 = L.ubase0, ubase1 = L.ubase1;
   const bool own_real = L.own_real, quad_real = L.quad_real, enabled = lane_enabled(tid);
   const int lr = tid >> LG, lc = tid & (LC - 1);
-  const double relax = c->relax, lo = c->fz_min, hi = c->fz_max;
-  const double mu = leg_mu<MU4>(c, bj);   // this block lane's leg (block = 4 k + leg): one scalar unless MU4
+  const double relax = c->relax, lo = (MU4 && !AS) ? body_val<MU4>(c, rec, BODY_FZ_MIN) : c->fz_min, hi = (MU4 && !AS) ? body_val<MU4>(c, rec, BODY_FZ_MAX) : c->fz_max;
+  const double mu = leg_mu<MU4>(c, rec, bj);   // this block lane's leg (block = 4 k + leg): one scalar unless MU4
   const double kA = 1.0 / (1.0 + 2.0 * mu * mu), kB = 1.0 / (1.0 + mu * mu);
   // ---- block-lane state: Ch block = L_k^+ C_leg by forward substitution (zero pivots give zero rows) ----
   // Lanes with b0 = 1 hold the rows rotated by three (see qp_wrench_robot).
@@ -719,10 +720,23 @@ __device__ __forceinline__ void qp_sched_robot(const DevCfg *__restrict__ c, con
       }
       __syncthreads();
     };
-    auto mu_of = [&](const int blk, const int ty) -> double { return row_mu<MU4>(c, blk & 3, ty); };
+    auto mu_of = [&](const int blk, const int ty) -> double { return row_mu<MU4>(c, rec, blk & 3, ty); };
     // rows of the packed inverse beyond the LDS part: this workgroup's slab (the audit launch, which may run beside a re-solve launch, has its own range)
     double *gT = (LY::SPILL > 0 && c->as_spill) ? c->as_spill + (size_t)((int)blockIdx.x + (mode == RG_QP_AUDIT ? c->as_spill_audit_base : 0)) * LY::SPILL : nullptr;
-    const bool as_ok = sched_active_set<H, LG>(lds, gT, apply_G, mu_of, tid, enabled, lo, hi, it);
+    bool as_ok;
+    if constexpr (MU4) {
+      // The robot's own mass m_b, solved in the config's force units: with f = k f~, k = m_b / m (config mass), the normal-force
+      // bounds scale * m_b * g become the config's (lo, hi: the config's in the AS instantiations), the friction cone is unchanged,
+      // and the minimiser of 1/2 f'Pf + q'f is k times that of 1/2 f~'Pf~ + (q / k)'f~.  So q (qh, LDS) is scaled by 1 / k before
+      // the solve and the solution (as_x, LDS) by k after it: no per-robot value is live across the active-set loop, which sits
+      // at the register limit of the re-solve kernels.
+      { const double kinv = c->mass * rec[REC_BODY + BODY_INV_MASS]; for (int e = tid; e < NW; e += NT) qh[e] *= kinv; }
+      __syncthreads();
+      as_ok = sched_active_set<H, LG>(lds, gT, apply_G, mu_of, tid, enabled, lo, hi, it);
+      { const double k = 1.0 / (c->mass * rec[REC_BODY + BODY_INV_MASS]); for (int e = tid; e < LY::NV; e += NT) as_x[e] *= k; }
+      __syncthreads();
+    }
+    else as_ok = sched_active_set<H, LG>(lds, gT, apply_G, mu_of, tid, enabled, lo, hi, it);
     const bool failed = !as_ok;
     if (failed && tid == 0 && mode != RG_QP_AUDIT) atomicAdd(&ka->st.counts[7], 1);
     as_failed = failed;

@@ -307,7 +307,7 @@ template <> struct FusedShape<20> { static constexpr int LG = 4, T1 = 4; };   //
 // G_U = U' W U, G_V = V' W V (m3 x m3; their periodic extensions when the tile is built by build_tile_kron6) and the two
 // per-variable coefficient tables of the linear term: q_(a,i) = 2 sum_{k >= a} [ c1(k,i) + (k - a + 1/2) c2(k,i) ].
 // cmask: contact mask whose set bits are the NC stance legs, in order.  Ends with a workgroup barrier.
-template <int NC, int H, int NT, bool KRON6>
+template <int NC, int H, int NT, bool KRON6, bool MU4 = false>
 __device__ __forceinline__ void force_space_tables(const DevCfg *__restrict__ c, const double *rec, const int cmask, const int tid, double *Bw, double *TBw,
                                                    double *GU, double *GV, double *EU, double *EV, double *c1, double *c2) {
   constexpr int m3 = 3 * NC, N = m3 * H;
@@ -330,7 +330,7 @@ __device__ __forceinline__ void force_space_tables(const DevCfg *__restrict__ c,
     int i = e / m3, j = e % m3;
     double gu = c->w[6] * Bw[i] * Bw[j] + c->w[7] * Bw[m3 + i] * Bw[m3 + j] + c->w[8] * Bw[2 * m3 + i] * Bw[2 * m3 + j];
     double gv = c->w[0] * TBw[i] * TBw[j] + c->w[1] * TBw[m3 + i] * TBw[m3 + j] + c->w[2] * TBw[2 * m3 + i] * TBw[2 * m3 + j];
-    if (i % 3 == j % 3) { gu += c->w[9 + i % 3] * c->inv_mass * c->inv_mass; gv += c->w[3 + i % 3] * c->inv_mass * c->inv_mass; }
+    if (i % 3 == j % 3) { gu += c->w[9 + i % 3] * body_val<MU4>(c, rec, BODY_INV_MASS) * body_val<MU4>(c, rec, BODY_INV_MASS); gv += c->w[3 + i % 3] * body_val<MU4>(c, rec, BODY_INV_MASS) * body_val<MU4>(c, rec, BODY_INV_MASS); }
     GU[e] = gu * dt * dt;
     GV[e] = gv * dt * dt * dt * dt;
     if constexpr (KRON6) { put_periodic6(EU, i, j, GU[e]); put_periodic6(EV, i, j, GV[e]); }
@@ -344,13 +344,13 @@ __device__ __forceinline__ void force_space_tables(const DevCfg *__restrict__ c,
     double e_y = kd * (rec[REC_TANP] * om[0] + om[2]) - kd * cm[2];
     double e_x = kd * vb[0] - kd * cm[0];
     double e_yy = kd * vb[1] - kd * cm[1];
-    double e_z = rec[REC_COMZ] + kd * vb[2] - 0.5 * kd * kd * c->g - c->body_height;
+    double e_z = rec[REC_COMZ] + kd * vb[2] - 0.5 * kd * kd * c->g - body_val<MU4>(c, rec, BODY_HEIGHT);
     double e_w0 = om[0], e_w1 = om[1], e_w2 = om[2] - cm[2];
     double e_v0 = vb[0] - cm[0], e_v1 = vb[1] - cm[1], e_v2 = vb[2] - kd * c->g;
     int d = i % 3;
     double ev = (d == 0) ? c->w[9] * e_v0 : (d == 1 ? c->w[10] * e_v1 : c->w[11] * e_v2);
     double ep = (d == 0) ? c->w[3] * e_x : (d == 1 ? c->w[4] * e_yy : c->w[5] * e_z);
-    c1[e] = dt * (Bw[i] * c->w[6] * e_w0 + Bw[m3 + i] * c->w[7] * e_w1 + Bw[2 * m3 + i] * c->w[8] * e_w2 + c->inv_mass * ev);
-    c2[e] = dt * dt * (TBw[i] * c->w[0] * e_r + TBw[m3 + i] * c->w[1] * e_p + TBw[2 * m3 + i] * c->w[2] * e_y + c->inv_mass * ep);
+    c1[e] = dt * (Bw[i] * c->w[6] * e_w0 + Bw[m3 + i] * c->w[7] * e_w1 + Bw[2 * m3 + i] * c->w[8] * e_w2 + body_val<MU4>(c, rec, BODY_INV_MASS) * ev);
+    c2[e] = dt * dt * (TBw[i] * c->w[0] * e_r + TBw[m3 + i] * c->w[1] * e_p + TBw[2 * m3 + i] * c->w[2] * e_y + body_val<MU4>(c, rec, BODY_INV_MASS) * ep);
   }
 }

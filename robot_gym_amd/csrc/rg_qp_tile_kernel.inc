@@ -45,7 +45,8 @@ __device__ __forceinline__ void qp_tile_robot(const DevCfg *__restrict__ c, cons
   double *dyprev = ychk + NP;        // NP (ADMM only): movement of y over the previous vote window
   double *sum3 = dyprev + NP;        // 16 (ADMM only): sum3_publish / _collect slots [0..11], largest extrapolation gain of the stage [12], remaining_distance_factor of the last vote [13]
   double rho = c->rho;   // second ADMM stage: c->rho2 (see the stage loop below)
-  const double relax = c->relax, lo = c->fz_min, hi = c->fz_max;
+  const double relax = c->relax;
+  double lo = c->fz_min, hi = c->fz_max;   // (MU4: the robot's, once its record is in LDS)
   // the one matrix row whose scalar ADMM state this lane owns after the reduce-scatter
   const bool owner = lc < T;
   // T == 8: the reduce-scatter below pairs lanes as (7-i), (i^1), (i^2) -> kept row 4*b2 + 2*b0 + b1; T == 4: 2*b0 + b1
@@ -60,7 +61,8 @@ __device__ __forceinline__ void qp_tile_robot(const DevCfg *__restrict__ c, cons
     if (tid < 24) grf[tid] = 0.0;
     __syncthreads();
     const int cmask = (int)rec[REC_CONTACT];
-    force_space_tables<NC, H, NT, KRON6>(c, rec, cmask, tid, Bw, TBw, GU, GV, EU, EV, c1, c2);
+    if constexpr (MU4) { lo = body_val<MU4>(c, rec, BODY_FZ_MIN); hi = body_val<MU4>(c, rec, BODY_FZ_MAX); }
+    force_space_tables<NC, H, NT, KRON6, MU4>(c, rec, cmask, tid, Bw, TBw, GU, GV, EU, EV, c1, c2);
     __syncthreads();
     // ADMM runs in up to two stages with their own factorisation: robots that have not converged after admm_switch
     // iterations at rho are stragglers with many constraints active in stiff directions; they re-factorise with the larger
@@ -128,7 +130,7 @@ __device__ __forceinline__ void qp_tile_robot(const DevCfg *__restrict__ c, cons
     __syncthreads();
     const int blk = own_real ? io - io % 3 : 0, dax = io % 3;
     // friction coefficient of the leg of this lane's force block (block = step * NC + stance-leg slot) and the projection's constants
-    const double mu = leg_mu<MU4>(c, MU4 ? nth_leg(cmask, (blk / 3) % NC) : 0);
+    const double mu = leg_mu<MU4>(c, rec, MU4 ? nth_leg(cmask, (blk / 3) % NC) : 0);
     const double kA = 1.0 / (1.0 + 2.0 * mu * mu), kB = 1.0 / (1.0 + mu * mu);
     if (owner) vv[iov_pad] = own_real ? rho * (z - y) - qi : 0.0;
     __syncthreads();

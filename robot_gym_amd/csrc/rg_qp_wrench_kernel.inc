@@ -160,7 +160,8 @@ __device__ __forceinline__ void qp_wrench_robot(const DevCfg *__restrict__ c, co
   // first-stage rho of this body: admm_rho x admm_rho34_scale (the wrench-space iteration converges in fewer iterations at a
   // lower rho than the force-space one, at every percentile of the population); second ADMM stage: c->rho2 (stage loop below)
   double rho = c->rho * c->rho34_scale;
-  const double relax = c->relax, lo = c->fz_min, hi = c->fz_max, dt = c->dt;
+  const double relax = c->relax, dt = c->dt;
+  double lo = c->fz_min, hi = c->fz_max;   // (MU4: the robot's, once its record is in LDS)
 
   {
     __syncthreads();
@@ -169,6 +170,7 @@ __device__ __forceinline__ void qp_wrench_robot(const DevCfg *__restrict__ c, co
     if (tid >= NW && tid < NP) vv[TileShape<T>::pad(tid)] = 0.0;   // padding of the mat-vec input: never written again, must not hold NaN bits
     __syncthreads();
     const int cmask = (int)rec[REC_CONTACT];
+    if constexpr (MU4) { lo = body_val<MU4>(c, rec, BODY_FZ_MIN); hi = body_val<MU4>(c, rec, BODY_FZ_MAX); }
     if (tid < m3) {
       const int l = nth_leg(cmask, tid / 3), d = tid % 3;
       const double *rr = &rec[REC_FEETW + 3 * l];
@@ -248,10 +250,10 @@ __device__ __forceinline__ void qp_wrench_robot(const DevCfg *__restrict__ c, co
       if (cc == 0) { p0 = c->w[6] * om[0]; r0 = icp * c->w[0] * rec[REC_ROLL]; r1 = icp * c->w[0] * icp * om[0] + tnp * c->w[2] * yawr; }
       else if (cc == 1) { p0 = c->w[7] * om[1]; r0 = c->w[1] * rec[REC_PITCH]; r1 = c->w[1] * om[1]; }
       else if (cc == 2) { p0 = c->w[8] * (om[2] - cm[2]); r1 = c->w[2] * yawr; }
-      else if (cc < 5) { const double ev = vb[cc - 3] - cm[cc - 3]; p0 = c->w[9 + cc - 3] * ev * c->inv_mass; r1 = c->w[3 + cc - 3] * ev * c->inv_mass; }
+      else if (cc < 5) { const double ev = vb[cc - 3] - cm[cc - 3]; p0 = c->w[9 + cc - 3] * ev * body_val<MU4>(c, rec, BODY_INV_MASS); r1 = c->w[3 + cc - 3] * ev * body_val<MU4>(c, rec, BODY_INV_MASS); }
       else {
-        p0 = c->w[11] * vb[2] * c->inv_mass; p1 = -c->w[11] * c->g * c->inv_mass;
-        r0 = c->w[5] * (rec[REC_COMZ] - c->body_height) * c->inv_mass; r1 = c->w[5] * vb[2] * c->inv_mass; r2 = -0.5 * c->w[5] * c->g * c->inv_mass;
+        p0 = c->w[11] * vb[2] * body_val<MU4>(c, rec, BODY_INV_MASS); p1 = -c->w[11] * c->g * body_val<MU4>(c, rec, BODY_INV_MASS);
+        r0 = c->w[5] * (rec[REC_COMZ] - body_val<MU4>(c, rec, BODY_HEIGHT)) * body_val<MU4>(c, rec, BODY_INV_MASS); r1 = c->w[5] * vb[2] * body_val<MU4>(c, rec, BODY_INV_MASS); r2 = -0.5 * c->w[5] * c->g * body_val<MU4>(c, rec, BODY_INV_MASS);
       }
       double acc = 0.0;
       for (int k = a; k < H; k++) {
@@ -264,7 +266,7 @@ __device__ __forceinline__ void qp_wrench_robot(const DevCfg *__restrict__ c, co
     __syncthreads();
     if (tid < 36) {
       const int i = tid / 6, j = tid % 6;
-      const double im2 = c->inv_mass * c->inv_mass;
+      const double im2 = body_val<MU4>(c, rec, BODY_INV_MASS) * body_val<MU4>(c, rec, BODY_INV_MASS);
       double su = 0.0, sv = 0.0;
 #pragma unroll
       for (int r = 0; r < 6; r++) {
@@ -344,7 +346,7 @@ __device__ __forceinline__ void qp_wrench_robot(const DevCfg *__restrict__ c, co
     }
     const int ubase0 = L.ubase0, ubase1 = L.ubase1;   // u6 rows 0..2 and 3..5 in this lane's order
     // friction coefficient of this block lane's leg and the projection's constants (one scalar set unless MU4)
-    const double mu = leg_mu<MU4>(c, MU4 ? nth_leg(cmask, bj) : 0);
+    const double mu = leg_mu<MU4>(c, rec, MU4 ? nth_leg(cmask, bj) : 0);
     const double kA = 1.0 / (1.0 + 2.0 * mu * mu), kB = 1.0 / (1.0 + mu * mu);
     // (the constant terms qh[rA], qh[rB], qh[io] are re-read from LDS inside the loop: three more LDS reads per
     // iteration cost less than the scratch reloads six more live VGPRs caused)
