@@ -311,31 +311,19 @@ class MPCVecEnv:
             try:
                 rows = body_rows(env_cfgs)
             except ValueError as e:
-                if not self._blocking:
-                    self.close()   # the worker processes (in-process envs stay the caller's)
+                self._release()   # the worker processes (in-process envs stay the caller's)
                 raise ValueError(f"MPCVecEnv: the envs' controller configs differ beyond the per-robot body model ({e}); pass config= "
                                  "to run them all on one config") from None
             if any(not np.all(rows[k] == rows[k][..., :1]) for k in BODY_ROW_FIELDS):
                 self.body_rows = rows
-        # the GPU context is created only now, after the workers were started
-        from robot_gym_amd.core.sharding import shard_bounds
-        devs = list(devices) if devices else [device]
-        if len(devs) > B:
-            raise ValueError(f"{len(devs)} devices for {B} envs")
-        pin = torch.cuda.is_available()
-        # ONE pinned host buffer for the state of every shard (shard s: a contiguous [82, n_s] block) and ONE action slab
-        self._host_buffer = torch.zeros(SLAB_WORDS * B, dtype=torch.float32, pin_memory=pin)
-        self._act_host = torch.zeros(B, 60, dtype=torch.float32, pin_memory=pin)
-        self._shards = []
-        for s, dv in enumerate(devs):
-            lo, hi = shard_bounds(B, s, len(devs))
-            ctl = BatchedMPCController(hi - lo, self.cfg, device=dv, extra_outputs=False)
-            if self.body_rows is not None:   # this shard's slice of the rows
-                ctl.set_body(**{k: v[..., lo:hi] for k, v in self.body_rows.items()})
-            state = PackedState(hi - lo, ctl.device, pin, host_storage=self._host_buffer[SLAB_WORDS * lo:SLAB_WORDS * hi])
-            stream = torch.cuda.Stream(device=ctl.device) if (ctl.device.type == "cuda" and len(devs) > 1) else None
-            self._shards.append(_Shard(lo, hi, ctl, state, stream))
-        self.controllers = [sh.controller for sh in self._shards]
+        # the GPU context is created only now, after the workers were started.  A failure from here on destroys the handles
+        # made so far and shuts the workers down; in-process envs stay the caller's.
+        self.controllers, self._shards = [], []
+        try:
+            self._make_shards(B, list(devices) if devices else [device])
+        except BaseException:
+            self._release()
+            raise
         self._dev, self._state = self.controller.device, self._shards[0].state
         if self._blocking:
             self._groups = []
@@ -347,6 +335,28 @@ class MPCVecEnv:
             self._slots = [sl for g in self._groups for sl in g.slots]
         self.batched_calls = 0
         self._broken = None   # set when a tick failed half-way: the batch is then in no defined state
+
+    def _make_shards(self, B, devs):
+        from robot_gym_amd.core.sharding import shard_bounds
+        if len(devs) > B:
+            raise ValueError(f"{len(devs)} devices for {B} envs")
+        pin = torch.cuda.is_available()
+        # ONE pinned host buffer for the state of every shard (shard s: a contiguous [82, n_s] block) and ONE action slab
+        self._host_buffer = torch.zeros(SLAB_WORDS * B, dtype=torch.float32, pin_memory=pin)
+        self._act_host = torch.zeros(B, 60, dtype=torch.float32, pin_memory=pin)
+        for s, dv in enumerate(devs):
+            lo, hi = shard_bounds(B, s, len(devs))
+            ctl = BatchedMPCController(hi - lo, self.cfg, device=dv, extra_outputs=False)
+            self.controllers.append(ctl)   # closed by _release() if anything below fails
+            if self.body_rows is not None:   # this shard's slice of the rows
+                ctl.set_body(**{k: v[..., lo:hi] for k, v in self.body_rows.items()})
+            state = PackedState(hi - lo, ctl.device, pin, host_storage=self._host_buffer[SLAB_WORDS * lo:SLAB_WORDS * hi])
+            stream = None
+            if ctl.device.type == "cuda" and len(devs) > 1:
+                stream = torch.cuda.Stream(device=ctl.device)
+                # a new stream does not wait for the default stream, which zero-filled dev_slab and ran the create-time uploads
+                stream.wait_stream(torch.cuda.current_stream(ctl.device))
+            self._shards.append(_Shard(lo, hi, ctl, state, stream))
 
     @property
     def controller(self):
@@ -456,8 +466,12 @@ class MPCVecEnv:
             for w in self._workers:   # phase 1 of every slice runs concurrently
                 w.conn.send((_STEP, batch_actions[w.lo:w.lo + w.n] if batch_actions is not None else [actions[i] for i in range(w.lo, w.lo + w.n)]))
             resets = [r for w in self._workers for r in w.receive(_READY)]
-            for sh in self._shards:   # shared slab -> the shards' blocks of the pinned buffer (1.3 MB at B = 4096)
-                sh.state.host_slab.numpy()[:] = self._shared_slab[:, sh.lo:sh.hi]
+            # shared slab -> the shards' blocks of the pinned buffer (1.3 MB at B = 4096): the state and command rows by column,
+            # the clock (rows 0-1: B float64 values back to back, not one per column) through float64 views
+            shared_clock = self._shared_slab[0:2].reshape(-1).view(np.float64)
+            for sh in self._shards:
+                sh.state.host_slab.numpy()[2:] = self._shared_slab[2:, sh.lo:sh.hi]
+                sh.state.host_clock.numpy()[:] = shared_clock[sh.lo:sh.hi]
             self._shared_act[:] = self._controller_call(resets)
             for w in self._workers:   # ... and phase 3
                 w.conn.send((_ACT, None))
@@ -497,6 +511,10 @@ class MPCVecEnv:
             for env in self._envs or []:
                 if hasattr(env, "close"):
                     env.close()
+        self._release()
+
+    def _release(self):
+        """The worker processes, the shared memory and the controller handles: everything this wrapper made itself."""
         for w in self._workers:
             try:
                 w.conn.send((_CLOSE, None))

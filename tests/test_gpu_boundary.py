@@ -205,6 +205,104 @@ def test_vec_env_two_handles_on_one_gpu_match_one_handle():
     assert np.isfinite(rows2[-1]).all() and np.abs(rows2[-1]).max() > 1.0   # real commands, not zeros
 
 
+# route: (worker processes, None = envs in this process; devices, None = one handle).  B = 13 over 2 or 3 shards gives uneven
+# shards, and the worker slices ([0, 4) [4, 8) [8, 13), or [0, 6) [6, 13)) cross the shard boundaries.
+VEC_ENV_ROUTES = {
+    "in_process": (None, None),
+    "in_process_3": (None, [0, 0, 0]),
+    "workers": (3, None),
+    "workers_2": (3, [0, 0]),
+    "workers_3": (2, [0, 0, 0]),
+    "workers_2_body_rows": (3, [0, 0]),
+}
+ROUTE_B, ROUTE_TICKS, ROUTE_SEED = 13, 30, 29
+# env 0, and envs on both sides of every shard boundary (6|7; 4|5, 8|9) and worker boundary (3|4, 7|8; 5|6)
+ROUTE_RESETS = {9: [0, 4, 6, 7, 9, 12], 19: [0, 2, 5, 8, 11]}
+
+
+def _run_vec_env_route(O, route, fleet):
+    """One MPCVecEnv over FakeRobotGymEnvs (observation: [GetTimeSinceReset(), steps applied]), checked tick by tick against
+    B separate oracle controllers, each stepped at the clock its env reported before the tick.  fleet "ghost": one config;
+    "body_rows": alternating ghost / k3lso planner models, no config= (per-robot body rows and offsets).  The configs are made
+    here and handed to the envs, so that worker processes run the lane grid this suite runs with.
+    Returns the action rows and observations of every tick and the worst figures over the run."""
+    import functools
+    from robot_gym_amd.gym.vec_env import MPCVecEnv
+    from robot_gym_amd.core.sharding import shard_bounds
+    from tests.fake_envs import make_fake_env
+    from tests.test_body_rows import RowOracle, k3lso_body, offsets_of
+    workers, devices = VEC_ENV_ROUTES[route]
+    B = ROUTE_B
+    cfg = MPCConfig.for_robot("ghost")
+    cfgs = [cfg if fleet == "ghost" or b % 2 == 0 else k3lso_body(cfg) for b in range(B)]
+    ctors = [functools.partial(make_fake_env, "base", "ghost", ROUTE_SEED, B, b, config=cfgs[b]) for b in range(B)]
+    if workers:
+        venv = MPCVecEnv(blocking=False, constructors=ctors, workers=workers, devices=devices)
+    else:
+        venv = MPCVecEnv([c() for c in ctors], devices=devices)
+    try:
+        assert (venv.body_rows is not None) == (fleet == "body_rows")
+        clean = {k: v for k, v in synthetic.make_states(B, cfg, seed=ROUTE_SEED)[0].items() if k != "_flip"}
+        ob = RowOracle(O, cfgs, np.zeros(B)).ob
+        acts = np.random.default_rng(ROUTE_SEED).uniform(-1, 1, (ROUTE_TICKS, B, 3)).astype(np.float32)
+        ones = np.ones((4, B), dtype=np.int32)
+        clock = venv.reset()[:, 0].copy()          # every env's own GetTimeSinceReset(), read from its observation
+        assert clock.dtype == np.float64 and not clock.any()
+        rows, obs, worst = [], [], {}
+        for k in range(ROUTE_TICKS):
+            if k in ROUTE_RESETS:
+                idx = ROUTE_RESETS[k]
+                clock[idx] = venv.reset(idx)[:, 0]
+                assert not clock[idx].any()
+                ob.reset(idx, 0.0)
+            o, r, d, info = venv.step(acts[k])
+            got = {"action": venv._act_host.numpy().copy()}
+            for name in ("leg_state", "desired_state", "phase"):
+                got[name] = np.concatenate([c.extra[name].cpu().numpy() for c in venv.controllers])
+            coff = (acts[k].T + offsets_of(cfgs)).astype(np.float32)
+            ref = helpers.oracle_step_each(O, ob, clock, helpers.oracle_inputs(O, clean, coff, ones))
+            m = helpers.compare_tick(got, ref)
+            assert m["tau_rel_max"] <= 1e-4 and m["q_abs"] <= 1e-5, (route, k, m)
+            assert m["leg_state_mismatch"] == 0 and m["desired_mismatch"] == 0 and m["phase_bits"] == 0, (route, k, m)
+            for key in ("tau_rel_max", "q_abs"):
+                worst[key] = max(worst.get(key, 0.0), m[key])
+            assert np.all(o[:, 0] > clock)
+            clock = o[:, 0].copy()
+            rows.append(got["action"])
+            obs.append(o)
+        # the resets did what the test needs: at least two different clocks in every shard and every worker slice
+        spans = [shard_bounds(B, s, len(devices or [0])) for s in range(len(devices or [0]))]
+        spans += [(w.lo, w.lo + w.n) for w in venv._workers]
+        assert all(len(set(clock[lo:hi])) >= 2 for lo, hi in spans), (spans, clock)
+    finally:
+        venv.close()
+    return rows, obs, worst
+
+
+@pytest.mark.parametrize("route", list(VEC_ENV_ROUTES))
+def test_vec_env_routes_match_per_env_oracles(oracle_lib, monkeypatch, route):
+    """Every way MPCVecEnv gets envs to the kernels -- envs in this process or in worker processes, one handle or several --
+    against B separate float64 oracle controllers, robot by robot, after two partial resets that leave different clocks in
+    every shard and worker slice.  With worker processes the state of every env travels through one shared slab; its clock
+    rows hold B float64 values back to back, which a copy by column would hand to the wrong shard.  Each route's action rows
+    are also bit-identical to those of the in-process, one-handle route over the same fleet."""
+    from robot_gym_amd.gym import vec_env
+    from robot_gym_amd.controllers.mpc.batched import BatchedMPCController
+
+    class WithExtras(BatchedMPCController):   # leg states and gait phase for the comparison
+        def __init__(self, batch, cfg=None, device=None, extra_outputs=False):
+            super().__init__(batch, cfg, device=device, extra_outputs=True)
+    monkeypatch.setattr(vec_env, "BatchedMPCController", WithExtras)
+    fleet = "body_rows" if route.endswith("_body_rows") else "ghost"
+    rows, obs, worst = _run_vec_env_route(oracle_lib, route, fleet)
+    print(f"route {route}: worst over {ROUTE_B} robots x {ROUTE_TICKS} ticks:", worst)
+    if route != "in_process":
+        rows1, obs1, _ = _run_vec_env_route(oracle_lib, "in_process", fleet)
+        for k in range(ROUTE_TICKS):
+            assert np.array_equal(rows[k], rows1[k]), (route, k, float(np.abs(rows[k] - rows1[k]).max()))
+            assert np.array_equal(obs[k], obs1[k]), (route, k)
+
+
 def test_partial_reset_matches_fresh_controllers(oracle_lib):
     """rg_mpc_reset on a subset == new oracle controllers for that subset (LocomotionController.reset)."""
     from robot_gym_amd.controllers.mpc.batched import BatchedMPCController

@@ -343,6 +343,102 @@ def test_vec_env_worker_processes_match_the_in_process_path(monkeypatch):
     assert par.controller.closed
 
 
+def test_vec_env_worker_processes_feed_every_shard_its_own_clocks(monkeypatch):
+    """blocking=False with devices=[...]: the workers write ONE shared slab, and every shard's handle must get exactly its
+    columns of it.  Rows 0-1 are not per-column -- they hold B float64 clocks back to back -- so a column slice of them hands a
+    shard other robots' clocks.  After two partial resets every shard and every worker slice holds envs at different clocks;
+    each shard's recorded call must equal the single-handle call's columns [lo, hi) bit for bit, t_robot included.  B = 13
+    (odd: the clock of robot 6 straddles the two clock rows) and worker slices that cross the shard boundaries."""
+    import functools
+    import torch
+    from robot_gym_amd.gym import vec_env
+    from tests.fake_envs import make_fake_env
+    monkeypatch.setattr(vec_env, "BatchedMPCController", _RecordingBatchedController)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    cfg = MPCConfig.for_robot("ghost")
+    B = 13
+    ctors = [functools.partial(make_fake_env, "base", "ghost", 3, B, b) for b in range(B)]
+    acts = np.random.default_rng(7).uniform(-1, 1, (8, B, 3)).astype(np.float32)
+    resets = {3: [0, 4, 6, 7, 9, 12], 5: [0, 2, 5, 8, 11]}   # env 0, both sides of every shard and worker boundary
+
+    def run(workers, devices):
+        venv = vec_env.MPCVecEnv(blocking=False, constructors=ctors, workers=workers, config=cfg, devices=devices)
+        controllers = list(venv.controllers)
+        try:
+            venv.reset()
+            for k in range(len(acts)):
+                if k in resets:
+                    venv.reset(resets[k])
+                venv.step(acts[k])
+        finally:
+            venv.close()
+        return controllers
+    for workers, devices in ((3, [None, None]), (2, [None, None, None])):
+        one, = run(workers, None)
+        shards = run(workers, devices)
+        assert [c.batch for c in shards] == [hi - lo for lo, hi in (shard_bounds(B, s, len(devices)) for s in range(len(devices)))]
+        # the single-handle run itself: every env at its own clock at the last tick (FakeSimulation: 10 steps of 1 ms per tick)
+        counters = np.array([20, 70, 20, 70, 40, 20, 40, 40, 20, 40, 70, 20, 40])
+        np.testing.assert_array_equal(one.calls[-1]["t_robot"].numpy(), counters * 0.001)
+        lo = 0
+        for s, ctl in enumerate(shards):
+            hi = lo + ctl.batch
+            assert len(ctl.calls) == len(one.calls) == len(acts)
+            for k, (call, ref) in enumerate(zip(ctl.calls, one.calls)):
+                assert sorted(call) == sorted(ref)
+                for name, v in ref.items():
+                    want = v[lo:hi] if name == "t_robot" else v[:, lo:hi]
+                    assert torch.equal(call[name], want), (devices, s, k, name, call[name].numpy(), want.numpy())
+            lo = hi
+
+
+def test_vec_env_cleans_up_when_a_shard_fails_to_build(monkeypatch):
+    """The second shard's controller raises in the constructor: the handle already made is closed, the worker processes have
+    exited and the shared memory is gone; in-process envs stay open (they are the caller's, as on the body-rows refusal)."""
+    import functools
+    import torch
+    from multiprocessing import shared_memory
+    from robot_gym_amd.gym import vec_env
+    from robot_gym_amd.controllers.mpc.slot_controller import BatchSlotController
+    from tests.fake_envs import FakeGoEnv, make_fake_env
+    made, workers = [], []
+
+    class FailsSecond(_RecordingBatchedController):
+        def __init__(self, *args, **kw):
+            if len(made) == 1:
+                raise RuntimeError("second handle refused")
+            super().__init__(*args, **kw)
+            made.append(self)
+
+    class Worker(vec_env._Worker):
+        def __init__(self, ctx, constructors, lo, batch, shm_state, shm_act, *rest):
+            super().__init__(ctx, constructors, lo, batch, shm_state, shm_act, *rest)
+            self.shm_names = (shm_state, shm_act)
+            workers.append(self)
+    monkeypatch.setattr(vec_env, "BatchedMPCController", FailsSecond)
+    monkeypatch.setattr(vec_env, "_Worker", Worker)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    cfg = MPCConfig.for_robot("ghost")
+    B = 5
+    ctors = [functools.partial(make_fake_env, "go", "ghost", 3, B, b) for b in range(B)]
+    with pytest.raises(RuntimeError, match="second handle refused"):
+        vec_env.MPCVecEnv(blocking=False, constructors=ctors, workers=2, config=cfg, devices=[None, None])
+    assert len(made) == 1 and made[0].closed
+    assert len(workers) == 2
+    for w in workers:
+        assert not w.process.is_alive() and w.process.exitcode is not None
+    for name in workers[0].shm_names:
+        with pytest.raises(FileNotFoundError):
+            shared_memory.SharedMemory(name=name)
+    made.clear()
+    state, _, _ = synthetic.make_states(B, cfg, seed=3)
+    envs = [FakeGoEnv(cfg, state, b, BatchSlotController) for b in range(B)]
+    with pytest.raises(RuntimeError, match="second handle refused"):
+        vec_env.MPCVecEnv(envs, config=cfg, devices=[None, None, None])
+    assert len(made) == 1 and made[0].closed
+    assert not any(e.closed for e in envs)
+
+
 def test_vec_env_refuses_a_non_repeatable_step_before_anything_is_applied(monkeypatch):
     """An env without pre_step / post_step is stepped twice per tick (capture + replay).  If its pre-controller code derives a
     different command on the second pass, the slot controller refuses INSIDE get_action -- before ApplyStepAction -- the wrapper
