@@ -260,6 +260,58 @@ int rg_mpc_set_gait(rg_mpc_handle *h, const double *stance_duration, const doubl
 int rg_mpc_set_body(rg_mpc_handle *h, const int32_t *idx_host, int32_t n, const double *mass, const double *inertia,
                     const double *body_height, const double *mu, const double *hip, void *stream);
 
+/* State rows: save, restore and clone per-robot controller state.
+ * A state row is one robot's persistent controller state in a fixed number of bytes (rg_mpc_state_layout), as 32-bit words:
+ *   header   magic "RGST", layout version, 64-bit layout hash (over the field list, window, horizon, RG_WARM_N and RG_WS_MAX),
+ *            the robot the row was saved from and the handle's step count at the save (both for information only), 2 reserved;
+ *   fields   reset_time, flags, last_desired, the velocity window (ring [3][window], ring_len, ring_head, fsum, fcorr), the
+ *            latched swing start, swing_q / swing_valid, the set_command copy (cmd), the warm start (warm_key, warm_z, warm_y,
+ *            ws_cnt, ws_ids), the direct-routing mark (hard), and the previous tick's stance-leg count and solver iterations
+ *            (ncs, iters: the front kernel predicts the robot's cost class and the exact body's size from them).
+ * Not in the row: what every tick rebuilds (front->QP record, swing IK inputs, work lists), the handle's counters (step count,
+ * audit ring and statistics, direct-launch hint), and the per-robot gait and body rows of rg_mpc_set_gait / rg_mpc_set_body:
+ * those are configuration and stay with the robot slot, so set them equal on both sides when a row moves.
+ * Results after a restore are BIT-IDENTICAL to the robot's uninterrupted run when the destination handle has the same config,
+ * gait and body rows, lane grid and batch plan, and (direct routing of persistently hard robots, horizon 10: every 16th tick a
+ * marked robot tries ADMM again, at (step count ^ robot index) % 16 == 0) its step count and the robot's index agree with the
+ * source's modulo 16.  Otherwise a restored robot that the exact solver had taken over may rejoin ADMM at another tick (a
+ * result within admm_tol of the exact one).  A row saved from a robot that was reset at a non-finite clock is refused. */
+
+/* Row size and layout of `cfg` (only window and horizon matter).  desc: one line, "rg_mpc_state v1 window=.. horizon=..
+ * warm_n=.. ws_max=.. header_bytes=.. row_bytes=.. fields=name:type:count:c|r@byte_offset,..." (c: component-major device
+ * array [count][B], r: robot-major [B][count]), valid until this thread's next call.  No handle, no GPU; refusal text in
+ * rg_mpc_last_error(NULL). */
+int rg_mpc_state_layout(const rg_mpc_config *cfg, int64_t *row_bytes, const char **desc);
+
+/* The validator of rg_mpc_load_state on n HOST rows (rows_bytes must be n * row_bytes), without a handle or a GPU:
+ * header (magic, version, layout hash), ranges (ring_len in [0, window], ring_head in [0, window), ws_cnt in [0, RG_WS_MAX],
+ * every ws_ids entry below the exact bodies' constraint count (240), warm_key in [-1, 15], hard in [0, 16], ncs in [0, 4],
+ * iters in [0, 2^24]), bit masks (flags 2 bits, last_desired 4, swing_valid 12) and finite values where the step computes with
+ * them (reset_time, fsum, fcorr, latched, swing_q where swing_valid is set, the ring_len samples of the window, warm_z / warm_y
+ * while warm_key names a contact set).  dst_idx_host (may be NULL): destination robots, in [0, batch) and not repeated.
+ * Every row rg_mpc_save_state writes passes; no row that passes can make a kernel address outside its arrays.
+ * RG_MPC_ERR_INVALID naming the first bad row, its robot and the field: rg_mpc_last_error(NULL). */
+int rg_mpc_state_check(const rg_mpc_config *cfg, const void *rows_host, int32_t n, int64_t rows_bytes, const int32_t *dst_idx_host,
+                       int32_t batch);
+
+/* Rows of the robots idx_host[0..n) (HOST; NULL: robots 0..n-1, n == batch; repeats allowed) into rows_host (HOST, n * row_bytes),
+ * in that order: gathered on the device on `stream` (behind the ticks already enqueued), copied to the host; the call waits. */
+int rg_mpc_save_state(rg_mpc_handle *h, const int32_t *idx_host, int32_t n, void *rows_host, void *stream);
+
+/* Writes n HOST rows into the robots idx_host[0..n) (NULL: 0..n-1, n == batch).  Every row and index is validated first
+ * (rg_mpc_state_check); a refused call names the first bad robot and field and leaves the handle untouched -- nothing reaches
+ * the device.  clock_shift_host (may be NULL, finite): reset_time of row k is increased by clock_shift_host[k], for a resume
+ * on a clock that runs shifted by that amount.  Uploads and scatters on `stream`, then waits.  Takes effect from the next step. */
+int rg_mpc_load_state(rg_mpc_handle *h, const int32_t *idx_host, int32_t n, const void *rows_host, const double *clock_shift_host,
+                      void *stream);
+
+/* Robot src_idx_host[k]'s state into robot dst_idx_host[k] for k < n (HOST lists; destinations in range and not repeated,
+ * sources may repeat), on the device only and asynchronously on `stream`: all sources are gathered into the staging rows
+ * before any destination is written, so permutations and overlapping sets behave as if every source was read first.
+ * Like every call of a handle, the state calls belong on the handle's one stream (they are ordered with its ticks there).  The
+ * staging rows they share are ordered across streams as well: a state call waits for the last copy before it touches them. */
+int rg_mpc_copy_state(rg_mpc_handle *h, const int32_t *src_idx_host, const int32_t *dst_idx_host, int32_t n, void *stream);
+
 /* MPCController.get_action (mpc_controller.py:102-106) for all B robots at clock value t. */
 int rg_mpc_step(rg_mpc_handle *h, double t, const rg_mpc_state_ptrs *in, const rg_mpc_out_ptrs *out, void *stream);
 

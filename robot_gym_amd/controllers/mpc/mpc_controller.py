@@ -104,6 +104,19 @@ class MPCController(Controller):
     def reset(self):
         self._batched.reset(None, t0=self.get_time_since_reset())
 
+    def save_state(self):
+        """This robot's controller state (a one-row ControllerState; include/rg_mpc.h "State rows") -- what copy.deepcopy of
+        the reference's controller would keep, to pair with PyBullet's saveState."""
+        return self._batched.save_state()
+
+    def load_state(self, state, clock_shift=None):
+        """Restore a one-row ControllerState -- saved from this controller, or robot k of a batched controller
+        (`state.select([k])`) -- e.g. after PyBullet's restoreState.  clock_shift: added to the saved reset time when this
+        controller's clock (get_time_since_reset) runs shifted against the one the state was saved under."""
+        if len(state) != 1:
+            raise ValueError(f"MPCController.load_state: one row expected, got {len(state)}")
+        self._batched.load_state(state, idx=[0], clock_shift=clock_shift)
+
     @staticmethod
     def get_standing_action():
         return 0., 0.

@@ -52,7 +52,7 @@ class COutPtrs(C.Structure):
     _fields_ = [(n, fp) for n in ("action", "grf", "tau_stance", "leg_state", "desired_state", "phase", "foot_target", "v_body")]
 
 
-EXPORTS = ("rg_mpc_create", "rg_mpc_reset", "rg_mpc_reset_at", "rg_mpc_set_command", "rg_mpc_set_gait", "rg_mpc_set_body", "rg_mpc_step", "rg_mpc_step_host", "rg_mpc_hybrid_to_torque",
+EXPORTS = ("rg_mpc_create", "rg_mpc_reset", "rg_mpc_reset_at", "rg_mpc_set_command", "rg_mpc_set_gait", "rg_mpc_set_body", "rg_mpc_state_layout", "rg_mpc_state_check", "rg_mpc_save_state", "rg_mpc_load_state", "rg_mpc_copy_state", "rg_mpc_step", "rg_mpc_step_host", "rg_mpc_hybrid_to_torque",
            "rg_mpc_hybrid_to_torque_substeps",
            "rg_mpc_last_bin_counts", "rg_mpc_last_solver_stats", "rg_mpc_last_iterations", "rg_mpc_audit_stats", "rg_mpc_last_direct_count", "rg_mpc_profile_begin", "rg_mpc_profile_stride", "rg_mpc_profile_end", "rg_mpc_kernel_names", "rg_mpc_plan_description", "rg_mpc_profile_window_names", "rg_mpc_debug_poison_lds", "rg_mpc_destroy", "rg_mpc_last_error",
            "rg_mpc_abi_version", "rg_mpc_config_size")
@@ -90,6 +90,16 @@ def load_library(path=None):
     L.rg_mpc_set_gait.restype = i32
     L.rg_mpc_set_body.argtypes = [fp, C.POINTER(i32), i32, fp, fp, fp, fp, fp, fp]
     L.rg_mpc_set_body.restype = i32
+    L.rg_mpc_state_layout.argtypes = [C.POINTER(CConfig), C.POINTER(C.c_int64), C.POINTER(C.c_char_p)]
+    L.rg_mpc_state_layout.restype = i32
+    L.rg_mpc_state_check.argtypes = [C.POINTER(CConfig), fp, i32, C.c_int64, C.POINTER(i32), i32]
+    L.rg_mpc_state_check.restype = i32
+    L.rg_mpc_save_state.argtypes = [fp, C.POINTER(i32), i32, fp, fp]
+    L.rg_mpc_save_state.restype = i32
+    L.rg_mpc_load_state.argtypes = [fp, C.POINTER(i32), i32, fp, C.POINTER(d), fp]
+    L.rg_mpc_load_state.restype = i32
+    L.rg_mpc_copy_state.argtypes = [fp, C.POINTER(i32), C.POINTER(i32), i32, fp]
+    L.rg_mpc_copy_state.restype = i32
     L.rg_mpc_last_bin_counts.argtypes = [fp, C.POINTER(i32 * 5), fp]
     L.rg_mpc_last_bin_counts.restype = i32
     L.rg_mpc_last_solver_stats.argtypes = [fp, C.POINTER(C.c_int64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), fp]
@@ -127,6 +137,44 @@ def load_library(path=None):
     if path is None:
         _lib = L
     return L
+
+
+def _i32_array(idx):
+    """An index list as a ctypes int32 array (None stays None)."""
+    if idx is None:
+        return None
+    import numpy as np
+    a = np.asarray(idx).reshape(-1)
+    if a.size and a.dtype.kind not in "iu":
+        if not np.all(np.equal(np.mod(a.astype(np.float64), 1), 0)):
+            raise ValueError("index lists must hold integers")
+    a = a.astype(np.int64) if a.dtype.kind != "u" else a
+    if a.size and (a.min() < -(1 << 31) or a.max() >= (1 << 31)):
+        raise ValueError(f"index {int(a.max()) if a.max() >= (1 << 31) else int(a.min())} outside the int32 range of the C-ABI")
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    return (i32 * len(a)).from_buffer_copy(a.tobytes()) if len(a) else (i32 * 0)()
+
+
+def state_layout(cfg):
+    """rg_mpc_state_layout: (row_bytes, description line) of the state rows of `cfg` (no handle, no GPU)."""
+    lib = load_library()
+    nb, desc = C.c_int64(), C.c_char_p()
+    rc = lib.rg_mpc_state_layout(C.byref(make_cconfig(cfg)), C.byref(nb), C.byref(desc))
+    if rc != 0:
+        raise RgMpcError(rc, lib.rg_mpc_last_error(None).decode())
+    return nb.value, desc.value.decode()
+
+
+def state_check(cfg, rows, dst=None, batch=0):
+    """rg_mpc_state_check on host rows (a numpy buffer of n rows): raises RgMpcError naming the first bad row, robot and field."""
+    import numpy as np
+    lib = load_library()
+    rows = np.ascontiguousarray(rows)
+    n = rows.shape[0] if rows.ndim > 1 else (0 if rows.size == 0 else 1)
+    rc = lib.rg_mpc_state_check(C.byref(make_cconfig(cfg)), rows.ctypes.data if rows.size else None, int(n), int(rows.nbytes),
+                                _i32_array(dst), int(batch))
+    if rc != 0:
+        raise RgMpcError(rc, lib.rg_mpc_last_error(None).decode())
 
 
 def make_cconfig(cfg):
@@ -207,6 +255,21 @@ class MpcHandle:
             return a.ctypes.data
         ia = None if idx is None else (i32 * len(idx))(*[int(i) for i in idx])
         self._check(self._lib.rg_mpc_set_body(self._h, ia, int(n), ptr(mass), ptr(inertia), ptr(body_height), ptr(mu), ptr(hip), stream))
+
+    def save_state(self, idx, n, rows_ptr, stream=None):
+        """rg_mpc_save_state: n rows (idx None: every robot) into host memory at rows_ptr; waits."""
+        self._check(self._lib.rg_mpc_save_state(self._h, _i32_array(idx), int(n), rows_ptr, stream))
+
+    def load_state(self, idx, n, rows_ptr, clock_shift=None, stream=None):
+        """rg_mpc_load_state: n host rows at rows_ptr into the robots idx (None: every robot); validated first; waits."""
+        cs = None if clock_shift is None else (d * n)(*[float(x) for x in clock_shift])
+        self._check(self._lib.rg_mpc_load_state(self._h, _i32_array(idx), int(n), rows_ptr, cs, stream))
+
+    def copy_state(self, src, dst, stream=None):
+        """rg_mpc_copy_state: robot src[k]'s state into robot dst[k], on the device, asynchronously on `stream`."""
+        if len(src) != len(dst):
+            raise ValueError("copy_state: src and dst must have the same length")
+        self._check(self._lib.rg_mpc_copy_state(self._h, _i32_array(src), _i32_array(dst), len(src), stream))
 
     def hybrid_to_torque(self, action_ptr, q_ptr, qd_ptr, tau_ptr, stream=None, substeps=None):
         if substeps is None:

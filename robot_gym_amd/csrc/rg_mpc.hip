@@ -27,6 +27,7 @@
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
+#include <cmath>
 #include <initializer_list>
 #include <map>
 #include <mutex>
@@ -45,6 +46,13 @@
 #include "rg_qp_exact_kernel.inc"
 #include "rg_qp_sched_kernel.inc"
 #include "rg_qp_fused_kernel.inc"
+// state rows (rg_mpc_save_state / load / copy): layout, validator and the launchers of their kernels (rg_mpc_state.hip)
+#include "rg_mpc_state.h"
+#if 0   // never compiled here: rg_mpc_state.hip is a translation unit of its own (Makefile).  Named so that the source hash
+        // that ties committed evidence to the library (bench.compiled_sources follows the includes of this file) covers it.
+#include "rg_mpc_state.hip"
+#endif
+static_assert(RG_WS_MAX == RG_STATE_WS_MAX, "the state row carries the whole working-set store");
 
 // ------------------------------------------------------------------------------------
 // small kernels
@@ -129,6 +137,13 @@ struct rg_mpc_handle {
   hipEvent_t front_done = nullptr, direct_done = nullptr;
   int *hint_host = nullptr;         // pinned: exact solves of a recent tick, written by the end-of-tick launch
   long long direct_launches = 0;    // ticks whose direct lists had their own concurrent launch
+  // state rows (rg_mpc_save_state / rg_mpc_load_state / rg_mpc_copy_state), allocated on first use
+  RgStateLayout state_layout;
+  uint32_t *state_rows = nullptr;   // [B][row words] device staging
+  int *state_idx_dev = nullptr;     // [2][B] copy_state: source and destination indices
+  int *state_idx_host = nullptr;    // pinned [2][B]: their upload source, reused once state_idx_done has passed
+  hipEvent_t state_idx_done = nullptr;
+  hipEvent_t state_rows_done = nullptr;   // recorded after each copy's scatter: a later state call on another stream waits for it
 };
 
 // Every entry point runs on the handle's device and leaves the calling thread's current device as it found it: a process that
@@ -364,6 +379,7 @@ int rg_mpc_create(const rg_mpc_config *cfg, int32_t batch, int32_t device, rg_mp
   // for one / two legs, the schedule QP's wrench-space active-set body for the rest); horizon 20 -- the 256-lane wrench-space one
   h->retry_max_nc = h->auto_retry ? 4 : 0;
   int rc = build_devcfg(cfg, &h->hcfg, h->err);
+  if (!rc && !rg_state_layout_build(cfg->window, cfg->horizon, &h->state_layout, h->err)) rc = RG_MPC_ERR_INVALID;
   h->hcfg.plan = h->fused ? 1 : 0;
   h->hcfg.exact12 = h->exact12 ? (cfg->solver == RG_SOLVER_ACTIVE_SET ? 2 : 1) : 0;
   h->hcfg.body_rec = h->mu4 ? 1 : 0;
@@ -449,6 +465,9 @@ void rg_mpc_destroy(rg_mpc_handle *h) {
     }
     for (void *p : h->allocs) (void)hipFree(p);
     if (h->hint_host) (void)hipHostFree(h->hint_host);
+    if (h->state_idx_host) { if (h->state_idx_done) (void)hipEventSynchronize(h->state_idx_done); (void)hipHostFree(h->state_idx_host); }
+    if (h->state_idx_done) (void)hipEventDestroy(h->state_idx_done);
+    if (h->state_rows_done) { (void)hipEventSynchronize(h->state_rows_done); (void)hipEventDestroy(h->state_rows_done); }
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
   }
   delete h;
@@ -613,6 +632,145 @@ int rg_mpc_set_body(rg_mpc_handle *h, const int32_t *idx_host, int32_t n, const 
   HIPCHK(h, hipStreamSynchronize(s));
   h->body_on = true;
   describe_plan(h);
+  return RG_MPC_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// state rows: one robot's persistent controller state, read out, written back, copied between robots (rg_mpc_state.h)
+// ------------------------------------------------------------------------------------
+static thread_local RgStateLayout g_state_layout;   // rg_mpc_state_layout's description lives here until the thread's next call
+
+int rg_mpc_state_layout(const rg_mpc_config *cfg, int64_t *row_bytes, const char **desc) {
+  if (!cfg) { g_create_err = "state_layout: null config"; return RG_MPC_ERR_INVALID; }
+  if (!rg_state_layout_build(cfg->window, cfg->horizon, &g_state_layout, g_create_err)) return RG_MPC_ERR_INVALID;
+  if (row_bytes) *row_bytes = 4 * (int64_t)g_state_layout.row_words;
+  if (desc) *desc = g_state_layout.desc.c_str();
+  return RG_MPC_OK;
+}
+
+int rg_mpc_state_check(const rg_mpc_config *cfg, const void *rows_host, int32_t n, int64_t rows_bytes, const int32_t *dst_idx_host, int32_t batch) {
+  RgStateLayout L;
+  if (!cfg) { g_create_err = "state_check: null config"; return RG_MPC_ERR_INVALID; }
+  if (!rg_state_layout_build(cfg->window, cfg->horizon, &L, g_create_err)) return RG_MPC_ERR_INVALID;
+  if (n < 0 || rows_bytes != (int64_t)n * 4 * L.row_words) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "state_check: %lld bytes for %d rows of %d bytes (truncated or padded buffer)", (long long)rows_bytes, n, 4 * L.row_words);
+    g_create_err = msg;
+    return RG_MPC_ERR_INVALID;
+  }
+  if (dst_idx_host && batch < 1) { g_create_err = "state_check: batch < 1 with destination indices"; return RG_MPC_ERR_INVALID; }
+  return rg_state_validate(L, rows_host, n, dst_idx_host, batch, g_create_err) ? RG_MPC_OK : RG_MPC_ERR_INVALID;
+}
+
+// The staging rows (and the copy's device index lists) are shared by the handle's state calls.  save / load wait for their own
+// stream before they return; a copy does not, so the next state call -- on whatever stream -- waits for the last copy first.
+static int state_staging(rg_mpc_handle *h, hipStream_t s) {
+  if (!h->state_rows) {
+    if (int r = dev_alloc(h, &h->state_rows, (size_t)h->B * h->state_layout.row_words)) return r;
+    HIPCHK(h, hipEventCreateWithFlags(&h->state_rows_done, hipEventDisableTiming));
+    HIPCHK(h, hipEventRecord(h->state_rows_done, s));
+  }
+  HIPCHK(h, hipStreamWaitEvent(s, h->state_rows_done, 0));
+  return RG_MPC_OK;
+}
+
+// n robots idx_host[0..n) (null: 0..n-1, n == batch) in range; what: the call's name
+static int state_indices(rg_mpc_handle *h, const int32_t *idx_host, int32_t n, const char *what) {
+  char msg[160];
+  if (idx_host ? (n < 0 || n > h->B) : n != h->B) {
+    snprintf(msg, sizeof(msg), "%s: n must be the batch without an index list, 0..batch with one", what);
+    h->err = msg;
+    return RG_MPC_ERR_INVALID;
+  }
+  for (int k = 0; idx_host && k < n; k++)
+    if (idx_host[k] < 0 || idx_host[k] >= h->B) {
+      snprintf(msg, sizeof(msg), "%s: entry %d: robot %d out of range [0, %d)", what, k, idx_host[k], h->B);
+      h->err = msg;
+      return RG_MPC_ERR_INVALID;
+    }
+  return RG_MPC_OK;
+}
+
+int rg_mpc_save_state(rg_mpc_handle *h, const int32_t *idx_host, int32_t n, void *rows_host, void *stream) {
+  if (!h) return RG_MPC_ERR_INVALID;
+  if (!rows_host) { h->err = "save_state: null rows"; return RG_MPC_ERR_INVALID; }
+  if (int r = state_indices(h, idx_host, n, "save_state")) return r;
+  if (n == 0) return RG_MPC_OK;
+  hipStream_t s = (hipStream_t)stream;
+  DeviceScope dev_(h->device); HIPCHK(h, dev_.err);
+  if (int r = state_staging(h, s)) return r;
+  const int *idx = nullptr;
+  if (idx_host) { HIPCHK(h, hipMemcpyAsync(h->idx_dev, idx_host, sizeof(int) * n, hipMemcpyHostToDevice, s)); idx = h->idx_dev; }
+  HIPCHK(h, rg_state_gather(h->state_layout, h->st, h->B, idx, n, h->steps, h->state_rows, s));
+  HIPCHK(h, hipMemcpyAsync(rows_host, h->state_rows, (size_t)n * 4 * h->state_layout.row_words, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  return RG_MPC_OK;
+}
+
+int rg_mpc_load_state(rg_mpc_handle *h, const int32_t *idx_host, int32_t n, const void *rows_host, const double *clock_shift_host, void *stream) {
+  if (!h) return RG_MPC_ERR_INVALID;
+  if (int r = state_indices(h, idx_host, n, "load_state")) return r;
+  if (n == 0) return RG_MPC_OK;
+  // every row and index is checked before anything is copied: a refused call leaves the handle as it was
+  std::vector<int32_t> ident;
+  if (!idx_host) { ident.resize((size_t)n); for (int k = 0; k < n; k++) ident[(size_t)k] = k; }
+  if (!rg_state_validate(h->state_layout, rows_host, n, idx_host ? idx_host : ident.data(), h->B, h->err)) { h->err = "load_state: " + h->err; return RG_MPC_ERR_INVALID; }
+  for (int k = 0; clock_shift_host && k < n; k++)
+    if (!std::isfinite(clock_shift_host[k])) {
+      char msg[128];
+      snprintf(msg, sizeof(msg), "load_state: clock_shift[%d] is not finite", k);
+      h->err = msg;
+      return RG_MPC_ERR_INVALID;
+    }
+  hipStream_t s = (hipStream_t)stream;
+  DeviceScope dev_(h->device); HIPCHK(h, dev_.err);
+  if (int r = state_staging(h, s)) return r;
+  HIPCHK(h, hipMemcpyAsync(h->state_rows, rows_host, (size_t)n * 4 * h->state_layout.row_words, hipMemcpyHostToDevice, s));
+  const int *idx = nullptr;
+  if (idx_host) { HIPCHK(h, hipMemcpyAsync(h->idx_dev, idx_host, sizeof(int) * n, hipMemcpyHostToDevice, s)); idx = h->idx_dev; }
+  const double *shift = nullptr;
+  if (clock_shift_host) { HIPCHK(h, hipMemcpyAsync(h->t0_dev, clock_shift_host, sizeof(double) * n, hipMemcpyHostToDevice, s)); shift = h->t0_dev; }
+  HIPCHK(h, rg_state_scatter(h->state_layout, h->st, h->B, idx, n, h->state_rows, shift, s));
+  HIPCHK(h, hipStreamSynchronize(s));   // the caller's rows and the index / shift staging are free again
+  return RG_MPC_OK;
+}
+
+int rg_mpc_copy_state(rg_mpc_handle *h, const int32_t *src_idx_host, const int32_t *dst_idx_host, int32_t n, void *stream) {
+  if (!h) return RG_MPC_ERR_INVALID;
+  if (!src_idx_host || !dst_idx_host) { h->err = "copy_state: null index list"; return RG_MPC_ERR_INVALID; }
+  if (int r = state_indices(h, src_idx_host, n, "copy_state (source)")) return r;
+  if (int r = state_indices(h, dst_idx_host, n, "copy_state (destination)")) return r;
+  {
+    std::vector<char> seen((size_t)h->B, 0);
+    for (int k = 0; k < n; k++) {
+      if (seen[(size_t)dst_idx_host[k]]) {
+        char msg[128];
+        snprintf(msg, sizeof(msg), "copy_state: entry %d: destination robot %d repeated", k, dst_idx_host[k]);
+        h->err = msg;
+        return RG_MPC_ERR_INVALID;
+      }
+      seen[(size_t)dst_idx_host[k]] = 1;
+    }
+  }
+  if (n == 0) return RG_MPC_OK;
+  hipStream_t s = (hipStream_t)stream;
+  DeviceScope dev_(h->device); HIPCHK(h, dev_.err);
+  if (int r = state_staging(h, s)) return r;
+  if (!h->state_idx_host) {
+    if (int r = dev_alloc(h, &h->state_idx_dev, 2 * (size_t)h->B)) return r;
+    HIPCHK(h, hipHostMalloc((void **)&h->state_idx_host, sizeof(int) * 2 * (size_t)h->B, hipHostMallocDefault));
+    HIPCHK(h, hipEventCreateWithFlags(&h->state_idx_done, hipEventDisableTiming));
+  } else HIPCHK(h, hipEventSynchronize(h->state_idx_done));   // the previous copy's index upload has left the pinned buffer
+  memcpy(h->state_idx_host, src_idx_host, sizeof(int) * n);
+  memcpy(h->state_idx_host + h->B, dst_idx_host, sizeof(int) * n);
+  HIPCHK(h, hipMemcpyAsync(h->state_idx_dev, h->state_idx_host, sizeof(int) * n, hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(h->state_idx_dev + h->B, h->state_idx_host + h->B, sizeof(int) * n, hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipEventRecord(h->state_idx_done, s));
+  // every source row is staged before any destination is written: permutations and overlapping sets behave as if all
+  // sources were read first
+  HIPCHK(h, rg_state_gather(h->state_layout, h->st, h->B, h->state_idx_dev, n, h->steps, h->state_rows, s));
+  HIPCHK(h, rg_state_scatter(h->state_layout, h->st, h->B, h->state_idx_dev + h->B, n, h->state_rows, nullptr, s));
+  HIPCHK(h, hipEventRecord(h->state_rows_done, s));
   return RG_MPC_OK;
 }
 
