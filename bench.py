@@ -9,16 +9,22 @@ states already resident in HBM.
   python bench.py --gpus 2 --dry-launch                 (CPU: the whole multi-rank protocol over gloo with a stub controller)
   python bench.py ... --dump-outputs DIR                (also writes the last timed step's outputs as DIR/<name>.npy: seeded
                                                          inputs, so two builds run with the same arguments compare output for output)
+  python bench.py ... --full                            (also every measurement beyond the headline figure, see below)
 
-Rank 0 prints ONE JSON line.  Extra objects: "roofline" (dominant kernel, hipEvent-timed over
-the timed region, algorithmic bytes from DESIGN.md section 5) and, at N=1, "cpu_baseline" (the float64
-C oracle = a port of the algorithm, OpenMP over robots, on this box's host cores).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line:
+`value` / `ms_per_step` and "roofline" (dominant kernel, hipEvent-timed over the timed region itself, algorithmic bytes
+from DESIGN.md section 5).  `--full` adds the measurements that take passes or processes of their own, reported next to
+`value` and never in it: at N=1 the static-input, cold-start, steady-state, audit-off, sustained and PCIe-inclusive rates
+(config.*; --no-extras drops them), the batch-1 drop-in latency and "cpu_baseline" (the float64 C oracle = a port of
+the algorithm, OpenMP over robots, on this box's host cores; --no-cpu-baseline drops it); under a process group the
+rates with the action all-gather under both schedules and without it.  A plain line keeps those config keys, null, and
+has no "cpu_baseline".
 
 Inputs vary from tick to tick like they do under a live gym (reference gym/robot_gym_env.py:117-129 hands the
 controller a new robot state every tick): a ring of RING pre-generated state slabs resident in HBM (velocity,
 attitude, rates, foot positions perturbed smoothly per tick; measured contacts following the gait), one slab per
 step, outside the timed kernels' critical path.  `--static-inputs` feeds one frozen slab (the round-1 bench); the
-default line reports that variant too (config.static_inputs_steps_per_s).
+--full line reports that variant too (config.static_inputs_steps_per_s).
 """
 import argparse
 import json
@@ -532,7 +538,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=BATCH_PER_GPU, help="robots per GPU")
     ap.add_argument("--total-batch", type=int, default=None, help="robots over ALL ranks, sharded with core.sharding.shard_bounds (shards may differ by one robot); overrides --batch")
-    ap.add_argument("--allgather", action="store_true", help="`value` includes the RCCL all-gather of the action slab inside the timed step (default: further timed passes report it as config.with_allgather_steps_per_s / with_allgather_direct_steps_per_s)")
+    ap.add_argument("--full", action="store_true", help="after the headline figure, also run every side measurement (extra timed passes, the CPU baseline, "
+                    "the all-gather passes under a process group); a plain run reports `value` and what the timed steps recorded")
+    ap.add_argument("--allgather", action="store_true", help="`value` includes the RCCL all-gather of the action slab inside the timed step (default: with --full, further timed passes report it as config.with_allgather_steps_per_s / with_allgather_direct_steps_per_s)")
     ap.add_argument("--allgather-schedule", choices=("ring", "direct"), default="ring", help="schedule of the all-gather that --allgather puts into `value` (core/sharding.py)")
     ap.add_argument("--dry-launch", action="store_true", help="CPU dry run of the multi-rank protocol: gloo, a stub controller, no GPU")
     ap.add_argument("--force-launcher", action="store_true", help="start the ranks through self_launch even for --gpus 1 (tests the launcher on a 1-GPU box)")
@@ -540,7 +548,7 @@ def main():
     ap.add_argument("--chain-geometry", action="store_true", help="synthetic foot positions / Jacobians = forward kinematics of the synthetic joint angles (what kin_mode 1 computes on the device), so that --kin-mode 0 and 1 solve the same QPs")
     ap.add_argument("--robot", default="ghost")
     ap.add_argument("--audit-k", type=int, default=None, help="audit lane picks per tick (0 = off)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--admm-iters", type=int, default=None, help="fixed ADMM iteration count (disables the convergence test)")
     ap.add_argument("--solver", type=int, default=None, help="0 = ADMM only, 1 = exact active set for every robot, 2 = ADMM with the exact re-solve behind it, 3 = hybrid (default): exact for one / two stance legs, ADMM for three / four")
     ap.add_argument("--cold-start", action="store_true", help="start ADMM from scratch every tick (default: warm start from the robot's previous-tick iterate)")
@@ -564,8 +572,8 @@ def main():
     ap.add_argument("--static-inputs", action="store_true", help="feed one frozen state slab every tick (the round-1 bench) instead of the input ring")
     ap.add_argument("--ring", type=int, default=RING, help="state slabs in the input ring")
     ap.add_argument("--jitter", type=float, default=0.1, help="amplitude of the per-tick input variation")
-    ap.add_argument("--no-extras", action="store_true", help="skip the static-input and PCIe-inclusive side measurements")
-    ap.add_argument("--sustain-s", type=float, default=5.0, help="seconds of back-to-back ticks behind config.sustained_steps_per_s (0 = skip; part of the extras)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the single-GPU side measurements (static-input, cold-start, steady-state, audit-off, sustained, PCIe-inclusive, drop-in)")
+    ap.add_argument("--sustain-s", type=float, default=5.0, help="seconds of back-to-back ticks behind config.sustained_steps_per_s (0 = skip; part of the --full extras)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, rank 0 writes what the last one returned as DIR/<name>.npy: "
                     "action [B, 60] float32, and action_allgathered [robots, 60] when the all-gather is inside the timed step (at most 64 MB, a seeded row sample beyond)")
     args = ap.parse_args()
@@ -712,13 +720,13 @@ def main():
         dump_outputs(args.dump_outputs, last_outputs)
     elapsed = max_over_ranks(elapsed)
     # SURVEY.md 8e asks for both rates -- without the all-gather and with it -- and the exchange has two schedules (ring /
-    # direct, core/sharding.py): further timed passes of the same steps, only when there is a process group to gather over
+    # direct, core/sharding.py): further timed passes of the same steps (--full), only when there is a process group to gather over
     ag_elapsed = {}
     plain_elapsed = None if use_ag else elapsed
     ag_note = None
-    if dist is not None:
-        if use_ag:
-            ag_elapsed[args.allgather_schedule] = elapsed
+    if use_ag:
+        ag_elapsed[args.allgather_schedule] = elapsed
+    if dist is not None and args.full:
         if "ring" not in ag_elapsed:
             ctl.close()
             e_, _, _, _, ctl = run(slabs, args.steps, args.warmup, False, allgather="ring")
@@ -735,13 +743,13 @@ def main():
         dist.all_gather(allk, mine)
         per_rank_kms = [[round(float(v), 4) for v in t.tolist()] for t in allk]
 
-    # Side measurements (reported separately, never `value`), single GPU only:
+    # Side measurements (--full; reported separately, never `value`), single GPU only:
     #  - the same steps with ONE frozen input slab (round 1's bench; flatters the cost-class launch order, whose
     #    prediction from the previous tick is then perfect)
     #  - PCIe-inclusive rate: the gym side holds the robot state on the host -- pinned buffers, one upload of all inputs
     #    and one download of the action slab per tick
     pcie_value = static_value = cold_value = steady_value = dropin_us = audit_off_value = sustained = None
-    if world == 1 and dist is None and not args.no_extras and not dry:
+    if args.full and world == 1 and dist is None and not args.no_extras and not dry:
         from robot_gym_amd.controllers.mpc.batched import PackedState
         names_io = ("rpy", "rpy_rate", "v_world", "quat", "q", "foot_pos", "jac", "contact")
         ps = PackedState(B, device)     # what MPCVecEnv uses: one pinned slab -> one H2D copy per tick
@@ -865,7 +873,7 @@ def main():
                        "with_allgather_steps_per_s": (total_units / ag_elapsed["ring"] if "ring" in ag_elapsed else None),
                        "with_allgather_direct_steps_per_s": (total_units / ag_elapsed["direct"] if "direct" in ag_elapsed else None),
                        "allgather_schedule": (args.allgather_schedule if use_ag else None), "allgather_note": ag_note,
-                       "without_allgather_steps_per_s": total_units / plain_elapsed,
+                       "without_allgather_steps_per_s": (total_units / plain_elapsed if plain_elapsed is not None else None),
                        "rccl_ranks": (dist.get_world_size() if dist is not None else 1), "backend": (dist.get_backend() if dist is not None else None),
                        "kernel_ms_per_rank": per_rank_kms, "dry_launch": dry,
                        "audit": audit,
@@ -884,7 +892,7 @@ def main():
                          "robots_per_stance_count": robots,
                          "note": "path is instruction-issue/latency-bound, not HBM-bound (SURVEY.md 7.3-2): see issue_view and DESIGN.md section 5"},
         }
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             try:
                 out["cpu_baseline"] = cpu_baseline(cfg, B, fixed_cmd=fixed_cmd, gait_seed=(0 if args.random_schedule else None),
                                                    schedule=args.random_schedule, ring=ring, amp=args.jitter,
@@ -908,7 +916,7 @@ def main():
                 emit_line()
 
     finished = threading.Event()
-    if dist is not None and "direct" not in ag_elapsed and os.environ.get("RG_BENCH_DIRECT_ALLGATHER", "1") != "0":
+    if args.full and dist is not None and "direct" not in ag_elapsed and os.environ.get("RG_BENCH_DIRECT_ALLGATHER", "1") != "0":
         def watchdog():
             if not finished.wait(float(os.environ.get("RG_BENCH_DIRECT_TIMEOUT_S", "120"))):
                 nonlocal ag_note

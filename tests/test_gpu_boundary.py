@@ -567,14 +567,14 @@ def test_bench_under_torchrun_world_size_1(tmp_path):
 def test_bench_self_launch_one_rank(tmp_path):
     """`python bench.py --gpus N` starts its own ranks when RANK is not set (the driver's form for the scaling runs).  On the
     one GPU of a test box: --force-launcher makes --gpus 1 go through the same launcher -- a fresh torch.distributed.run child,
-    started before the parent has touched the GPU -- and the line reports the RCCL world, per-rank kernel times and both the
-    with- and without-all-gather rates."""
+    started before the parent has touched the GPU -- and the --full line reports the RCCL world, per-rank kernel times and both
+    the with- and without-all-gather rates."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-launcher", "--steps", "3", "--warmup", "1",
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-launcher", "--full", "--steps", "3", "--warmup", "1",
                           "--batch", "512", "--no-cpu-baseline"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -583,6 +583,31 @@ def test_bench_self_launch_one_rank(tmp_path):
     assert c["with_allgather_steps_per_s"] > 0 and c["without_allgather_steps_per_s"] == out["value"]
     assert len(c["kernel_ms_per_rank"]) == 1 and c["kernel_ms_per_rank"][0][1] > 0
     assert c["admm_iterations"]["failures"] == 0 and c["audit"]["audit_over_tol"] == 0
+
+
+def test_bench_plain_run_reports_only_the_timed_pass(tmp_path):
+    """`python bench.py --gpus 1` without --full: set-up, warm-up, the timed steps (with their per-kernel events: the
+    roofline), --dump-outputs and the line -- no side pass and no CPU baseline, whose fields stay null / absent."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "512",
+                          "--dump-outputs", str(tmp_path / "out")], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    c = out["config"]
+    assert out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup"] == 1 and out["value"] > 0 and out["dtype"] == "f64"
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 512) < 1e-6 * 512
+    assert out["roofline"]["kernel"] == "rg_qp_fused_kernel" and out["roofline"]["avg_launch_ms"] > 0
+    assert c["admm_iterations"]["failures"] == 0 and c["rccl_ranks"] == 1 and c["without_allgather_steps_per_s"] == out["value"]
+    assert "cpu_baseline" not in out
+    for k in ("static_inputs_steps_per_s", "cold_start_steps_per_s", "steady_state_steps_per_s", "audit_off_steady_state_steps_per_s",
+              "sustained", "pcie_inclusive_steps_per_s", "dropin_get_action_latency_us", "with_allgather_steps_per_s"):
+        assert c[k] is None, k
+    act = np.load(tmp_path / "out" / "action.npy")
+    assert act.shape == (512, 60) and np.isfinite(act).all()
 
 
 def test_set_gait_validation_and_return_to_config_gait(oracle_lib):

@@ -86,8 +86,8 @@ def test_all_gather_actions_on_a_subgroup_world_size_3_gloo(tmp_path):
 
 def test_bench_launches_its_own_ranks_dry_run_world_size_2(tmp_path):
     """`python bench.py --gpus 2` without RANK in the environment must start its own ranks (the driver's form for the
-    scaling runs): a fresh torch.distributed.run child with two processes.  --dry-launch runs the whole protocol on CPU over
-    gloo with a stub controller: rendezvous on 127.0.0.1, barriers, MAX-over-ranks timing, both all-gather variants, the
+    scaling runs): a fresh torch.distributed.run child with two processes.  --dry-launch --full runs the whole protocol on CPU
+    over gloo with a stub controller: rendezvous on 127.0.0.1, barriers, MAX-over-ranks timing, both all-gather variants, the
     per-rank kernel-time gather and the JSON contract.  --dump-outputs writes the timed pass's last action slab: the stub
     adds one to every entry per call, so it also counts the warm-up and timed steps that ran."""
     import json
@@ -95,7 +95,7 @@ def test_bench_launches_its_own_ranks_dry_run_world_size_2(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-launch", "--batch", "64", "--steps", "3",
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-launch", "--full", "--batch", "64", "--steps", "3",
                           "--warmup", "1", "--ring", "4", "--dump-outputs", str(tmp_path / "out")], cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -115,6 +115,30 @@ def test_bench_launches_its_own_ranks_dry_run_world_size_2(tmp_path):
     assert res.returncode != 0 and "GPU(s)" in res.stderr
 
 
+def test_bench_plain_run_times_only_its_headline_dry_run_world_size_2(tmp_path):
+    """Without --full the ranks run the timed pass and nothing after it: with --allgather the exchange is inside `value` (the
+    ring rate IS `value`), and the passes with the other schedule and without the exchange are not run -- their rates are
+    null.  --dump-outputs still writes the timed pass's last action slab (warm-up + timed steps = 1 + 3 calls of the stub)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-launch", "--allgather", "--batch", "64", "--steps", "3",
+                          "--warmup", "1", "--ring", "4", "--dump-outputs", str(tmp_path / "out")], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    c = out["config"]
+    assert out["n_gpus"] == 2 and out["steps"] == 3 and out["value"] > 0 and c["allgather"] is True and c["allgather_schedule"] == "ring"
+    assert c["with_allgather_steps_per_s"] == out["value"]
+    assert c["with_allgather_direct_steps_per_s"] is None and c["without_allgather_steps_per_s"] is None and c["allgather_note"] is None
+    assert sorted(os.listdir(tmp_path / "out")) == ["action.npy", "action_allgathered.npy"]
+    act, gathered = np.load(tmp_path / "out" / "action.npy"), np.load(tmp_path / "out" / "action_allgathered.npy")
+    assert (act == 1 + 3).all() and gathered.shape == (128, 60) and (gathered == 1 + 3).all()
+
+
 def test_bench_dry_run_world_size_8_uneven_shards():
     """The shape of the driver's scaling run at N = 8 (SCALE record: n_gpus, eight ranks in the process group, both all-gather
     rates -- ring and direct -- next to the rate without, one row of kernel times per rank), on CPU over gloo, and with a batch
@@ -125,7 +149,7 @@ def test_bench_dry_run_world_size_8_uneven_shards():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--dry-launch", "--total-batch", str(8 * 64 + 5), "--steps", "2",
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--dry-launch", "--full", "--total-batch", str(8 * 64 + 5), "--steps", "2",
                           "--warmup", "1", "--ring", "2"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]

@@ -15,11 +15,11 @@ run() {   # key mode args...
   tools/collect_profiles.sh $tag $mode "$@" > gpurun_out/collect_$key.log 2>&1
   echo "$key: $(python3 -c "import json;d=json.loads(open('gpurun_out/bench_$key.json').read());c=d['config'];print(round(d['value']/1e6,3),'M steps/s', round(d['ms_per_step'],4),'ms', d['roofline']['kernel_ms'], 'sustained', c.get('sustained'), 'audit cost %', c.get('audit_cost_pct'), 'dropin', c.get('dropin_get_action_latency_us'), 'cpu', d.get('cpu_baseline',{}).get('value'))")"
 }
-run headline full
-run config2 full --batch 1024 --fixed-cmd
-run b1 full --batch 1
-run h20 full --horizon 20
-run config5 full --horizon 20 --random-schedule
-run b32768 stats --batch 32768
-run kin1 stats --kin-mode 1
-run config2_grid1 stats --batch 1024 --fixed-cmd --lane-grid 1
+run headline full --full
+run config2 full --full --batch 1024 --fixed-cmd
+run b1 full --full --batch 1
+run h20 full --full --horizon 20
+run config5 full --full --horizon 20 --random-schedule
+run b32768 stats --full --batch 32768
+run kin1 stats --full --kin-mode 1
+run config2_grid1 stats --full --batch 1024 --fixed-cmd --lane-grid 1

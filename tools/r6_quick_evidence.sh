@@ -13,9 +13,9 @@ run() {   # key mode args...
   tools/collect_profiles.sh $tag $mode "$@" > gpurun_out/collect_$key.log 2>&1
   echo "$key: $(python3 -c "import json;d=json.loads(open('gpurun_out/bench_$key.json').read());c=d['config'];print(round(d['value']/1e6,3),'M steps/s', round(d['ms_per_step'],4),'ms', d['roofline']['kernel_ms'], 'sustained', c.get('sustained'), 'dropin', c.get('dropin_get_action_latency_us'))")"
 }
-run headline ${1:-stats}
-run config2 stats --batch 1024 --fixed-cmd
-run b1 stats --batch 1
+run headline ${1:-stats} --full
+run config2 stats --full --batch 1024 --fixed-cmd
+run b1 stats --full --batch 1
 { echo "# $HDR; tests/studies/fused_launch_schedule.py (make stamp build)"
   python3 tests/studies/fused_launch_schedule.py 4096 2>&1 | grep -v amdgpu.ids | cut -c1-600; } > gpurun_out/r6_launch_schedule.txt
 tail -3 gpurun_out/r6_gpu_tests.log
