@@ -1,9 +1,10 @@
 """The position-mode controllers on the GPU against golden vectors recorded from the reference classes themselves
 (tests/golden/make_posctl_golden.py): the Bezier trot, the pose IK and the POSITION motor model.
 
-Tolerances: phi and last_time bit-identical every tick (one subtraction and one IEEE division, the branches taken on
-them); alpha and frames within 1e-9 * max(1, |value|) (irregular ticks put the swing phase far above 1, where the
-degree-11 curve puts frames far from the body); angles within 2e-6 rad; torques within one float32 ulp."""
+Tolerances (defined once, in tests/posctl_fixtures.py): phi and last_time bit-identical every tick (one subtraction and
+one IEEE division, the branches taken on them); alpha and frames within 1e-9 * max(1, |value|) (irregular ticks put the
+swing phase far above 1, where the degree-11 curve puts frames far from the body); angles within 2e-6 rad; torques
+within one float32 ulp.  The same operations on configurations other than the default: tests/test_posctl_configs_gpu.py."""
 import os
 import types
 
@@ -11,12 +12,12 @@ import numpy as np
 import pytest
 import torch
 
+from tests.posctl_fixtures import ANG_TOL, REL_TOL, Replay, clean as _clean
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-ANG_TOL = 2e-6
-REL_TOL = 1e-9
 
 
 @pytest.fixture(scope="module")
@@ -35,53 +36,6 @@ def dev():
 def _bezier(batch, dev):
     from robot_gym_amd.controllers.bezier.batched import BatchedBezierController
     return BatchedBezierController(batch, device=dev)
-
-
-class Replay:
-    """Feeds robot b the inputs of golden stream sidx[b] and checks every tick against that stream's recording."""
-
-    def __init__(self, g, sidx, dev):
-        self.g, self.sidx, self.dev = g, np.asarray(sidx), dev
-        si = torch.as_tensor(self.sidx, device=dev)
-        self.params = torch.as_tensor(g["params"], device=dev)[si]          # [B, T, 4]
-        self.clock = torch.as_tensor(g["clock"], device=dev)[si]            # [B, T]
-        self.phi = torch.as_tensor(g["phi"], device=dev)[si]
-        self.last = torch.as_tensor(g["last_time"], device=dev)[si]
-        self.alpha = torch.as_tensor(g["alpha"], device=dev)[si]
-        self.angles = torch.as_tensor(g["angles"], device=dev)[si]          # [B, T, 12]
-        self.frames = torch.as_tensor(g["frames"], device=dev)[si]          # [B, F, 4, 3]
-        self.reset = g["reset"][self.sidx]                                  # host [B, T]
-        self.t0 = g["t0"][self.sidx]
-
-    def tick(self, ctrl, k, clock_shift=0.0):
-        robots = np.nonzero(self.reset[:, k])[0]
-        if robots.size:
-            ctrl.reset(robots, t0=self.t0[robots, k] + clock_shift)
-        ctrl.update_controller_params(self.params[:, k], self.clock[:, k] + clock_shift)
-        return ctrl.get_action()
-
-    def check(self, ctrl, k, angles, bad):
-        st = ctrl.state
-        bad["phi"] += int((st[0] != self.phi[:, k]).sum())
-        bad["last_time"] += int((st[1] != self.last[:, k]).sum())
-        bad["alpha"] += int(((st[2] - self.alpha[:, k]).abs() > REL_TOL * self.alpha[:, k].abs().clamp(min=1)).sum())
-        bad["angles"] += int(((angles - self.angles[:, k]).abs() > ANG_TOL).sum())
-        if (k + 1) % int(self.g["frame_ticks"][0] + 1) == 0:
-            j = (k + 1) // int(self.g["frame_ticks"][0] + 1) - 1
-            want = self.frames[:, j].reshape(-1, 12).t()
-            bad["frames"] += int(((st[3:] - want).abs() > REL_TOL * want.abs().clamp(min=1)).sum())
-
-    def run(self, ctrl, ticks=None, start=0):
-        bad = dict(phi=0, last_time=0, alpha=0, angles=0, frames=0)
-        T = self.g["phi"].shape[1] if ticks is None else ticks
-        for k in range(start, T):
-            a = self.tick(ctrl, k)
-            self.check(ctrl, k, a, bad)
-        return bad
-
-
-def _clean(bad):
-    return all(v == 0 for v in bad.values())
 
 
 def test_golden_streams_one_robot_each(gait, dev):
