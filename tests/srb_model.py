@@ -1,0 +1,342 @@
+"""A float64 model of the batched single-rigid-body simulator of include/rg_srb.h, in plain numpy, vectorised over robots.
+
+It restates robot_gym_amd/csrc/rg_srb.hip (and the leg_fk / leg_ik of rg_mpc_dev.h it reuses) operation for operation:
+every product and sum is formed in the kernel's order, nothing is contracted, and what the library's host code
+precomputes with libm (joint-origin rotations, normalised axes, the inverse inertia, the cosine of the tilt threshold) is
+precomputed here with Python's math module, which is the same libm.  The differences that remain: leg_fk's joint rotations
+come from sincos_joint (rg_mpc_dev.h: a Cody-Waite reduction and fdlibm polynomials in explicit fma(), which no contraction
+pragma touches) where this model calls numpy's sin / cos (< 1 ulp each, reaching the q and jac rows only), and numpy's
+arctan2 / arcsin / sqrt / division stand against the device's.  It is what the GPU kernels are tested against
+(tests/test_srb_gpu.py), the CPU suite holds it to known answers (tests/test_srb_model_cpu.py), and driven by
+oracle.OracleBatch it is the reference closed loop (tests/srb_fixtures.py).
+"""
+import math
+
+import numpy as np
+
+STATE_ROWS = 43
+ROW_P, ROW_QUAT, ROW_V, ROW_W, ROW_FOOT, ROW_Q, ROW_STANCE, ROW_STEPS, ROW_STATUS = 0, 3, 7, 10, 13, 25, 37, 41, 42
+RESET_IK_PASSES = 4
+IK_DONE = 1e-18
+SWING = 0
+OBS_FIELDS = (("rpy", 3, np.float32), ("rpy_rate", 3, np.float32), ("v_world", 3, np.float32), ("quat", 4, np.float32),
+              ("q", 12, np.float32), ("foot_pos", 12, np.float32), ("jac", 36, np.float32), ("contact", 4, np.int32))
+
+
+def _rot_zyx(rpy):
+    cr, sr, cp, sp, cy, sy = math.cos(rpy[0]), math.sin(rpy[0]), math.cos(rpy[1]), math.sin(rpy[1]), math.cos(rpy[2]), math.sin(rpy[2])
+    return [cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr,
+            sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr,
+            -sp, cp * sr, cp * cr]
+
+
+def inverse_inertia(I):
+    """check_inertia of rg_srb.hip on Python floats: the cofactor inverse, in its order."""
+    I = [float(x) for x in I]
+    c00 = I[4] * I[8] - I[5] * I[7]; c01 = I[5] * I[6] - I[3] * I[8]; c02 = I[3] * I[7] - I[4] * I[6]
+    det = I[0] * c00 + I[1] * c01 + I[2] * c02
+    d = 1.0 / det
+    return [c00 * d, (I[2] * I[7] - I[1] * I[8]) * d, (I[1] * I[5] - I[2] * I[4]) * d,
+            c01 * d, (I[0] * I[8] - I[2] * I[6]) * d, (I[2] * I[3] - I[0] * I[5]) * d,
+            c02 * d, (I[1] * I[6] - I[0] * I[7]) * d, (I[0] * I[4] - I[1] * I[3]) * d]
+
+
+def quat_rot(qt):
+    x, y, z, w = qt
+    return [1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+            2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+            2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]
+
+
+def rot(R, v):
+    return [R[0] * v[0] + R[1] * v[1] + R[2] * v[2], R[3] * v[0] + R[4] * v[1] + R[5] * v[2], R[6] * v[0] + R[7] * v[1] + R[8] * v[2]]
+
+
+def rot_t(R, v):
+    return [R[0] * v[0] + R[3] * v[1] + R[6] * v[2], R[1] * v[0] + R[4] * v[1] + R[7] * v[2], R[2] * v[0] + R[5] * v[1] + R[8] * v[2]]
+
+
+def _m3mul(a, b):
+    return [a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j] for i in range(3) for j in range(3)]
+
+
+class Chain:
+    """leg_fk / leg_ik of rg_mpc_dev.h over N (robot, leg) entries at once, on the kinematic fields as rg_srb.hip fills them."""
+
+    def __init__(self, cfg):
+        f = lambda v, n: np.asarray(v, dtype=np.float64).reshape(n)
+        self.jxyz = f(cfg.jxyz, (4, 3, 3))
+        jrpy, jax = f(cfg.jrpy, (4, 3, 3)), f(cfg.jaxis, (4, 3, 3))
+        self.jRf = np.array([[_rot_zyx([float(x) for x in jrpy[l, j]]) for j in range(3)] for l in range(4)])
+        self.jaxis = np.zeros((4, 3, 3))
+        for l in range(4):
+            for j in range(3):
+                a = [float(x) for x in jax[l, j]]
+                nrm = math.sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2])
+                self.jaxis[l, j] = [a[k] / nrm for k in range(3)]
+        self.tip = (f(cfg.toe_xyz, 12) + f(cfg.toe_com, 12)).reshape(4, 3)
+        self.base_com = f(cfg.base_com, 3)
+        self.mdir, self.moff = f(cfg.motor_dir, (4, 3)), f(cfg.motor_off, (4, 3))
+        self.ik_iters, self.damping, self.max_step = int(cfg.ik_iters), float(cfg.ik_damping), float(cfg.ik_max_step)
+
+    def fk(self, leg, q):
+        """leg [N] int, q = 3 arrays [N] -> p (3 arrays), J (9 arrays, d foot_i / d joint_j at 3 i + j)."""
+        N = leg.shape[0]
+        one, zero = np.ones(N), np.zeros(N)
+        R = [one, zero, zero, zero, one, zero, zero, zero, one]
+        o = [zero, zero, zero]
+        axw, org = [], []
+        for j in range(3):
+            t = rot(R, [self.jxyz[leg, j, k] for k in range(3)])
+            o = [o[k] + t[k] for k in range(3)]
+            R = _m3mul(R, [self.jRf[leg, j, k] for k in range(9)])
+            x, y, z = (self.jaxis[leg, j, k] for k in range(3))
+            axw.append(rot(R, [x, y, z]))
+            org.append(list(o))
+            th = q[j] * self.mdir[leg, j] + self.moff[leg, j]
+            s, cs = np.sin(th), np.cos(th)
+            C = 1.0 - cs
+            Rq = [cs + x * x * C, x * y * C - z * s, x * z * C + y * s,
+                  y * x * C + z * s, cs + y * y * C, y * z * C - x * s,
+                  z * x * C - y * s, z * y * C + x * s, cs + z * z * C]
+            R = _m3mul(R, Rq)
+        t = rot(R, [self.tip[leg, k] for k in range(3)])
+        pf = [o[k] + t[k] for k in range(3)]
+        J = [None] * 9
+        for j in range(3):
+            d0, d1, d2 = pf[0] - org[j][0], pf[1] - org[j][1], pf[2] - org[j][2]
+            J[j] = axw[j][1] * d2 - axw[j][2] * d1
+            J[3 + j] = axw[j][2] * d0 - axw[j][0] * d2
+            J[6 + j] = axw[j][0] * d1 - axw[j][1] * d0
+        return [pf[k] - self.base_com[k] for k in range(3)], J
+
+    def ik(self, leg, target, q0):
+        """The damped-Newton IK with its early exit per entry -> q (3 arrays)."""
+        q = [np.array(x, dtype=np.float64, copy=True) for x in q0]
+        active = np.ones(leg.shape[0], dtype=bool)
+        for _ in range(self.ik_iters):
+            if not active.any():
+                break
+            p, J = self.fk(leg, q)
+            J = [J[3 * i + j] * self.mdir[leg, j] for i in range(3) for j in range(3)]
+            e = [target[i] - p[i] for i in range(3)]
+            active = active & ~(e[0] * e[0] + e[1] * e[1] + e[2] * e[2] < IK_DONE)
+            A = [J[3 * i] * J[3 * j] + J[3 * i + 1] * J[3 * j + 1] + J[3 * i + 2] * J[3 * j + 2] + (self.damping if i == j else 0.0)
+                 for i in range(3) for j in range(3)]
+            c00 = A[4] * A[8] - A[5] * A[7]; c01 = A[5] * A[6] - A[3] * A[8]; c02 = A[3] * A[7] - A[4] * A[6]
+            det = A[0] * c00 + A[1] * c01 + A[2] * c02
+            active = active & (det != 0.0)
+            with np.errstate(all="ignore"):
+                inv = 1.0 / det
+                i01 = (A[2] * A[7] - A[1] * A[8]) * inv; i02 = (A[1] * A[5] - A[2] * A[4]) * inv
+                i11 = (A[0] * A[8] - A[2] * A[6]) * inv; i12 = (A[2] * A[3] - A[0] * A[5]) * inv
+                i21 = (A[1] * A[6] - A[0] * A[7]) * inv; i22 = (A[0] * A[4] - A[1] * A[3]) * inv
+                y = [c00 * inv * e[0] + i01 * e[1] + i02 * e[2], c01 * inv * e[0] + i11 * e[1] + i12 * e[2],
+                     c02 * inv * e[0] + i21 * e[1] + i22 * e[2]]
+                for j in range(3):
+                    dq = J[j] * y[0] + J[3 + j] * y[1] + J[6 + j] * y[2]
+                    dq = np.minimum(np.maximum(dq, -self.max_step), self.max_step)
+                    q[j] = np.where(active, q[j] + dq, q[j])
+        return q
+
+
+class SRBModel:
+    """state [43, B] float64 and obs (float32 / int32 component-major arrays + t_robot float64 [B]), as BatchedSRBSim holds them."""
+
+    def __init__(self, batch, cfg, dt_sim=0.001, substeps=10, fall_height_scale=0.5, fall_tilt=1.0, init_q=None):
+        from robot_gym_amd.model.robots.robot_constants import ROBOTS
+        B = self.B = int(batch)
+        self.cfg, self.chain = cfg, Chain(cfg)
+        self.dt, self.S, self.g = float(dt_sim), int(substeps), float(cfg.gravity)
+        self.body_height = float(cfg.body_height)
+        self.fall_z = float(fall_height_scale) * self.body_height
+        self.cos_tilt = math.cos(float(fall_tilt))
+        self.hip = np.asarray(cfg.hip, dtype=np.float64).reshape(4, 3)
+        self.init_q = np.asarray(ROBOTS[cfg.robot].init_motor_angles if init_q is None else init_q, dtype=np.float64).reshape(4, 3)
+        self.state = np.zeros((STATE_ROWS, B))
+        self.state[ROW_STATUS] = 1.0
+        self.obs = {name: np.zeros((comps, B), dtype=dt) for name, comps, dt in OBS_FIELDS}
+        self.obs["t_robot"] = np.zeros(B)
+        self.set_body()
+
+    # -- the true body ------------------------------------------------------------------
+    def set_body(self, idx=None, mass=None, inertia=None):
+        B = self.B
+        if mass is None and inertia is None:
+            self.mass = np.full(B, float(self.cfg.mass))
+            self.I = np.tile(np.asarray(self.cfg.inertia, dtype=np.float64).reshape(9, 1), (1, B))
+            self.Iinv = np.tile(np.asarray(inverse_inertia(self.cfg.inertia)).reshape(9, 1), (1, B))
+            return
+        idx = np.arange(B) if idx is None else np.asarray(idx, dtype=np.int64)
+        if mass is not None:
+            self.mass[idx] = np.asarray(mass, dtype=np.float64)
+        if inertia is not None:
+            inertia = np.asarray(inertia, dtype=np.float64)
+            if inertia.shape == (len(idx), 3, 3):
+                inertia = inertia.reshape(len(idx), 9).T
+            self.I[:, idx] = inertia
+            self.Iinv[:, idx] = np.array([inverse_inertia(inertia[:, k]) for k in range(len(idx))]).T.reshape(9, len(idx))
+
+    # -- step 4: the observation -----------------------------------------------------------
+    def _observe(self, idx, passes, q0=None):
+        """Writes q (state) and the observation of robots idx from their state; q0 [4, 3, n] overrides the stored start point."""
+        st, n = self.state, len(idx)
+        p = [st[ROW_P + i, idx] for i in range(3)]
+        qt = [st[ROW_QUAT + i, idx] for i in range(4)]
+        w = [st[ROW_W + i, idx] for i in range(3)]
+        R = quat_rot(qt)
+        leg = np.repeat(np.arange(4), n)
+        cat = lambda per_leg: np.concatenate(per_leg)
+        fb = [[None] * 3 for _ in range(4)]
+        for l in range(4):
+            d = [st[ROW_FOOT + 3 * l + i, idx] - p[i] for i in range(3)]
+            fb[l] = rot_t(R, d)
+        target = [cat([fb[l][i] for l in range(4)]) for i in range(3)]
+        q = [cat([(st[ROW_Q + 3 * l + i, idx] if q0 is None else q0[l, i]) for l in range(4)]) for i in range(3)]
+        todo = np.ones(4 * n, dtype=bool)
+        J = [np.zeros(4 * n) for _ in range(9)]
+        for _ in range(passes):
+            sel = np.nonzero(todo)[0]
+            if sel.size == 0:
+                break
+            qs = self.chain.ik(leg[sel], [t[sel] for t in target], [x[sel] for x in q])
+            pf, Js = self.chain.fk(leg[sel], qs)
+            for i in range(3):
+                q[i][sel] = qs[i]
+            for i in range(9):
+                J[i][sel] = Js[i]
+            e = [target[i][sel] - pf[i] for i in range(3)]
+            todo[sel] = ~(e[0] * e[0] + e[1] * e[1] + e[2] * e[2] < IK_DONE)
+        o = self.obs
+        for l in range(4):
+            s = slice(l * n, (l + 1) * n)
+            for i in range(3):
+                st[ROW_Q + 3 * l + i, idx] = q[i][s]
+                o["q"][3 * l + i, idx] = q[i][s].astype(np.float32)
+                o["foot_pos"][3 * l + i, idx] = fb[l][i].astype(np.float32)
+            for i in range(9):
+                o["jac"][9 * l + i, idx] = J[i][s].astype(np.float32)
+            o["contact"][l, idx] = st[ROW_STANCE + l, idx].astype(np.int32)
+        wb = rot_t(R, w)
+        sp = np.minimum(np.maximum(R[6], -1.0), 1.0)
+        o["rpy"][0, idx] = np.arctan2(R[7], R[8]).astype(np.float32)
+        o["rpy"][1, idx] = (-np.arcsin(sp)).astype(np.float32)
+        o["rpy"][2, idx] = np.arctan2(R[3], R[0]).astype(np.float32)
+        for i in range(3):
+            o["rpy_rate"][i, idx] = wb[i].astype(np.float32)
+            o["v_world"][i, idx] = st[ROW_V + i, idx].astype(np.float32)
+        for i in range(4):
+            o["quat"][i, idx] = qt[i].astype(np.float32)
+        o["t_robot"][idx] = st[ROW_STEPS, idx] * self.dt
+
+    # -- reset -------------------------------------------------------------------------------
+    def reset(self, idx=None, xy=None, yaw=None, height=None):
+        idx = np.arange(self.B) if idx is None else np.asarray(idx, dtype=np.int64).reshape(-1)
+        n = len(idx)
+        if n == 0:
+            return
+        xy = np.zeros((n, 2)) if xy is None else np.asarray(xy, dtype=np.float64).reshape(n, 2)
+        yaw = np.broadcast_to(np.zeros(n) if yaw is None else np.asarray(yaw, dtype=np.float64), (n,))
+        height = np.broadcast_to(np.full(n, self.body_height) if height is None else np.asarray(height, dtype=np.float64), (n,))
+        x, y = xy[:, 0], xy[:, 1]
+        zero = np.zeros(n)
+        qt = [zero, zero, np.sin(0.5 * yaw), np.cos(0.5 * yaw)]
+        R = quat_rot(qt)
+        st = self.state
+        for l in range(4):
+            h = rot(R, [np.full(n, self.hip[l, k]) for k in range(3)])
+            st[ROW_FOOT + 3 * l, idx], st[ROW_FOOT + 3 * l + 1, idx], st[ROW_FOOT + 3 * l + 2, idx] = h[0] + x, h[1] + y, 0.0
+            st[ROW_STANCE + l, idx] = 1.0
+        st[ROW_P, idx], st[ROW_P + 1, idx], st[ROW_P + 2, idx] = x, y, height
+        for i in range(3):
+            st[ROW_V + i, idx] = 0.0
+            st[ROW_W + i, idx] = 0.0
+        for i in range(4):
+            st[ROW_QUAT + i, idx] = qt[i]
+        st[ROW_STEPS, idx] = 0.0
+        st[ROW_STATUS, idx] = 0.0
+        q0 = np.tile(self.init_q[:, :, None], (1, 1, n))
+        self._observe(idx, RESET_IK_PASSES, q0)
+
+    # -- one control tick ------------------------------------------------------------------------
+    def step(self, grf, foot_target, desired_state, ext=None):
+        """grf [B,12], foot_target [B,12] (float32 values), desired_state [B,4] int, ext [6,B] float64 or None."""
+        B, st, dt = self.B, self.state, self.dt
+        grf = np.asarray(grf).astype(np.float64).reshape(B, 4, 3)
+        ft = np.asarray(foot_target).astype(np.float64).reshape(B, 4, 3)
+        swing = np.asarray(desired_state).reshape(B, 4) == SWING
+        ext = np.zeros((6, B)) if ext is None else np.asarray(ext, dtype=np.float64)
+        running = st[ROW_STATUS] == 0.0
+        p = [st[ROW_P + i].copy() for i in range(3)]
+        qt = [st[ROW_QUAT + i].copy() for i in range(4)]
+        v = [st[ROW_V + i].copy() for i in range(3)]
+        w = [st[ROW_W + i].copy() for i in range(3)]
+        foot = [[st[ROW_FOOT + 3 * l + i].copy() for i in range(3)] for l in range(4)]
+        stance = [st[ROW_STANCE + l].copy() for l in range(4)]
+        mass, I, Iinv = self.mass, list(self.I), list(self.Iinv)
+        R = quat_rot(qt)
+        fbody = []
+        with np.errstate(all="ignore"):
+            # 1. feet
+            for l in range(4):
+                sw = swing[:, l]
+                r = rot(R, [ft[:, l, k] for k in range(3)])
+                land = ~sw & (stance[l] == 0.0)
+                for i in range(3):
+                    foot[l][i] = np.where(sw, p[i] + r[i], foot[l][i])
+                foot[l][2] = np.where(land, 0.0, foot[l][2])
+                stance[l] = np.where(sw, 0.0, 1.0)
+                fbody.append([np.where(sw, 0.0, -grf[:, l, i]) for i in range(3)])
+            wz = mass * -self.g
+            # 2. sub-steps
+            for _ in range(self.S):
+                R = quat_rot(qt)
+                f, tq = [], []
+                for l in range(4):
+                    fl = rot(R, fbody[l])
+                    r = [foot[l][i] - p[i] for i in range(3)]
+                    f.append(fl)
+                    tq.append([r[1] * fl[2] - r[2] * fl[1], r[2] * fl[0] - r[0] * fl[2], r[0] * fl[1] - r[1] * fl[0]])
+                F = [(f[0][i] + f[1][i]) + (f[2][i] + f[3][i]) for i in range(3)]
+                T = [(tq[0][i] + tq[1][i]) + (tq[2][i] + tq[3][i]) for i in range(3)]
+                F = [F[0] + ext[0], F[1] + ext[1], F[2] + wz + ext[2]]
+                T = [T[0] + ext[3], T[1] + ext[4], T[2] + ext[5]]
+                tb, wb = rot_t(R, T), rot_t(R, w)
+                Iw = rot(I, wb)
+                rhs = [tb[0] - (wb[1] * Iw[2] - wb[2] * Iw[1]), tb[1] - (wb[2] * Iw[0] - wb[0] * Iw[2]), tb[2] - (wb[0] * Iw[1] - wb[1] * Iw[0])]
+                aw = rot(R, rot(Iinv, rhs))
+                for i in range(3):
+                    w[i] = w[i] + dt * aw[i]
+                    v[i] = v[i] + dt * F[i] / mass
+                    p[i] = p[i] + dt * v[i]
+                ax, ay, az = 0.5 * dt * w[0], 0.5 * dt * w[1], 0.5 * dt * w[2]
+                dx = ax * qt[3] + ay * qt[2] - az * qt[1]
+                dy = ay * qt[3] + az * qt[0] - ax * qt[2]
+                dz = az * qt[3] + ax * qt[1] - ay * qt[0]
+                dw = -(ax * qt[0]) - ay * qt[1] - az * qt[2]
+                qt = [qt[0] + dx, qt[1] + dy, qt[2] + dz, qt[3] + dw]
+                nrm = np.sqrt(qt[0] * qt[0] + qt[1] * qt[1] + qt[2] * qt[2] + qt[3] * qt[3])
+                qt = [qt[i] / nrm for i in range(4)]
+            # 3. fall
+            finite = np.ones(B, dtype=bool)
+            for a in p + v + w + qt + [foot[l][i] for l in range(4) for i in range(3)]:
+                finite &= np.isfinite(a)
+            fallen = ~finite | (p[2] < self.fall_z) | ((1 - 2 * (qt[0] * qt[0] + qt[1] * qt[1])) < self.cos_tilt)
+        st[ROW_STATUS] = np.where(running, np.where(fallen, 1.0, 0.0), st[ROW_STATUS])
+        store = running & finite
+        idx = np.nonzero(store)[0]
+        for i in range(3):
+            st[ROW_P + i, idx], st[ROW_V + i, idx], st[ROW_W + i, idx] = p[i][idx], v[i][idx], w[i][idx]
+        for i in range(4):
+            st[ROW_QUAT + i, idx] = qt[i][idx]
+        for l in range(4):
+            for i in range(3):
+                st[ROW_FOOT + 3 * l + i, idx] = foot[l][i][idx]
+            st[ROW_STANCE + l, idx] = stance[l][idx]
+        st[ROW_STEPS, idx] = st[ROW_STEPS, idx] + float(self.S)
+        # 4. observation
+        if idx.size:
+            self._observe(idx, 1)
+
+    def fallen(self):
+        return self.state[ROW_STATUS] != 0

@@ -1,0 +1,116 @@
+"""Times the single-rigid-body simulator next to the controller, in one process and run: the controller-only tick (open loop
+on a fixed observation), the simulator tick alone (fixed controller outputs) and the closed-loop tick (controller +
+simulator through rollout), at batch 1, 1024, 4096 and 32768.  hipEvents around at least one second of ticks after a
+warm-up, one synchronisation at the end of each measurement.  For the record, not a gate.
+
+    python tools/srb_bench.py [--robot ghost] [--batches 1,1024,4096,32768] [--seconds 1.0] [--out profiles/srb_tick.json]
+
+Kernel statistics come from a run of their own:  rocprofv3 --kernel-trace --stats -d DIR -- python tools/srb_bench.py --batches 4096
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bench  # noqa: E402
+from robot_gym_amd.controllers.mpc.batched import BatchedMPCController  # noqa: E402
+from robot_gym_amd.core.config import MPCConfig  # noqa: E402
+from robot_gym_amd.sim import BatchedSRBSim, rollout  # noqa: E402
+
+
+CLOCK_ROWS = 500
+
+
+def timed(fn, seconds, probe=20):
+    """us per call of fn() over at least `seconds` of device time: a probe sizes the run, events bracket it, one wait."""
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(probe):
+        fn()
+    torch.cuda.synchronize()
+    start.record()
+    for _ in range(probe):
+        fn()
+    stop.record()
+    torch.cuda.synchronize()
+    per = max(start.elapsed_time(stop) / probe, 1e-3)          # ms
+    n = max(probe, int(np.ceil(1000.0 * seconds / per)))
+    start.record()
+    for _ in range(n):
+        fn()
+    stop.record()
+    torch.cuda.synchronize()
+    return 1000.0 * start.elapsed_time(stop) / n, n
+
+
+def srb_hash():
+    """sha256 (16 hex digits) over the simulator's own sources: bench.source_hash() covers the MPC kernels only."""
+    import hashlib
+    h = hashlib.sha256()
+    for rel in ("robot_gym_amd/csrc/rg_srb.hip", "include/rg_srb.h"):
+        h.update(open(os.path.join(ROOT, rel), "rb").read())
+    return h.hexdigest()[:16]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--robot", default="ghost")
+    ap.add_argument("--batches", default="1,1024,4096,32768")
+    ap.add_argument("--seconds", type=float, default=1.0)
+    ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    cfg = MPCConfig.for_robot(args.robot)
+    commit, dirty = bench.git_head()
+    rows = []
+    for B in [int(x) for x in args.batches.split(",")]:
+        rng = np.random.default_rng(B)
+        ctl, sim = BatchedMPCController(B, cfg, device=dev), BatchedSRBSim(B, cfg, device=dev)
+        cmd = np.stack([rng.uniform(-0.35, 0.35, B), rng.uniform(-0.2, 0.2, B), rng.uniform(-0.4, 0.4, B)], 1).astype(np.float32)
+        sim.reset(height=cfg.body_height * rng.uniform(0.9, 1.1, B))
+        ctl.reset()
+        ctl.update_controller_params(torch.as_tensor(cmd, device=dev))
+        rollout(ctl, sim, None, args.warmup)                    # into the trot: the contact mix of a running batch
+        closed_us, n = timed(lambda: (ctl.get_action(0.0, sim.obs), sim.step(ctl)), args.seconds)
+        fallen = int(sim.fallen().sum())
+        # the simulator alone: the controller's last outputs, held (the robots coast; their state stays finite or they freeze)
+        sim_us, _ = timed(lambda: sim.step(ctl), args.seconds)
+        sim.reset(height=cfg.body_height * rng.uniform(0.9, 1.1, B))
+        ctl.reset()
+        rollout(ctl, sim, None, args.warmup)
+        obs = {k: v.clone() for k, v in sim.obs.items()}
+        # the observation of one moment of the trot, held; the clock goes on from a table built before the timing starts, so
+        # that the timed call is the controller's launches and nothing else.  CLOCK_ROWS ticks are a whole number of gait
+        # cycles (stance_duration / duty_factor = 0.5 s), so the wrap leaves the gait phase continuous.
+        clocks = (obs["t_robot"][None, :] + 0.01 * torch.arange(1, CLOCK_ROWS + 1, device=dev, dtype=torch.float64)[:, None]).contiguous()
+        tick = [0]
+
+        def ctl_only():
+            obs["t_robot"] = clocks[tick[0] % CLOCK_ROWS]
+            tick[0] += 1
+            ctl.get_action(0.0, obs)
+        ctl_us, _ = timed(ctl_only, args.seconds)
+        rows.append(dict(batch=B, ticks=n, sim_us=round(sim_us, 2), ctl_us=round(ctl_us, 2), closed_us=round(closed_us, 2),
+                         closed_robot_steps_per_s=round(B / closed_us * 1e6), fallen_during_timing=fallen))
+        print(json.dumps(rows[-1]), flush=True)
+        ctl.close()
+        sim.close()
+    result = dict(what="single-rigid-body simulator tick next to the controller tick, one process and run", robot=args.robot,
+                  commit=commit, dirty=dirty, source_hash=bench.source_hash(), srb_source_sha256=srb_hash(), device=torch.cuda.get_device_name(0),
+                  seconds_per_measurement=args.seconds, rows=rows)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
