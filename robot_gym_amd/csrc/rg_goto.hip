@@ -1,0 +1,552 @@
+// rg_goto.hip -- the batched go-to-target task of include/rg_goto.h.  Its own translation unit of librg_mpc.so.
+//
+// Layout of the tick kernel: one 64-lane wave per robot, one wave per workgroup, because a robot's work is a scan over its
+// (at most n_max) path points and every branch of the tick is then uniform over the workgroup.  The lanes read x and y in
+// coalesced 64-point chunks; one pass keeps the running (distance, lowest index) to pos and to prev_pos and tests
+// the window, compacting the visible points in path order into LDS with a ballot and a prefix count.  Each lane then holds
+// visible points `lane` and `lane + 64` in registers; the greedy chain is one wave arg-min (an xor butterfly on
+// (distance, index), so every lane ends with the same winner) per link, the chain and its cumulative length go to LDS,
+// lanes 0 .. num_cam_pts-1 each resample one point, and lane 0 stores the scalars.  The reward and termination values
+// are uniform over the wave and computed by every lane.  No global read-modify-write, no scratch.
+// LDS: 5 arrays of RG_GOTO_MAX_VISIBLE doubles = 5120 bytes per workgroup.
+//
+// Parity: tests/goto_model.py restates this file operation for operation in float64 numpy.  Contraction is off.  What
+// remains different: the device's atan2 / sincos / sqrt / division against libm's.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+#include "../../include/rg_goto.h"
+#include "../../include/rg_srb.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kMaxVis = RG_GOTO_MAX_VISIBLE;
+constexpr int kPreBlock = 256;
+constexpr int kStageRows = 5;   // set_path staging [kStageRows][n]: robot, npts, length, target x, target y
+
+struct GotoCfg {
+  int B, n_max, ncp, ncheck, max_visible;
+  double wh, wt, wb, wd;
+  double max_err, inv_max_err, prog_window, prog_limit, radius, penalty, cp_reward, max_steps, brk;
+  double lo[2], hi[2];
+  float off[3];
+};
+
+struct Paths {
+  const double *x, *y, *s;
+  const int *fsx;
+  const double *hdr;
+};
+
+// (d, i) <- the lexicographic minimum over the wave, in every lane
+__device__ __forceinline__ void wave_argmin(double &d, int &i) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) {
+    const double od = __shfl_xor(d, m);
+    const int oi = __shfl_xor(i, m);
+    if (od < d || (od == d && oi < i)) { d = od; i = oi; }
+  }
+}
+
+__device__ __forceinline__ double yaw_of(const double *__restrict__ sim, size_t sB, int b) {
+  const double x = sim[(RG_SRB_ROW_QUAT + 0) * sB + b], y = sim[(RG_SRB_ROW_QUAT + 1) * sB + b];
+  const double z = sim[(RG_SRB_ROW_QUAT + 2) * sB + b], w = sim[(RG_SRB_ROW_QUAT + 3) * sB + b];
+  return atan2(2 * (x * y + z * w), 1 - 2 * (y * y + z * z));
+}
+
+__global__ void __launch_bounds__(kWave) rg_goto_post_kernel(GotoCfg c, int observe_only, double *__restrict__ task,
+                                                            const double *__restrict__ sim, Paths P, float *__restrict__ obs,
+                                                            float *__restrict__ reward, int *__restrict__ done_out) {
+  __shared__ double vx[kMaxVis], vy[kMaxVis];                 // visible points, robot frame, path order
+  __shared__ double cx[kMaxVis], cy[kMaxVis], cs[kMaxVis];    // the chain and its cumulative length
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const size_t sB = (size_t)c.B;
+  const double inf = __builtin_inf();
+  int n = (int)P.hdr[b];
+  n = n > c.n_max ? c.n_max : n;
+  const bool frozen = task[RG_GOTO_ROW_DONE * sB + b] != 0.0 || n < 2;
+  if (frozen) {   // uniform over the workgroup
+    if (lane < 2 * c.ncp) obs[lane * sB + b] = (float)task[(RG_GOTO_ROW_OBS + lane) * sB + b];
+    if (lane == 0 && !observe_only) { reward[b] = 0.0f; done_out[b] = 1; }
+    return;
+  }
+  // 1. pose
+  const double ox = task[(RG_GOTO_ROW_POS + 0) * sB + b], oy = task[(RG_GOTO_ROW_POS + 1) * sB + b], oyaw = task[(RG_GOTO_ROW_POS + 2) * sB + b];
+  double px = sim[(RG_SRB_ROW_P + 0) * sB + b], py = sim[(RG_SRB_ROW_P + 1) * sB + b], yaw = yaw_of(sim, sB, b);
+  const bool bad = !(isfinite(px) && isfinite(py) && isfinite(yaw));
+  if (bad) { px = ox; py = oy; yaw = oyaw; }
+  const bool fallen = bad || sim[RG_SRB_ROW_STATUS * sB + b] != 0.0;
+  double sn, cz;
+  sincos(yaw, &sn, &cz);
+  // the window's corners in the world, clockwise
+  const double lcx[4] = {c.wd + c.wh, c.wd + c.wh, c.wd, c.wd};
+  const double lcy[4] = {c.wt / 2, -(c.wt / 2), -(c.wb / 2), c.wb / 2};
+  double wx[4], wy[4];
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    wx[e] = px + (cz * lcx[e] - sn * lcy[e]);
+    wy[e] = py + (sn * lcx[e] + cz * lcy[e]);
+  }
+  // 2a. one pass over the path: nearest point to pos and to prev_pos, and the visible points
+  const double *X = P.x + (size_t)b * c.n_max, *Y = P.y + (size_t)b * c.n_max, *S = P.s + (size_t)b * c.n_max;
+  const int *F = P.fsx + (size_t)b * c.n_max;
+  double bd = inf, bpd = inf;
+  int bi = INT_MAX, bpi = INT_MAX, count = 0;
+  for (int base = 0; base < n; base += kWave) {
+    const int i = base + lane;
+    const bool valid = i < n;
+    const double x = valid ? X[i] : 0.0, y = valid ? Y[i] : 0.0;
+    const double dx = x - px, dy = y - py, dn = sqrt(dx * dx + dy * dy);
+    const double ex = x - ox, ey = y - oy, en = sqrt(ex * ex + ey * ey);
+    if (valid && dn < bd) { bd = dn; bi = i; }
+    if (valid && en < bpd) { bpd = en; bpi = i; }
+    bool vis = valid;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const int f = (e + 1) & 3;
+      const double cr = (wx[f] - wx[e]) * (y - wy[e]) - (wy[f] - wy[e]) * (x - wx[e]);
+      vis = vis && cr <= 0.0;
+    }
+    const unsigned long long m = __ballot(vis);
+    const int rank = count + __popcll(m & ((1ull << lane) - 1ull));
+    if (vis && rank < c.max_visible) {   // rank < max_visible <= kMaxVis: never past the arrays
+      vx[rank] = cz * dx + sn * dy;
+      vy[rank] = cz * dy - sn * dx;
+    }
+    count += __popcll(m);
+  }
+  wave_argmin(bd, bi);
+  wave_argmin(bpd, bpi);
+  const int nvis = count < c.max_visible ? count : c.max_visible;
+  __syncthreads();
+  // 2b. sort_points
+  const bool has0 = lane < nvis, has1 = lane + kWave < nvis;
+  const double p0x = has0 ? vx[lane] : 0.0, p0y = has0 ? vy[lane] : 0.0;
+  const double p1x = has1 ? vx[lane + kWave] : 0.0, p1y = has1 ? vy[lane + kWave] : 0.0;
+  bool free0 = has0, free1 = has1;
+  int clen = 0;
+  double acc = 0.0;
+  if (nvis > 0) {
+    double tx = 0.0, ty = 0.0;   // the chain's tail; the origin before the first point
+    for (;;) {
+      const double a0 = p0x - tx, b0 = p0y - ty, a1 = p1x - tx, b1 = p1y - ty;
+      double d = free0 ? sqrt(a0 * a0 + b0 * b0) : inf;
+      int w = lane;
+      const double d1 = free1 ? sqrt(a1 * a1 + b1 * b1) : inf;
+      if (d1 < d) { d = d1; w = lane + kWave; }
+      wave_argmin(d, w);
+      if (clen > 0) {
+        if (d > c.brk) break;
+        acc = acc + d;
+      }
+      const int owner = w & (kWave - 1), slot = w >> 6;
+      tx = __shfl(slot ? p1x : p0x, owner);
+      ty = __shfl(slot ? p1y : p0y, owner);
+      if (lane == owner) { if (slot) free1 = false; else free0 = false; }
+      if (lane == 0) { cx[clen] = tx; cy[clen] = ty; cs[clen] = acc; }
+      clen++;
+      if (clen == nvis) break;
+    }
+  }
+  __syncthreads();
+  // 2c. interpolate_points, one output point per lane
+  const bool fresh = clen >= 2 && acc > 0.0;
+  if (lane < c.ncp) {
+    double qx = task[(RG_GOTO_ROW_OBS + 2 * lane) * sB + b], qy = task[(RG_GOTO_ROW_OBS + 2 * lane + 1) * sB + b];
+    if (fresh) {
+      const double seg = c.ncp > 1 ? acc / (double)(c.ncp - 1) : 0.0;
+      const double t = (double)lane * seg;
+      if (!(t > acc + 1e-6)) {
+        if (t >= acc) { qx = cx[clen - 1]; qy = cy[clen - 1]; }
+        else {
+          int k = 0;
+          while (k < clen - 2 && !(t < cs[k + 1])) k++;
+          const double fr = (t - cs[k]) / (cs[k + 1] - cs[k]);
+          qx = cx[k] + fr * (cx[k + 1] - cx[k]);
+          qy = cy[k] + fr * (cy[k + 1] - cy[k]);
+        }
+        task[(RG_GOTO_ROW_OBS + 2 * lane) * sB + b] = qx;
+        task[(RG_GOTO_ROW_OBS + 2 * lane + 1) * sB + b] = qy;
+      }
+    }
+    obs[(2 * lane) * sB + b] = (float)qx;
+    obs[(2 * lane + 1) * sB + b] = (float)qy;
+  }
+  if (lane == 0) {
+    task[(RG_GOTO_ROW_PREV + 0) * sB + b] = ox; task[(RG_GOTO_ROW_PREV + 1) * sB + b] = oy; task[(RG_GOTO_ROW_PREV + 2) * sB + b] = oyaw;
+    task[(RG_GOTO_ROW_POS + 0) * sB + b] = px; task[(RG_GOTO_ROW_POS + 1) * sB + b] = py; task[(RG_GOTO_ROW_POS + 2) * sB + b] = yaw;
+    if (count > c.max_visible) task[RG_GOTO_ROW_OVERFLOW * sB + b] = 1.0;
+    task[RG_GOTO_ROW_VISIBLE * sB + b] = (double)count;
+    task[RG_GOTO_ROW_CHAIN * sB + b] = (double)clen;
+    task[RG_GOTO_ROW_LATCHED * sB + b] = fresh ? 1.0 : 0.0;
+  }
+  if (observe_only) return;
+  // 3. reward (uniform over the wave)
+  const int last = n - 1;
+  bi = bi > last ? 0 : bi;       // INT_MAX only if no distance compared (a path slab overwritten with NaN): stay in bounds
+  bpi = bpi > last ? 0 : bpi;
+  int i1 = F[bpi], i2 = F[bi];
+  i1 = i1 < 0 ? 0 : (i1 > last ? last : i1);
+  i2 = i2 < 0 ? 0 : (i2 > last ? last : i2);
+  const double track_err = bd;
+  const double err_norm = track_err * c.inv_max_err;
+  double dl = 0.0;
+  if (i1 != i2) {
+    const int first = i1 < i2 ? i1 : i2, second = i1 < i2 ? i2 : i1;
+    const double len1 = S[second] - S[first];
+    const double gx = X[second] - X[first], gy = Y[second] - Y[first];
+    const double len2 = S[first] + sqrt(gx * gx + gy * gy) + (S[last] - S[second]);
+    if (len1 < len2) dl = i1 < i2 ? len1 : -len1;
+    else dl = i1 < i2 ? -len2 : len2;
+  }
+  double pot = task[RG_GOTO_ROW_POT * sB + b] + dl;
+  double progress = task[RG_GOTO_ROW_PROGRESS * sB + b];
+  int nci = (int)task[RG_GOTO_ROW_NEXT_CP * sB + b];
+  bool path_done = task[RG_GOTO_ROW_PATH_DONE * sB + b] != 0.0;
+  const double length = P.hdr[sB + b];
+  double r = 0.0;
+  if (pot - progress < c.prog_window) {
+    int k = 0;
+    if (!path_done) {
+      if (pot > progress) progress = pot;
+      const double per = length / (double)c.ncheck;
+      while (k < c.ncheck && progress >= (double)(nci + 1) * per) {
+        nci++;
+        k++;
+        if (nci >= c.ncheck - 1) { path_done = true; break; }
+      }
+    }
+    const double u = 1.0 - err_norm;
+    r = r + (double)k * c.cp_reward * (u * u);
+  }
+  r = r - c.penalty;
+  const bool off_progress = fabs(pot - progress) > c.prog_limit, off_track = track_err > c.max_err;
+  if (off_progress || off_track) r = RG_GOTO_LIMIT_REWARD;
+  // 4. termination
+  const double tgx = px - P.hdr[2 * sB + b], tgy = py - P.hdr[3 * sB + b];
+  const bool on_target = sqrt(tgx * tgx + tgy * tgy) <= c.radius;
+  int reason = RG_GOTO_REASON_NONE;
+  if (fallen) reason = RG_GOTO_REASON_FALLEN;
+  else if (path_done) reason = RG_GOTO_REASON_PATH_DONE;
+  else if (on_target) reason = RG_GOTO_REASON_ON_TARGET;
+  else if (off_progress) reason = RG_GOTO_REASON_PROGRESS;
+  else if (off_track) reason = RG_GOTO_REASON_TRACK;
+  else if (sim[RG_SRB_ROW_STEPS * sB + b] > c.max_steps) reason = RG_GOTO_REASON_TIME;
+  if (lane == 0) {
+    task[RG_GOTO_ROW_POT * sB + b] = pot;
+    task[RG_GOTO_ROW_PROGRESS * sB + b] = progress;
+    task[RG_GOTO_ROW_NEXT_CP * sB + b] = (double)nci;
+    task[RG_GOTO_ROW_PATH_DONE * sB + b] = path_done ? 1.0 : 0.0;
+    task[RG_GOTO_ROW_ENV_STEPS * sB + b] = task[RG_GOTO_ROW_ENV_STEPS * sB + b] + 1.0;
+    task[RG_GOTO_ROW_DONE * sB + b] = reason ? 1.0 : 0.0;
+    task[RG_GOTO_ROW_REASON * sB + b] = (double)reason;
+    task[RG_GOTO_ROW_TRACK_ERR * sB + b] = track_err;
+    reward[b] = (float)r;
+    done_out[b] = reason ? 1 : 0;
+  }
+}
+
+__global__ void __launch_bounds__(kPreBlock) rg_goto_pre_kernel(GotoCfg c, const double *__restrict__ task, const double *__restrict__ sim,
+                                                                const double *__restrict__ hdr, const float *__restrict__ action,
+                                                                float *__restrict__ cmd) {
+  const int b = blockIdx.x * kPreBlock + threadIdx.x;
+  if (b >= c.B) return;   // no cross-lane operation in this kernel
+  const size_t sB = (size_t)c.B;
+  double a[2] = {(double)action[2 * (size_t)b], (double)action[2 * (size_t)b + 1]};
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    if (!(a[i] == a[i])) a[i] = 0.0;
+    a[i] = a[i] < c.lo[i] ? c.lo[i] : (a[i] > c.hi[i] ? c.hi[i] : a[i]);
+  }
+  const double tx = sim[(RG_SRB_ROW_P + 0) * sB + b] - hdr[2 * sB + b], ty = sim[(RG_SRB_ROW_P + 1) * sB + b] - hdr[3 * sB + b];
+  const bool stand = task[RG_GOTO_ROW_DONE * sB + b] != 0.0 || hdr[b] < 2.0 || sqrt(tx * tx + ty * ty) <= c.radius;
+  if (stand) { a[0] = 0.0; a[1] = 0.0; }
+  cmd[b] = (float)a[0] + c.off[0];
+  cmd[sB + b] = 0.0f + c.off[1];
+  cmd[2 * sB + b] = (float)a[1] + c.off[2];
+}
+
+// set_path: header columns from the staging rows, task state columns zeroed.  One thread per entry.
+__global__ void __launch_bounds__(kPreBlock) rg_goto_set_kernel(int B, int n, const double *__restrict__ st, double *__restrict__ hdr,
+                                                                double *__restrict__ task) {
+  const int k = blockIdx.x * kPreBlock + threadIdx.x;
+  if (k >= n) return;
+  const size_t sB = (size_t)B, sn = (size_t)n;
+  const int b = (int)st[k];
+  for (int r = 0; r < RG_GOTO_HDR_ROWS; r++) hdr[r * sB + b] = st[(1 + r) * sn + k];
+  for (int r = 0; r < RG_GOTO_STATE_ROWS; r++) task[r * sB + b] = 0.0;
+}
+
+struct DeviceScope {
+  int prev = -1;
+  bool switched = false;
+  hipError_t err = hipSuccess;
+  explicit DeviceScope(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess && prev >= 0; }
+  }
+  ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
+};
+
+thread_local std::string g_create_err;
+
+}  // namespace
+
+struct rg_goto_handle {
+  GotoCfg c{};
+  rg_goto_config cfg{};
+  int B = 0, device = 0;
+  double *stage = nullptr;   // [kStageRows][B]
+  std::vector<double> stage_host;
+  std::string err;
+};
+
+namespace {
+
+bool validate(const rg_goto_config *cfg, int32_t batch, std::string &err) {
+  char msg[200];
+  if (cfg->abi_version != RG_GOTO_ABI_VERSION) {
+    snprintf(msg, sizeof(msg), "config.abi_version: %d, this library is version %d", cfg->abi_version, RG_GOTO_ABI_VERSION);
+    err = msg;
+    return false;
+  }
+  if (cfg->reserved0 != 0) { err = "config.reserved0: must be 0"; return false; }
+  if (cfg->reserved1 != 0) { err = "config.reserved1: must be 0"; return false; }
+  if (batch < 1 || batch > RG_GOTO_MAX_BATCH) {
+    snprintf(msg, sizeof(msg), "batch: %d outside [1, %d]", batch, RG_GOTO_MAX_BATCH);
+    err = msg;
+    return false;
+  }
+  struct F { const char *name; const double *p; int n; bool positive; };
+  const F fields[] = {{"window_height", &cfg->window_height, 1, true}, {"window_top_width", &cfg->window_top_width, 1, true},
+                      {"window_bottom_width", &cfg->window_bottom_width, 1, true}, {"window_distance", &cfg->window_distance, 1, false},
+                      {"max_track_err", &cfg->max_track_err, 1, true}, {"progress_window", &cfg->progress_window, 1, true},
+                      {"progress_limit", &cfg->progress_limit, 1, true}, {"target_radius", &cfg->target_radius, 1, true},
+                      {"time_penalty", &cfg->time_penalty, 1, false}, {"checkpoint_reward_total", &cfg->checkpoint_reward_total, 1, false},
+                      {"max_time", &cfg->max_time, 1, true}, {"continuity_break", &cfg->continuity_break, 1, true},
+                      {"action_low", cfg->action_low, 2, false}, {"action_high", cfg->action_high, 2, false},
+                      {"cmd_offset", cfg->cmd_offset, 3, false}, {"dt_sim", &cfg->dt_sim, 1, true}};
+  for (const F &f : fields)
+    for (int i = 0; i < f.n; i++) {
+      const double v = f.p[i];
+      if (!std::isfinite(v) || (f.positive && !(v > 0))) {
+        if (f.n > 1) snprintf(msg, sizeof(msg), "config.%s[%d]: %g is not finite", f.name, i, v);
+        else snprintf(msg, sizeof(msg), "config.%s: %g must be finite%s", f.name, v, f.positive ? " and > 0" : "");
+        err = msg;
+        return false;
+      }
+    }
+  for (int i = 0; i < 2; i++)
+    if (cfg->action_low[i] > cfg->action_high[i]) {
+      snprintf(msg, sizeof(msg), "config.action_low[%d]: %g above action_high[%d] = %g", i, cfg->action_low[i], i, cfg->action_high[i]);
+      err = msg;
+      return false;
+    }
+  struct I { const char *name; int v, lo, hi; };
+  const I ints[] = {{"substeps", cfg->substeps, 1, RG_SRB_MAX_SUBSTEPS}, {"num_cam_pts", cfg->num_cam_pts, 1, RG_GOTO_MAX_CAM_PTS},
+                    {"num_checkpoints", cfg->num_checkpoints, 1, RG_GOTO_MAX_CHECKPOINTS}, {"n_max", cfg->n_max, 2, RG_GOTO_MAX_PATH},
+                    {"max_visible", cfg->max_visible, 2, RG_GOTO_MAX_VISIBLE}};
+  for (const I &f : ints)
+    if (f.v < f.lo || f.v > f.hi) {
+      snprintf(msg, sizeof(msg), "config.%s: %d outside [%d, %d]", f.name, f.v, f.lo, f.hi);
+      err = msg;
+      return false;
+    }
+  return true;
+}
+
+int hip_fail(rg_goto_handle *h, const char *what, hipError_t e) {
+  h->err = std::string(what) + ": " + hipGetErrorString(e);
+  return RG_GOTO_ERR_HIP;
+}
+
+int no_device(rg_goto_handle *h) {
+  h->err = "host-only handle (RG_GOTO_DEVICE_NONE): the arguments are valid, there is no device to run on";
+  return RG_GOTO_ERR_NO_DEVICE;
+}
+
+int launch_status(rg_goto_handle *h, const char *what) {
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(h, what, e) : RG_GOTO_OK;
+}
+
+bool paths_ok(const rg_goto_path_ptrs *p) { return p && p->x && p->y && p->s && p->first_same_x && p->hdr; }
+
+Paths to_paths(const rg_goto_path_ptrs *p) { return {p->x, p->y, p->s, p->first_same_x, p->hdr}; }
+
+int post(rg_goto_handle *h, const char *who, int observe_only, double *task_state, const double *sim_state, const rg_goto_path_ptrs *paths,
+         float *obs, float *reward, int32_t *done, void *stream) {
+  if (!h) { g_create_err = std::string(who) + ": null handle"; return RG_GOTO_ERR_INVALID; }
+  if (!task_state) { h->err = std::string(who) + ": null task_state"; return RG_GOTO_ERR_INVALID; }
+  if (!sim_state) { h->err = std::string(who) + ": null sim_state"; return RG_GOTO_ERR_INVALID; }
+  if (!paths_ok(paths)) { h->err = std::string(who) + ": null paths pointer"; return RG_GOTO_ERR_INVALID; }
+  if (!obs) { h->err = std::string(who) + ": null obs"; return RG_GOTO_ERR_INVALID; }
+  if (!observe_only && (!reward || !done)) { h->err = std::string(who) + ": null reward or done"; return RG_GOTO_ERR_INVALID; }
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  hipLaunchKernelGGL(rg_goto_post_kernel, dim3((unsigned)h->B), dim3(kWave), 0, (hipStream_t)stream, h->c, observe_only, task_state, sim_state,
+                     to_paths(paths), obs, reward, done);
+  return launch_status(h, "rg_goto_post_kernel launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t rg_goto_abi_version(void) { return RG_GOTO_ABI_VERSION; }
+int32_t rg_goto_config_size(void) { return (int32_t)sizeof(rg_goto_config); }
+int32_t rg_goto_state_rows(void) { return RG_GOTO_STATE_ROWS; }
+const char *rg_goto_last_error(const rg_goto_handle *h) { return h ? h->err.c_str() : g_create_err.c_str(); }
+
+int rg_goto_create(const rg_goto_config *cfg, int32_t batch, int32_t device, rg_goto_handle **out) {
+  if (!cfg || !out) { g_create_err = "create: null config or out"; return RG_GOTO_ERR_INVALID; }
+  *out = nullptr;
+  std::string err;
+  if (!validate(cfg, batch, err)) { g_create_err = err; return RG_GOTO_ERR_INVALID; }
+  if (device == RG_GOTO_DEVICE_NONE) {   // a host-only handle: the configuration, for argument checks on any machine
+    rg_goto_handle *h = new rg_goto_handle();
+    h->B = batch;
+    h->device = device;
+    h->cfg = *cfg;
+    h->c.B = batch; h->c.n_max = cfg->n_max;
+    h->stage_host.resize((size_t)kStageRows * batch);
+    *out = h;
+    return RG_GOTO_OK;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_err = "no HIP device available"; return RG_GOTO_ERR_NO_DEVICE; }
+  if (device < 0 || device >= ndev) { g_create_err = "device index out of range"; return RG_GOTO_ERR_INVALID; }
+  DeviceScope dev(device);
+  if (dev.err != hipSuccess) { g_create_err = std::string("hipSetDevice failed: ") + hipGetErrorString(dev.err); return RG_GOTO_ERR_HIP; }
+  rg_goto_handle *h = new rg_goto_handle();
+  h->B = batch;
+  h->device = device;
+  h->cfg = *cfg;
+  GotoCfg &c = h->c;
+  c.B = batch; c.n_max = cfg->n_max; c.ncp = cfg->num_cam_pts; c.ncheck = cfg->num_checkpoints; c.max_visible = cfg->max_visible;
+  c.wh = cfg->window_height; c.wt = cfg->window_top_width; c.wb = cfg->window_bottom_width; c.wd = cfg->window_distance;
+  c.max_err = cfg->max_track_err; c.inv_max_err = 1.0 / cfg->max_track_err;
+  c.prog_window = cfg->progress_window; c.prog_limit = cfg->progress_limit; c.radius = cfg->target_radius;
+  c.penalty = cfg->time_penalty; c.cp_reward = cfg->checkpoint_reward_total / (double)cfg->num_checkpoints;
+  c.max_steps = cfg->max_time / (cfg->dt_sim * (double)cfg->substeps);
+  c.brk = cfg->continuity_break;
+  for (int i = 0; i < 2; i++) { c.lo[i] = cfg->action_low[i]; c.hi[i] = cfg->action_high[i]; }
+  for (int i = 0; i < 3; i++) c.off[i] = (float)cfg->cmd_offset[i];
+  h->stage_host.resize((size_t)kStageRows * batch);
+  const hipError_t e = hipMalloc((void **)&h->stage, (size_t)kStageRows * batch * sizeof(double));
+  if (e != hipSuccess) {
+    g_create_err = std::string("hipMalloc failed: ") + hipGetErrorString(e);
+    rg_goto_destroy(h);
+    return RG_GOTO_ERR_ALLOC;
+  }
+  *out = h;
+  return RG_GOTO_OK;
+}
+
+void rg_goto_destroy(rg_goto_handle *h) {
+  if (!h) return;
+  if (h->device >= 0) {
+    DeviceScope dev(h->device);
+    if (h->stage) (void)hipFree(h->stage);
+  }
+  delete h;
+}
+
+int rg_goto_set_path(rg_goto_handle *h, const int32_t *idx_host, int32_t n, const int32_t *npts, const double *length,
+                     const double *target, const double *x, const double *y, const double *s, const int32_t *first_same_x,
+                     const rg_goto_path_ptrs *paths, double *task_state, void *stream) {
+  if (!h) { g_create_err = "set_path: null handle"; return RG_GOTO_ERR_INVALID; }
+  if (!npts || !length || !target || !x || !y || !s || !first_same_x) { h->err = "set_path: null host array"; return RG_GOTO_ERR_INVALID; }
+  if (!paths_ok(paths)) { h->err = "set_path: null paths pointer"; return RG_GOTO_ERR_INVALID; }
+  if (!task_state) { h->err = "set_path: null task_state"; return RG_GOTO_ERR_INVALID; }
+  const int B = h->B, n_max = h->c.n_max;
+  if (idx_host ? (n < 1 || n > B) : n != B) { h->err = "set_path: n must be the batch without an index list, 1..batch with one"; return RG_GOTO_ERR_INVALID; }
+  const size_t sn = (size_t)n;
+  char msg[200];
+  std::vector<char> taken(idx_host ? (size_t)B : 0, 0);
+  double *st = h->stage_host.data();
+  for (int k = 0; k < n; k++) {
+    const int b = idx_host ? idx_host[k] : k;
+    auto bad = [&](const char *what) {
+      snprintf(msg, sizeof(msg), "set_path: entry %d (robot %d): %s", k, b, what);
+      h->err = msg;
+      return RG_GOTO_ERR_INVALID;
+    };
+    if (b < 0 || b >= B) return bad("robot out of range");
+    if (idx_host) {
+      if (taken[b]) return bad("robot given twice");
+      taken[b] = 1;
+    }
+    if (npts[k] > n_max) { snprintf(msg, sizeof(msg), "set_path: entry %d (robot %d): npts %d above n_max %d", k, b, npts[k], n_max); h->err = msg; return RG_GOTO_ERR_INVALID; }
+    if (npts[k] < 2) { snprintf(msg, sizeof(msg), "set_path: entry %d (robot %d): npts %d below 2", k, b, npts[k]); h->err = msg; return RG_GOTO_ERR_INVALID; }
+    if (!(length[k] > 0 && length[k] <= 1e300)) return bad("length must be positive and finite");
+    if (!(fabs(target[k]) <= 1e300 && fabs(target[sn + k]) <= 1e300)) return bad("target must be finite");
+    const size_t row = (size_t)k * n_max;
+    for (int i = 0; i < npts[k]; i++) {
+      if (!(fabs(x[row + i]) <= 1e300 && fabs(y[row + i]) <= 1e300 && fabs(s[row + i]) <= 1e300)) return bad("x, y and s must be finite");
+      if (first_same_x[row + i] < 0 || first_same_x[row + i] > i) return bad("first_same_x[i] outside [0, i]");
+    }
+    st[k] = (double)b; st[sn + k] = (double)npts[k]; st[2 * sn + k] = length[k]; st[3 * sn + k] = target[k]; st[4 * sn + k] = target[sn + k];
+  }
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  hipStream_t q = (hipStream_t)stream;
+  hipError_t e = hipMemcpyAsync(h->stage, st, kStageRows * sn * sizeof(double), hipMemcpyHostToDevice, q);
+  const size_t rd = (size_t)n_max * sizeof(double), ri = (size_t)n_max * sizeof(int32_t);
+  if (!idx_host) {   // the whole slab, one copy per array
+    if (e == hipSuccess) e = hipMemcpyAsync(paths->x, x, sn * rd, hipMemcpyHostToDevice, q);
+    if (e == hipSuccess) e = hipMemcpyAsync(paths->y, y, sn * rd, hipMemcpyHostToDevice, q);
+    if (e == hipSuccess) e = hipMemcpyAsync(paths->s, s, sn * rd, hipMemcpyHostToDevice, q);
+    if (e == hipSuccess) e = hipMemcpyAsync(paths->first_same_x, first_same_x, sn * ri, hipMemcpyHostToDevice, q);
+  } else {
+    for (int k = 0; k < n && e == hipSuccess; k++) {
+      const size_t src = (size_t)k * n_max, dst = (size_t)idx_host[k] * n_max;
+      e = hipMemcpyAsync(paths->x + dst, x + src, rd, hipMemcpyHostToDevice, q);
+      if (e == hipSuccess) e = hipMemcpyAsync(paths->y + dst, y + src, rd, hipMemcpyHostToDevice, q);
+      if (e == hipSuccess) e = hipMemcpyAsync(paths->s + dst, s + src, rd, hipMemcpyHostToDevice, q);
+      if (e == hipSuccess) e = hipMemcpyAsync(paths->first_same_x + dst, first_same_x + src, ri, hipMemcpyHostToDevice, q);
+    }
+  }
+  if (e != hipSuccess) return hip_fail(h, "set_path copy", e);
+  hipLaunchKernelGGL(rg_goto_set_kernel, dim3(((unsigned)n + kPreBlock - 1) / kPreBlock), dim3(kPreBlock), 0, q, B, n, h->stage, paths->hdr, task_state);
+  const int rc = launch_status(h, "rg_goto_set_kernel launch");
+  if (rc) return rc;
+  e = hipStreamSynchronize(q);   // the staging buffer and the caller's host arrays are free after this
+  return e != hipSuccess ? hip_fail(h, "set_path", e) : RG_GOTO_OK;
+}
+
+int rg_goto_pre_step(rg_goto_handle *h, const double *task_state, const double *sim_state, const rg_goto_path_ptrs *paths,
+                     const float *action, float *cmd_out, void *stream) {
+  if (!h) { g_create_err = "pre_step: null handle"; return RG_GOTO_ERR_INVALID; }
+  if (!task_state) { h->err = "pre_step: null task_state"; return RG_GOTO_ERR_INVALID; }
+  if (!sim_state) { h->err = "pre_step: null sim_state"; return RG_GOTO_ERR_INVALID; }
+  if (!paths_ok(paths)) { h->err = "pre_step: null paths pointer"; return RG_GOTO_ERR_INVALID; }
+  if (!action) { h->err = "pre_step: null action"; return RG_GOTO_ERR_INVALID; }
+  if (!cmd_out) { h->err = "pre_step: null cmd_out"; return RG_GOTO_ERR_INVALID; }
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  hipLaunchKernelGGL(rg_goto_pre_kernel, dim3(((unsigned)h->B + kPreBlock - 1) / kPreBlock), dim3(kPreBlock), 0, (hipStream_t)stream, h->c,
+                     task_state, sim_state, paths->hdr, action, cmd_out);
+  return launch_status(h, "rg_goto_pre_kernel launch");
+}
+
+int rg_goto_post_step(rg_goto_handle *h, double *task_state, const double *sim_state, const rg_goto_path_ptrs *paths,
+                      float *obs, float *reward, int32_t *done, void *stream) {
+  return post(h, "post_step", 0, task_state, sim_state, paths, obs, reward, done, stream);
+}
+
+int rg_goto_observe(rg_goto_handle *h, double *task_state, const double *sim_state, const rg_goto_path_ptrs *paths, float *obs, void *stream) {
+  return post(h, "observe", 1, task_state, sim_state, paths, obs, nullptr, nullptr, stream);
+}
+
+}  // extern "C"
