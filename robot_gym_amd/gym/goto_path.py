@@ -168,12 +168,13 @@ def chain_sort(points, origin=(0.0, 0.0), continuity_break=CONTINUITY_BREAK):
     return points[order], order
 
 
-def build_path(points, num_checkpoints=NUM_CHECKPOINTS, target=None):
-    """Path.__init__: n = int(len / 1e-2) points at equal arc length along the way points, `length` of the INTERPOLATED
-    polyline, checkpoints at i * length / num_checkpoints, start_xy, start_angle in [0, 2 pi) from the first segment -- and
-    the tables the kernel reads: cumulative arc length s and first_same_x[i], the first j with x[j] == x[i]."""
+def build_path(points, num_checkpoints=NUM_CHECKPOINTS, target=None, spacing=SPACING):
+    """Path.__init__: n = int(len / spacing) points (the reference's 1e-2) at equal arc length along the way points,
+    `length` of the INTERPOLATED polyline, checkpoints at i * length / num_checkpoints, start_xy, start_angle in [0, 2 pi)
+    from the first segment -- and the tables the kernel reads: cumulative arc length s and first_same_x[i], the first j
+    with x[j] == x[i]."""
     points = np.asarray(points, dtype=np.float64).reshape(-1, 2)
-    n = int(arc_table(points)[-1] / SPACING)
+    n = int(arc_table(points)[-1] / spacing)
     if n < 2:
         raise ValueError(f"build_path: the way points span {n} path points, at least 2 are needed")
     pts = interpolate_points(points, n)

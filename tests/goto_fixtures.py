@@ -1,5 +1,8 @@
 """Shared inputs of the go-to-target tests: planned paths, synthetic pose sequences near them, and the model run over them.
 
+RawTask is the task's handle on caller-owned buffers between guard rows (torch is imported when one is made, so this module
+loads without it).
+
 A pose sequence is written straight into a simulator state, so no controller takes part: robot r starts at a random arc
 position of its own planned path and moves along it at its own speed, with a lateral offset up to 0.12 m and a heading up
 to 0.6 rad off the tangent, both slowly varying.  A few robots are teleported 0.6 m ahead at some tick, a few fall.  Tick 0
@@ -12,7 +15,7 @@ from concurrent.futures import ProcessPoolExecutor
 
 import numpy as np
 
-from robot_gym_amd.core import goto_abi
+from robot_gym_amd.core import goto_abi, srb_abi
 from robot_gym_amd.gym import goto_path
 from tests import goto_model
 
@@ -70,7 +73,62 @@ def pose_sequences(paths, ticks, seed, substeps=10):
     return np.ascontiguousarray(np.stack([pose_sequence(p, ticks, rng, substeps) for p in paths], axis=-1))
 
 
-RECORD = ("visible", "chain", "latched", "next_cp", "done", "reason", "reward", "margin", "margin_frame", "frozen", "overflow")
+GUARD = 777
+
+
+class RawTask:
+    """The task's handle and caller-owned buffers without controller or simulator: poses are written into `sim`."""
+
+    def __init__(self, paths, dev, packed=None, **task):
+        """packed: the host arrays handed to set_path in place of goto_path.pack_paths(paths, n_max) (a test that changes them)."""
+        import torch
+        B = self.batch = len(paths)
+        self.torch = torch
+        self.handle = goto_abi.GotoHandle(B, None, dev, **task)
+        f = self.handle.fields
+        n_max, self.ncp = f["n_max"], f["num_cam_pts"]
+        z = lambda *shape, dtype=torch.float64: torch.zeros(*shape, dtype=dtype, device=dev)
+        self._guarded = []
+
+        def g(rows, dtype=torch.float64):
+            """rows x B zeros between two guard rows of GUARD that the kernels must leave as they are"""
+            back = torch.full((rows + 2, B), GUARD, dtype=dtype, device=dev)
+            back[1:-1] = 0
+            self._guarded.append(back)
+            return back[1:-1]
+        self.state, self.sim = g(goto_abi.STATE_ROWS), z(srb_abi.STATE_ROWS, B)
+        self.px, self.py, self.ps, self.pf, self.hdr = z(B, n_max), z(B, n_max), z(B, n_max), z(B, n_max, dtype=torch.int32), z(goto_abi.HDR_ROWS, B)
+        self.ptrs = goto_abi.CPathPtrs(self.px.data_ptr(), self.py.data_ptr(), self.ps.data_ptr(), self.pf.data_ptr(), self.hdr.data_ptr())
+        self.obs, self.reward, self.done = g(2 * self.ncp, torch.float32), g(1, torch.float32)[0], g(1, torch.int32)[0]
+        self.action, self.cmd = z(B, 2, dtype=torch.float32), g(3, torch.float32)
+        self.handle.set_path(self.ptrs, self.state.data_ptr(), None, **(packed or goto_path.pack_paths(paths, n_max)))
+
+    def set_path(self, idx, paths):
+        """New paths for robots idx (rg_goto_set_path with an index list)."""
+        self.handle.set_path(self.ptrs, self.state.data_ptr(), idx, **goto_path.pack_paths(paths, self.handle.n_max))
+
+    def guards_intact(self):
+        return all(bool((t[0] == GUARD).all()) and bool((t[-1] == GUARD).all()) for t in self._guarded)
+
+    def pose(self, rows):
+        """rows [POSE_ROWS, B] host array -> the simulator state rows the task reads."""
+        t = self.torch.as_tensor(rows, device=self.sim.device)
+        self.sim[srb_abi.ROW_P:srb_abi.ROW_P + 2] = t[0:2]
+        self.sim[srb_abi.ROW_QUAT + 2:srb_abi.ROW_QUAT + 4] = t[2:4]
+        self.sim[srb_abi.ROW_STEPS], self.sim[srb_abi.ROW_STATUS] = t[4], t[5]
+
+    def observe(self):
+        self.handle.observe(self.state.data_ptr(), self.sim.data_ptr(), self.ptrs, self.obs.data_ptr())
+
+    def post(self):
+        self.handle.post_step(self.state.data_ptr(), self.sim.data_ptr(), self.ptrs, self.obs.data_ptr(), self.reward.data_ptr(), self.done.data_ptr())
+
+    def pre(self):
+        self.handle.pre_step(self.state.data_ptr(), self.sim.data_ptr(), self.ptrs, self.action.data_ptr(), self.cmd.data_ptr())
+
+
+RECORD = ("visible", "chain", "latched", "next_cp", "done", "reason", "reward", "margin", "margin_frame", "frozen", "overflow",
+          "margin_frame_ties_ok", "zero_links")
 
 
 def run_model_robot(c, path, poses):
@@ -82,7 +140,7 @@ def run_model_robot(c, path, poses):
     obs = np.zeros((T, 2 * c["num_cam_pts"]), dtype=np.float32)
     p = poses[0]
     first = goto_model.post_step(c, st, path, p[0:2], (0.0, 0.0, p[2], p[3]), p[5], p[4], observe_only=True)
-    obs0, margin0 = first["obs"], first["margin_frame"]
+    obs0, margin0, margin0_ties_ok = first["obs"], first["margin_frame"], first["margin_frame_ties_ok"]
     for t in range(1, T + 1):
         p = poses[t]
         r = goto_model.post_step(c, st, path, p[0:2], (0.0, 0.0, p[2], p[3]), p[5], p[4])
@@ -91,8 +149,8 @@ def run_model_robot(c, path, poses):
         rec["visible"][k], rec["chain"][k], rec["latched"][k] = st[goto_abi.ROW_VISIBLE], st[goto_abi.ROW_CHAIN], st[goto_abi.ROW_LATCHED]
         rec["next_cp"][k], rec["done"][k], rec["reason"][k] = st[goto_abi.ROW_NEXT_CP], r["done"], st[goto_abi.ROW_REASON]
         rec["reward"][k], rec["margin"][k], rec["frozen"][k], rec["overflow"][k] = r["reward"], r["margin"], r["frozen"], st[goto_abi.ROW_OVERFLOW]
-        rec["margin_frame"][k] = r["margin_frame"]
-    rec["obs"], rec["obs0"], rec["margin0"] = obs, obs0, margin0
+        rec["margin_frame"][k], rec["margin_frame_ties_ok"][k], rec["zero_links"][k] = r["margin_frame"], r["margin_frame_ties_ok"], r["zero_links"]
+    rec["obs"], rec["obs0"], rec["margin0"], rec["margin0_ties_ok"] = obs, obs0, margin0, margin0_ties_ok
     return rec
 
 
@@ -117,20 +175,22 @@ def run_model(c, paths, poses, workers=None):
     recs = [r for part in parts for r in part]
     out = {k: np.stack([r[k] for r in recs], axis=-1) for k in RECORD + ("obs", "obs0")}
     out["margin0"] = np.array([r["margin0"] for r in recs])
+    out["margin0_ties_ok"] = np.array([r["margin0_ties_ok"] for r in recs])
     return out
 
 
-def excluded(model, threshold=1e-9):
-    """(tick, obs): two bool [T, B] masks of the robot-ticks a comparison may leave out.
+def excluded(model, threshold=1e-9, ties_ok=False):
+    """(tick, obs): two bool [T, B] masks of the robot-ticks a comparison may leave out.  ties_ok: judge by
+    margin_frame_ties_ok, which does not count the exact tie between copies of one path point, so that those ticks are compared.
     tick: a rounding-sensitive decision of THAT tick (goto_model's margin_frame: window edge, chain arg-min, continuity
     break) lay within `threshold` of flipping -- every output of the tick may be left out.
     obs: the same ticks, and after such a tick (or such a reset observation) the following ticks for as long as the model
     keeps the latch (latched == 0, or the robot is frozen): the observation they show is the doubtful one carried on.
     Nothing else is carried: reward, checkpoints, done and its cause do not depend on those decisions."""
-    tick = model["margin_frame"] < threshold
+    tick = model["margin_frame_ties_ok" if ties_ok else "margin_frame"] < threshold
     kept = (model["latched"] == 0) | (model["frozen"] != 0)
     obs = np.zeros_like(tick)
-    carry = model["margin0"] < threshold
+    carry = model["margin0_ties_ok" if ties_ok else "margin0"] < threshold
     for t in range(len(tick)):
         carry = tick[t] | (carry & kept[t])
         obs[t] = carry

@@ -16,6 +16,14 @@ reward and the termination work on sums, products, square roots and quotients of
 fixes to the bit in a fixed order: two implementations of this file's order agree there even at an exact tie (and on a
 1 cm path whose length is a round number the progress DOES sit exactly on a checkpoint), so those margins are reported but
 are no ground to leave anything out.
+
+Exact ties.  A path may hold the same point more than once (the reference's planner repeats coordinates).  Copies of a point
+have bitwise equal robot-frame coordinates and so tie exactly in the chain's arg-min: `margin_frame` is 0 there although
+nothing is in doubt -- the lowest index wins on both sides, and either copy puts the same coordinates into the chain.
+`margin_frame_ties_ok` is margin_frame with the arg-min gap taken over the candidates that are NOT bitwise copies of the
+winner; a comparison built on it compares the tie ticks too.  The nearest-point arg-min (`nearest`, `nearest_prev`) is not
+among FRAME_MARGINS: it is compared even at a tie, and this model takes the lowest index there as the kernel does (np.argmin
+returns the first minimum; tests/test_goto_model_cpu.py holds it to that).
 """
 import math
 
@@ -85,16 +93,24 @@ def _argmin2(d):
     return i, float(rest.min() - d[i])
 
 
+def _same_point(lx, ly, w):
+    """Mask of the points whose coordinates are BITWISE those of point w."""
+    bx, by = np.ascontiguousarray(lx).view(np.int64), np.ascontiguousarray(ly).view(np.int64)
+    return (bx == bx[w]) & (by == by[w])
+
+
 def chain_points(lx, ly, continuity_break):
     """sort_points as the kernel does it, on points (lx, ly) seen from the origin: start at the nearest, chain the nearest
     free point, distances compared after the root with the lowest index winning a tie, stop before the first link above
     continuity_break.  -> (chain [(x, y)], cumulative length per chain point, total length, the smallest gap between the
-    best and the second best of an arg-min, the smallest distance of a link from the break)."""
+    best and the second best of an arg-min, the smallest distance of a link from the break, and the smallest gap once more
+    with the candidates left out whose coordinates are bitwise the winner's: a copy of the winner is at the same distance
+    in any IEEE arithmetic, the lowest index takes it, and whichever copy is taken the chain holds the same coordinates)."""
     nvis = len(lx)
     chain, cs, acc = [], [], 0.0
     free = np.ones(nvis, dtype=bool)
     tx, ty = 0.0, 0.0
-    chain_gap, brk_margin = INF, INF
+    chain_gap, brk_margin, gap_ties_ok = INF, INF, INF
     while len(chain) < nvis:
         a, b = lx - tx, ly - ty
         d = np.where(free, np.sqrt(a * a + b * b), INF)
@@ -106,18 +122,21 @@ def chain_points(lx, ly, continuity_break):
                 break
             acc = acc + dist
         chain_gap = min(chain_gap, g)
+        rivals = d[free & ~_same_point(lx, ly, w)]
+        if len(rivals):
+            gap_ties_ok = min(gap_ties_ok, float(rivals.min() - d[w]))
         tx, ty = float(lx[w]), float(ly[w])
         free[w] = False
         chain.append((tx, ty))
         cs.append(acc)
-    return chain, cs, acc, chain_gap, brk_margin
+    return chain, cs, acc, chain_gap, brk_margin, gap_ties_ok
 
 
 def post_step(c, state, path, sim_xy, quat, sim_status=0.0, sim_steps=0.0, observe_only=False):
     """One tick on `state` (modified in place).  Returns a dict: obs float32 [2 num_cam_pts], reward float32, done int,
     margin (metres / reward units: the distance of the tick's nearest decision from flipping) and its parts."""
     ncp = c["num_cam_pts"]
-    out = dict(margin=INF, margin_frame=INF, margins={})
+    out = dict(margin=INF, margin_frame=INF, margin_frame_ties_ok=INF, zero_links=0, margins={})
     n = 0 if path is None else min(path.n, c["n_max"])
     if state[ROW_DONE] != 0.0 or n < 2:
         out.update(obs=state[ROW_OBS:ROW_OBS + 2 * ncp].astype(np.float32), reward=np.float32(0.0), done=1, frozen=True)
@@ -157,7 +176,7 @@ def post_step(c, state, path, sim_xy, quat, sim_status=0.0, sim_steps=0.0, obser
     ly = cz * dy[idx] - sn * dx[idx]
     nvis = len(idx)
     # 2b. sort_points
-    chain, cs, acc, chain_gap, brk_margin = chain_points(lx, ly, c["continuity_break"])
+    chain, cs, acc, chain_gap, brk_margin, gap_ties_ok = chain_points(lx, ly, c["continuity_break"])
     if brk_margin < INF:
         marg["continuity"] = brk_margin
     marg["chain_argmin"] = chain_gap
@@ -188,6 +207,8 @@ def post_step(c, state, path, sim_xy, quat, sim_status=0.0, sim_steps=0.0, obser
     out["obs"] = state[ROW_OBS:ROW_OBS + 2 * ncp].astype(np.float32)
     out.update(visible=count, chain=clen, latched=int(fresh), nearest=bi, nearest_prev=bpi)
     out["margin_frame"] = min(marg[k] for k in FRAME_MARGINS if k in marg)
+    out["margin_frame_ties_ok"] = min([gap_ties_ok] + [marg[k] for k in FRAME_MARGINS if k in marg and k != "chain_argmin"])
+    out["zero_links"] = sum(1 for k in range(1, clen) if cs[k] == cs[k - 1])      # chain links of length zero: copies of a point
     if observe_only:
         out["margin"] = min(marg.values())
         return out

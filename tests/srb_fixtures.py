@@ -30,6 +30,10 @@ PUSH_AT, PUSH_TICKS = 100, 10
 PUSH_RUN_TICKS = PUSH_AT + PUSH_TICKS + 400
 PUSH_NEWTON = 80.0
 
+# kernel against model on the joint angles (tests/srb_streams.Comparison)
+Q_TOL = 2e-8          # rad: the early exit of leg_ik may fire one pass apart on the two sides (its comment: a pass moves < 1e-8 rad)
+Q_ULP = 4             # float32 ulp on the q / jac observation rows, for the same reason
+
 ROBOTS = ("ghost", "k3lso")
 CMD_BOX = (0.35, 0.2, 0.4)        # vx, vy, wz: the ranges synthetic.make_states draws commands from
 HEIGHT_RANGE = (0.9, 1.1)         # start height / body_height

@@ -27,7 +27,7 @@ BATCH, TICKS = 4096, 200
 CASES = {"defaults": ({}, 101, 102), "every_field_moved": (F.CONFIG_B, 201, 202)}   # task settings, path seed, pose seed
 MARGIN, MAX_LEFT_OUT = 1e-9, 0.01
 REWARD_REL, OBS_ABS = 1e-9, 1e-6
-GUARD = 777
+RawTask = F.RawTask
 
 
 @pytest.fixture(scope="module")
@@ -48,50 +48,6 @@ def models():
         poses = F.pose_sequences(paths, TICKS, pose_seed, c["substeps"])
         out[case] = (c, paths, poses, F.run_model(c, paths, poses))
     return out
-
-
-class RawTask:
-    """The task's handle and caller-owned buffers without controller or simulator: poses are written into `sim`."""
-
-    def __init__(self, paths, dev, **task):
-        B = self.batch = len(paths)
-        self.handle = goto_abi.GotoHandle(B, None, dev, **task)
-        f = self.handle.fields
-        n_max, self.ncp = f["n_max"], f["num_cam_pts"]
-        z = lambda *shape, dtype=torch.float64: torch.zeros(*shape, dtype=dtype, device=dev)
-        self._guarded = []
-
-        def g(rows, dtype=torch.float64):
-            """rows x B zeros between two guard rows of GUARD that the kernels must leave as they are"""
-            back = torch.full((rows + 2, B), GUARD, dtype=dtype, device=dev)
-            back[1:-1] = 0
-            self._guarded.append(back)
-            return back[1:-1]
-        self.state, self.sim = g(goto_abi.STATE_ROWS), z(srb_abi.STATE_ROWS, B)
-        self.px, self.py, self.ps, self.pf, self.hdr = z(B, n_max), z(B, n_max), z(B, n_max), z(B, n_max, dtype=torch.int32), z(goto_abi.HDR_ROWS, B)
-        self.ptrs = goto_abi.CPathPtrs(self.px.data_ptr(), self.py.data_ptr(), self.ps.data_ptr(), self.pf.data_ptr(), self.hdr.data_ptr())
-        self.obs, self.reward, self.done = g(2 * self.ncp, torch.float32), g(1, torch.float32)[0], g(1, torch.int32)[0]
-        self.action, self.cmd = z(B, 2, dtype=torch.float32), g(3, torch.float32)
-        self.handle.set_path(self.ptrs, self.state.data_ptr(), None, **goto_path.pack_paths(paths, n_max))
-
-    def guards_intact(self):
-        return all(bool((t[0] == GUARD).all()) and bool((t[-1] == GUARD).all()) for t in self._guarded)
-
-    def pose(self, rows):
-        """rows [POSE_ROWS, B] host array -> the simulator state rows the task reads."""
-        t = torch.as_tensor(rows, device=self.sim.device)
-        self.sim[srb_abi.ROW_P:srb_abi.ROW_P + 2] = t[0:2]
-        self.sim[srb_abi.ROW_QUAT + 2:srb_abi.ROW_QUAT + 4] = t[2:4]
-        self.sim[srb_abi.ROW_STEPS], self.sim[srb_abi.ROW_STATUS] = t[4], t[5]
-
-    def observe(self):
-        self.handle.observe(self.state.data_ptr(), self.sim.data_ptr(), self.ptrs, self.obs.data_ptr())
-
-    def post(self):
-        self.handle.post_step(self.state.data_ptr(), self.sim.data_ptr(), self.ptrs, self.obs.data_ptr(), self.reward.data_ptr(), self.done.data_ptr())
-
-    def pre(self):
-        self.handle.pre_step(self.state.data_ptr(), self.sim.data_ptr(), self.ptrs, self.action.data_ptr(), self.cmd.data_ptr())
 
 
 STATE_FIGURES = dict(visible=goto_abi.ROW_VISIBLE, chain=goto_abi.ROW_CHAIN, latched=goto_abi.ROW_LATCHED, next_cp=goto_abi.ROW_NEXT_CP,

@@ -224,6 +224,33 @@ def test_the_models_chain_reproduces_the_recorded_sort_points():
     assert len(co) - 1 >= 200
     for k in range(len(co) - 1):
         cloud, want = g["sort_clouds"][co[k]:co[k + 1]], g["sort_chains"][ho[k]:ho[k + 1]]
-        chain, cs, acc, _, _ = goto_model.chain_points(cloud[:, 0].copy(), cloud[:, 1].copy(), 30e-3)
+        chain, cs, acc, *_ = goto_model.chain_points(cloud[:, 0].copy(), cloud[:, 1].copy(), 30e-3)
         assert np.array_equal(np.array(chain).reshape(-1, 2), want), k
         assert len(cs) == len(chain) and abs(acc - np.hypot(*np.diff(want, axis=0).T).sum()) < 1e-12
+
+
+def test_copies_of_a_point_tie_exactly_and_only_the_old_margin_counts_it(straight):
+    """Every 2nd point of the straight path given twice: the chain's arg-min ties exactly between the copies, so margin_frame
+    is 0, margin_frame_ties_ok is not; the copies enter the chain in index order (goto_path.chain_sort, strict <, reports
+    the indices), as links of length zero; and the nearest-point arg-min takes the lower index of two copies."""
+    from tests import goto_edges
+    p = goto_edges.with_copies(straight, every=2)
+    assert p.n == 300 and p.x[0] == p.x[1] and p.s[1] == 0.0 and p.first_same_x[1] == 0
+    plain_st, plain = start(straight, (0.5, 0.0))
+    st, r = start(p, (0.5, 0.0))
+    assert plain["margin_frame"] > 1e-6 and plain["margin_frame_ties_ok"] == plain["margin_frame"] and plain["zero_links"] == 0
+    assert r["margin_frame"] == 0.0 and r["margin_frame_ties_ok"] > 1e-6 and r["zero_links"] >= 5
+    assert r["visible"] == plain["visible"] + r["zero_links"] == r["chain"] and r["latched"] == 1
+    assert np.array_equal(r["obs"], plain["obs"])                 # copies add no length: the resampled line is the same
+    vis = np.nonzero((p.x - 0.5 >= 0.112) & (p.x - 0.5 <= 0.272))[0]
+    pts, order = goto_path.chain_sort(np.stack((p.x[vis] - 0.5, p.y[vis]), axis=-1))
+    assert np.array_equal(order, np.arange(len(vis)))            # index order, the copies included
+    chain, cs, acc, gap, _, gap_ties_ok = goto_model.chain_points(p.x[vis] - 0.5, p.y[vis].copy(), 30e-3)
+    assert np.array_equal(np.array(chain), pts) and gap == 0.0 and gap_ties_ok > 1e-6
+    assert goto_model._argmin2(np.array([3.0, 1.0, 1.0, 2.0])) == (1, 0.0)
+    r = goto_model.post_step(C, st, p, (p.x[100], 0.0), QUAT0)    # on a doubled point: copies 99 and 100
+    assert p.x[99] == p.x[100] and (r["nearest"], r["margin"]) == (99, 0.0) and r["first_same"][1] == 99
+    # a stretch of triple points
+    p3 = goto_edges.with_copies(straight, triple=(60, 90))
+    st, r = start(p3, (0.5, 0.0))
+    assert r["margin_frame"] == 0.0 and r["margin_frame_ties_ok"] > 1e-6 and r["zero_links"] >= 10 and np.array_equal(r["obs"], plain["obs"])

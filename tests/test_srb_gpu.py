@@ -8,12 +8,9 @@ import torch
 from robot_gym_amd.core.config import MPCConfig
 from tests import srb_fixtures as F
 from tests import srb_model as M
-from tests.posctl_fixtures import REL_TOL, within_ulp
+from tests import srb_streams as S
 
 pytestmark = pytest.mark.gpu
-
-Q_TOL = 2e-8          # rad: the early exit of leg_ik may fire one pass apart on the two sides (its comment: a pass moves < 1e-8 rad)
-Q_ULP = 4             # float32 ulp on the q / jac observation rows, for the same reason
 
 
 @pytest.fixture(scope="module")
@@ -54,84 +51,7 @@ def _figures(traj):
     return F.figures(traj.permute(1, 0, 2).cpu().numpy())
 
 
-def _within_ulps(got, want, n):
-    want = np.asarray(want)
-    return np.abs(np.asarray(got) - want) <= n * np.spacing(np.abs(want))
-
-
-# ---- the kernels against the model ----
-
-def _streams(cfg, B, T, seed):
-    """What is drawn ahead of the run, one seeded stream per robot.  desired_state [T,B,4]: a crawl, one leg in swing at a time, with
-    the robot's own period, duty and phase (both states, lift-off and touch-down, three- and four-leg ticks: the stance feet
-    can then realise any wrench, which _stream_grf needs); foot_target
-    [T,B,12] float32: around the hips, lifted; force noise; ext [T,6,B] for the robots 0 and 1 mod 4; a true body for the
-    odd robots (so a quarter of the batch has both, a quarter neither); robots 63 mod 64 lose their forces at tick 45 and fall."""
-    rng = np.random.default_rng(seed)
-    period = rng.integers(16, 48, B)
-    duty = rng.uniform(0.76, 0.95, B)
-    phase0 = rng.uniform(0, 1, B)
-    k = np.arange(T)[:, None]
-    ph = np.stack([(k / period + phase0 + off) % 1.0 for off in (0.0, 0.5, 0.75, 0.25)], 2)     # FR, FL, RR, RL
-    desired = (ph < duty[None, :, None]).astype(np.int32)                                          # 1 STANCE, 0 SWING
-    true_mass = np.full(B, cfg.mass)
-    true_mass[1::2] *= rng.uniform(0.85, 1.15, B // 2)
-    inertia = np.tile(np.asarray(cfg.inertia).reshape(9, 1), (1, B))
-    scale = rng.uniform(0.8, 1.25, (3, B // 2))
-    for a in range(3):
-        inertia[4 * a, 1::2] *= scale[a]
-    off = rng.uniform(-0.004, 0.004, B // 2)
-    inertia[1, 1::2] = off
-    inertia[3, 1::2] = off
-    hip = np.asarray(cfg.hip).reshape(4, 3)
-    ft = np.zeros((T, B, 4, 3))
-    ft[..., 0] = hip[:, 0] + rng.uniform(-0.06, 0.06, (T, B, 4))
-    ft[..., 1] = hip[:, 1] + rng.uniform(-0.04, 0.04, (T, B, 4))
-    ft[..., 2] = -cfg.body_height + rng.uniform(0.0, 0.07, (T, B, 4))
-    ext = np.zeros((T, 6, B))
-    pushed = np.arange(B) % 4 < 2
-    ext[:, :3, pushed] = rng.uniform(-4.0, 4.0, (T, 3, int(pushed.sum())))
-    ext[:, 3:, pushed] = rng.uniform(-0.15, 0.15, (T, 3, int(pushed.sum())))
-    return dict(desired=desired, foot_target=ft.reshape(T, B, 12).astype(np.float32), ext=ext, mass=true_mass, inertia=inertia,
-                fall=np.arange(B) % 64 == 63, noise=rng.uniform(-1.0, 1.0, (T, B, 12)))
-
-
-def _stream_grf(model, cfg, s, k):
-    """The grf row of tick k, float32 [B,12]: so that the streams keep the robots near their stance (feet the chain can
-    reach) without a controller, the forces are the least-norm ones over the tick's stance feet of a wrench that holds the
-    TRUE weight and damps height, tilt and velocities, computed from the MODEL's state before the tick, plus the stream's
-    noise.  Deterministic given the seed; the kernels and the model are handed the same float32 values."""
-    st, B = model.state, model.B
-    R = np.stack(M.quat_rot([st[M.ROW_QUAT + i] for i in range(4)]), 1).reshape(B, 3, 3)
-    p, v, w = st[M.ROW_P:M.ROW_P + 3].T, st[M.ROW_V:M.ROW_V + 3].T, st[M.ROW_W:M.ROW_W + 3].T
-    wrench = np.zeros((B, 6))
-    wrench[:, :3] = -8.0 * s["mass"][:, None] * v
-    wrench[:, 2] += s["mass"] * (cfg.gravity + 60.0 * (cfg.body_height - p[:, 2]))
-    tilt = np.stack([np.arctan2(R[:, 2, 1], R[:, 2, 2]), -np.arcsin(np.clip(R[:, 2, 0], -1, 1)), np.zeros(B)], 1)
-    Idiag = np.asarray(cfg.inertia)[[0, 4, 8]]
-    wrench[:, 3:] = np.einsum("bij,bj->bi", R, Idiag * (-80.0 * tilt - 12.0 * np.einsum("bji,bj->bi", R, w)))
-    stance = s["desired"][k] == 1
-    A = np.zeros((B, 6, 12))
-    for l in range(4):
-        r = st[M.ROW_FOOT + 3 * l:M.ROW_FOOT + 3 * l + 3].T - p
-        # a swing foot that comes down this tick lands where it is, at z = 0
-        r[:, 2] = np.where(stance[:, l] & (st[M.ROW_STANCE + l] == 0), -p[:, 2], r[:, 2])
-        on = stance[:, l].astype(np.float64)
-        for c in range(3):
-            A[:, c, 3 * l + c] = on
-        A[:, 3, 3 * l + 1], A[:, 3, 3 * l + 2] = -r[:, 2] * on, r[:, 1] * on
-        A[:, 4, 3 * l], A[:, 4, 3 * l + 2] = r[:, 2] * on, -r[:, 0] * on
-        A[:, 5, 3 * l], A[:, 5, 3 * l + 1] = -r[:, 1] * on, r[:, 0] * on
-    ok = np.isfinite(A).all((1, 2)) & np.isfinite(wrench).all(1)
-    f = np.zeros((B, 12))
-    f[ok] = np.einsum("bij,bj->bi", np.linalg.pinv(A[ok], rcond=1e-6), wrench[ok])
-    f = f.reshape(B, 4, 3) + 1.5 * s["noise"][k].reshape(B, 4, 3)
-    grf = -np.einsum("bji,blj->bli", R, f)                # body frame, negated: what the controller's grf output holds
-    grf[np.isfinite(grf) == False] = 0.0                 # noqa: E712
-    if k >= 45:
-        grf[s["fall"]] = 0.0
-    return grf.reshape(B, 12).astype(np.float32)
-
+# ---- the kernels against the model (streams and comparison: tests/srb_streams.py) ----
 
 @pytest.mark.parametrize("robot,seed", [("ghost", 101), ("k3lso", 102)])
 def test_kernel_vs_model(robot, seed, dev):
@@ -144,7 +64,7 @@ def test_kernel_vs_model(robot, seed, dev):
     from robot_gym_amd.sim import BatchedSRBSim
     B, T = 4096, 100
     cfg = MPCConfig.for_robot(robot)
-    s = _streams(cfg, B, T, seed)
+    s = S.streams(cfg, B, T, seed)
     rng = np.random.default_rng(seed + 1000)
     sim, model = BatchedSRBSim(B, cfg, device=dev), M.SRBModel(B, cfg)
     assert bool(sim.fallen().all()) and model.fallen().all()          # nothing runs before its reset
@@ -154,32 +74,11 @@ def test_kernel_vs_model(robot, seed, dev):
     xy, yaw, hs = rng.uniform(-2, 2, (B, 2)), rng.uniform(-np.pi, np.pi, B), cfg.body_height * rng.uniform(0.9, 1.1, B)
     sim.reset(xy=xy, yaw=yaw, height=hs)
     model.reset(xy=xy, yaw=yaw, height=hs)
-    int_rows = list(range(M.ROW_STANCE, M.ROW_STANCE + 4)) + [M.ROW_STEPS, M.ROW_STATUS]
-    q_rows = list(range(M.ROW_Q, M.ROW_Q + 12))
-    f_rows = [r for r in range(M.STATE_ROWS) if r not in int_rows and r not in q_rows]
-    worst = dict(state_rel=0.0, q_abs=0.0, obs_ulp=0.0, qjac_ulp=0.0)
-    bad = dict(ints=0, t_robot=0, contact=0, state=0, q=0, obs=0, qjac=0)
+    cmp = S.Comparison()
+    worst, bad = cmp.worst, cmp.bad
 
     def check():
-        st = sim.state.cpu().numpy()
-        obs = {k: v.cpu().numpy() for k, v in sim.obs.items()}
-        ms = model.state
-        bad["ints"] += int((st[int_rows] != ms[int_rows]).sum())
-        bad["t_robot"] += int((obs["t_robot"] != model.obs["t_robot"]).sum())
-        bad["contact"] += int((obs["contact"] != model.obs["contact"]).sum())
-        rel = np.abs(st[f_rows] - ms[f_rows]) / np.maximum(1.0, np.abs(ms[f_rows]))
-        worst["state_rel"] = max(worst["state_rel"], float(rel.max()))
-        bad["state"] += int((~(rel <= REL_TOL)).sum())
-        dq = np.abs(st[q_rows] - ms[q_rows])
-        worst["q_abs"] = max(worst["q_abs"], float(dq.max()))
-        bad["q"] += int((~(dq <= Q_TOL)).sum())
-        for name in ("rpy", "rpy_rate", "v_world", "quat", "foot_pos", "q", "jac"):
-            want = model.obs[name]
-            ulps = np.abs(obs[name].astype(np.float64) - want.astype(np.float64)) / np.spacing(np.abs(want)).astype(np.float64)
-            key, n = ("qjac_ulp", Q_ULP) if name in ("q", "jac") else ("obs_ulp", 1)
-            worst[key] = max(worst[key], float(ulps.max()))
-            ok = _within_ulps(obs[name], want, n) if name in ("q", "jac") else within_ulp(obs[name], want)
-            bad["qjac" if name in ("q", "jac") else "obs"] += int((~ok).sum())
+        cmp.check(sim.state.cpu().numpy(), {k: v.cpu().numpy() for k, v in sim.obs.items()}, model.state, model.obs)
 
     check()
     seen = dict(swing=0, stance=0, liftoff=0, touchdown=0)
@@ -195,7 +94,7 @@ def test_kernel_vs_model(robot, seed, dev):
             seen["touchdown"] += int(((s["desired"][k - 1] == 0) & (d == 1)).sum())
         seen["swing"] += int((d == 0).sum())
         seen["stance"] += int((d == 1).sum())
-        grf = _stream_grf(model, cfg, s, k)
+        grf = S.stream_grf(model, cfg, s, k)
         outputs = dict(grf=torch.as_tensor(grf, device=dev), foot_target=torch.as_tensor(s["foot_target"][k], device=dev),
                        desired_state=torch.as_tensor(d, device=dev))
         ext = s["ext"][k] if k % 3 else None       # every third tick without a wrench: the NULL path
