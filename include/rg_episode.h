@@ -1,0 +1,180 @@
+/*
+ * rg_episode.h -- C-ABI of the episode reset of librg_mpc.so: what BatchedGoEnv.reset(idx) does on the host -- draw a target,
+ * plan a path, build its tables, put the robot at the path's start, observe -- for the robots a DEVICE mask names, with no
+ * host in the loop.  With it a vectorised environment resets finished robots inside its step.
+ *
+ * It restates robot_gym_amd/gym/goto_path.py (plan_path, build_path) for the device and reuses the reset of the simulator
+ * (rg_srb.h) and the observation of the task (rg_goto.h) as they are: the device code of both is shared, not copied.
+ *
+ * Conventions (those of rg_goto.h)
+ *   - return 0 on success, a negative rg_episode_status otherwise; nothing throws across the ABI; rg_episode_last_error()
+ *     gives the text of the last failure on a handle (or of create(), with a NULL handle).
+ *   - the CALLER owns every buffer (device memory).  The handle holds the three configurations and the leg kinematics.
+ *   - all work is enqueued on the hipStream_t passed in (NULL = default stream); NO call synchronises or stages anything.
+ *   - one handle per (device, stream); calls on one handle are not thread-safe.  Every call leaves the calling thread's
+ *     current HIP device as it found it.
+ *   - every value is computed in IEEE float64 with floating-point contraction off.
+ *
+ * Episode state (owned by the caller): double episode_state[RG_EPISODE_ROWS][B], component-major, integers stored as
+ * exactly representable doubles, rows
+ *      0  episode      number of resets on the device this robot has had (the index of its next drawn target)
+ *      1  plan_status  RG_EPISODE_PLAN_* of the robot's last reset attempt
+ *      2  return       sum of the rewards of the running episode (rg_episode_accumulate)
+ *      3  length       its number of ticks
+ *      4  last_return  return ...
+ *      5  last_length  ... length ...
+ *      6  last_reason  ... and done_reason (RG_GOTO_REASON_*) of the episode that ended last, latched at the reset
+ *      7  npts         path points of the current plan
+ *      8  nway         way points of the current plan (start, descent cells, target)
+ *      9  key          the robot's key in the target stream.  THE CALLER INITIALISES IT, usually to the robot's index, and
+ *                      nothing here writes it: a clone copies the column, so a cloned robot draws the targets its source
+ *                      draws.  The stream is keyed by this row, never by the robot's position in the batch.
+ *     10  ended        1 from the tick that ended the episode until the reset: accumulate skips the robot
+ *     11  reserved
+ *   Save, restore and clone are plain copies of columns.
+ *
+ * rg_episode_reset, per robot b with mask[b] != 0 (a robot whose mask is 0 costs its wave a load or two and an exit)
+ *   a. Target.  targets[0][b], targets[1][b] if both are not NaN (an infinite entry is taken and fails the plan); otherwise,
+ *      or with targets == NULL, a draw.  The stream is a counter-based hash, stateless: with
+ *          mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31   (uint64)
+ *          h = seed;  for w in (key, episode, attempt, axis):  h = mix((h ^ w) + 0x9E3779B97F4A7C15)
+ *          u = (h >> 11) * 2^-53
+ *      key and episode are the robot's rows 9 and 0 as uint64, attempt counts from 0, axis is 0 (x) or 1 (y).  Then
+ *      v = -2.5 + 5 u, c = rint(100 v), 0 < c < 100 -> 100, -100 < c < 0 -> -100, coordinate = (c + 0.0) / 100.0 (the sum
+ *      turns -0.0 into 0.0).  (0, 0) is drawn again with attempt + 1 (at most 64 times).  This restates go_env.py:163-175 /
+ *      goto_path.random_target for a stream that does not depend on who else resets; it is NOT bit-compatible with numpy's
+ *      generator.  tests/episode_model.py is the stream in numpy.
+ *   b. Plan.  goto_path.plan_path: steepest descent over the 8 neighbours in MOTION order ((1,0), (0,1), (-1,0), (0,-1),
+ *      (-1,-1), (-1,1), (1,-1), (1,1); the first of equally low neighbours wins, cells outside the grid are +inf) on the
+ *      potential (0.5 kp) hypot(x - gx, y - gy) [+ (0.5 eta) (1 / max(dq, 0.1) - 1 / robot_radius)^2 where the distance dq to the
+ *      nearest obstacle is <= robot_radius; of equally near obstacles the last wins], evaluated at the cells it visits,
+ *      cell coordinates ix * grid + minx with minx, xw, ... formed as _potential_map forms them (no obstacle: its dummy one at
+ *      (area_width + 1, area_width + 1)).  Stops when hypot(target - cell) < grid or the last `oscillation_length` cells
+ *      hold a repeat; the target is appended.  hypot is the device's, not libm's: potentials are only compared with each
+ *      other and their gaps are far above an ulp, but the stop test can go the other way where the distance is within
+ *      an ulp or two of the grid step.
+ *   c. Path.  goto_path.build_path: n = int(length of the way points / spacing) points at i * (length / (n - 1)) by
+ *      interpolate_along's segment rule, none past length + 1e-6; s by arc_table's IN-ORDER sum; first_same_x; the header
+ *      (n, length of the interpolated polyline, target).  sqrt, division, multiplication and addition are correctly
+ *      rounded, so x, y, s, first_same_x and the header are bit-identical to numpy's for the same way points.  Written
+ *      straight into the caller's path slab.
+ *   d. Failure.  RG_EPISODE_PLAN_TARGET (a non-finite target), _WAYPOINTS (more than max_waypoints way points, or a
+ *      descent with no finite neighbour), _SHORT (n < 2), _LONG (n > n_max).  Nothing of the robot is reset or written then
+ *      (every check comes before the first store to its path rows): it stays done and frozen, row 1 says which case,
+ *      reset_mask_out[b] = 0.  The robot-local form of build_path's ValueError.
+ *   e. For robots whose plan succeeded: rows 4..6 are latched from rows 2, 3 and the task's done_reason, rows 2, 3 and 10
+ *      zeroed, row 0 incremented; the task-state column is zeroed (as rg_goto_set_path does); the simulator is reset at
+ *      p = (x[0], y[0], body_height), yaw = build_path's start_angle (atan2 of the first segment, in [0, 2 pi)), everything
+ *      else exactly as rg_srb_reset writes it; steps 1 and 2 of the task's tick (rg_goto_observe) give obs;
+ *      reset_mask_out[b] = 1 -- the mask rg_mpc_reset_masked takes.
+ *   For EVERY robot with mask[b] != 0, whatever its plan: final_obs column b = obs column b as it was before the call.
+ *   reset_mask_out[b] = 0 for every other robot after the call (the buffer must hold zeros before its first use: a robot
+ *   whose mask is 0 only clears a flag it finds set).
+ *
+ * Launches: a plan kernel (target, plan, path, latch; one 64-lane wave per robot, way points and tables in LDS) and a
+ * reset kernel (simulator reset on four lanes, observation on the wave), both with wave-uniform branches around every
+ * cross-lane operation.  rg_episode_accumulate is one thread per robot.
+ */
+#ifndef RG_EPISODE_H
+#define RG_EPISODE_H
+
+#include <stdint.h>
+#include "rg_goto.h"
+#include "rg_srb.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define RG_EPISODE_ABI_VERSION 1
+#define RG_EPISODE_ROWS 12
+#define RG_EPISODE_ROW_EPISODE 0
+#define RG_EPISODE_ROW_PLAN_STATUS 1
+#define RG_EPISODE_ROW_RETURN 2
+#define RG_EPISODE_ROW_LENGTH 3
+#define RG_EPISODE_ROW_LAST_RETURN 4
+#define RG_EPISODE_ROW_LAST_LENGTH 5
+#define RG_EPISODE_ROW_LAST_REASON 6
+#define RG_EPISODE_ROW_NPTS 7
+#define RG_EPISODE_ROW_NWAY 8
+#define RG_EPISODE_ROW_KEY 9
+#define RG_EPISODE_ROW_ENDED 10
+#define RG_EPISODE_MAX_WAYPOINTS 64
+#define RG_EPISODE_MAX_OBSTACLES 16
+#define RG_EPISODE_MAX_OSCILLATION 8
+#define RG_EPISODE_MAX_BATCH (1 << 24)
+#define RG_EPISODE_DEVICE_NONE (-1) /* create(): a host-only handle, see rg_episode_create */
+
+#define RG_EPISODE_PLAN_OK 0
+#define RG_EPISODE_PLAN_TARGET 1
+#define RG_EPISODE_PLAN_WAYPOINTS 2
+#define RG_EPISODE_PLAN_SHORT 3
+#define RG_EPISODE_PLAN_LONG 4
+
+typedef enum {
+  RG_EPISODE_OK = 0,
+  RG_EPISODE_ERR_INVALID = -1,   /* bad argument / configuration (the text names the field) */
+  RG_EPISODE_ERR_HIP = -2,       /* HIP runtime error (text in last_error) */
+  RG_EPISODE_ERR_NO_DEVICE = -3, /* no usable GPU */
+  RG_EPISODE_ERR_ALLOC = -4
+} rg_episode_status;
+
+/* The defaults (robot_gym_amd/core/episode_abi.py) are goto_path.py's constants; every one is a field. */
+typedef struct {
+  int32_t abi_version;         /* RG_EPISODE_ABI_VERSION */
+  int32_t reserved0;           /* must be 0 */
+  double kp;                   /* 5.0    attractive potential gain */
+  double eta;                  /* 100.0  repulsive potential gain */
+  double area_width;           /* 5.0    margin of the potential area around start, target and obstacles */
+  double grid;                 /* 0.5    cell size */
+  double robot_radius;         /* 0.25   reach of the repulsive potential */
+  double spacing;              /* 0.01   path point spacing */
+  uint64_t seed;               /* of the target stream */
+  int32_t oscillation_length;  /* 3      (1 .. RG_EPISODE_MAX_OSCILLATION) */
+  int32_t max_waypoints;       /* 64     way points of a plan at most, start and target included (2 .. RG_EPISODE_MAX_WAYPOINTS) */
+  int32_t num_obstacles;       /* 0      (0 .. RG_EPISODE_MAX_OBSTACLES), shared by the batch */
+  int32_t reserved1;           /* must be 0 */
+  double obstacles[RG_EPISODE_MAX_OBSTACLES][2]; /* x, y; entries past num_obstacles must be finite and are not read */
+} rg_episode_config;
+
+typedef struct rg_episode_handle rg_episode_handle;
+
+/* Validates ecfg (abi_version, reserved fields, finite values, positive kp / area_width / grid / robot_radius / spacing,
+ * eta >= 0, the integer ranges above, finite obstacles), then scfg and gcfg exactly as rg_srb_create and rg_goto_create do
+ * (their texts, prefixed "srb " / "goto "), and batch (1 .. RG_EPISODE_MAX_BATCH), all BEFORE it looks for a device.  scfg and
+ * gcfg are the configurations the simulator and the task were created with.  device = RG_EPISODE_DEVICE_NONE makes a
+ * host-only handle: every later call checks its arguments (RG_EPISODE_ERR_INVALID, naming the argument) and, where they
+ * are valid, returns RG_EPISODE_ERR_NO_DEVICE. */
+int rg_episode_create(const rg_episode_config *ecfg, const rg_srb_config *scfg, const rg_goto_config *gcfg, int32_t batch, int32_t device,
+                      rg_episode_handle **out);
+void rg_episode_destroy(rg_episode_handle *h);
+const char *rg_episode_last_error(const rg_episode_handle *h);   /* h may be NULL: the last create() failure of this thread */
+int32_t rg_episode_abi_version(void);
+int32_t rg_episode_config_size(void);
+int32_t rg_episode_state_rows(void);
+
+/* The reset described at the top of this file.  Device pointers:
+ *   mask            int32 [B]                       which robots (an environment passes its `done` output)
+ *   targets         float64 [2][B], or NULL         NaN entries (or NULL) are drawn
+ *   episode_state   float64 [RG_EPISODE_ROWS][B]
+ *   task_state      float64 [RG_GOTO_STATE_ROWS][B]
+ *   sim_state       float64 [RG_SRB_STATE_ROWS][B]
+ *   sim_obs         the simulator's observation tensors
+ *   paths           the task's path slab
+ *   obs, final_obs  float32 [2 * num_cam_pts][B]
+ *   reset_mask_out  int32 [B], must not alias mask
+ * Every pointer but targets is required. */
+int rg_episode_reset(rg_episode_handle *h, const int32_t *mask, const double *targets, double *episode_state, double *task_state,
+                     double *sim_state, const rg_srb_obs_ptrs *sim_obs, const rg_goto_path_ptrs *paths, float *obs, float *final_obs,
+                     int32_t *reset_mask_out, void *stream);
+
+/* After a tick, before the reset: for every robot whose row `ended` is 0, return += reward[b], length += 1, and
+ * ended = 1 if done[b] != 0 -- so the terminal reward is counted and the frozen ticks after it are not.  reward float32 [B],
+ * done int32 [B], device pointers. */
+int rg_episode_accumulate(rg_episode_handle *h, double *episode_state, const float *reward, const int32_t *done, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RG_EPISODE_H */

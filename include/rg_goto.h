@@ -85,7 +85,8 @@
  *   3. The reference moves its window incrementally with rotate and translate, so rounding accumulates; here the window
  *      comes from the pose each tick.
  *   4. The follower's velocity, its cam_* points and the plots are not ported.
- *   5. There is no auto-reset: a reset is a host call (rg_srb_reset takes host arrays).
+ *   5. The tick does not reset a robot that is done.  rg_goto_set_path / rg_srb_reset are host calls; the reset on the
+ *      device, for the robots a device mask names, is rg_episode.h (a vectorised environment calls it after post_step).
  *   6. The reference's interpolate_points raises on a chain of zero length (coincident points); here the latch is kept.
  */
 #ifndef RG_GOTO_H

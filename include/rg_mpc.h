@@ -229,6 +229,11 @@ int rg_mpc_reset(rg_mpc_handle *h, const int32_t *idx_host, int32_t n, double t0
  * 0..n-1).  Lets a vectorised env reset its sub-envs at different times in one call. */
 int rg_mpc_reset_at(rg_mpc_handle *h, const int32_t *idx_host, const double *t0_host, int32_t n, void *stream);
 
+/* The reset of rg_mpc_reset for every robot b with mask_dev[b] != 0: mask_dev is a DEVICE int32 [B] (e.g. the mask an
+ * episode reset on the device wrote, rg_episode.h), one clock value t0 for all of them (a closed-loop simulator restarts
+ * its t_robot at 0).  Fully asynchronous: no staging, no wait; a robot whose mask is 0 is not touched. */
+int rg_mpc_reset_masked(rg_mpc_handle *h, const int32_t *mask_dev, double t0, void *stream);
+
 /* MPCController.update_controller_params (mpc_controller.py:83-100): cmd = [3][B] device
  * pointer, offsets already added.  Copied into the handle. */
 int rg_mpc_set_command(rg_mpc_handle *h, const float *cmd, void *stream);

@@ -343,6 +343,14 @@ class BatchedMPCController:
             idx = [int(i) for i in (idx.tolist() if hasattr(idx, "tolist") else idx)]
         self._handle.reset(idx, t0, self._stream())
 
+    def reset_masked(self, mask, t0=0.0):
+        """reset() for the robots b with mask[b] != 0: mask is a contiguous int32 [batch] tensor on this device (the mask an
+        episode reset on the device wrote).  Enqueued on the current stream: no host copy, no wait."""
+        if not torch.is_tensor(mask) or mask.dtype != torch.int32 or tuple(mask.shape) != (self.batch,) or not mask.is_contiguous() \
+                or mask.device != self.device:
+            raise ValueError(f"reset_masked: mask must be a contiguous int32 [{self.batch}] tensor on {self.device}")
+        self._handle.reset_masked(mask.data_ptr(), t0, self._stream())
+
     def reset_at(self, t0s, idx=None):
         """Per-robot reset clock values (phase offsets between sub-envs)."""
         self._handle.reset_at(list(t0s), None if idx is None else list(idx), self._stream())

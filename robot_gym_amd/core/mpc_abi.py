@@ -52,7 +52,7 @@ class COutPtrs(C.Structure):
     _fields_ = [(n, fp) for n in ("action", "grf", "tau_stance", "leg_state", "desired_state", "phase", "foot_target", "v_body")]
 
 
-EXPORTS = ("rg_mpc_create", "rg_mpc_reset", "rg_mpc_reset_at", "rg_mpc_set_command", "rg_mpc_set_gait", "rg_mpc_set_body", "rg_mpc_state_layout", "rg_mpc_state_check", "rg_mpc_save_state", "rg_mpc_load_state", "rg_mpc_copy_state", "rg_mpc_step", "rg_mpc_step_host", "rg_mpc_hybrid_to_torque",
+EXPORTS = ("rg_mpc_create", "rg_mpc_reset", "rg_mpc_reset_at", "rg_mpc_reset_masked", "rg_mpc_set_command", "rg_mpc_set_gait", "rg_mpc_set_body", "rg_mpc_state_layout", "rg_mpc_state_check", "rg_mpc_save_state", "rg_mpc_load_state", "rg_mpc_copy_state", "rg_mpc_step", "rg_mpc_step_host", "rg_mpc_hybrid_to_torque",
            "rg_mpc_hybrid_to_torque_substeps",
            "rg_mpc_last_bin_counts", "rg_mpc_last_solver_stats", "rg_mpc_last_iterations", "rg_mpc_audit_stats", "rg_mpc_last_direct_count", "rg_mpc_profile_begin", "rg_mpc_profile_stride", "rg_mpc_profile_end", "rg_mpc_kernel_names", "rg_mpc_plan_description", "rg_mpc_profile_window_names", "rg_mpc_debug_poison_lds", "rg_mpc_destroy", "rg_mpc_last_error",
            "rg_mpc_abi_version", "rg_mpc_config_size")
@@ -76,6 +76,8 @@ def load_library(path=None):
     L.rg_mpc_reset.restype = i32
     L.rg_mpc_reset_at.argtypes = [fp, C.POINTER(i32), C.POINTER(d), i32, fp]
     L.rg_mpc_reset_at.restype = i32
+    L.rg_mpc_reset_masked.argtypes = [fp, fp, d, fp]
+    L.rg_mpc_reset_masked.restype = i32
     L.rg_mpc_set_command.argtypes = [fp, fp, fp]
     L.rg_mpc_set_command.restype = i32
     L.rg_mpc_step.argtypes = [fp, d, C.POINTER(CStatePtrs), C.POINTER(COutPtrs), fp]
@@ -227,6 +229,10 @@ class MpcHandle:
         t0 = (d * n)(*[float(x) for x in t0s])
         ia = None if idx is None else (i32 * n)(*[int(i) for i in idx])
         self._check(self._lib.rg_mpc_reset_at(self._h, ia, t0, n, stream))
+
+    def reset_masked(self, mask_ptr, t0=0.0, stream=None):
+        """rg_mpc_reset_masked: mask_ptr is a DEVICE int32 [batch]; nothing is staged and nothing waits."""
+        self._check(self._lib.rg_mpc_reset_masked(self._h, mask_ptr, float(t0), stream))
 
     def set_command(self, cmd_ptr, stream=None):
         self._check(self._lib.rg_mpc_set_command(self._h, cmd_ptr, stream))

@@ -62,17 +62,9 @@ __global__ void rg_reset_kernel(const DevCfg *__restrict__ c, DevState st, const
   if (k >= n) return;
   int b = idx ? idx[k] : k;
   if (b < 0 || b >= B) return;
-  st.reset_time[b] = t0v ? t0v[k] : t0;
-  st.flags[b] = 3;
-  int ld = 0;
-  for (int l = 0; l < 4; l++) ld |= ((st.g_init ? st.g_init[l * B + b] : c->init_state[l]) & 1) << l;
-  st.last_desired[b] = ld;
-  st.ring_len[b] = 0; st.ring_head[b] = 0;
-  for (int a = 0; a < 3; a++) { st.fsum[a * B + b] = 0.0; st.fcorr[a * B + b] = 0.0; }
-  st.swing_valid[b] = 0;
-  st.warm_key[b] = -1;
-  st.hard[b] = 0;    // a reset robot is a fresh robot: ADMM first, no direct routing, no cost prediction from before
-  st.iters[b] = 0;
+#define RG_RESET_T0 (t0v ? t0v[k] : t0)
+#include "rg_reset_body.inc"
+#undef RG_RESET_T0
 }
 
 // RobotMotorModel.convert_to_torque HYBRID (reference model/robots/simple_motor.py:128-140), for S consecutive
@@ -505,6 +497,15 @@ int rg_mpc_reset(rg_mpc_handle *h, const int32_t *idx_host, int32_t n, double t0
 int rg_mpc_reset_at(rg_mpc_handle *h, const int32_t *idx_host, const double *t0_host, int32_t n, void *stream) {
   if (h && !t0_host) { h->err = "reset_at: null t0 array"; return RG_MPC_ERR_INVALID; }
   return reset_impl(h, idx_host, t0_host, n, 0.0, stream);
+}
+
+int rg_mpc_reset_masked(rg_mpc_handle *h, const int32_t *mask_dev, double t0, void *stream) {
+  if (!h) return RG_MPC_ERR_INVALID;
+  if (!mask_dev) { h->err = "reset_masked: null mask"; return RG_MPC_ERR_INVALID; }
+  if (!std::isfinite(t0)) { h->err = "reset_masked: t0 is not finite"; return RG_MPC_ERR_INVALID; }
+  DeviceScope dev_(h->device); HIPCHK(h, dev_.err);
+  HIPCHK(h, rg_state_reset_masked(h->dcfg, h->st, h->B, mask_dev, t0, (hipStream_t)stream));
+  return RG_MPC_OK;
 }
 
 int rg_mpc_set_command(rg_mpc_handle *h, const float *cmd, void *stream) {

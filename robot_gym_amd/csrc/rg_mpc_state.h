@@ -8,6 +8,7 @@
 #include <string>
 
 struct DevState;
+struct DevCfg;
 
 #define RG_STATE_MAGIC 0x54534752u   // "RGST"
 #define RG_STATE_VERSION 1
@@ -48,3 +49,8 @@ hipError_t rg_state_gather(const RgStateLayout &L, const DevState &st, int B, co
                            uint32_t *rows, hipStream_t s);
 hipError_t rg_state_scatter(const RgStateLayout &L, const DevState &st, int B, const int *idx, int n, const uint32_t *rows,
                             const double *shift, hipStream_t s);
+
+// rg_reset_kernel's work (rg_reset_body.inc) for every robot b with mask[b] != 0; mask: device int32 [B].  Enqueued on s,
+// no staging, no wait.  The kernel and this launcher are in rg_episode.hip: the kernel sets of rg_mpc.hip and rg_mpc_state.hip
+// are pinned by tests.
+hipError_t rg_state_reset_masked(const DevCfg *cfg_dev, const DevState &st, int B, const int *mask, double t0, hipStream_t s);

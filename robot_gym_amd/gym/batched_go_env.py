@@ -9,14 +9,19 @@ six termination causes (include/rg_goto.h).  The planner and the path builder ru
     obs = env.reset()                         # [B, 16] float32 device tensor
     obs, reward, done = env.step(action)      # action [B, 2] (vx, wz) device tensor; no synchronisation, no host copy
 
-obs, reward and done are views of buffers the next step overwrites.  There is no auto-reset: a done robot stays frozen
-(reward 0, done 1, its last observation) until reset(idx).
+obs, reward and done are views of buffers the next step overwrites.  By default there is no auto-reset: a done robot stays
+frozen (reward 0, done 1, its last observation) until reset(idx) -- host work -- or reset_on_device() -- none.
+
+    env = BatchedGoEnv(B, cfg, auto_reset=True)   # step() resets finished robots on the device (include/rg_episode.h)
+    obs, reward, done = env.step(action)          # the usual vector-env contract: on the tick a robot finishes, reward and
+                                                  # done are the terminal ones, obs is the first observation of its next
+                                                  # episode and env.final_obs holds the terminal one
 """
 import numpy as np
 import torch
 
 from robot_gym_amd.controllers.mpc.batched import BatchedMPCController
-from robot_gym_amd.core import goto_abi
+from robot_gym_amd.core import episode_abi, goto_abi
 from robot_gym_amd.core.config import MPCConfig
 from robot_gym_amd.gym import goto_path
 from robot_gym_amd.sim.srb import BatchedSRBSim
@@ -25,9 +30,12 @@ from robot_gym_amd.sim.srb import BatchedSRBSim
 class BatchedGoEnv:
     """Owns ctl (BatchedMPCController), sim (BatchedSRBSim) and the task (goto_abi.GotoHandle) with its buffers:
     task_state float64 [50, B], the path slab (path_x / path_y / path_s float64 [B, n_max], path_first_same_x int32
-    [B, n_max], path_hdr float64 [4, B]) and the outputs."""
+    [B, n_max], path_hdr float64 [4, B]) and the outputs; and the episode reset on the device (episode_abi.EpisodeHandle)
+    with episode_state float64 [12, B] (rows: rg_episode.h), final_obs and reset_mask int32 [B] (the robots the last
+    reset_on_device reset).  episode_settings: planner settings of episode_abi.DEFAULTS other than the seed."""
 
-    def __init__(self, batch, cfg: MPCConfig = None, targets=None, obstacles=None, seed=0, device=None, sim_settings=None, **task):
+    def __init__(self, batch, cfg: MPCConfig = None, targets=None, obstacles=None, seed=0, device=None, sim_settings=None, auto_reset=False,
+                 episode_settings=None, **task):
         # The default robot is ghost WITH ITS COMMAND OFFSETS ZEROED: vy_offset / wz_offset trim a drift of the reference's
         # PyBullet robot that the reduced model does not have, and with them a straight command walks a curve off the path.
         # A cfg passed in is taken as it is, offsets included.
@@ -59,11 +67,55 @@ class BatchedGoEnv:
         self.obstacles = () if obstacles is None else obstacles
         self.targets = np.zeros((B, 2))
         self.paths = [None] * B
+        self.auto_reset = bool(auto_reset)
+        self._episode = episode_abi.EpisodeHandle(B, self.cfg, dev, obstacles=self.obstacles, sim_settings=sim_settings, task_settings=task,
+                                                  seed=seed, **(episode_settings or {}))
+        self.episode_state = torch.zeros(episode_abi.ROWS, B, dtype=torch.float64, device=dev)
+        self.episode_state[episode_abi.ROW_KEY] = torch.arange(B, dtype=torch.float64, device=dev)   # the robot's key in the target stream
+        self._final_obs_cm = torch.zeros_like(self._obs_cm)
+        self.reset_mask = torch.zeros(B, dtype=torch.int32, device=dev)
+        # the constructor's targets as a per-robot device table, uploaded once
+        self._target_table = None
+        if self._fixed_targets is not None:
+            tab = self._fixed_targets[np.arange(B) % len(self._fixed_targets)]
+            self._target_table = torch.as_tensor(np.ascontiguousarray(tab.T), device=dev)
+        self._mirrors_stale = False
 
     @property
     def obs(self):
         """[B, 2 * num_cam_pts] view of the observation buffer."""
         return self._obs_cm.t()
+
+    @property
+    def final_obs(self):
+        """[B, 2 * num_cam_pts] view: the observation each robot had before its last reset on the device (the terminal one)."""
+        return self._final_obs_cm.t()
+
+    @property
+    def episode_count(self):
+        """int64 [B]: resets on the device each robot has had."""
+        return self.episode_state[episode_abi.ROW_EPISODE].to(torch.int64)
+
+    @property
+    def last_return(self):
+        """float64 [B]: return of the episode each robot ended last (latched at its reset on the device)."""
+        return self.episode_state[episode_abi.ROW_LAST_RETURN]
+
+    @property
+    def last_length(self):
+        """int64 [B]: ticks of that episode."""
+        return self.episode_state[episode_abi.ROW_LAST_LENGTH].to(torch.int64)
+
+    @property
+    def last_reason(self):
+        """int64 [B]: RG_GOTO_REASON_* of that episode."""
+        return self.episode_state[episode_abi.ROW_LAST_REASON].to(torch.int64)
+
+    @property
+    def plan_status(self):
+        """int64 [B]: RG_EPISODE_PLAN_* of each robot's last reset on the device (episode_abi.PLAN_STATUS names them); a robot
+        whose plan failed was not reset and stays done."""
+        return self.episode_state[episode_abi.ROW_PLAN_STATUS].to(torch.int64)
 
     @property
     def done_reason(self):
@@ -107,6 +159,12 @@ class BatchedGoEnv:
             self.paths[b], self.targets[b] = built[k], tg[k]
         rows = goto_path.pack_paths(built, self.n_max)
         whole = n == B and np.array_equal(idx, np.arange(B))
+        self._mirrors_stale = self._mirrors_stale and not whole
+        running = [episode_abi.ROW_RETURN, episode_abi.ROW_LENGTH, episode_abi.ROW_ENDED]   # a new episode: nothing accumulated yet
+        if whole:
+            self.episode_state[running] = 0.0
+        else:
+            self.episode_state[torch.as_tensor(running, device=self.device)[:, None], torch.as_tensor(idx, device=self.device)[None, :]] = 0.0
         self._handle.set_path(self._paths, self.task_state.data_ptr(), None if whole else idx, **rows)
         self.sim.reset(None if whole else idx, xy=np.array([p.start_xy for p in built]), yaw=np.array([p.start_angle for p in built]))
         self.ctl.reset(None if whole else idx)
@@ -125,21 +183,58 @@ class BatchedGoEnv:
         self.ctl.get_action(0.0, self.sim.obs)
         self.sim.step(self.ctl)
         self._handle.post_step(ts, ss, self._paths, self._obs_cm.data_ptr(), self.reward.data_ptr(), self.done.data_ptr())
+        if self.auto_reset:
+            self._episode.accumulate(self.episode_state.data_ptr(), self.reward.data_ptr(), self.done.data_ptr())
+            self.reset_on_device(self.done)
+            self.ctl.reset_masked(self.reset_mask)
         return self.obs, self.reward, self.done
 
+    def reset_on_device(self, mask=None, targets=None):
+        """reset() with no host work and no synchronisation, for the robots b with mask[b] != 0: target, plan, path, task state,
+        simulator and observation (include/rg_episode.h), enqueued on the current stream.  mask: int32 [B] tensor on this
+        device (None: self.done).  targets: float64 [B,2] or [2,B] tensor on this device (with B == 2: [B,2]); None: the
+        constructor's targets if it had any, else drawn from the device's target stream; NaN entries are drawn too.
+        Usable with or without auto_reset.  It writes self.reset_mask (1 where a robot was reset, 0 elsewhere and where the
+        plan failed: that robot stays done, plan_status says why) and self.final_obs; the CONTROLLER is reset by
+        self.ctl.reset_masked(self.reset_mask), which step() calls under auto_reset and a caller of this method calls itself.
+        The host mirrors self.paths / self.targets are maintained by reset() only: which robots were reset here is not known
+        on the host, so every entry becomes None (NaN in self.targets) until reset() fills it again.  Returns obs."""
+        B = self.batch
+        mask = self.done if mask is None else mask
+        if not torch.is_tensor(mask) or mask.dtype != torch.int32 or tuple(mask.shape) != (B,) or mask.device != self.device or not mask.is_contiguous():
+            raise ValueError(f"reset_on_device: mask must be a contiguous int32 [{B}] tensor on {self.device}")
+        if targets is None:
+            targets = self._target_table
+        else:
+            if not torch.is_tensor(targets) or targets.dtype != torch.float64 or targets.device != self.device or tuple(targets.shape) not in ((B, 2), (2, B)):
+                raise ValueError(f"reset_on_device: targets must be a float64 [{B},2] or [2,{B}] tensor on {self.device}")
+            targets = targets.t().contiguous() if tuple(targets.shape) == (B, 2) else targets.contiguous()
+        self._episode.reset(mask.data_ptr(), None if targets is None else targets.data_ptr(), self.episode_state.data_ptr(), self.task_state.data_ptr(),
+                            self.sim.state.data_ptr(), self.sim._obs_ptrs, self._paths, self._obs_cm.data_ptr(), self._final_obs_cm.data_ptr(),
+                            self.reset_mask.data_ptr())
+        if not self._mirrors_stale:
+            self.paths = [None] * B
+            self.targets[:] = np.nan
+            self._mirrors_stale = True
+        return self.obs
+
     def clone(self, src, dst):
-        """Branch rollouts: controller, simulator, task state and path of robot src[k] into robot dst[k].  For bit-identical
-        continuations keep dst = src modulo 16 (robot_gym_amd.sim.clone)."""
+        """Branch rollouts: controller, simulator, task state, path and episode state of robot src[k] into robot dst[k].  For
+        bit-identical continuations keep dst = src modulo 16 (robot_gym_amd.sim.clone).  The episode-state column carries the
+        robot's key in the target stream, so a clone draws the targets its source draws."""
         from robot_gym_amd.sim.srb import clone as sim_clone
         sim_clone(self.ctl, self.sim, src, dst)   # copies sim.obs too, the command among it
         s, t = self.sim._index(src), self.sim._index(dst)
         for ten, dim in ((self.task_state, 1), (self.path_hdr, 1), (self.path_x, 0), (self.path_y, 0), (self.path_s, 0),
-                         (self.path_first_same_x, 0), (self._obs_cm, 1)):
-            ten.index_copy_(dim, t, ten.index_select(dim, s))
+                         (self.path_first_same_x, 0), (self._obs_cm, 1), (self.episode_state, 1), (self._final_obs_cm, 1),
+                         (self._target_table, 1)):
+            if ten is not None:
+                ten.index_copy_(dim, t, ten.index_select(dim, s))
         sh, th = s.cpu().numpy(), t.cpu().numpy()
         for a, b in zip(sh, th):
             self.paths[b], self.targets[b] = self.paths[a], self.targets[a]
 
     def close(self):
+        self._episode.close()
         self._handle.close()
         self.sim.close()
