@@ -336,6 +336,7 @@ __device__ __forceinline__ bool exact_epilogue(const DevCfg *__restrict__ c, con
 // force space: one and two stance legs (N = 30 / 60 variables), 8 x 8 lanes with 8 x 8 register tiles of -G (rows reordered
 // for the DPP reduce-scatter, as in the ADMM loop); every lane owns one matrix row after the reduce
 // =====================================================================================================================
+constexpr bool RG_RANK5_H20 = false;
 template <int NC, int H, int Q, int LG = 3, int T = 8>
 struct ExactLds {
   static constexpr int m3 = 3 * NC, N = m3 * H, LC = 1 << LG, NT = LC * LC, NP = T * LC, TS = TileShape<T>::TS, NPAD = TS * LC, NPB = NPAD + 2, NB = N / 3;
@@ -345,6 +346,11 @@ struct ExactLds {
   static constexpr bool SYM6 = T == 8;
   static_assert(T == 4 || (N % 6 == 0 && ((LG == 3 && N <= 60) || (LG == 4 && N <= 120))), "8 x 8 tiles: the symmetric 6 x 6-block sweep covers the matrix");
   static constexpr int NBS = N / 6;                // block rows of the symmetric sweep
+  // two stance legs: one direction of every 6 x 6 block is known in closed form (force_space_rank5), the sweep runs on the
+  // 5 x 5 corners of the blocks (sym6_sweep<.., 5>: three pivot buffers) and sym5_back_transform restores the 6 x 6 blocks
+  // (RG_RANK5_H20: the 256-lane grid of horizon 20 keeps the 6 x 6 sweep -- with the set-up helper in it the hybrid horizon-20
+  // launch holds one more scalar across the solve than it has registers for, and the spill costs it a VGPR and 4 B of scratch)
+  static constexpr bool RANK5 = SYM6 && NC == 2 && (LG == 3 || RG_RANK5_H20);
   static constexpr int LAMC = (6 * NB + 63) / 64 * 64 < 128 ? 128 : (6 * NB + 63) / 64 * 64;
   // live through the solve
   static constexpr int rec = 0;                    // RG_REC_N
@@ -360,9 +366,11 @@ struct ExactLds {
   static constexpr int Tm = rv + Q;                // T = (C_A G C_A')^-1, zero beyond q x q
   // set-up only, dead once the tile is swept and q is on the owner lanes: ALIASED by T (which is zeroed after the set-up)
   static constexpr int pbuf = Tm;                  // the sweep's ping-pong pivot buffers
-  static constexpr int PBUF = SYM6 ? 2 * Sym6<SYM6 ? NBS : 1>::PB : 2 * NPB;
+  static constexpr int PBUF = SYM6 ? (RANK5 ? 3 : 2) * Sym6<SYM6 ? NBS : 1>::PB : 2 * NPB;
   static constexpr int GU = pbuf + PBUF, GV = GU + m3 * m3, c1 = GV + m3 * m3, c2 = c1 + N, Bw = c2 + N, TBw = Bw + 3 * m3;
-  static constexpr int setup_end = TBw + 3 * m3;
+  static constexpr int hv = TBw + 3 * m3;          // RG_RANK5_HV (RANK5) the reflector and what force_space_rank5 derives from it
+  static constexpr int setup_end = hv + (RANK5 ? RG_RANK5_HV : 0);
+  static_assert(GU % 2 == 0 && hv % 2 == 0, "16-byte loads of the Gram blocks and of the reflector");
   static constexpr int stage_end = SYM6 ? vv + Sym6<SYM6 ? NBS : 1>::STG : 0;   // staging area of sym6_to_tile8: from vv on
   template <bool PACKED> static constexpr int total = cmax(cmax((size_t)(Tm + ExactT<Q, PACKED>::doubles), (size_t)setup_end), (size_t)stage_end);
   // what stays live through sym6_to_tile8 ends where the staging area starts, and the staging area fits the layout
@@ -405,6 +413,7 @@ __device__ __forceinline__ void qp_exact_robot(const DevCfg *__restrict__ c, con
     cmask = (int)rec[REC_CONTACT];
     force_space_tables<NC, H, NT, false, MU4>(c, rec, cmask, tid, Bw, TBw, GU, GV, nullptr, nullptr, c1, c2);
     __syncthreads();
+    if constexpr (LY::RANK5) force_space_rank5<NT, MU4>(c, rec, cmask, tid, Bw, TBw, GU, GV, lds + LY::hv);
     // ---- my T x T tile of P = 2 (N (x) G_U + S (x) G_V) + alpha I (identity in the padding), and q of the row I own ----
     int lrv = tid >> LG, lcv = tid & (LC - 1);
     asm volatile("" : "+v"(lrv), "+v"(lcv));
@@ -429,7 +438,10 @@ __device__ __forceinline__ void qp_exact_robot(const DevCfg *__restrict__ c, con
       if constexpr (m3 == 6) sym6_build_kron6<H>(X, tabN, tabS, GU, GV, sbc, sbr, son, c->alpha);
       else sym6_build_kron3<H>(X, tabN, tabS, GU, GV, sbc, sbr, son, c->alpha);
       stamp_phase(1);
-      sym6_sweep<NBS, NBS, NT>(X, pbuf, sbr, sbc, son);
+      if constexpr (LY::RANK5) {
+        sym6_sweep<NBS, NBS, NT, 5>(X, pbuf, sbr, sbc, son);
+        sym5_back_transform(X, lds + LY::hv, sbr, sbc, son);   // (hv is read before sym6_to_tile8's first barrier frees the staging area)
+      } else sym6_sweep<NBS, NBS, NT>(X, pbuf, sbr, sbc, son);
       stamp_phase(2);
       sym6_to_tile8<NBS, NBS, LG, NT>(X, sbr, sbc, son, tile, lds + LY::vv, tid);
     } else {

@@ -30,12 +30,14 @@
 // Measured (tests/studies/sweep_bench.hip, profiles/r6_sweep_bench_study.txt; build + inversion + move, 60 x 60, us per robot):
 // 16.4 -> 14.9 alone, 28.1 -> 24.3 with two waves per SIMD; its floor without any LDS traffic is 17.2 under load, the three
 // ds_write_b128 of a pivot cost 4.7 and reading them back 2.4.  A CPU model of the index algebra: tests/test_sym6_model.py.
+// Two stance legs in force space sweep only the 5 x 5 corners of their blocks (sym6_sweep<.., 5>, sym5_back_transform below; CPU
+// model: tests/test_sym5_model.py).
 // ------------------------------------------------------------------------------------
 
 template <int NB> struct Sym6 {
   static constexpr int NBLK = NB * (NB + 1) / 2;   // lanes that hold a block
   static constexpr int DS = 6 * NB;                // slot of the pivot d behind the pivot vector
-  static constexpr int PB = 6 * NB + 2;            // doubles per pivot buffer (two of them: ping-pong)
+  static constexpr int PB = 6 * NB + 2;            // doubles per pivot buffer (two of them: ping-pong; three for the five-wide sweep)
   static constexpr int PB2 = 12 * NB + 4;          // ... of the two-pivot form: two rows and the 2 x 2 pivot block
   static constexpr int STG = NBLK * 36;            // doubles of the staging area of sym6_to_tile8
 };
@@ -110,8 +112,18 @@ __device__ __forceinline__ int sym6_lane_of(const int r, const int c) {
 template <int NB>
 __device__ __forceinline__ void sym6_groups(const int br, const int bc, int &gr, int &gc) { gr = bc; gc = br; }
 
-template <int NB, int NBR, int NT>
+// W: the active edge of every block.  W = 6 is the sweep above.  W = 5 sweeps the 5 NB x 5 NB matrix whose blocks are the leading
+// 5 x 5 corners of X (two stance legs in force space: the sixth direction of every block is known in closed form, see
+// force_space_rank5 / sym5_back_transform): five rows, five columns and five pivots per block row, the turn-over in front of pivot
+// (kb, 4).  Lanes, groups of six doubles in the pivot buffers (the sixth slot is padding) and the 16-byte stores stay as they
+// are; row 5 and column 5 of X are neither read nor written.  Five pivots per block row have no parity to pick the buffer by,
+// so this form rotates through THREE buffers (pivot ko of a block row: 0, 1, 0, 1, 2 -- static, and no two pivots in a row
+// share one, which is all the ping-pong is for).
+template <int W> __device__ __forceinline__ constexpr int sym6_buf(const int ko) { return (W == 5 && ko == 4) ? 2 : (ko & 1); }
+
+template <int NB, int NBR, int NT, int W = 6>
 __device__ __forceinline__ void sym6_sweep(double (&X)[6][6], double *pbuf, const int br, const int bc, const bool on) {
+  static_assert(W == 6 || W == 5, "blocks are swept whole or without their sixth row and column");
   constexpr int PB = Sym6<NB>::PB, DS = Sym6<NB>::DS;
   int gr = bc, gc = br;
   auto publish = [&](const int ko, const int kb, double *pb) {
@@ -120,7 +132,7 @@ __device__ __forceinline__ void sym6_sweep(double (&X)[6][6], double *pbuf, cons
       double *dst = pb + 6 * gc;
       double w[6];
 #pragma unroll
-      for (int e = 0; e < 6; e++) w[e] = X[ko][e];
+      for (int e = 0; e < 6; e++) w[e] = e < W ? X[ko][e] : 0.0;
       if constexpr (NT > 64) { if (dg) pb[DS] = w[ko]; }
       w[ko] -= dg ? 1.0 : 0.0;
 #pragma unroll
@@ -147,18 +159,18 @@ __device__ __forceinline__ void sym6_sweep(double (&X)[6][6], double *pbuf, cons
   double invd = fast_rcp(d);
   for (int kb = 0; kb < NBR; kb++) {
 #pragma unroll
-    for (int ko = 0; ko < 6; ko++) {
-      const int kon = (ko + 1) % 6;               // row of the next pivot inside its blocks (static)
-      const int kbn = (ko == 5) ? kb + 1 : kb;    // its block row
-      if (ko == 5) {
+    for (int ko = 0; ko < W; ko++) {
+      const int kon = (ko + 1) % W;                   // row of the next pivot inside its blocks (static)
+      const int kbn = (ko == W - 1) ? kb + 1 : kb;    // its block row
+      if (ko == W - 1) {
         // the lanes of block-row kb + 1 turn their block over before they publish its first row (their column phase is over)
         if (on && br == kb + 1 && gr != br) {
 #pragma unroll
-          for (int a = 0; a < 6; a++)
+          for (int a = 0; a < W; a++)
 #pragma unroll
-            for (int b = a + 1; b < 6; b++) { const double t = X[a][b]; X[a][b] = X[b][a]; X[b][a] = t; }
+            for (int b = a + 1; b < W; b++) { const double t = X[a][b]; X[a][b] = X[b][a]; X[b][a] = t; }
 #pragma unroll
-          for (int e = 0; e < 6; e++) { const double t = pr[e]; pr[e] = pc[e]; pc[e] = t; }
+          for (int e = 0; e < W; e++) { const double t = pr[e]; pr[e] = pc[e]; pc[e] = t; }
           gr = br; gc = bc;
         }
       }
@@ -169,36 +181,83 @@ __device__ __forceinline__ void sym6_sweep(double (&X)[6][6], double *pbuf, cons
       double npr[6], npc[6], nd = 0.0;
       if constexpr (NT == 64) nd = pivot(kon, kbn);
 #pragma unroll
-      for (int b = 0; b < 6; b++) if (b != kon) X[kon][b] = fma(nk, pc[b], X[kon][b]);
+      for (int b = 0; b < W; b++) if (b != kon) X[kon][b] = fma(nk, pc[b], X[kon][b]);
       // ... handed on and read back at once (after the last pivot: nobody publishes, the read returns old finite values)
-      double *pbn = pbuf + ((ko + 1) & 1) * PB;   // pivot k = 6 kb + ko: k & 1 == ko & 1
+      double *pbn = pbuf + sym6_buf<W>(kon) * PB;   // W = 6: pivot k = 6 kb + ko, k & 1 == ko & 1
       publish(kon, kbn, pbn);
       sym6_sync<NT>();
       fetch(pbn, npr, npc, nd);
-      // the other five rows, with the five dependent steps of 1 / d (next pivot) spread between them: a lone wave issues in
+      // the other rows, with the dependent steps of 1 / d (next pivot) spread between them: a lone wave issues in
       // order, and behind the rows the chain would add its full latency to every pivot
       __builtin_amdgcn_sched_barrier(0);
       double xr = __builtin_amdgcn_rcp(nd), er = 0.0;
       asm volatile("" : "+v"(xr));   // (pins the step here: left alone the optimiser sinks the whole chain behind the rows)
       int row = 0;
 #pragma unroll
-      for (int a = 0; a < 6; a++) {
+      for (int a = 0; a < W; a++) {
         if (a == kon) continue;
         const double na = -pr[a] * invd;
 #pragma unroll
-        for (int b = 0; b < 6; b++) X[a][b] = fma(na, pc[b], X[a][b]);
+        for (int b = 0; b < W; b++) X[a][b] = fma(na, pc[b], X[a][b]);
         __builtin_amdgcn_sched_barrier(0);
         if (row == 0 || row == 2) { er = fma(-nd, xr, 1.0); asm volatile("" : "+v"(er)); }
         if (row == 1 || row == 3) { xr = fma(xr, er, xr); asm volatile("" : "+v"(xr)); }
         row++;
       }
 #pragma unroll
-      for (int a = 0; a < 6; a++) asm volatile("" : "+v"(X[a][0]), "+v"(X[a][1]), "+v"(X[a][2]), "+v"(X[a][3]), "+v"(X[a][4]), "+v"(X[a][5]));
+      for (int a = 0; a < W; a++) {
+        if constexpr (W == 6) asm volatile("" : "+v"(X[a][0]), "+v"(X[a][1]), "+v"(X[a][2]), "+v"(X[a][3]), "+v"(X[a][4]), "+v"(X[a][5]));
+        else asm volatile("" : "+v"(X[a][0]), "+v"(X[a][1]), "+v"(X[a][2]), "+v"(X[a][3]), "+v"(X[a][4]));
+      }
 #pragma unroll
-      for (int e = 0; e < 6; e++) { pr[e] = npr[e]; pc[e] = npc[e]; }
+      for (int e = 0; e < W; e++) { pr[e] = npr[e]; pc[e] = npc[e]; }
       invd = xr;
     }
   }
+}
+
+// ---- two stance legs in force space: the swept 5 x 5 blocks back into the 6 x 6 blocks of -G + 2 I ----
+// After sym6_sweep<.., 5> on P5 = alpha I + 2 N (x) (Q5' G_U Q5) + 2 S (x) (Q5' G_V Q5) (force_space_rank5, rg_qp_tile.inc) a lane
+// holds the 5 x 5 block M of -P5^-1 (+ 2 I on diagonal blocks) in the leading corner of X.  With Q = I - beta v v' the reflector
+// whose first five columns are Q5 and whose sixth is -+n, the direction in which P is alpha:
+//     block of -P^-1 (+ 2 I) = Q [ M 0 ; 0 c ] Q,   c = 2 - 1 / alpha on diagonal blocks, 0 elsewhere
+//                            = M6 - v w~' - u~ v',  u~ = beta M6 v,  w~ = beta M6' v - beta^2 (v' M6 v) v.
+// In place: two mat-vecs, then two FMAs per entry; no second block is live.  hv (LDS, per robot): v[0..5], beta, 2 - 1 / alpha.
+__device__ __forceinline__ void sym5_back_transform(double (&X)[6][6], const double *hv, const int br, const int bc, const bool on) {
+  double v[6];
+#pragma unroll
+  for (int e = 0; e < 6; e += 2) { const double2 t = *reinterpret_cast<const double2 *>(hv + e); v[e] = t.x; v[e + 1] = t.y; }
+  const double2 bc2 = *reinterpret_cast<const double2 *>(hv + 6);
+  const double beta = bc2.x, c55 = (on && br == bc) ? bc2.y : 0.0;
+  double u[6], w[6];
+#pragma unroll
+  for (int a = 0; a < 5; a++) {
+    double t = X[a][0] * v[0];
+#pragma unroll
+    for (int b = 1; b < 5; b++) t = fma(X[a][b], v[b], t);
+    u[a] = t;
+  }
+#pragma unroll
+  for (int b = 0; b < 5; b++) {
+    double t = X[0][b] * v[0];
+#pragma unroll
+    for (int a = 1; a < 5; a++) t = fma(X[a][b], v[a], t);
+    w[b] = t;
+  }
+  u[5] = c55 * v[5]; w[5] = u[5];
+  double s = u[0] * v[0];
+#pragma unroll
+  for (int a = 1; a < 6; a++) s = fma(u[a], v[a], s);
+  const double b2s = beta * beta * s;
+#pragma unroll
+  for (int e = 0; e < 6; e++) { u[e] *= beta; w[e] = fma(beta, w[e], -b2s * v[e]); }
+#pragma unroll
+  for (int a = 0; a < 6; a++)
+#pragma unroll
+    for (int b = 0; b < 6; b++) {
+      const double m = (a < 5 && b < 5) ? X[a][b] : ((a == 5 && b == 5) ? c55 : 0.0);
+      X[a][b] = fma(-v[a], w[b], fma(-u[a], v[b], m));
+    }
 }
 
 // floor(i / 6) for 0 <= i <= 130 (the callers stay below 128: rows / columns of a 16 x 16 grid of 8 x 8 tiles)

@@ -354,3 +354,90 @@ __device__ __forceinline__ void force_space_tables(const DevCfg *__restrict__ c,
     c2[e] = dt * dt * (TBw[i] * c->w[0] * e_r + TBw[m3 + i] * c->w[1] * e_p + TBw[2 * m3 + i] * c->w[2] * e_y + body_val<MU4>(c, rec, BODY_INV_MASS) * ep);
   }
 }
+
+// ---- two stance legs: the direction of force space in which P is alpha, taken out before the sweep ----
+// With the stance feet at r1, r2 and e = (r1 - r2) / |r1 - r2| the force pair n = (e, -e) / sqrt 2 has no net force and no net
+// torque: B_w n = Iw^-1 ((r1 - r2) x e) / sqrt 2 = 0 and (e - e) / m = 0, so G_U n = G_V n = 0 and P = 2 (N (x) G_U + S (x) G_V)
+// + alpha I is alpha in the ten directions (step k) (x) n.  With Q = I - beta v v', v = n + sign(n_5) e_6, beta = 2 / v'v =
+// 1 / (1 + |n_5|) (v'v >= 2: no cancellation) the reflector that maps e_6 to -+n, and Q5 its first five columns,
+//     P^-1 = (I (x) Q5) (alpha I + 2 N (x) Q5' G_U Q5 + 2 S (x) Q5' G_V Q5)^-1 (I (x) Q5') + I (x) n n' / alpha:
+// only a 5 NB x 5 NB matrix is swept (sym6_sweep<.., 5>) and sym5_back_transform puts the sixth direction back.
+// Runs after force_space_tables<2, ..>: overwrites GU / GV with the projected Gram blocks, built from B_w Q5, T B_w Q5 and
+// [I I] Q5 -- so that the dropped sixth row and column are zero by construction, not by cancellation -- and padded to 6 x 6
+// with zeros (sym6_build_kron6 keeps its addresses).  hv (RG_RANK5_HV = 18 doubles, 17 used): v[0..5], beta, 2 - 1 / alpha (what
+// the sweep's result has in the sixth direction of a diagonal block) in hv[0..7], then beta (B_w v), beta (T B_w v),
+// beta ([I I] v), three entries each, in hv[8..16].
+// Coincident feet (or a difference that is not finite) take e = x: any unit e is right there, the null space only grows.
+// Ends with a workgroup barrier.
+constexpr int RG_RANK5_HV = 18;   // doubles of hv (even: what follows it in a layout stays 16-byte aligned)
+static_assert(8 + 9 <= RG_RANK5_HV && RG_RANK5_HV % 2 == 0, "hv holds v, beta, 2 - 1 / alpha and nine projections");
+template <int NT, bool MU4 = false>
+__device__ __forceinline__ void force_space_rank5(const DevCfg *__restrict__ c, const double *rec, const int cmask, const int tid, const double *Bw_, const double *TBw_,
+                                                  double *GU_, double *GV_, double *hv_) {
+  constexpr int m3 = 6;
+  // KEEP the odd forms below; tests/test_kernel_resources.py fails without them.  Whatever is loop-invariant in this helper is
+  // hoisted out of the re-solve kernel's work loop (rg_qp_resolve_kernel) and held in VGPRs across its robots: with M_SQRT1_2,
+  // INFINITY and the LDS addresses as literals that kernel needed 8 VGPRs more (231 -> 239), with a byte compare of i % 3 one
+  // more (LAB_NOTES).  So: every LDS address is one opaque register (a zero the compiler cannot see through) plus a constant;
+  // the only floating-point constants are inline ones (0.5, 1.0, 2.0), which occupy no register -- 1 / sqrt 2 comes out of
+  // v_rsq_f64 and two Newton steps, finiteness is tested as d2 - d2 == 0; i % 3 is made an opaque 32-bit value.
+  int opaque0 = 0;
+  asm volatile("" : "+v"(opaque0));
+  double *hv = hv_ + opaque0;
+  const double *Bw = hv + (Bw_ - hv_), *TBw = hv + (TBw_ - hv_);
+  double *GU = hv + (GU_ - hv_), *GV = hv + (GV_ - hv_);
+  if (tid < 8) {
+    const double *r1 = &rec[REC_FEETW + 3 * nth_leg(cmask, 0)], *r2 = &rec[REC_FEETW + 3 * nth_leg(cmask, 1)];
+    double e0 = r1[0] - r2[0], e1 = r1[1] - r2[1], e2 = r1[2] - r2[2];
+    double d2 = 2.0 * fma(e0, e0, fma(e1, e1, e2 * e2));
+    if (!(d2 > 0.0 && (d2 - d2) == 0.0)) { e0 = 1.0; e1 = 0.0; e2 = 0.0; d2 = 2.0; }   // coincident feet, or a difference that is not finite: e = x
+    // y = 1 / sqrt(2 |r1 - r2|^2): n = (r1 - r2, r2 - r1) y
+    double y = __builtin_amdgcn_rsq(d2);
+#pragma unroll
+    for (int it = 0; it < 2; it++) { const double er = fma(-d2 * y, y, 1.0); y = fma(0.5 * y, er, y); }
+    const double n5 = -e2 * y;
+    const int a = tid % 3;
+    const double ea = a == 0 ? e0 : (a == 1 ? e1 : e2);
+    double o = tid < 3 ? ea * y : -ea * y;                           // n
+    if (tid == 5) o += n5 < 0.0 ? -1.0 : 1.0;                        // v = n + sign(n_5) e_6
+    if (tid == 6) o = 1.0 / (1.0 + fabs(n5));                        // beta
+    if (tid == 7) o = 2.0 - 1.0 / c->alpha;
+    hv[tid] = o;
+  }
+  __syncthreads();
+  if (tid < 9) {
+    const int r = tid % 3;
+    double s;
+    if (tid < 6) {
+      const double *src = (tid < 3 ? Bw : TBw) + r * m3;
+      s = src[0] * hv[0];
+#pragma unroll
+      for (int i = 1; i < m3; i++) s = fma(src[i], hv[i], s);
+    } else s = hv[r] + hv[3 + r];
+    hv[8 + tid] = hv[6] * s;
+  }
+  __syncthreads();
+  for (int e = tid; e < m3 * m3; e += NT) {
+    const int i = e / m3, j = e % m3;
+    double gu = 0.0, gv = 0.0;
+    if (i < 5 && j < 5) {
+      const double vi = hv[i], vj = hv[j];
+      const double im2 = body_val<MU4>(c, rec, BODY_INV_MASS) * body_val<MU4>(c, rec, BODY_INV_MASS);
+      const double *cw = c->w;
+      int ia = i % 3, ja = j % 3;
+      asm volatile("" : "+v"(ia), "+v"(ja));   // (32-bit compares against inline constants: a byte compare takes its constant from a register)
+#pragma unroll
+      for (int r = 0; r < 3; r++) {
+        const double bi = fma(-hv[8 + r], vi, Bw[r * m3 + i]), bj = fma(-hv[8 + r], vj, Bw[r * m3 + j]);
+        const double ti = fma(-hv[11 + r], vi, TBw[r * m3 + i]), tj = fma(-hv[11 + r], vj, TBw[r * m3 + j]);
+        const double ei = fma(-hv[14 + r], vi, ia == r ? 1.0 : 0.0), ej = fma(-hv[14 + r], vj, ja == r ? 1.0 : 0.0);
+        gu = fma(cw[6 + r] * bi, bj, fma(cw[9 + r] * im2 * ei, ej, gu));
+        gv = fma(cw[r] * ti, tj, fma(cw[3 + r] * im2 * ei, ej, gv));
+      }
+    }
+    const double dt = c->dt;
+    GU[e] = gu * dt * dt;
+    GV[e] = gv * dt * dt * dt * dt;
+  }
+  __syncthreads();
+}
