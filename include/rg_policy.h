@@ -1,0 +1,166 @@
+/*
+ * rg_policy.h -- C-ABI of the acting and collecting side of the PPO agent in librg_mpc.so: the Gaussian policy and the
+ * value network of the reference's agents/ppo (ForwardGaussianPolicy of scripts/networks.py), its sampling, its streaming
+ * normalisers (normalize.py), the rollout slots and the returns (utility.py), for B robots with no host in the loop.  The
+ * update itself is torch on the same parameter memory (robot_gym_amd/agents/ppo).
+ *
+ * Conventions (those of rg_episode.h)
+ *   - return 0 on success, a negative rg_policy_status otherwise; nothing throws across the ABI; rg_policy_last_error()
+ *     gives the text of the last failure on a handle (or of create() / param_layout(), with a NULL handle).
+ *   - the CALLER owns every buffer (device memory).  The handle holds the configuration, the layout of the parameters and a
+ *     fixed workspace for the partial sums of rg_policy_record.
+ *   - all work is enqueued on the hipStream_t passed in (NULL = default stream); NO call synchronises or stages anything.
+ *   - one handle per (device, stream); calls on one handle are not thread-safe.  Every call leaves the calling thread's
+ *     current HIP device as it found it.
+ *   - float64 arithmetic is IEEE with floating-point contraction off; the two networks are float32 with explicit fused
+ *     multiply-adds (below).
+ *
+ * Networks.  Hidden layers relu(W x + b); the mean head tanh(W x + b) to act_dim; the value head linear to a scalar; logstd
+ * a free vector of act_dim.  Two contiguous float32 buffers, policy_params and value_params, each laid out layer after
+ * layer (hidden layers, then the head) as W[in][out] (out contiguous) followed by b[out]; logstd sits at the end of the
+ * policy buffer.  rg_policy_param_layout gives the counts and every offset.
+ *   Arithmetic of one output neuron: acc = 0; for i = 0 .. in-1 in order: acc = fma(W[i][j], x[i], acc); then acc + b[j], then
+ *   the activation (tanhf for the mean head).  The order is a function of the configuration alone: not of B, not of the
+ *   robot's index or place in its tile.
+ *
+ * Act state (caller): int64 act_state[2][B]; row 0 `key` (THE CALLER INITIALISES IT, usually to the robot's index; nothing
+ * here writes it), row 1 `counter` (incremented by every sampling act).  A clone is a column copy.
+ *
+ * Normaliser state (caller): double norm_state[RG_POLICY_NORM_ROWS] = [3][RG_POLICY_NORM_COLS]: rows count (an exact
+ * integer), mean, var_sum; columns 0 .. obs_dim-1 the observation components (columns up to 63 are reserved for them),
+ * column RG_POLICY_NORM_REWARD (64) the reward.  All zeros is the empty state.
+ *   transform (observation): v - mean; / (sqrt(var_sum / (count - 1) + 1e-4) + 1e-8) when count > 1; clipped to +-obs_clip
+ *   when obs_clip > 0.  The reward is scaled only (no mean), clipped to +-reward_clip.
+ *   update over the n values v of a batch (n = 0: nothing changes): count += n; new_mean = mean + sum(v - mean) / count, or
+ *   the one value itself when count has become 1; var_sum += sum((v - mean) * (v - new_mean)).  Sums over the batch are
+ *   formed as partial sums per workgroup (a fixed tree) and one finishing pass in a fixed order: the result is a function of
+ *   the inputs and B alone.  No atomics.
+ *
+ * Noise.  Counter-based and stateless, on the mix of rg_episode.h:
+ *     h(draw) = seed;  for w in (key, counter, axis, draw):  h = mix((h ^ w) + 0x9E3779B97F4A7C15)
+ *     u1 = ((h(0) >> 11) + 1) * 2^-53  (never 0),  u2 = (h(1) >> 11) * 2^-53
+ *     eps = sqrt(-2 ln u1) * cos(6.283185307179586 * u2)   in float64, rounded to float32
+ * axis is the action component.  tests/policy_model.py is the stream in numpy (ln and cos are the device's: an eps can
+ * differ from numpy's in its last float32 bit).
+ *
+ * rg_policy_act, per robot: the observation through the transform (float64, rounded to float32); both networks;
+ *   SAMPLE: action = mean + expf(logstd) * eps (float32, two roundings), counter += 1;  MEAN: action = mean, eps = 0, the
+ *   counter is left alone; logprob = -0.5 sum eps^2 - sum logstd - 0.5 act_dim ln(2 pi) (float64 over the float32 eps and
+ *   logstd, rounded to float32).  The action is not clipped: the task clips it (rg_goto.h).
+ * rg_policy_record: copies obs, reward and done into rollout slots and updates both normalisers over the robots with
+ *   mask[b] != 0.
+ * rg_policy_returns, per robot, backwards over T ticks in float64, float32 out:
+ *   r' = reward / (std + 1e-8) when count > 1, clipped;  nd_t = 1 - (done_t != 0)
+ *   delta_t = r'_t + discount nd_t V_{t+1} - V_t,  V_T = bootstrap ? last_value : 0
+ *   A_t = delta_t + discount gae_lambda nd_t A_{t+1},  A_T = 0;   adv = A, ret = A + V.
+ *
+ * Launches.  act: one kernel, RG_POLICY_TILE robots per 512-thread workgroup, the policy network on threads 0..255 and the
+ * value network on threads 256..511, one output neuron per thread, activations in LDS, weights read coalesced along `out`.
+ * record: three kernels (copy + first partial sums; second partial sums; finish).  returns: one thread per robot.
+ */
+#ifndef RG_POLICY_H
+#define RG_POLICY_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define RG_POLICY_ABI_VERSION 1
+#define RG_POLICY_MAX_OBS 64
+#define RG_POLICY_MAX_ACT 4
+#define RG_POLICY_MAX_LAYERS 3
+#define RG_POLICY_MAX_WIDTH 256
+#define RG_POLICY_TILE 8                 /* robots per workgroup of the act kernel */
+#define RG_POLICY_NORM_COLS 65
+#define RG_POLICY_NORM_REWARD 64
+#define RG_POLICY_NORM_ROWS 195          /* 3 * RG_POLICY_NORM_COLS */
+#define RG_POLICY_MAX_BATCH (1 << 24)
+#define RG_POLICY_MAX_T (1 << 20)
+#define RG_POLICY_DEVICE_NONE (-1)       /* create(): a host-only handle, see rg_policy_create */
+#define RG_POLICY_MODE_SAMPLE 0
+#define RG_POLICY_MODE_MEAN 1
+
+typedef enum {
+  RG_POLICY_OK = 0,
+  RG_POLICY_ERR_INVALID = -1,   /* bad argument / configuration (the text names the field) */
+  RG_POLICY_ERR_HIP = -2,       /* HIP runtime error (text in last_error) */
+  RG_POLICY_ERR_NO_DEVICE = -3, /* no usable GPU */
+  RG_POLICY_ERR_ALLOC = -4
+} rg_policy_status;
+
+/* The defaults (robot_gym_amd/core/policy_abi.py) are the reference's configs.py / networks.py. */
+typedef struct {
+  int32_t abi_version;       /* RG_POLICY_ABI_VERSION */
+  int32_t obs_dim;           /* 16     (1 .. RG_POLICY_MAX_OBS) */
+  int32_t act_dim;           /* 2      (1 .. RG_POLICY_MAX_ACT) */
+  int32_t n_policy_layers;   /* 2      hidden layers of the policy (0 .. RG_POLICY_MAX_LAYERS) */
+  int32_t n_value_layers;    /* 2      hidden layers of the value network (0 .. RG_POLICY_MAX_LAYERS) */
+  int32_t reserved0;         /* must be 0 */
+  int32_t policy_layers[3];  /* 200, 100   widths (1 .. RG_POLICY_MAX_WIDTH); entries past n_policy_layers must be 0 */
+  int32_t value_layers[3];   /* 200, 100   likewise */
+  double obs_clip;           /* 5.0    >= 0; 0 = no clipping */
+  double reward_clip;        /* 10.0   >= 0; 0 = no clipping */
+  double discount;           /* 0.985  in [0, 1] */
+  double gae_lambda;         /* 1.0    in [0, 1] */
+  uint64_t seed;             /* of the noise stream */
+} rg_policy_config;
+
+/* Layers count the head: n_policy = n_policy_layers + 1.  Offsets are in floats from the start of the net's buffer. */
+typedef struct {
+  int32_t policy_count;      /* floats in policy_params, logstd included */
+  int32_t value_count;       /* floats in value_params */
+  int32_t n_policy;
+  int32_t n_value;
+  int32_t logstd_offset;
+  int32_t reserved0;
+  int32_t policy_in[4], policy_out[4], policy_w[4], policy_b[4];
+  int32_t value_in[4], value_out[4], value_w[4], value_b[4];
+} rg_policy_layout;
+
+typedef struct rg_policy_handle rg_policy_handle;
+
+/* Validates cfg (abi_version, reserved0, the ranges above, finite values) and batch (1 .. RG_POLICY_MAX_BATCH) BEFORE it looks
+ * for a device.  device = RG_POLICY_DEVICE_NONE makes a host-only handle: every later call checks its arguments
+ * (RG_POLICY_ERR_INVALID, naming the argument) and, where they are valid, returns RG_POLICY_ERR_NO_DEVICE. */
+int rg_policy_create(const rg_policy_config *cfg, int32_t batch, int32_t device, rg_policy_handle **out);
+void rg_policy_destroy(rg_policy_handle *h);
+const char *rg_policy_last_error(const rg_policy_handle *h);   /* h may be NULL: the last create() / param_layout() failure of this thread */
+int32_t rg_policy_abi_version(void);
+int32_t rg_policy_config_size(void);
+int32_t rg_policy_layout_size(void);
+int32_t rg_policy_norm_rows(void);
+int32_t rg_policy_tile(void);
+
+/* The layout rule for cfg (validated as in create).  Needs no device. */
+int rg_policy_param_layout(const rg_policy_config *cfg, rg_policy_layout *out);
+
+/* Device pointers:
+ *   obs            float32 [obs_dim][B], component-major
+ *   norm_state     float64 [RG_POLICY_NORM_ROWS]
+ *   policy_params  float32 [policy_count]
+ *   value_params   float32 [value_count]
+ *   act_state      int64 [2][B]; may be NULL with mode = RG_POLICY_MODE_MEAN
+ *   action         float32 [B][act_dim]
+ *   mean           float32 [B][act_dim], or NULL
+ *   value, logprob float32 [B], or NULL */
+int rg_policy_act(rg_policy_handle *h, const float *obs, const double *norm_state, const float *policy_params, const float *value_params,
+                  int64_t *act_state, int32_t mode, float *action, float *mean, float *value, float *logprob, void *stream);
+
+/* obs float32 [obs_dim][B] (the observation that was acted on), reward float32 [B], done int32 [B], mask int32 [B] or NULL (all
+ * robots), norm_state as above; ro_obs float32 [obs_dim][B], ro_reward float32 [B], ro_done int32 [B]: the rollout slot, each may
+ * be NULL. */
+int rg_policy_record(rg_policy_handle *h, const float *obs, const float *reward, const int32_t *done, const int32_t *mask, double *norm_state,
+                     float *ro_obs, float *ro_reward, int32_t *ro_done, void *stream);
+
+/* reward, value float32 [T][B], done int32 [T][B], last_value float32 [B] (required when bootstrap != 0), norm_state as above (read
+ * only); ret, adv float32 [T][B].  T in 1 .. RG_POLICY_MAX_T. */
+int rg_policy_returns(rg_policy_handle *h, const float *reward, const float *value, const int32_t *done, const float *last_value,
+                      const double *norm_state, int32_t T, int32_t bootstrap, float *ret, float *adv, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RG_POLICY_H */

@@ -1,0 +1,7 @@
+"""The PPO agent on the device: acting, sampling, normalisers, rollout storage and returns as HIP kernels
+(include/rg_policy.h), the update in torch on the same parameter memory."""
+from robot_gym_amd.agents.ppo.algorithm import PPO, diag_normal_kl, diag_normal_logpdf
+from robot_gym_amd.agents.ppo.policy import BatchedGaussianPolicy
+from robot_gym_amd.agents.ppo.rollout import RolloutBuffer, collect, play
+
+__all__ = ["BatchedGaussianPolicy", "RolloutBuffer", "PPO", "collect", "play", "diag_normal_kl", "diag_normal_logpdf"]
