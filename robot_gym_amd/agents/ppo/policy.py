@@ -109,15 +109,38 @@ class BatchedGaussianPolicy:
                          ptr.get("value"), ptr.get("logprob"))
         return out
 
+    def _ptr(self, call, name, t, shape, dtype, optional=False):
+        """data_ptr() of a tensor the kernels may follow: contiguous, of this shape and dtype, on this device.  None gives None
+        where the argument is optional.  The kernels check nothing: a pointer that passes here is read or written as it stands."""
+        if t is None and optional:
+            return None
+        if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
+            kind = "float32" if dtype == torch.float32 else "int32"
+            raise ValueError(f"{call}: {name} must be a contiguous {kind} {list(shape)} tensor on {self.device}" + (" or None" if optional else ""))
+        return t.data_ptr()
+
     def record(self, obs_cm, reward, done, mask=None, ro_obs=None, ro_reward=None, ro_done=None):
-        """rg_policy_record: the rollout slot and both normalisers (robots with mask != 0; None: all)."""
-        p = lambda t: None if t is None else t.data_ptr()
-        self._handle.record(p(obs_cm), p(reward), p(done), p(mask), self.norm_state.data_ptr(), p(ro_obs), p(ro_reward), p(ro_done))
+        """rg_policy_record: the rollout slot and both normalisers (robots with mask != 0; None: all).  obs_cm, ro_obs: contiguous
+        float32 [obs_dim, B]; reward, ro_reward: float32 [B]; done, mask, ro_done: int32 [B]; all on this device."""
+        B, f32, i32 = self.batch, torch.float32, torch.int32
+        ptrs = [self._ptr("record", "obs_cm", obs_cm, (self.obs_dim, B), f32), self._ptr("record", "reward", reward, (B,), f32),
+                self._ptr("record", "done", done, (B,), i32), self._ptr("record", "mask", mask, (B,), i32, True), self.norm_state.data_ptr(),
+                self._ptr("record", "ro_obs", ro_obs, (self.obs_dim, B), f32, True), self._ptr("record", "ro_reward", ro_reward, (B,), f32, True),
+                self._ptr("record", "ro_done", ro_done, (B,), i32, True)]
+        self._handle.record(*ptrs)
 
     def returns(self, rollout, bootstrap=True):
-        """rg_policy_returns over a RolloutBuffer: fills rollout.ret and rollout.adv."""
-        self._handle.returns(rollout.reward.data_ptr(), rollout.value.data_ptr(), rollout.done.data_ptr(), rollout.last_value.data_ptr(),
-                             self.norm_state.data_ptr(), rollout.T, bootstrap, rollout.ret.data_ptr(), rollout.adv.data_ptr())
+        """rg_policy_returns over a RolloutBuffer of this batch: fills rollout.ret and rollout.adv.  reward, value, ret, adv:
+        contiguous float32 [T, B]; done: int32 [T, B]; last_value: float32 [B] (may be None without bootstrap)."""
+        T, B, f32 = int(rollout.T), self.batch, torch.float32
+        if int(rollout.batch) != B:
+            raise ValueError(f"returns: rollout.batch is {rollout.batch}, the policy's batch is {B}")
+        if T < 1:
+            raise ValueError(f"returns: rollout.T is {T}, it must be at least 1")
+        ptr = {name: self._ptr("returns", "rollout." + name, getattr(rollout, name), (T, B), f32) for name in ("reward", "value", "ret", "adv")}
+        done = self._ptr("returns", "rollout.done", rollout.done, (T, B), torch.int32)
+        last = self._ptr("returns", "rollout.last_value", rollout.last_value, (B,), f32, optional=not bootstrap)
+        self._handle.returns(ptr["reward"], ptr["value"], done, last, self.norm_state.data_ptr(), T, bootstrap, ptr["ret"], ptr["adv"])
 
     # ---- the same arithmetic in torch, for the update -----------------------------------------------------------------
 

@@ -127,6 +127,50 @@ def forward(x, layers, head, dtype=np.float64):
     return x
 
 
+def fma32(w, x, acc):
+    """fmaf(w, x, acc) of float32 arrays (broadcast), correctly rounded, in numpy.  The product of two float32 values is exact
+    in float64.  s = fl64(p + acc) and TwoSum's err (s + err = p + acc exactly) locate the true sum: no float32 rounding
+    boundary lies strictly between s and s + err (the boundaries are float64 numbers), so rounding s to float32 is the answer
+    unless s is itself a float32 midpoint and err != 0; then s moves one float64 ulp to err's side first."""
+    w, x, acc = (np.asarray(v, dtype=np.float32) for v in (w, x, acc))
+    p = w.astype(np.float64) * x.astype(np.float64)
+    a = np.broadcast_to(acc.astype(np.float64), p.shape)
+    s = np.atleast_1d(p + a)
+    # candidates first, cheaply: a midpoint of two normal float32 values has the low 29 bits of its float64 mantissa equal to
+    # 2^28; below the normal range every s is looked at.  The exact test then runs on the candidates alone.
+    cand = np.flatnonzero((((s.view(np.uint64) & np.uint64(0x1FFFFFFF)) == np.uint64(0x10000000)) | (np.abs(s) < 2.0 ** -125)).ravel())
+    if len(cand):
+        pc, ac, sc = np.atleast_1d(p).ravel()[cand], np.atleast_1d(a).ravel()[cand], s.ravel()[cand]
+        t = sc - pc
+        err = (pc - (sc - t)) + (ac - t)
+        with np.errstate(over="ignore", invalid="ignore"):
+            r = sc.astype(np.float32)
+            other = np.nextafter(r, np.where(sc > r, np.inf, -np.inf).astype(np.float32))
+            mid = np.isfinite(other) & (r.astype(np.float64) != sc) & ((r.astype(np.float64) + other.astype(np.float64)) * 0.5 == sc)   # the sum of two float32 neighbours is exact
+        nudge = mid & (err != 0.0)
+        s = s.copy().ravel()
+        s[cand[nudge]] = np.nextafter(sc[nudge], np.where(err[nudge] > 0.0, np.inf, -np.inf))
+    with np.errstate(over="ignore"):
+        return s.reshape(p.shape).astype(np.float32)
+
+
+def forward_exact(x, layers, head):
+    """x float32 [n, in] through float32 [(W, b), ...] in the arithmetic rg_policy.h pins for a neuron: acc = 0, then
+    acc = fma(W[i][j], x[i], acc) for i in order, then acc + b[j] in float32; relu as where(v > 0, v, 0).  head "linear": the
+    float32 output; head "tanh": the float32 PRE-activation of the head (tanhf itself is the device's)."""
+    assert head in ("tanh", "linear")
+    x = np.asarray(x, dtype=np.float32)
+    for k, (W, b) in enumerate(layers):
+        W, b = np.asarray(W, dtype=np.float32), np.asarray(b, dtype=np.float32)
+        acc = np.zeros((x.shape[0], W.shape[1]), dtype=np.float32)
+        for i in range(W.shape[0]):
+            acc = fma32(W[i][None, :], x[:, i:i + 1], acc)
+        v = acc + b[None, :]
+        assert v.dtype == np.float32
+        x = v if k == len(layers) - 1 else np.where(v > 0, v, np.float32(0))
+    return x
+
+
 def logprob(eps_, logstd):
     """-0.5 sum eps^2 - sum logstd - 0.5 act_dim ln(2 pi), eps_ [n, act_dim]."""
     e, ls = np.asarray(eps_, dtype=np.float64), np.asarray(logstd, dtype=np.float64)
