@@ -1,0 +1,975 @@
+// rg_ppo.hip -- the PPO update of include/rg_ppo.h.  Its own translation unit of librg_mpc.so: it shares no device code with
+// the others (the neuron arithmetic and the observation transform of rg_policy.hip are restated here, line for line, so that
+// the forward pass gives rg_policy_act's mean to the bit).
+//
+// Sweeps (rg_ppo_policy_forward_kernel, rg_ppo_policy_backward_kernel, rg_ppo_value_backward_kernel): G workgroups of 256
+// threads, workgroup g walks the tiles g, g + G, ... of kTile samples.  LDS (dynamic): the tile's activations of every layer
+// as a[layer][neuron * kTile + sample] (the normalised observation first) and two delta buffers of the widest layer, i.e.
+// (obs_dim + sum(out) + 2 max(out)) * kTile floats: 45 KB at the defaults, 86 KB at the limits (64 -> 3 x 256 -> 4).
+//   forward   thread j owns output neuron j: kTile accumulators, acc = fma(W[i][j], x[i][s], acc) for i in order; W read once
+//             per (tile, neuron) coalesced along j, x as float4 broadcasts.
+//   head      thread s < kTile owns sample s: float64 over the float32 mean (rg_ppo.h), delta rounded to float32.
+//   backward  per layer, last to first: thread j folds sum_s x[i][s] delta[j][s] (an fma chain over s) into
+//             slab[g][W[i][j]] for every i, coalesced along j -- the slab is the workgroup's own and each of its elements belongs
+//             to one thread (which clears it first), so the running sum over the workgroup's tiles is plain loads and stores; thread i forms
+//             dx[i][s] = sum_j Wt[j][i] delta[j][s] from the transposed copy, coalesced along i, and masks it by x[i][s] > 0.
+// rg_ppo_grad_finish_kernel adds the G slabs per element in index order in float64; rg_ppo_loss_finish_kernel the float64
+// partials of the loss and of the logstd gradient (a strided sum per thread, a shuffle tree, the four waves in order).
+// The descriptors live in the workspace (rg_ppo_describe_kernel, first in every entry that sweeps) and are read with scalar loads.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include "../../include/rg_ppo.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kTile = RG_PPO_TILE;
+constexpr int kThreads = 256;
+constexpr int kMaxGroups = RG_PPO_MAX_GROUPS;
+constexpr int kMaxAct = RG_POLICY_MAX_ACT;
+constexpr int kCols = RG_POLICY_NORM_COLS;
+constexpr int kPart = 1 + kMaxAct;   // per (workgroup, lane): the loss sum, then the logstd gradient
+constexpr int kPrep = 3;             // per workgroup of prepare: n, sum(adv), sum((adv - m)^2)
+// dynamic LDS of a sweep at the widest configuration: (obs + three hidden layers + head + two delta buffers) * kTile floats
+constexpr int kMaxLds = (RG_POLICY_MAX_OBS + RG_POLICY_MAX_LAYERS * RG_POLICY_MAX_WIDTH + RG_POLICY_MAX_ACT + 2 * RG_POLICY_MAX_WIDTH) * kTile * 4;
+static_assert(kMaxLds == 86272 && kMaxLds <= 160 * 1024, "a sweep's tile fits a compute unit's LDS at every configuration");
+constexpr int kScal = 8;             // workspace scalars: n (clamped), m, sd, n
+
+static_assert(kTile == 16, "the sweeps read a neuron's tile as four float4");
+static_assert(RG_POLICY_MAX_WIDTH <= kThreads && RG_POLICY_MAX_OBS <= kThreads, "one neuron per thread");
+static_assert(kMaxGroups <= kThreads, "finish_sum holds one workgroup's partial per thread");
+
+struct NetDesc {
+  int n;                       // layers, the head included
+  int in[4], out[4], w[4], b[4];
+};
+
+struct SweepCfg {
+  int T, B, N, G, ntiles;
+  int obs_dim, act_dim, logstd_off, count;
+  int asum, dmax;              // LDS: floats per sample of the activations, of one delta buffer
+  double obs_clip, c, thr, coef;
+  NetDesc nd;
+};
+
+struct RoDev {
+  const float *obs, *action, *mean, *logstd, *adv, *ret;
+  const int *mask;
+};
+
+struct Desc {                  // in the workspace: what a sweep reads of its call
+  SweepCfg net[2];             // policy, value
+  RoDev ro;
+  const double *norm, *penalty;   // norm_state; the penalty of opt_state (NULL where the entry takes none)
+  double *scal, *klr, *kls, *part;   // the workspace's regions
+  float *wt, *slabs;
+};
+
+__device__ __forceinline__ double norm_scale(double count, double var_sum) {
+  return count > 1.0 ? sqrt(var_sum / (count - 1.0) + 1e-4) + 1e-8 : 1.0;
+}
+
+__device__ __forceinline__ double clip_sym(double v, double c) { return c > 0.0 ? (v < -c ? -c : (v > c ? c : v)) : v; }
+
+// the sum of v over the workgroup of 256, the same in every thread: a shuffle tree in each wave, the four waves in order
+__device__ __forceinline__ double block_sum(double v, double *sh) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off);
+  __syncthreads();   // sh may still be read from the call before
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+// sum over idx = 0 .. n-1 of p[idx * stride]: thread t takes t, t + 256, ... in order, then block_sum
+__device__ __forceinline__ double strided_sum(const double *__restrict__ p, int n, int stride, double *sh) {
+  double s = 0.0;
+  for (int idx = threadIdx.x; idx < n; idx += kThreads) s = s + p[(size_t)idx * stride];
+  return block_sum(s, sh);
+}
+
+// ---- prepare --------------------------------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(kThreads) rg_ppo_prepare_first_kernel(const int N, const int GP, const float *__restrict__ adv,
+                                                                        const int *__restrict__ mask, double *__restrict__ prep) {
+  __shared__ double sh[4];
+  double n = 0.0, s = 0.0;
+  for (int k = blockIdx.x * kThreads + (int)threadIdx.x; k < N; k += GP * kThreads)
+    if (mask[k] != 0) { n = n + 1.0; s = s + (double)adv[k]; }
+  n = block_sum(n, sh);
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) { prep[blockIdx.x * kPrep + 0] = n; prep[blockIdx.x * kPrep + 1] = s; }
+}
+
+__global__ void __launch_bounds__(kThreads) rg_ppo_prepare_second_kernel(const int N, const int GP, const float *__restrict__ adv,
+                                                                         const int *__restrict__ mask, double *__restrict__ prep) {
+  __shared__ double sh[4];
+  const double n = strided_sum(prep + 0, GP, kPrep, sh);
+  const double s = strided_sum(prep + 1, GP, kPrep, sh);
+  const double m = s / (n > 1.0 ? n : 1.0);
+  double q = 0.0;
+  for (int k = blockIdx.x * kThreads + (int)threadIdx.x; k < N; k += GP * kThreads)
+    if (mask[k] != 0) { const double d = (double)adv[k] - m; q = q + d * d; }
+  q = block_sum(q, sh);
+  if (threadIdx.x == 0) prep[blockIdx.x * kPrep + 2] = q;
+}
+
+__global__ void __launch_bounds__(kThreads) rg_ppo_prepare_finish_kernel(const int GP, const double *__restrict__ prep, double *__restrict__ scal) {
+  __shared__ double sh[4];
+  const double n = strided_sum(prep + 0, GP, kPrep, sh);
+  const double s = strided_sum(prep + 1, GP, kPrep, sh);
+  const double q = strided_sum(prep + 2, GP, kPrep, sh);
+  if (threadIdx.x == 0) {
+    const double nc = n > 1.0 ? n : 1.0;
+    scal[0] = nc;
+    scal[1] = s / nc;
+    scal[2] = sqrt(q / nc) + 1e-8;
+    scal[3] = n;
+  }
+}
+
+// ---- the transposed copy of the weights -------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(kThreads) rg_ppo_transpose_kernel(const NetDesc nd, const float *__restrict__ P, float *__restrict__ Wt) {
+  const int e = blockIdx.x * kThreads + (int)threadIdx.x;
+#pragma unroll
+  for (int l = 0; l < 4; l++) {
+    if (l < nd.n) {
+      const int k = e - nd.w[l];
+      if (k >= 0 && k < nd.in[l] * nd.out[l]) {
+        const int i = k / nd.out[l], j = k - i * nd.out[l];
+        Wt[nd.w[l] + j * nd.in[l] + i] = P[e];
+      }
+    }
+  }
+}
+
+// the two descriptors and the rollout's pointers into the workspace, where the sweeps index them (dynamic indexing of a by-value kernel argument
+// ends on the stack)
+struct Regions {
+  const double *norm, *penalty;
+  double *scal, *klr, *kls, *part;
+  float *wt, *slabs;
+};
+
+__global__ void rg_ppo_describe_kernel(const SweepCfg pol, const SweepCfg val, const RoDev ro, const Regions r, Desc *__restrict__ dst) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    dst->net[0] = pol;
+    dst->net[1] = val;
+    dst->ro = ro;
+    dst->norm = r.norm; dst->penalty = r.penalty;
+    dst->scal = r.scal; dst->klr = r.klr; dst->kls = r.kls; dst->part = r.part;
+    dst->wt = r.wt; dst->slabs = r.slabs;
+  }
+}
+
+// ---- the sweeps -------------------------------------------------------------------------------------------------------
+
+// y[j][s] = act(sum_i W[i][j] x[i][s] + b[j]): rg_policy_act_kernel's neuron, kTile samples wide.  mode 0 relu, 1 tanhf, 2 linear
+__device__ __forceinline__ void forward_layer(const float *__restrict__ P, const int nin, const int nout, const int woff, const int boff,
+                                              const float *x, float *y, const int mode) {
+  const int j = threadIdx.x;
+  if (j < nout) {
+    const float *__restrict__ W = P + woff + j;
+    float acc[kTile];
+#pragma unroll
+    for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
+#pragma unroll 4
+    for (int i = 0; i < nin; i++) {
+      const float w = W[(size_t)i * nout];
+      const float4 xa = *reinterpret_cast<const float4 *>(x + i * kTile);
+      const float4 xb = *reinterpret_cast<const float4 *>(x + i * kTile + 4);
+      const float4 xc = *reinterpret_cast<const float4 *>(x + i * kTile + 8);
+      const float4 xd = *reinterpret_cast<const float4 *>(x + i * kTile + 12);
+      acc[0] = __builtin_fmaf(w, xa.x, acc[0]); acc[1] = __builtin_fmaf(w, xa.y, acc[1]);
+      acc[2] = __builtin_fmaf(w, xa.z, acc[2]); acc[3] = __builtin_fmaf(w, xa.w, acc[3]);
+      acc[4] = __builtin_fmaf(w, xb.x, acc[4]); acc[5] = __builtin_fmaf(w, xb.y, acc[5]);
+      acc[6] = __builtin_fmaf(w, xb.z, acc[6]); acc[7] = __builtin_fmaf(w, xb.w, acc[7]);
+      acc[8] = __builtin_fmaf(w, xc.x, acc[8]); acc[9] = __builtin_fmaf(w, xc.y, acc[9]);
+      acc[10] = __builtin_fmaf(w, xc.z, acc[10]); acc[11] = __builtin_fmaf(w, xc.w, acc[11]);
+      acc[12] = __builtin_fmaf(w, xd.x, acc[12]); acc[13] = __builtin_fmaf(w, xd.y, acc[13]);
+      acc[14] = __builtin_fmaf(w, xd.z, acc[14]); acc[15] = __builtin_fmaf(w, xd.w, acc[15]);
+    }
+    const float bias = P[boff + j];
+    float *yj = y + j * kTile;
+#pragma unroll
+    for (int r = 0; r < kTile; r++) {
+      float v = acc[r] + bias;
+      if (mode == 0) v = v > 0.0f ? v : 0.0f;
+      else if (mode == 1) v = tanhf(v);
+      yj[r] = v;
+    }
+  }
+}
+
+// slab[W[i][j]] += sum_s x[i][s] delta[j][s], slab[b[j]] += sum_s delta[j][s]
+__device__ __forceinline__ void backward_weights(float *__restrict__ slab, const int nin, const int nout, const int woff, const int boff,
+                                                 const float *x, const float *dl) {
+  const int j = threadIdx.x;
+  if (j < nout) {
+    float d[kTile];
+#pragma unroll
+    for (int q = 0; q < kTile / 4; q++) {
+      const float4 v = *reinterpret_cast<const float4 *>(dl + j * kTile + 4 * q);
+      d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w;
+    }
+    float bs = d[0];
+#pragma unroll
+    for (int r = 1; r < kTile; r++) bs = bs + d[r];
+    slab[boff + j] = slab[boff + j] + bs;
+    float *__restrict__ sw = slab + woff + j;
+#pragma unroll 4
+    for (int i = 0; i < nin; i++) {
+      const float4 xa = *reinterpret_cast<const float4 *>(x + i * kTile);
+      const float4 xb = *reinterpret_cast<const float4 *>(x + i * kTile + 4);
+      const float4 xc = *reinterpret_cast<const float4 *>(x + i * kTile + 8);
+      const float4 xd = *reinterpret_cast<const float4 *>(x + i * kTile + 12);
+      float v = xa.x * d[0];
+      v = __builtin_fmaf(xa.y, d[1], v); v = __builtin_fmaf(xa.z, d[2], v); v = __builtin_fmaf(xa.w, d[3], v);
+      v = __builtin_fmaf(xb.x, d[4], v); v = __builtin_fmaf(xb.y, d[5], v); v = __builtin_fmaf(xb.z, d[6], v); v = __builtin_fmaf(xb.w, d[7], v);
+      v = __builtin_fmaf(xc.x, d[8], v); v = __builtin_fmaf(xc.y, d[9], v); v = __builtin_fmaf(xc.z, d[10], v); v = __builtin_fmaf(xc.w, d[11], v);
+      v = __builtin_fmaf(xd.x, d[12], v); v = __builtin_fmaf(xd.y, d[13], v); v = __builtin_fmaf(xd.z, d[14], v); v = __builtin_fmaf(xd.w, d[15], v);
+      const size_t o = (size_t)i * nout;
+      sw[o] = sw[o] + v;
+    }
+  }
+}
+
+// dn[i][s] = x[i][s] > 0 ? sum_j Wt[j][i] dl[j][s] : 0
+__device__ __forceinline__ void backward_inputs(const float *__restrict__ Wt, const int nin, const int nout, const int woff, const float *x,
+                                                const float *dl, float *dn) {
+  const int i = threadIdx.x;
+  if (i < nin) {
+    const float *__restrict__ W = Wt + woff + i;
+    float acc[kTile];
+#pragma unroll
+    for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
+#pragma unroll 4
+    for (int j = 0; j < nout; j++) {
+      const float w = W[(size_t)j * nin];
+      const float4 da = *reinterpret_cast<const float4 *>(dl + j * kTile);
+      const float4 db = *reinterpret_cast<const float4 *>(dl + j * kTile + 4);
+      const float4 dc = *reinterpret_cast<const float4 *>(dl + j * kTile + 8);
+      const float4 dd = *reinterpret_cast<const float4 *>(dl + j * kTile + 12);
+      acc[0] = __builtin_fmaf(w, da.x, acc[0]); acc[1] = __builtin_fmaf(w, da.y, acc[1]);
+      acc[2] = __builtin_fmaf(w, da.z, acc[2]); acc[3] = __builtin_fmaf(w, da.w, acc[3]);
+      acc[4] = __builtin_fmaf(w, db.x, acc[4]); acc[5] = __builtin_fmaf(w, db.y, acc[5]);
+      acc[6] = __builtin_fmaf(w, db.z, acc[6]); acc[7] = __builtin_fmaf(w, db.w, acc[7]);
+      acc[8] = __builtin_fmaf(w, dc.x, acc[8]); acc[9] = __builtin_fmaf(w, dc.y, acc[9]);
+      acc[10] = __builtin_fmaf(w, dc.z, acc[10]); acc[11] = __builtin_fmaf(w, dc.w, acc[11]);
+      acc[12] = __builtin_fmaf(w, dd.x, acc[12]); acc[13] = __builtin_fmaf(w, dd.y, acc[13]);
+      acc[14] = __builtin_fmaf(w, dd.z, acc[14]); acc[15] = __builtin_fmaf(w, dd.w, acc[15]);
+    }
+    const float *xi = x + i * kTile;
+    float *di = dn + i * kTile;
+#pragma unroll
+    for (int r = 0; r < kTile; r++) di[r] = xi[r] > 0.0f ? acc[r] : 0.0f;
+  }
+}
+
+template <bool kPolicy, bool kBackward>
+__device__ __forceinline__ void sweep(const Desc *__restrict__ dp, const float *__restrict__ P) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, g = blockIdx.x;
+  const SweepCfg &c = dp->net[kPolicy ? 0 : 1];
+  const RoDev &ro = dp->ro;
+  const double *__restrict__ norm = dp->norm;
+  const float *__restrict__ Wt = dp->wt;
+  const double *__restrict__ scal = dp->scal;
+  const double *__restrict__ klr = dp->klr;
+  double *__restrict__ kls = dp->kls;
+  const NetDesc &nd = c.nd;
+  float *d0 = lds + c.asum * kTile, *d1 = d0 + c.dmax * kTile;
+  float *slab = dp->slabs + (size_t)g * c.count;
+  const double inv = 1.0 / ((double)c.T * (double)c.B);
+  double loss = 0.0, gls[kMaxAct] = {0.0, 0.0, 0.0, 0.0};
+  if (kBackward) {   // every element of the slab belongs to the thread that accumulates it: that thread clears it
+    for (int l = 0; l < nd.n; l++) {
+      if (tid < nd.out[l]) {
+        slab[nd.b[l] + tid] = 0.0f;
+        for (int i = 0; i < nd.in[l]; i++) slab[nd.w[l] + (size_t)i * nd.out[l] + tid] = 0.0f;
+      }
+    }
+  }
+  for (int tile = g; tile < c.ntiles; tile += c.G) {
+    __syncthreads();   // the tile before has been read
+    // the observation through the normaliser, as rg_policy_act forms it
+    for (int idx = tid; idx < c.obs_dim * kTile; idx += kThreads) {
+      const int i = idx / kTile, n = tile * kTile + idx % kTile;
+      float xn = 0.0f;
+      if (n < c.N) {
+        const int t = n / c.B, b = n - t * c.B;
+        double v = (double)ro.obs[((size_t)t * c.obs_dim + i) * c.B + b] - norm[kCols + i];
+        v = v / norm_scale(norm[i], norm[2 * kCols + i]);
+        xn = (float)clip_sym(v, c.obs_clip);
+      }
+      lds[idx] = xn;
+    }
+    int ao = 0;   // where the input of layer l lies
+    for (int l = 0; l < nd.n; l++) {
+      __syncthreads();
+      const int an = ao + nd.in[l] * kTile;
+      forward_layer(P, nd.in[l], nd.out[l], nd.w[l], nd.b[l], lds + ao, lds + an, l < nd.n - 1 ? 0 : (kPolicy ? 1 : 2));
+      ao = an;
+    }
+    __syncthreads();
+    // the head: one sample per thread
+    if (tid < kTile) {
+      const int n = tile * kTile + tid;
+      const float *out = lds + c.asum * kTile - (kPolicy ? c.act_dim : 1) * kTile + tid;   // the head's activations, [k * kTile]
+      const bool live = n < c.N;
+      const bool valid = live && ro.mask[n] != 0;
+      if (kPolicy) {
+        const int b = live ? n % c.B : 0;
+        double kl = 0.0, lp = 0.0, lp0 = 0.0;
+        double z[kMaxAct], D[kMaxAct], q[kMaxAct], sg[kMaxAct], mu[kMaxAct];
+#pragma unroll
+        for (int k = 0; k < kMaxAct; k++) {
+          z[k] = D[k] = q[k] = mu[k] = 0.0;
+          sg[k] = 1.0;
+          if (k < c.act_dim && live) {
+            const double ls = (double)P[c.logstd_off + k], ls0 = (double)ro.logstd[k];
+            const double s1 = exp(ls), s0 = exp(ls0);
+            const double m1 = (double)out[k * kTile], m0 = (double)ro.mean[(size_t)n * c.act_dim + k];
+            const double a = (double)ro.action[(size_t)n * c.act_dim + k];
+            const double dk = m1 - m0, zk = (a - m1) / s1, z0 = (a - m0) / s0;
+            const double qk = (s0 * s0 + dk * dk) / (s1 * s1);
+            kl = kl + ((qk - 1.0) + 2.0 * (ls - ls0));
+            lp = lp + (-c.c * ls - 0.5 * (zk * zk));
+            lp0 = lp0 + (-c.c * ls0 - 0.5 * (z0 * z0));
+            z[k] = zk; D[k] = dk; q[k] = qk; sg[k] = s1; mu[k] = m1;
+          }
+        }
+        kl = 0.5 * kl;
+        if (!kBackward) {
+          if (live) kls[n] = valid ? kl : 0.0;
+        } else {
+          double ratio = 0.0, advn = 0.0, gb = 0.0;
+          if (valid) {
+            ratio = exp(lp - lp0);
+            advn = ((double)ro.adv[n] - scal[1]) / scal[2];
+            const double klb = klr[b];
+            gb = *dp->penalty + (klb > c.thr ? 2.0 * c.coef * (klb - c.thr) : 0.0);
+            loss = loss + ratio * advn;
+          }
+#pragma unroll
+          for (int k = 0; k < kMaxAct; k++) {
+            if (k < c.act_dim) {
+              float dlt = 0.0f;
+              if (valid) {
+                const double dmu = (-advn * ratio * z[k] / sg[k] + gb * D[k] / (sg[k] * sg[k])) * inv;
+                dlt = (float)(dmu * (1.0 - mu[k] * mu[k]));
+                gls[k] = gls[k] + (-advn * ratio * (z[k] * z[k] - c.c) + gb * (1.0 - q[k])) * inv;
+              }
+              d0[k * kTile + tid] = dlt;
+            }
+          }
+        }
+      } else {
+        float dlt = 0.0f;
+        if (valid) {
+          const double e = (double)ro.ret[n] - (double)out[0];
+          loss = loss + 0.5 * (e * e);
+          dlt = (float)(-e * inv);
+        }
+        d0[tid] = dlt;
+      }
+    }
+    if (kBackward) {
+      int cur = 0;
+      for (int l = nd.n - 1; l >= 0; l--) {
+        __syncthreads();
+        ao -= nd.in[l] * kTile;
+        const float *dl = cur ? d1 : d0;
+        float *dn = cur ? d0 : d1;
+        backward_weights(slab, nd.in[l], nd.out[l], nd.w[l], nd.b[l], lds + ao, dl);
+        if (l > 0) backward_inputs(Wt, nd.in[l], nd.out[l], nd.w[l], lds + ao, dl, dn);
+        cur ^= 1;
+      }
+    }
+  }
+  if (kBackward && tid < kTile) {
+    double *p = dp->part + ((size_t)g * kTile + tid) * kPart;
+    p[0] = loss;
+#pragma unroll
+    for (int k = 0; k < kMaxAct; k++) p[1 + k] = gls[k];
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) rg_ppo_policy_forward_kernel(const Desc *__restrict__ d, const float *__restrict__ P) {
+  sweep<true, false>(d, P);
+}
+
+__global__ void __launch_bounds__(kThreads) rg_ppo_policy_backward_kernel(const Desc *__restrict__ d, const float *__restrict__ P) {
+  sweep<true, true>(d, P);
+}
+
+__global__ void __launch_bounds__(kThreads) rg_ppo_value_backward_kernel(const Desc *__restrict__ d, const float *__restrict__ P) {
+  sweep<false, true>(d, P);
+}
+
+// KL_b = (sum_t kls[t][b]) / T, t in order
+__global__ void __launch_bounds__(kThreads) rg_ppo_robot_kl_kernel(const int T, const int B, const double *__restrict__ kls, double *__restrict__ out) {
+  const int b = blockIdx.x * kThreads + (int)threadIdx.x;
+  if (b >= B) return;
+  double s = 0.0;
+  for (int t = 0; t < T; t++) s = s + kls[(size_t)t * B + b];
+  out[b] = s / (double)T;
+}
+
+// grad[e] = (float) sum_g slab[g][e], g in order, for the first n elements (the networks; logstd is the loss kernel's)
+__global__ void __launch_bounds__(kThreads) rg_ppo_grad_finish_kernel(const int n, const int count, const int G, const float *__restrict__ slabs,
+                                                                      float *__restrict__ grad) {
+  const int e = blockIdx.x * kThreads + (int)threadIdx.x;
+  if (e >= n) return;
+  double s = 0.0;
+  for (int g = 0; g < G; g++) s = s + (double)slabs[(size_t)g * count + e];
+  grad[e] = (float)s;
+}
+
+struct LossCfg {
+  int policy, T, B, G, act_dim, logstd_off;
+  double thr, coef;
+};
+
+__global__ void __launch_bounds__(kThreads) rg_ppo_loss_finish_kernel(const LossCfg c, const double *__restrict__ part, const double *__restrict__ klr,
+                                                                      const double *__restrict__ penalty, float *__restrict__ grad,
+                                                                      double *__restrict__ loss_out, double *__restrict__ loss_out2) {
+  __shared__ double sh[4];
+  const double s1 = strided_sum(part, c.G * kTile, kPart, sh);
+  const double inv = 1.0 / ((double)c.T * (double)c.B);
+  double loss = s1 * inv;
+  if (c.policy) {
+    const double pen = *penalty;
+    double s2 = 0.0;
+    for (int b = threadIdx.x; b < c.B; b += kThreads) {
+      const double k = klr[b], over = k - c.thr;
+      s2 = s2 + (pen * k + (k > c.thr ? c.coef * (over * over) : 0.0));
+    }
+    s2 = block_sum(s2, sh);
+    loss = -(s1 * inv) + s2 / (double)c.B;
+#pragma unroll
+    for (int k = 0; k < kMaxAct; k++) {
+      if (k < c.act_dim) {   // uniform
+        const double gk = strided_sum(part + 1 + k, c.G * kTile, kPart, sh);
+        if (threadIdx.x == 0) grad[c.logstd_off + k] = (float)gk;
+      }
+    }
+  }
+  if (threadIdx.x == 0) {
+    *loss_out = loss;
+    if (loss_out2) *loss_out2 = loss;
+  }
+}
+
+// ---- Adam -----------------------------------------------------------------------------------------------------------
+
+struct AdamCfg {
+  int count;
+  double lr, b1, b2, eps;
+};
+
+__global__ void __launch_bounds__(kThreads) rg_ppo_adam_kernel(const AdamCfg c, float *__restrict__ p, const float *__restrict__ grad,
+                                                               float *__restrict__ m, float *__restrict__ v, const long long *__restrict__ step) {
+  const int e = blockIdx.x * kThreads + (int)threadIdx.x;
+  if (e >= c.count) return;
+  const double t = (double)(*step + 1);
+  const double bc1 = 1.0 - pow(c.b1, t), bc2s = sqrt(1.0 - pow(c.b2, t));
+  const float b1 = (float)c.b1, b2 = (float)c.b2, o1 = (float)(1.0 - c.b1), o2 = (float)(1.0 - c.b2);
+  const float gg = grad[e];
+  const float t1 = b1 * m[e], t2 = o1 * gg;
+  const float mn = t1 + t2;
+  const float t3 = b2 * v[e], t4 = gg * gg;
+  const float t5 = o2 * t4;
+  const float vn = t3 + t5;
+  m[e] = mn;
+  v[e] = vn;
+  const double denom = sqrt((double)vn) / bc2s + c.eps;
+  p[e] = (float)((double)p[e] - (c.lr / bc1) * (double)mn / denom);
+}
+
+__global__ void rg_ppo_adam_count_kernel(long long *__restrict__ step) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *step = *step + 1;
+}
+
+// ---- the penalty ------------------------------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(kThreads) rg_ppo_penalty_kernel(const int B, const double target, const int epochs_policy, const int epochs_value,
+                                                                  const double *__restrict__ klr, double *__restrict__ penalty,
+                                                                  double *__restrict__ stats) {
+  __shared__ double sh[4];
+  const double s = strided_sum(klr, B, 1, sh);
+  if (threadIdx.x == 0) {
+    const double change = s / (double)B;
+    double pen = *penalty;
+    if (change > 1.3 * target) pen = pen * 1.5;
+    else if (change < 0.7 * target) pen = pen / 1.5;
+    *penalty = pen;
+    stats[4] = change;
+    stats[5] = pen;
+    if (epochs_policy == 0) stats[0] = stats[1] = nan("");
+    if (epochs_value == 0) stats[2] = stats[3] = nan("");
+  }
+}
+
+struct DeviceScope {
+  int prev = -1;
+  bool switched = false;
+  hipError_t err = hipSuccess;
+  explicit DeviceScope(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess && prev >= 0; }
+  }
+  ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
+};
+
+thread_local std::string g_create_err;
+
+size_t round8(size_t n) { return (n + 7) & ~(size_t)7; }
+
+}  // namespace
+
+struct rg_ppo_handle {
+  rg_policy_config pcfg{};
+  rg_ppo_config cfg{};
+  SweepCfg pol{}, val{};
+  int T = 0, B = 0, N = 0, G = 0, GP = 0, device = 0, maxc = 0;
+  size_t lds_pol = 0, lds_val = 0;
+  // byte offsets into the workspace
+  size_t o_desc = 0, o_scal = 0, o_prep = 0, o_klr = 0, o_kls = 0, o_part = 0, o_grad = 0, o_wt = 0, o_slab = 0, ws_bytes = 0, opt_bytes = 0;
+  std::string err;
+};
+
+namespace {
+
+bool validate_policy(const rg_policy_config *cfg, std::string &err) {
+  char msg[200];
+  if (cfg->abi_version != RG_POLICY_ABI_VERSION) {
+    snprintf(msg, sizeof(msg), "policy_cfg.abi_version: %d, this library is version %d", cfg->abi_version, RG_POLICY_ABI_VERSION);
+    err = msg;
+    return false;
+  }
+  if (cfg->reserved0 != 0) { err = "policy_cfg.reserved0: must be 0"; return false; }
+  struct I { const char *name; int v, lo, hi; };
+  const I ints[] = {{"obs_dim", cfg->obs_dim, 1, RG_POLICY_MAX_OBS}, {"act_dim", cfg->act_dim, 1, RG_POLICY_MAX_ACT},
+                    {"n_policy_layers", cfg->n_policy_layers, 0, RG_POLICY_MAX_LAYERS}, {"n_value_layers", cfg->n_value_layers, 0, RG_POLICY_MAX_LAYERS}};
+  for (const I &f : ints)
+    if (f.v < f.lo || f.v > f.hi) {
+      snprintf(msg, sizeof(msg), "policy_cfg.%s: %d outside [%d, %d]", f.name, f.v, f.lo, f.hi);
+      err = msg;
+      return false;
+    }
+  for (int net = 0; net < 2; net++) {
+    const char *name = net ? "value_layers" : "policy_layers";
+    const int32_t *w = net ? cfg->value_layers : cfg->policy_layers;
+    const int n = net ? cfg->n_value_layers : cfg->n_policy_layers;
+    for (int k = 0; k < RG_POLICY_MAX_LAYERS; k++) {
+      if (k < n && (w[k] < 1 || w[k] > RG_POLICY_MAX_WIDTH)) {
+        snprintf(msg, sizeof(msg), "policy_cfg.%s[%d]: %d outside [1, %d]", name, k, w[k], RG_POLICY_MAX_WIDTH);
+        err = msg;
+        return false;
+      }
+      if (k >= n && w[k] != 0) {
+        snprintf(msg, sizeof(msg), "policy_cfg.%s[%d]: %d must be 0 past the %d layers in use", name, k, w[k], n);
+        err = msg;
+        return false;
+      }
+    }
+  }
+  if (!std::isfinite(cfg->obs_clip) || cfg->obs_clip < 0) {
+    snprintf(msg, sizeof(msg), "policy_cfg.obs_clip: %g must be finite and >= 0", cfg->obs_clip);
+    err = msg;
+    return false;
+  }
+  return true;
+}
+
+bool validate_ppo(const rg_ppo_config *cfg, std::string &err) {
+  char msg[200];
+  if (cfg->abi_version != RG_PPO_ABI_VERSION) {
+    snprintf(msg, sizeof(msg), "ppo_cfg.abi_version: %d, this library is version %d", cfg->abi_version, RG_PPO_ABI_VERSION);
+    err = msg;
+    return false;
+  }
+  struct I { const char *name; int v, lo, hi; };
+  const I ints[] = {{"epochs_policy", cfg->epochs_policy, 0, RG_PPO_MAX_EPOCHS}, {"epochs_value", cfg->epochs_value, 0, RG_PPO_MAX_EPOCHS},
+                    {"conv_logpdf", cfg->conv_logpdf, RG_PPO_LOGPDF_EXACT, RG_PPO_LOGPDF_REFERENCE}};
+  for (const I &f : ints)
+    if (f.v < f.lo || f.v > f.hi) {
+      snprintf(msg, sizeof(msg), "ppo_cfg.%s: %d outside [%d, %d]", f.name, f.v, f.lo, f.hi);
+      err = msg;
+      return false;
+    }
+  struct F { const char *name; double v; int kind; };   // kind 0: >= 0; 1: in [0, 1); 2: > 0
+  const F fields[] = {{"policy_lr", cfg->policy_lr, 0}, {"value_lr", cfg->value_lr, 0}, {"beta1", cfg->beta1, 1}, {"beta2", cfg->beta2, 1},
+                      {"adam_eps", cfg->adam_eps, 2}, {"kl_target", cfg->kl_target, 2}, {"kl_cutoff_factor", cfg->kl_cutoff_factor, 0},
+                      {"kl_cutoff_coef", cfg->kl_cutoff_coef, 0}};
+  for (const F &f : fields)
+    if (!std::isfinite(f.v) || f.v < 0 || (f.kind == 1 && f.v >= 1) || (f.kind == 2 && f.v <= 0)) {
+      snprintf(msg, sizeof(msg), "ppo_cfg.%s: %g must be finite and %s", f.name, f.v, f.kind == 0 ? ">= 0" : (f.kind == 1 ? "in [0, 1)" : "> 0"));
+      err = msg;
+      return false;
+    }
+  return true;
+}
+
+// the layout rule of rg_policy.h for one network: W[in][out] then b[out] per layer, the head last
+void fill_net(const rg_policy_config *cfg, int net, NetDesc &nd, int &count) {
+  const int32_t *widths = net ? cfg->value_layers : cfg->policy_layers;
+  const int nh = net ? cfg->n_value_layers : cfg->n_policy_layers;
+  std::memset(&nd, 0, sizeof(nd));
+  int off = 0, prev = cfg->obs_dim;
+  for (int l = 0; l <= nh; l++) {
+    const int width = l < nh ? widths[l] : (net ? 1 : cfg->act_dim);
+    nd.in[l] = prev; nd.out[l] = width;
+    nd.w[l] = off; off += prev * width;
+    nd.b[l] = off; off += width;
+    prev = width;
+  }
+  nd.n = nh + 1;
+  count = off;
+}
+
+int hip_fail(rg_ppo_handle *h, const char *what, hipError_t e) {
+  h->err = std::string(what) + ": " + hipGetErrorString(e);
+  return RG_PPO_ERR_HIP;
+}
+
+int no_device(rg_ppo_handle *h) {
+  h->err = "host-only handle (RG_PPO_DEVICE_NONE): the arguments are valid, there is no device to run on";
+  return RG_PPO_ERR_NO_DEVICE;
+}
+
+int launch_status(rg_ppo_handle *h, const char *what) {
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(h, what, e) : RG_PPO_OK;
+}
+
+int null_arg(rg_ppo_handle *h, const char *call, const char *name) {
+  h->err = std::string(call) + ": null " + name;
+  return RG_PPO_ERR_INVALID;
+}
+
+#define RG_NEED(call, ptr, name) \
+  do { if (!(ptr)) return null_arg(h, call, name); } while (0)
+
+RoDev ro_dev(const rg_ppo_rollout *ro) { return RoDev{ro->obs, ro->action, ro->mean, ro->logstd, ro->adv, ro->ret, (const int *)ro->mask}; }
+
+template <typename T>
+T *ws_at(void *workspace, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(workspace) + off); }
+
+const double *penalty_of(const void *opt_state) { return reinterpret_cast<const double *>(static_cast<const char *>(opt_state) + 16); }
+
+unsigned blocks_of(int n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+
+// ---- the launches of each entry, arguments checked and the device set by the caller ------------------------------------
+
+int run_describe(rg_ppo_handle *h, const rg_ppo_rollout *ro, const double *norm, const void *opt, void *ws, hipStream_t s) {
+  const Regions r{norm, opt ? penalty_of(opt) : nullptr, ws_at<double>(ws, h->o_scal), ws_at<double>(ws, h->o_klr), ws_at<double>(ws, h->o_kls),
+                  ws_at<double>(ws, h->o_part), ws_at<float>(ws, h->o_wt), ws_at<float>(ws, h->o_slab)};
+  hipLaunchKernelGGL(rg_ppo_describe_kernel, dim3(1), dim3(64), 0, s, h->pol, h->val, ro_dev(ro), r, ws_at<Desc>(ws, h->o_desc));
+  return launch_status(h, "rg_ppo_describe_kernel launch");
+}
+
+int run_prepare(rg_ppo_handle *h, const rg_ppo_rollout *ro, void *ws, hipStream_t s) {
+  double *prep = ws_at<double>(ws, h->o_prep), *scal = ws_at<double>(ws, h->o_scal);
+  hipLaunchKernelGGL(rg_ppo_prepare_first_kernel, dim3((unsigned)h->GP), dim3(kThreads), 0, s, h->N, h->GP, ro->adv, (const int *)ro->mask, prep);
+  int rc = launch_status(h, "rg_ppo_prepare_first_kernel launch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_ppo_prepare_second_kernel, dim3((unsigned)h->GP), dim3(kThreads), 0, s, h->N, h->GP, ro->adv, (const int *)ro->mask, prep);
+  rc = launch_status(h, "rg_ppo_prepare_second_kernel launch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_ppo_prepare_finish_kernel, dim3(1), dim3(kThreads), 0, s, h->GP, prep, scal);
+  return launch_status(h, "rg_ppo_prepare_finish_kernel launch");
+}
+
+int run_robot_kl(rg_ppo_handle *h, const rg_ppo_rollout *ro, const double *norm, const float *pp, void *ws, double *kl_out, hipStream_t s) {
+  double *kls = ws_at<double>(ws, h->o_kls);
+  hipLaunchKernelGGL(rg_ppo_policy_forward_kernel, dim3((unsigned)h->G), dim3(kThreads), h->lds_pol, s, ws_at<const Desc>(ws, h->o_desc), pp);
+  int rc = launch_status(h, "rg_ppo_policy_forward_kernel launch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_ppo_robot_kl_kernel, dim3(blocks_of(h->B)), dim3(kThreads), 0, s, h->T, h->B, kls, kl_out);
+  return launch_status(h, "rg_ppo_robot_kl_kernel launch");
+}
+
+int run_finish(rg_ppo_handle *h, bool policy, const double *penalty, void *ws, float *grad, double *loss_out, double *loss_out2, hipStream_t s) {
+  const SweepCfg &c = policy ? h->pol : h->val;
+  const int n = policy ? c.logstd_off : c.count;
+  hipLaunchKernelGGL(rg_ppo_grad_finish_kernel, dim3(blocks_of(n)), dim3(kThreads), 0, s, n, c.count, h->G, ws_at<float>(ws, h->o_slab), grad);
+  int rc = launch_status(h, "rg_ppo_grad_finish_kernel launch");
+  if (rc) return rc;
+  const LossCfg lc{policy ? 1 : 0, h->T, h->B, h->G, c.act_dim, c.logstd_off, c.thr, c.coef};
+  hipLaunchKernelGGL(rg_ppo_loss_finish_kernel, dim3(1), dim3(kThreads), 0, s, lc, ws_at<double>(ws, h->o_part), ws_at<double>(ws, h->o_klr), penalty,
+                     grad, loss_out, loss_out2);
+  return launch_status(h, "rg_ppo_loss_finish_kernel launch");
+}
+
+int run_policy_grad(rg_ppo_handle *h, const rg_ppo_rollout *ro, const double *norm, const float *pp, const void *opt, void *ws, float *grad,
+                    double *loss_out, double *loss_out2, hipStream_t s) {
+  float *wt = ws_at<float>(ws, h->o_wt);
+  hipLaunchKernelGGL(rg_ppo_transpose_kernel, dim3(blocks_of(h->pol.count)), dim3(kThreads), 0, s, h->pol.nd, pp, wt);
+  int rc = launch_status(h, "rg_ppo_transpose_kernel launch");
+  if (rc) return rc;
+  double *klr = ws_at<double>(ws, h->o_klr);
+  rc = run_robot_kl(h, ro, norm, pp, ws, klr, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_ppo_policy_backward_kernel, dim3((unsigned)h->G), dim3(kThreads), h->lds_pol, s, ws_at<const Desc>(ws, h->o_desc), pp);
+  rc = launch_status(h, "rg_ppo_policy_backward_kernel launch");
+  if (rc) return rc;
+  return run_finish(h, true, penalty_of(opt), ws, grad, loss_out, loss_out2, s);
+}
+
+int run_value_grad(rg_ppo_handle *h, const rg_ppo_rollout *ro, const double *norm, const float *vp, void *ws, float *grad, double *loss_out,
+                   double *loss_out2, hipStream_t s) {
+  float *wt = ws_at<float>(ws, h->o_wt);
+  hipLaunchKernelGGL(rg_ppo_transpose_kernel, dim3(blocks_of(h->val.count)), dim3(kThreads), 0, s, h->val.nd, vp, wt);
+  int rc = launch_status(h, "rg_ppo_transpose_kernel launch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_ppo_value_backward_kernel, dim3((unsigned)h->G), dim3(kThreads), h->lds_val, s, ws_at<const Desc>(ws, h->o_desc), vp);
+  rc = launch_status(h, "rg_ppo_value_backward_kernel launch");
+  if (rc) return rc;
+  return run_finish(h, false, nullptr, ws, grad, loss_out, loss_out2, s);
+}
+
+int run_adam(rg_ppo_handle *h, int which, float *params, const float *grad, void *opt, hipStream_t s) {
+  const int pc = h->pol.count, vc = h->val.count;
+  const int count = which == RG_PPO_POLICY ? pc : vc;
+  float *mom = reinterpret_cast<float *>(static_cast<char *>(opt) + RG_PPO_OPT_HEADER_BYTES);
+  float *m = which == RG_PPO_POLICY ? mom : mom + 2 * (size_t)pc;
+  long long *step = reinterpret_cast<long long *>(opt) + which;
+  const AdamCfg c{count, which == RG_PPO_POLICY ? h->cfg.policy_lr : h->cfg.value_lr, h->cfg.beta1, h->cfg.beta2, h->cfg.adam_eps};
+  hipLaunchKernelGGL(rg_ppo_adam_kernel, dim3(blocks_of(count)), dim3(kThreads), 0, s, c, params, grad, m, m + count, (const long long *)step);
+  int rc = launch_status(h, "rg_ppo_adam_kernel launch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_ppo_adam_count_kernel, dim3(1), dim3(64), 0, s, step);
+  return launch_status(h, "rg_ppo_adam_count_kernel launch");
+}
+
+int check_rollout(rg_ppo_handle *h, const char *call, const rg_ppo_rollout *ro, bool obs, bool action, bool mean, bool adv, bool ret) {
+  RG_NEED(call, ro, "rollout");
+  if (obs) RG_NEED(call, ro->obs, "rollout.obs");
+  if (action) RG_NEED(call, ro->action, "rollout.action");
+  if (mean) { RG_NEED(call, ro->mean, "rollout.mean"); RG_NEED(call, ro->logstd, "rollout.logstd"); }
+  if (adv) RG_NEED(call, ro->adv, "rollout.adv");
+  if (ret) RG_NEED(call, ro->ret, "rollout.ret");
+  RG_NEED(call, ro->mask, "rollout.mask");
+  return RG_PPO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t rg_ppo_abi_version(void) { return RG_PPO_ABI_VERSION; }
+int32_t rg_ppo_config_size(void) { return (int32_t)sizeof(rg_ppo_config); }
+int32_t rg_ppo_rollout_size(void) { return (int32_t)sizeof(rg_ppo_rollout); }
+int32_t rg_ppo_tile(void) { return RG_PPO_TILE; }
+const char *rg_ppo_last_error(const rg_ppo_handle *h) { return h ? h->err.c_str() : g_create_err.c_str(); }
+int64_t rg_ppo_workspace_bytes(const rg_ppo_handle *h) { return h ? (int64_t)h->ws_bytes : -1; }
+int64_t rg_ppo_opt_state_bytes(const rg_ppo_handle *h) { return h ? (int64_t)h->opt_bytes : -1; }
+int32_t rg_ppo_groups(const rg_ppo_handle *h) { return h ? h->G : -1; }
+int64_t rg_ppo_scalars_offset(const rg_ppo_handle *h) { return h ? (int64_t)h->o_scal : -1; }
+
+int rg_ppo_create(const rg_policy_config *policy_cfg, const rg_ppo_config *ppo_cfg, int32_t T, int32_t B, int32_t device, rg_ppo_handle **out) {
+  if (!policy_cfg || !ppo_cfg || !out) { g_create_err = "create: null policy_cfg, ppo_cfg or out"; return RG_PPO_ERR_INVALID; }
+  *out = nullptr;
+  char msg[128];
+  std::string err;
+  if (!validate_policy(policy_cfg, err) || !validate_ppo(ppo_cfg, err)) { g_create_err = err; return RG_PPO_ERR_INVALID; }
+  if (T < 1 || T > RG_POLICY_MAX_T) {
+    snprintf(msg, sizeof(msg), "T: %d outside [1, %d]", T, RG_POLICY_MAX_T);
+    g_create_err = msg;
+    return RG_PPO_ERR_INVALID;
+  }
+  if (B < 1 || B > RG_POLICY_MAX_BATCH) {
+    snprintf(msg, sizeof(msg), "B: %d outside [1, %d]", B, RG_POLICY_MAX_BATCH);
+    g_create_err = msg;
+    return RG_PPO_ERR_INVALID;
+  }
+  if ((long long)T * B > RG_PPO_MAX_SAMPLES) {
+    snprintf(msg, sizeof(msg), "T * B: %lld above %d", (long long)T * B, RG_PPO_MAX_SAMPLES);
+    g_create_err = msg;
+    return RG_PPO_ERR_INVALID;
+  }
+  rg_ppo_handle *h = new rg_ppo_handle();
+  h->pcfg = *policy_cfg;
+  h->cfg = *ppo_cfg;
+  h->T = T; h->B = B; h->N = T * B; h->device = device;
+  const int ntiles = (h->N + kTile - 1) / kTile;
+  h->G = ntiles < kMaxGroups ? ntiles : kMaxGroups;
+  h->GP = (h->N + kThreads - 1) / kThreads;
+  if (h->GP > kMaxGroups) h->GP = kMaxGroups;
+  for (int net = 0; net < 2; net++) {
+    SweepCfg &c = net ? h->val : h->pol;
+    fill_net(policy_cfg, net, c.nd, c.count);
+    c.T = T; c.B = B; c.N = h->N; c.G = h->G; c.ntiles = ntiles;
+    c.obs_dim = policy_cfg->obs_dim; c.act_dim = policy_cfg->act_dim;
+    c.logstd_off = c.count;
+    if (!net) c.count += policy_cfg->act_dim;
+    c.asum = policy_cfg->obs_dim;
+    c.dmax = 0;
+    for (int l = 0; l < c.nd.n; l++) {
+      c.asum += c.nd.out[l];
+      if (c.nd.out[l] > c.dmax) c.dmax = c.nd.out[l];
+    }
+    c.obs_clip = policy_cfg->obs_clip;
+    c.c = ppo_cfg->conv_logpdf == RG_PPO_LOGPDF_EXACT ? 1.0 : 0.5;
+    c.thr = ppo_cfg->kl_target * ppo_cfg->kl_cutoff_factor;
+    c.coef = ppo_cfg->kl_cutoff_coef;
+    (net ? h->lds_val : h->lds_pol) = sizeof(float) * (size_t)kTile * (size_t)(c.asum + 2 * c.dmax);
+  }
+  h->maxc = h->pol.count > h->val.count ? h->pol.count : h->val.count;
+  size_t off = 0;
+  h->o_desc = off; off += round8(sizeof(Desc));
+  h->o_scal = off; off += sizeof(double) * kScal;
+  h->o_prep = off; off += sizeof(double) * (size_t)h->GP * kPrep;
+  h->o_klr = off; off += sizeof(double) * (size_t)B;
+  h->o_kls = off; off += sizeof(double) * (size_t)h->N;
+  h->o_part = off; off += sizeof(double) * (size_t)h->G * kTile * kPart;
+  h->o_grad = off; off += round8(sizeof(float) * (size_t)h->maxc);
+  h->o_wt = off; off += round8(sizeof(float) * (size_t)h->maxc);
+  h->o_slab = off; off += round8(sizeof(float) * (size_t)h->G * (size_t)h->maxc);
+  h->ws_bytes = off;
+  h->opt_bytes = round8(RG_PPO_OPT_HEADER_BYTES + sizeof(float) * 2 * ((size_t)h->pol.count + (size_t)h->val.count));
+  if (device == RG_PPO_DEVICE_NONE) {   // a host-only handle: the configuration, for argument checks on any machine
+    *out = h;
+    return RG_PPO_OK;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_err = "no HIP device available"; delete h; return RG_PPO_ERR_NO_DEVICE; }
+  if (device < 0 || device >= ndev) { g_create_err = "device index out of range"; delete h; return RG_PPO_ERR_INVALID; }
+  DeviceScope dev(device);
+  if (dev.err != hipSuccess) { g_create_err = std::string("hipSetDevice failed: ") + hipGetErrorString(dev.err); delete h; return RG_PPO_ERR_HIP; }
+  // the sweeps' tiles may need more dynamic LDS than the default limit of a launch.  The attribute belongs to the function and
+  // the device, not to the handle: it is set to the most any configuration of the ABI needs, so handles do not undo each other
+  hipError_t e = hipFuncSetAttribute((const void *)rg_ppo_policy_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void *)rg_ppo_policy_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void *)rg_ppo_value_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+  if (e != hipSuccess) {
+    g_create_err = std::string("hipFuncSetAttribute failed: ") + hipGetErrorString(e);
+    delete h;
+    return RG_PPO_ERR_HIP;
+  }
+  *out = h;
+  return RG_PPO_OK;
+}
+
+void rg_ppo_destroy(rg_ppo_handle *h) { delete h; }
+
+int rg_ppo_prepare(rg_ppo_handle *h, const rg_ppo_rollout *ro, void *workspace, void *stream) {
+  if (!h) { g_create_err = "prepare: null handle"; return RG_PPO_ERR_INVALID; }
+  int rc = check_rollout(h, "prepare", ro, false, false, false, true, false);
+  if (rc) return rc;
+  RG_NEED("prepare", workspace, "workspace");
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  return run_prepare(h, ro, workspace, (hipStream_t)stream);
+}
+
+int rg_ppo_policy_grad(rg_ppo_handle *h, const rg_ppo_rollout *ro, const double *norm_state, const float *policy_params, const void *opt_state,
+                       void *workspace, float *grad_out, double *loss_out, void *stream) {
+  if (!h) { g_create_err = "policy_grad: null handle"; return RG_PPO_ERR_INVALID; }
+  int rc = check_rollout(h, "policy_grad", ro, true, true, true, true, false);
+  if (rc) return rc;
+  RG_NEED("policy_grad", norm_state, "norm_state");
+  RG_NEED("policy_grad", policy_params, "policy_params");
+  RG_NEED("policy_grad", opt_state, "opt_state");
+  RG_NEED("policy_grad", workspace, "workspace");
+  RG_NEED("policy_grad", grad_out, "grad_out");
+  RG_NEED("policy_grad", loss_out, "loss_out");
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  rc = run_describe(h, ro, norm_state, opt_state, workspace, (hipStream_t)stream);
+  if (rc) return rc;
+  return run_policy_grad(h, ro, norm_state, policy_params, opt_state, workspace, grad_out, loss_out, nullptr, (hipStream_t)stream);
+}
+
+int rg_ppo_value_grad(rg_ppo_handle *h, const rg_ppo_rollout *ro, const double *norm_state, const float *value_params, void *workspace,
+                      float *grad_out, double *loss_out, void *stream) {
+  if (!h) { g_create_err = "value_grad: null handle"; return RG_PPO_ERR_INVALID; }
+  int rc = check_rollout(h, "value_grad", ro, true, false, false, false, true);
+  if (rc) return rc;
+  RG_NEED("value_grad", norm_state, "norm_state");
+  RG_NEED("value_grad", value_params, "value_params");
+  RG_NEED("value_grad", workspace, "workspace");
+  RG_NEED("value_grad", grad_out, "grad_out");
+  RG_NEED("value_grad", loss_out, "loss_out");
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  rc = run_describe(h, ro, norm_state, nullptr, workspace, (hipStream_t)stream);
+  if (rc) return rc;
+  return run_value_grad(h, ro, norm_state, value_params, workspace, grad_out, loss_out, nullptr, (hipStream_t)stream);
+}
+
+int rg_ppo_adam(rg_ppo_handle *h, int32_t which, float *params, const float *grad, void *opt_state, void *stream) {
+  if (!h) { g_create_err = "adam: null handle"; return RG_PPO_ERR_INVALID; }
+  if (which != RG_PPO_POLICY && which != RG_PPO_VALUE) { h->err = "adam: which is neither RG_PPO_POLICY nor RG_PPO_VALUE"; return RG_PPO_ERR_INVALID; }
+  RG_NEED("adam", params, "params");
+  RG_NEED("adam", grad, "grad");
+  RG_NEED("adam", opt_state, "opt_state");
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  return run_adam(h, which, params, grad, opt_state, (hipStream_t)stream);
+}
+
+int rg_ppo_kl(rg_ppo_handle *h, const rg_ppo_rollout *ro, const double *norm_state, const float *policy_params, void *workspace, double *kl_out,
+              void *stream) {
+  if (!h) { g_create_err = "kl: null handle"; return RG_PPO_ERR_INVALID; }
+  int rc = check_rollout(h, "kl", ro, true, false, true, false, false);
+  if (rc) return rc;
+  RG_NEED("kl", norm_state, "norm_state");
+  RG_NEED("kl", policy_params, "policy_params");
+  RG_NEED("kl", workspace, "workspace");
+  RG_NEED("kl", kl_out, "kl_out");
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  rc = run_describe(h, ro, norm_state, nullptr, workspace, (hipStream_t)stream);
+  if (rc) return rc;
+  return run_robot_kl(h, ro, norm_state, policy_params, workspace, kl_out, (hipStream_t)stream);
+}
+
+int rg_ppo_update(rg_ppo_handle *h, const rg_ppo_rollout *ro, const double *norm_state, float *policy_params, float *value_params, void *opt_state,
+                  void *workspace, double *stats, void *stream) {
+  if (!h) { g_create_err = "update: null handle"; return RG_PPO_ERR_INVALID; }
+  int rc = check_rollout(h, "update", ro, true, true, true, true, true);
+  if (rc) return rc;
+  RG_NEED("update", norm_state, "norm_state");
+  RG_NEED("update", policy_params, "policy_params");
+  RG_NEED("update", value_params, "value_params");
+  RG_NEED("update", opt_state, "opt_state");
+  RG_NEED("update", workspace, "workspace");
+  RG_NEED("update", stats, "stats");
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  hipStream_t s = (hipStream_t)stream;
+  float *grad = ws_at<float>(workspace, h->o_grad);
+  rc = run_describe(h, ro, norm_state, opt_state, workspace, s);
+  if (!rc) rc = run_prepare(h, ro, workspace, s);
+  for (int e = 0; e < h->cfg.epochs_policy && !rc; e++) {
+    rc = run_policy_grad(h, ro, norm_state, policy_params, opt_state, workspace, grad, e == 0 ? stats + 0 : stats + 1, e == 0 ? stats + 1 : nullptr, s);
+    if (!rc) rc = run_adam(h, RG_PPO_POLICY, policy_params, grad, opt_state, s);
+  }
+  for (int e = 0; e < h->cfg.epochs_value && !rc; e++) {
+    rc = run_value_grad(h, ro, norm_state, value_params, workspace, grad, e == 0 ? stats + 2 : stats + 3, e == 0 ? stats + 3 : nullptr, s);
+    if (!rc) rc = run_adam(h, RG_PPO_VALUE, value_params, grad, opt_state, s);
+  }
+  if (rc) return rc;
+  double *klr = ws_at<double>(workspace, h->o_klr);
+  rc = run_robot_kl(h, ro, norm_state, policy_params, workspace, klr, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_ppo_penalty_kernel, dim3(1), dim3(kThreads), 0, s, h->B, h->cfg.kl_target, h->cfg.epochs_policy, h->cfg.epochs_value,
+                     (const double *)klr, reinterpret_cast<double *>(static_cast<char *>(opt_state) + 16), stats);
+  return launch_status(h, "rg_ppo_penalty_kernel launch");
+}
+
+}  // extern "C"
