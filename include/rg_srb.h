@@ -6,9 +6,10 @@
  * forward with the controller's own first-step forces and kinematic feet, for B robots per call with no host in the
  * loop.  It is for closed-loop validation of the controller, branched (cloned) rollouts and RL on the reduced model.
  *
- * Stated limits: flat ground at z = 0; feet that neither slip nor bounce; massless legs; touch-down and lift-off by the
- * gait schedule (the controller's desired_state), not by measured contact; first-order (semi-implicit Euler) integration.
- * Terrain, slip and early / late contact are out of scope.
+ * Stated limits: feet that neither slip nor bounce; massless legs; touch-down and lift-off by the gait schedule (the
+ * controller's desired_state), not by measured contact; first-order (semi-implicit Euler) integration.  The ground is the
+ * plane z = 0 or a heightfield (rg_srb_set_terrain, below): kinematic feet, schedule contact, no slip.  Slip, early / late
+ * contact and contact by measurement are out of scope on either.
  *
  * Conventions (those of rg_posctl.h)
  *   - return 0 on success, a negative rg_srb_status otherwise; nothing throws across the ABI; rg_srb_last_error() gives
@@ -16,7 +17,8 @@
  *   - the CALLER owns every buffer (device memory, e.g. torch-ROCm tensors passed as data_ptr()), the simulation state
  *     included; the handle holds the configuration and the per-robot true body.
  *   - all work is enqueued on the hipStream_t passed in (NULL = default stream); rg_srb_step never synchronises.
- *     rg_srb_reset and rg_srb_set_body take HOST arrays and wait for their own small host->device copy.
+ *     rg_srb_reset and rg_srb_set_body take HOST arrays and wait for their own small host->device copy; nothing else
+ *     synchronises.
  *   - one handle per (device, stream); calls on one handle are not thread-safe.  Every call leaves the calling thread's
  *     current HIP device as it found it.
  *   - every value is computed in IEEE float64 with floating-point contraction off; the observation is stored as float32.
@@ -35,7 +37,8 @@
  *
  * One control tick (rg_srb_step), given the controller's outputs of this tick
  *   1. Feet.  A leg whose desired_state is SWING (0) follows its target perfectly: foot_w = p + R foot_target, stance = 0.
- *      Otherwise a foot that was swinging lands where it is (foot_w.z = 0, stance = 1); a foot on the ground stays (no slip).
+ *      Otherwise a foot that was swinging lands where it is (foot_w.z = 0, on a terrain the ground's height there; stance = 1);
+ *      a foot on the ground stays (no slip).
  *   2. `substeps` sub-steps of dt_sim with the forces held in the body frame.  With the current rotation R of quat:
  *        f_l = R (-grf_l) for the legs not in SWING (grf is the negated first-step force: the ground pushes with -grf)
  *        F   = ((f_0 + f_1) + (f_2 + f_3)) + m (0, 0, -g) + ext_F
@@ -43,7 +46,8 @@
  *        w  += dt R I^-1 (R' tau - (R' w) x I (R' w))      [ = I_w^-1 (tau - w x I_w w) with I_w = R I R', in the body frame ]
  *        v  += dt F / m ;  p += dt v ;  quat += 1/2 dt (w, 0) (x) quat, then normalised
  *      Semi-implicit Euler in exactly this order; steps += substeps.
- *   3. Fall.  status = 1 if any state value is non-finite, p.z < fall_height_scale * body_height, or the body z axis is
+ *   3. Fall.  status = 1 if any state value is non-finite, p.z (on a terrain: p.z less the ground's height under the body)
+ *      < fall_height_scale * body_height, or the body z axis is
  *      tilted more than fall_tilt from vertical.  A robot whose new state is non-finite keeps its last state (only status
  *      is written).  A fallen robot is frozen: later ticks leave its state and its observation untouched until it is
  *      reset, so nothing non-finite ever reaches the controller.
@@ -52,6 +56,32 @@
  *      q = damped-Newton leg IK of foot_pos_l started from the stored q (chain, iteration count, damping and step limit of
  *      the configuration: the controller's own leg_ik), jac = the leg's Jacobian at the new q (d foot_i / d joint_j, index
  *      leg*9 + i*3 + j, as rg_mpc_state_ptrs.jac), t_robot = steps * dt_sim (float64).
+ *
+ * Terrain (rg_srb_set_terrain; an extension of the reference's model/world/terrain.py to the batched model)
+ *   The ground is a height h(x, y; robot) over a square lattice of vertices, float64 with contraction off.
+ *   RANDOM: the reference's `random` heightfield made stateless and unbounded.  Vertex (i, j) sits at (i cell, j cell) and
+ *     its height is amplitude * u(seed, key_robot, i >> 1, j >> 1) (arithmetic shifts: heights are constant over 2 x 2 vertex
+ *     groups, as in the reference), u = (h >> 11) * 2^-53 of the chain of rg_episode.h over the words (key, I, J):
+ *     h = seed; for w in (key, I, J): h = mix((h ^ w) + 0x9E3779B97F4A7C15), I and J as two's-complement 64-bit words.
+ *     key: a caller-owned int64 [B] device row the caller initialises (robots with equal keys walk the same world); NULL
+ *     means key 0 for every robot.  The reference's defaults: cell 0.05, amplitude 0.06.
+ *   GRID: caller-owned float64 heights[rows][cols] on the device, heights[i][j] at (x0 + i cell, y0 + j cell), indices
+ *     clamped at the edges (the ground goes on at its border value), shared by all robots; rows, cols in 2 .. 4096.
+ *   Inside a cell, with s = x / cell (grid: (x - x0) / cell), i = floor(s), u = s - i and likewise t, j, v from y, the cell
+ *     is split along the diagonal from (i, j) to (i+1, j+1):
+ *        u >= v:  h = h00 + u (h10 - h00) + v (h11 - h10)        otherwise:  h = h00 + u (h11 - h01) + v (h01 - h00)
+ *     evaluated left to right; the surface is continuous.  Which diagonal Bullet's heightfield shape uses is not pinned
+ *     anywhere this project can read: this is a choice, not a port.
+ *   Before the conversion to an integer, s and t are clamped to +-2^40 as fmin(fmax(s, -2^40), 2^40): a NaN becomes the
+ *     lower bound, no conversion is undefined, and any state value has a defined ground.
+ *   With a terrain set, three rules of the tick change and nothing else:
+ *     landing   foot_w.z = h(foot_w.x, foot_w.y) instead of 0.  A swinging foot still follows its target and is not tested
+ *               against the ground (no early or late contact): with amplitude 0 every value is the plane's, bit for bit.
+ *     fall      p.z - h(p.x, p.y) < fall_height_scale * body_height
+ *     reset     the flat reset followed by rg_srb_settle of the robots reset
+ *   Settle (rg_srb_settle), for the robots of a mask whose status is 0: foot_w.z = h_l = h(foot_w.xy) for each foot l,
+ *     p.z += ((h_0 + h_1) + (h_2 + h_3)) * 0.25, and the observation rewritten with RG_SRB_RESET_IK_PASSES IK passes from the
+ *     stored q.
  */
 #ifndef RG_SRB_H
 #define RG_SRB_H
@@ -164,5 +194,8 @@ int rg_srb_step(rg_srb_handle *h, double *state, const float *grf, const float *
 #ifdef __cplusplus
 }
 #endif
+
+/* The terrain entries (the ground struct, set_terrain, ground_height, settle): part of this ABI, declared in their own file. */
+#include "rg_srb_terrain.h"
 
 #endif /* RG_SRB_H */

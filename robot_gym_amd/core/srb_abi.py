@@ -45,6 +45,18 @@ class CObsPtrs(C.Structure):
     _fields_ = [(name, fp) for name in OBS_FIELDS]
 
 
+class CTerrain(C.Structure):
+    """rg_srb_terrain (include/rg_srb_terrain.h)."""
+    _fields_ = [("abi_version", i32), ("kind", i32), ("cell", d), ("amplitude", d), ("seed", C.c_uint64), ("key", fp), ("heights", fp),
+                ("rows", i32), ("cols", i32), ("x0", d), ("y0", d), ("reserved", C.c_int64 * 4)]
+
+
+TERRAIN_FLAT, TERRAIN_RANDOM, TERRAIN_GRID = 0, 1, 2
+TERRAIN_MAX_DIM = 4096   # RG_SRB_TERRAIN_MAX_DIM
+
+# the terrain entries, declared in include/rg_srb_terrain.h
+TERRAIN_EXPORTS = ("rg_srb_terrain_size", "rg_srb_terrain_check", "rg_srb_set_terrain", "rg_srb_ground_height", "rg_srb_settle")
+
 EXPORTS = ("rg_srb_create", "rg_srb_destroy", "rg_srb_last_error", "rg_srb_abi_version", "rg_srb_config_size", "rg_srb_state_rows",
            "rg_srb_set_body", "rg_srb_reset", "rg_srb_step")
 
@@ -80,15 +92,43 @@ def load_library(path=None):
     L.rg_srb_reset.restype = i32
     L.rg_srb_step.argtypes = [fp, fp, fp, fp, fp, fp, C.POINTER(CObsPtrs), fp]
     L.rg_srb_step.restype = i32
+    L.rg_srb_terrain_size.restype = i32
+    L.rg_srb_terrain_check.argtypes = [C.POINTER(CTerrain), C.c_char_p, i32]
+    L.rg_srb_terrain_check.restype = i32
+    L.rg_srb_set_terrain.argtypes = [fp, C.POINTER(CTerrain)]
+    L.rg_srb_set_terrain.restype = i32
+    L.rg_srb_ground_height.argtypes = [fp, fp, fp, i32, fp, fp]
+    L.rg_srb_ground_height.restype = i32
+    L.rg_srb_settle.argtypes = [fp, fp, fp, C.POINTER(CObsPtrs), fp]
+    L.rg_srb_settle.restype = i32
     if L.rg_srb_abi_version() != ABI_VERSION:
         raise ImportError("librg_mpc.so rg_srb ABI version mismatch")
     if L.rg_srb_config_size() != C.sizeof(CConfig):
         raise ImportError(f"rg_srb_config size mismatch: lib {L.rg_srb_config_size()} vs binding {C.sizeof(CConfig)}")
     if L.rg_srb_state_rows() != STATE_ROWS:
         raise ImportError(f"rg_srb state rows mismatch: lib {L.rg_srb_state_rows()} vs binding {STATE_ROWS}")
+    if L.rg_srb_terrain_size() != C.sizeof(CTerrain):
+        raise ImportError(f"rg_srb_terrain size mismatch: lib {L.rg_srb_terrain_size()} vs binding {C.sizeof(CTerrain)}")
     if path is None:
         _lib = L
     return L
+
+
+def make_cterrain(kind=TERRAIN_FLAT, cell=0.0, amplitude=0.0, seed=0, key=None, heights=None, rows=0, cols=0, x0=0.0, y0=0.0):
+    """CTerrain of the given fields; key / heights are device addresses (or None).  Nothing is checked here: the library does."""
+    t = CTerrain()
+    t.abi_version, t.kind = ABI_VERSION, int(kind)
+    t.cell, t.amplitude, t.seed = float(cell), float(amplitude), int(seed) & 0xFFFFFFFFFFFFFFFF
+    t.key, t.heights = key, heights
+    t.rows, t.cols, t.x0, t.y0 = int(rows), int(cols), float(x0), float(y0)
+    return t
+
+
+def terrain_check(t):
+    """(status, text) of rg_srb_terrain_check: needs the library, no device."""
+    buf = C.create_string_buffer(256)
+    rc = load_library().rg_srb_terrain_check(C.byref(t), buf, len(buf))
+    return rc, buf.value.decode()
 
 
 def sim_fields(cfg, **sim):
@@ -211,6 +251,16 @@ class SrbHandle:
     def step(self, state_ptr, grf_ptr, foot_target_ptr, desired_ptr, ext_ptr, obs: CObsPtrs):
         self._check(self._lib.rg_srb_step(self._h, state_ptr, grf_ptr, foot_target_ptr, desired_ptr, ext_ptr, C.byref(obs),
                                           _stream(self.device)))
+
+    def set_terrain(self, t: CTerrain = None):
+        """t None: back to the plane.  The caller keeps the device arrays t points at alive."""
+        self._check(self._lib.rg_srb_set_terrain(self._h, None if t is None else C.byref(t)))
+
+    def ground_height(self, xy_ptr, robot_ptr, n, out_ptr):
+        self._check(self._lib.rg_srb_ground_height(self._h, xy_ptr, robot_ptr, int(n), out_ptr, _stream(self.device)))
+
+    def settle(self, state_ptr, mask_ptr, obs: CObsPtrs):
+        self._check(self._lib.rg_srb_settle(self._h, state_ptr, mask_ptr, C.byref(obs), _stream(self.device)))
 
     def close(self):
         if self._h:

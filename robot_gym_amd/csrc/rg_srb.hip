@@ -29,12 +29,17 @@
 
 namespace {
 
-constexpr int kBlock = 256;            // 64 robots per workgroup
-constexpr int kBodyRows = 19;          // per-robot true body [kBodyRows][B]: mass, I[9], I^-1[9]
-constexpr int kResetRows = 5;          // reset staging [kResetRows][B]: robot, x, y, yaw, height
-
 // SrbCfg, Obs, the rotations, write_obs, srb_reset_robot and the configuration checks: shared with rg_episode.hip
 #include "rg_srb_dev.inc"
+
+}  // namespace
+
+// the handle and the host-side helpers: shared with rg_srb_terrain.hip
+#include "rg_srb_handle.h"
+
+namespace {
+
+constexpr int kBlock = kSrbBlock, kBodyRows = kSrbBodyRows, kResetRows = kSrbResetRows;
 
 // sum over the four lanes of a robot: (x_0 + x_1) + (x_2 + x_3) in every lane
 __device__ __forceinline__ double sum4(double x) {
@@ -172,37 +177,7 @@ __global__ void __launch_bounds__(kBlock) rg_srb_reset_kernel(const DevCfg *__re
   srb_reset_robot(kc, c, o, state, (int)rs[k], leg, rs[sn + k], rs[2 * sn + k], rs[3 * sn + k], rs[4 * sn + k]);
 }
 
-// The calling thread's current device is restored on scope exit (rg_mpc.h conventions).
-struct DeviceScope {
-  int prev = -1;
-  bool switched = false;
-  hipError_t err = hipSuccess;
-  explicit DeviceScope(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess && prev >= 0; }
-  }
-  ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
-};
-
 thread_local std::string g_create_err;
-
-
-}  // namespace
-
-struct rg_srb_handle {
-  SrbCfg c;
-  rg_srb_config cfg;
-  double cfg_Iinv[9];
-  int B = 0, device = 0;
-  DevCfg *dcfg = nullptr;     // the kinematic fields of the controller's DevCfg, for leg_fk / leg_ik
-  double *body = nullptr;     // [kBodyRows][B]
-  double *stage = nullptr;    // [kResetRows][B]
-  std::vector<double> body_host, stage_host;
-  std::string err;
-};
-
-namespace {
-
 
 void default_body(rg_srb_handle *h, int b) {
   const size_t B = (size_t)h->B;
@@ -210,23 +185,9 @@ void default_body(rg_srb_handle *h, int b) {
   for (int i = 0; i < 9; i++) { h->body_host[(1 + i) * B + b] = h->cfg.inertia[i]; h->body_host[(10 + i) * B + b] = h->cfg_Iinv[i]; }
 }
 
-int hip_fail(rg_srb_handle *h, const char *what, hipError_t e) {
-  h->err = std::string(what) + ": " + hipGetErrorString(e);
-  return RG_SRB_ERR_HIP;
-}
-
-int launch_status(rg_srb_handle *h, const char *what) {
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? hip_fail(h, what, e) : RG_SRB_OK;
-}
-
-bool obs_ok(const rg_srb_obs_ptrs *o) {
-  return o && o->rpy && o->rpy_rate && o->v_world && o->quat && o->q && o->foot_pos && o->jac && o->contact && o->t_robot;
-}
-
-Obs to_obs(const rg_srb_obs_ptrs *o) { return {o->rpy, o->rpy_rate, o->v_world, o->quat, o->q, o->foot_pos, o->jac, o->contact, o->t_robot}; }
-
 }  // namespace
+
+void rg_srb_thread_error(const char *text) { g_create_err = text; }
 
 extern "C" {
 
@@ -286,6 +247,7 @@ void rg_srb_destroy(rg_srb_handle *h) {
     if (h->dcfg) (void)hipFree(h->dcfg);
     if (h->body) (void)hipFree(h->body);
     if (h->stage) (void)hipFree(h->stage);
+    if (h->reset_mask) (void)hipFree(h->reset_mask);
   }
   delete h;
 }
@@ -362,8 +324,20 @@ int rg_srb_reset(rg_srb_handle *h, const int32_t *idx_host, int32_t n, const dou
   if (e != hipSuccess) return hip_fail(h, "reset copy", e);
   const unsigned lanes = 4u * (unsigned)n;
   hipLaunchKernelGGL(rg_srb_reset_kernel, dim3((lanes + kBlock - 1) / kBlock), dim3(kBlock), 0, s, h->dcfg, h->c, n, h->stage, state, to_obs(obs));
-  const int rc = launch_status(h, "rg_srb_reset_kernel launch");
+  int rc = launch_status(h, "rg_srb_reset_kernel launch");
   if (rc) return rc;
+  if (h->ground.kind != 0) {   // a reset on a terrain is the flat reset followed by settle, for the robots just reset
+    const int32_t *mask = nullptr;
+    if (idx_host || n != B) {
+      h->mask_host.assign((size_t)B, 0);
+      for (int k = 0; k < n; k++) h->mask_host[idx_host ? idx_host[k] : k] = 1;
+      e = hipMemcpyAsync(h->reset_mask, h->mask_host.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s);
+      if (e != hipSuccess) return hip_fail(h, "reset mask copy", e);
+      mask = h->reset_mask;
+    }
+    rc = rg_srb_terrain_settle_launch(h, state, mask, obs, s);
+    if (rc) return rc;
+  }
   e = hipStreamSynchronize(s);   // the staging buffers are reused by the next call
   return e != hipSuccess ? hip_fail(h, "reset", e) : RG_SRB_OK;
 }
@@ -374,6 +348,7 @@ int rg_srb_step(rg_srb_handle *h, double *state, const float *grf, const float *
   if (!state || !grf || !foot_target || !desired_state || !obs_ok(obs)) { h->err = "step: null state, controller output or observation pointer"; return RG_SRB_ERR_INVALID; }
   DeviceScope dev(h->device);
   if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  if (h->ground.kind != 0) return rg_srb_terrain_step_launch(h, state, grf, foot_target, desired_state, ext, obs, (hipStream_t)stream);
   const unsigned lanes = 4u * (unsigned)h->B;
   hipLaunchKernelGGL(rg_srb_step_kernel, dim3((lanes + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, h->dcfg, h->c, h->body,
                      state, grf, foot_target, desired_state, ext, to_obs(obs));

@@ -1,0 +1,388 @@
+// rg_srb_terrain.hip -- the heightfield ground of include/rg_srb.h: the ground function, the tick on it, settle and the
+// height query.  Its own translation unit of librg_mpc.so, so that rg_srb.hip keeps reporting exactly its two kernels.
+//
+// Layout: that of rg_srb.hip.  The step kernel is rg_srb_step_kernel with the ground function below where the plane has
+// the literal 0: lane = (robot, leg), float64, no LDS, every lane guarded at its stores only, lanes past the batch
+// computing on the last robot, no branch around a cross-lane operation.  The ground is asked at two points outside
+// the sub-step loop (a landing foot; the fall test), each a few dozen 64-bit integer operations (random: seven mix rounds
+// for the four vertices of a cell, the prefix over (key, I) shared) or four loads (grid).  The settle kernel computes all
+// four foot heights in every lane, so it needs no shuffle, and loads everything before it stores: the four lanes of a robot
+// share a wave, and leg 0 writes the p.z the others read.
+//
+// Parity: tests/terrain_model.py restates the ground function, the three changed rules and settle in float64 numpy.
+// Floating-point contraction is off for the whole file, the controller's leg_fk / leg_ik included.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+#include "../../include/rg_srb.h"
+
+#pragma clang fp contract(off)
+
+#include "rg_mpc_dev.h"
+
+namespace {
+
+#include "rg_srb_dev.inc"
+
+}  // namespace
+
+#include "rg_srb_handle.h"
+
+namespace {
+
+constexpr int kBlock = kSrbBlock;
+constexpr double kCoordBound = 1099511627776.0;   // 2^40: lattice coordinates are clamped to it before they become integers
+
+// sum over the four lanes of a robot: (x_0 + x_1) + (x_2 + x_3) in every lane
+__device__ __forceinline__ double sum4(double x) {
+  x = x + __shfl_xor(x, 1);
+  return x + __shfl_xor(x, 2);
+}
+
+// the chain of rg_episode.h
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27; z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z;
+}
+__device__ __forceinline__ unsigned long long mix_word(unsigned long long h, unsigned long long w) { return mix64((h ^ w) + 0x9E3779B97F4A7C15ull); }
+__device__ __forceinline__ double unit53(unsigned long long h) { return (double)(h >> 11) * 0x1.0p-53; }
+
+// h(x, y; robot b) of rg_srb.h.  g.kind is RANDOM or GRID (wave-uniform).
+struct Ground {
+  rg_srb_ground g;
+  __device__ __forceinline__ double operator()(int b, double x, double y) const {
+    double s, t;
+    if (g.kind == RG_SRB_TERRAIN_GRID) { s = (x - g.x0) / g.cell; t = (y - g.y0) / g.cell; }
+    else { s = x / g.cell; t = y / g.cell; }
+    s = fmin(fmax(s, -kCoordBound), kCoordBound);   // a NaN becomes the lower bound
+    t = fmin(fmax(t, -kCoordBound), kCoordBound);
+    const double fi = floor(s), fj = floor(t);
+    const double u = s - fi, v = t - fj;
+    const long long i = (long long)fi, j = (long long)fj;
+    double h00, h10, h01, h11;
+    if (g.kind == RG_SRB_TERRAIN_GRID) {
+      const long long rm = g.rows - 1, cm = g.cols - 1;
+      const size_t i0 = (size_t)(i < 0 ? 0 : (i > rm ? rm : i)), i1 = (size_t)(i + 1 < 0 ? 0 : (i + 1 > rm ? rm : i + 1));
+      const size_t j0 = (size_t)(j < 0 ? 0 : (j > cm ? cm : j)), j1 = (size_t)(j + 1 < 0 ? 0 : (j + 1 > cm ? cm : j + 1));
+      const size_t C = (size_t)g.cols;
+      h00 = g.heights[i0 * C + j0]; h10 = g.heights[i1 * C + j0];
+      h01 = g.heights[i0 * C + j1]; h11 = g.heights[i1 * C + j1];
+    } else {
+      const unsigned long long key = g.key ? (unsigned long long)g.key[b] : 0ull;
+      const unsigned long long hk = mix_word(g.seed, key);
+      const unsigned long long a0 = mix_word(hk, (unsigned long long)(i >> 1)), a1 = mix_word(hk, (unsigned long long)((i + 1) >> 1));
+      const unsigned long long J0 = (unsigned long long)(j >> 1), J1 = (unsigned long long)((j + 1) >> 1);
+      h00 = g.amplitude * unit53(mix_word(a0, J0)); h10 = g.amplitude * unit53(mix_word(a1, J0));
+      h01 = g.amplitude * unit53(mix_word(a0, J1)); h11 = g.amplitude * unit53(mix_word(a1, J1));
+    }
+    if (u >= v) return h00 + u * (h10 - h00) + v * (h11 - h10);
+    return h00 + u * (h11 - h01) + v * (h01 - h00);
+  }
+};
+
+// One control tick on the ground g: rg_srb_step_kernel (rg_srb.hip) with its two ground rules replaced -- where a foot lands and
+// the clearance of the fall test -- and otherwise its text, statement for statement.  A copy, not a shared body: moved into
+// a function templated on the ground, the flat kernel no longer compiled to the instructions it had.
+__global__ void __launch_bounds__(kBlock) rg_srb_terrain_step_kernel(const DevCfg *__restrict__ kc, SrbCfg c, rg_srb_ground g,
+                                                                      const double *__restrict__ body, double *__restrict__ state,
+                                                                      const float *__restrict__ grf, const float *__restrict__ foot_target,
+                                                                      const int *__restrict__ desired, const double *__restrict__ ext, Obs o) {
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  const Ground ground{g};
+  const int leg = t & 3;
+  const bool in_batch = (t >> 2) < c.B;
+  const int b = in_batch ? (t >> 2) : c.B - 1;   // lanes past the batch compute on the last robot and store nothing
+  const size_t sB = (size_t)c.B;
+  double p[3], qt[4], v[3], w[3], foot[3], q[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    p[i] = state[(RG_SRB_ROW_P + i) * sB + b];
+    v[i] = state[(RG_SRB_ROW_V + i) * sB + b];
+    w[i] = state[(RG_SRB_ROW_W + i) * sB + b];
+    foot[i] = state[(RG_SRB_ROW_FOOT + 3 * leg + i) * sB + b];
+    q[i] = state[(RG_SRB_ROW_Q + 3 * leg + i) * sB + b];
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) qt[i] = state[(RG_SRB_ROW_QUAT + i) * sB + b];
+  double stance = state[(RG_SRB_ROW_STANCE + leg) * sB + b];
+  double steps = state[RG_SRB_ROW_STEPS * sB + b];
+  const bool running = state[RG_SRB_ROW_STATUS * sB + b] == 0.0;
+  const double mass = body[b];
+  double I[9], Iinv[9];
+#pragma unroll
+  for (int i = 0; i < 9; i++) { I[i] = body[(1 + i) * sB + b]; Iinv[i] = body[(10 + i) * sB + b]; }
+  double R[9];
+  quat_rot(qt, R);
+  // 1. feet
+  const bool swing = desired[(size_t)b * 4 + leg] == 0 /* RG_LEG_SWING */;
+  double fbody[3] = {0.0, 0.0, 0.0};
+  if (swing) {
+    const double ft[3] = {foot_target[(size_t)b * 12 + 3 * leg], foot_target[(size_t)b * 12 + 3 * leg + 1], foot_target[(size_t)b * 12 + 3 * leg + 2]};
+    double r[3];
+    rot(R, ft, r);
+    foot[0] = p[0] + r[0]; foot[1] = p[1] + r[1]; foot[2] = p[2] + r[2];
+    stance = 0.0;
+  } else {
+    if (stance == 0.0) { foot[2] = ground(b, foot[0], foot[1]); stance = 1.0; }
+#pragma unroll
+    for (int i = 0; i < 3; i++) fbody[i] = -(double)grf[(size_t)b * 12 + 3 * leg + i];
+  }
+  double eF[3] = {0.0, 0.0, 0.0}, eT[3] = {0.0, 0.0, 0.0};
+  if (ext) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) { eF[i] = ext[i * sB + b]; eT[i] = ext[(3 + i) * sB + b]; }
+  }
+  const double dt = c.dt, wz = mass * -c.g;
+  // 2. sub-steps
+  for (int s = 0; s < c.substeps; s++) {
+    double f[3], r[3], tq[3];
+    quat_rot(qt, R);
+    rot(R, fbody, f);
+    r[0] = foot[0] - p[0]; r[1] = foot[1] - p[1]; r[2] = foot[2] - p[2];
+    tq[0] = r[1] * f[2] - r[2] * f[1];
+    tq[1] = r[2] * f[0] - r[0] * f[2];
+    tq[2] = r[0] * f[1] - r[1] * f[0];
+    double F[3], T[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) { F[i] = sum4(f[i]); T[i] = sum4(tq[i]); }
+    F[0] = F[0] + eF[0]; F[1] = F[1] + eF[1]; F[2] = F[2] + wz + eF[2];
+    T[0] = T[0] + eT[0]; T[1] = T[1] + eT[1]; T[2] = T[2] + eT[2];
+    double tb[3], wb[3], Iw[3], rhs[3], ab[3], aw[3];
+    rot_t(R, T, tb);
+    rot_t(R, w, wb);
+    rot(I, wb, Iw);
+    rhs[0] = tb[0] - (wb[1] * Iw[2] - wb[2] * Iw[1]);
+    rhs[1] = tb[1] - (wb[2] * Iw[0] - wb[0] * Iw[2]);
+    rhs[2] = tb[2] - (wb[0] * Iw[1] - wb[1] * Iw[0]);
+    rot(Iinv, rhs, ab);
+    rot(R, ab, aw);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      w[i] = w[i] + dt * aw[i];
+      v[i] = v[i] + dt * F[i] / mass;
+      p[i] = p[i] + dt * v[i];
+    }
+    const double ax = 0.5 * dt * w[0], ay = 0.5 * dt * w[1], az = 0.5 * dt * w[2];
+    const double dx = ax * qt[3] + ay * qt[2] - az * qt[1];
+    const double dy = ay * qt[3] + az * qt[0] - ax * qt[2];
+    const double dz = az * qt[3] + ax * qt[1] - ay * qt[0];
+    const double dw = -(ax * qt[0]) - ay * qt[1] - az * qt[2];
+    qt[0] = qt[0] + dx; qt[1] = qt[1] + dy; qt[2] = qt[2] + dz; qt[3] = qt[3] + dw;
+    const double nrm = sqrt(qt[0] * qt[0] + qt[1] * qt[1] + qt[2] * qt[2] + qt[3] * qt[3]);
+    qt[0] = qt[0] / nrm; qt[1] = qt[1] / nrm; qt[2] = qt[2] / nrm; qt[3] = qt[3] / nrm;
+  }
+  steps = steps + (double)c.substeps;
+  // 3. fall
+  int bad = 0;
+#pragma unroll
+  for (int i = 0; i < 3; i++) bad |= !isfinite(p[i]) || !isfinite(v[i]) || !isfinite(w[i]) || !isfinite(foot[i]);
+#pragma unroll
+  for (int i = 0; i < 4; i++) bad |= !isfinite(qt[i]);
+  bad |= __shfl_xor(bad, 1);
+  bad |= __shfl_xor(bad, 2);
+  const bool fallen = bad || p[2] - ground(b, p[0], p[1]) < c.fall_z || (1 - 2 * (qt[0] * qt[0] + qt[1] * qt[1])) < c.cos_tilt;
+  const bool live = in_batch && running;
+  if (live && leg == 0) state[RG_SRB_ROW_STATUS * sB + b] = fallen ? 1.0 : 0.0;
+  const bool store = live && !bad;
+  if (store) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) state[(RG_SRB_ROW_FOOT + 3 * leg + i) * sB + b] = foot[i];
+    state[(RG_SRB_ROW_STANCE + leg) * sB + b] = stance;
+    if (leg == 0) {
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        state[(RG_SRB_ROW_P + i) * sB + b] = p[i];
+        state[(RG_SRB_ROW_V + i) * sB + b] = v[i];
+        state[(RG_SRB_ROW_W + i) * sB + b] = w[i];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; i++) state[(RG_SRB_ROW_QUAT + i) * sB + b] = qt[i];
+      state[RG_SRB_ROW_STEPS * sB + b] = steps;
+    }
+  }
+  // 4. observation
+  write_obs(kc, c, o, state, b, leg, store, p, qt, v, w, foot, q, stance, steps, 1);
+}
+
+// Settle of rg_srb.h: lane = (robot, leg).  flat: the handle has no terrain and every height is 0.0.
+__global__ void __launch_bounds__(kBlock) rg_srb_terrain_settle_kernel(const DevCfg *__restrict__ kc, SrbCfg c, rg_srb_ground g, int flat,
+                                                                        double *state, const int *__restrict__ mask, Obs o) {
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  const int leg = t & 3;
+  const bool in_batch = (t >> 2) < c.B;
+  const int b = in_batch ? (t >> 2) : c.B - 1;
+  const size_t sB = (size_t)c.B;
+  const Ground ground{g};
+  // every load comes before the first store (leg 0 writes the p.z the other three lanes of the robot read)
+  double p[3], qt[4], v[3], w[3], foot[3], q[3], hs[4];
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    p[i] = state[(RG_SRB_ROW_P + i) * sB + b];
+    v[i] = state[(RG_SRB_ROW_V + i) * sB + b];
+    w[i] = state[(RG_SRB_ROW_W + i) * sB + b];
+    foot[i] = state[(RG_SRB_ROW_FOOT + 3 * leg + i) * sB + b];
+    q[i] = state[(RG_SRB_ROW_Q + 3 * leg + i) * sB + b];
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) qt[i] = state[(RG_SRB_ROW_QUAT + i) * sB + b];
+  const double stance = state[(RG_SRB_ROW_STANCE + leg) * sB + b];
+  const double steps = state[RG_SRB_ROW_STEPS * sB + b];
+  const bool running = state[RG_SRB_ROW_STATUS * sB + b] == 0.0;
+  const bool chosen = mask ? mask[b] != 0 : true;
+#pragma unroll
+  for (int l = 0; l < 4; l++) {
+    const double fx = state[(RG_SRB_ROW_FOOT + 3 * l) * sB + b], fy = state[(RG_SRB_ROW_FOOT + 3 * l + 1) * sB + b];
+    hs[l] = flat ? 0.0 : ground(b, fx, fy);
+  }
+  const double own = leg & 2 ? (leg & 1 ? hs[3] : hs[2]) : (leg & 1 ? hs[1] : hs[0]);
+  foot[2] = own;
+  p[2] = p[2] + ((hs[0] + hs[1]) + (hs[2] + hs[3])) * 0.25;
+  const bool store = in_batch && running && chosen;
+  if (store) {
+    state[(RG_SRB_ROW_FOOT + 3 * leg + 2) * sB + b] = foot[2];
+    if (leg == 0) state[(RG_SRB_ROW_P + 2) * sB + b] = p[2];
+  }
+  write_obs(kc, c, o, state, b, leg, store, p, qt, v, w, foot, q, stance, steps, RG_SRB_RESET_IK_PASSES);
+}
+
+// out[k] = h(x_k, y_k; robot_k)
+__global__ void __launch_bounds__(kBlock) rg_srb_terrain_height_kernel(rg_srb_ground g, int B, const double *__restrict__ xy,
+                                                                        const int *__restrict__ robot, int n, double *__restrict__ out) {
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= n) return;   // no cross-lane operation in this kernel
+  if (g.kind == RG_SRB_TERRAIN_FLAT) { out[k] = 0.0; return; }
+  int b = robot ? robot[k] : k;
+  b = b < 0 ? 0 : (b >= B ? B - 1 : b);   // the key row has B entries: an index outside it reads the nearest one, never past it
+  out[k] = Ground{g}(b, xy[k], xy[(size_t)n + k]);
+}
+
+bool refuse(char *msg, int n, const char *text) {
+  if (msg && n > 0) snprintf(msg, (size_t)n, "%s", text);
+  return false;
+}
+
+bool terrain_valid(const rg_srb_terrain *t, char *msg, int n) {
+  char buf[200];
+  if (!t) return refuse(msg, n, "terrain: null");
+  if (t->abi_version != RG_SRB_ABI_VERSION) {
+    snprintf(buf, sizeof(buf), "terrain.abi_version: %d, this library is version %d", t->abi_version, RG_SRB_ABI_VERSION);
+    return refuse(msg, n, buf);
+  }
+  if (t->kind != RG_SRB_TERRAIN_FLAT && t->kind != RG_SRB_TERRAIN_RANDOM && t->kind != RG_SRB_TERRAIN_GRID) {
+    snprintf(buf, sizeof(buf), "terrain.kind: %d is not 0 (flat), 1 (random) or 2 (grid)", t->kind);
+    return refuse(msg, n, buf);
+  }
+  for (int i = 0; i < 4; i++)
+    if (t->reserved[i] != 0) { snprintf(buf, sizeof(buf), "terrain.reserved[%d]: must be 0", i); return refuse(msg, n, buf); }
+  struct F { const char *name; double v; };
+  const F fields[] = {{"cell", t->cell}, {"amplitude", t->amplitude}, {"x0", t->x0}, {"y0", t->y0}};
+  for (const F &f : fields)
+    if (!std::isfinite(f.v)) { snprintf(buf, sizeof(buf), "terrain.%s: %g is not finite", f.name, f.v); return refuse(msg, n, buf); }
+  const bool random = t->kind == RG_SRB_TERRAIN_RANDOM, grid = t->kind == RG_SRB_TERRAIN_GRID;
+  if (random || grid) {
+    if (!(t->cell > 0)) { snprintf(buf, sizeof(buf), "terrain.cell: %g must be > 0", t->cell); return refuse(msg, n, buf); }
+  } else if (t->cell != 0) return refuse(msg, n, "terrain.cell: must be 0 for the flat kind");
+  if (random) {
+    if (!(t->amplitude >= 0)) { snprintf(buf, sizeof(buf), "terrain.amplitude: %g must be >= 0", t->amplitude); return refuse(msg, n, buf); }
+  } else {
+    if (t->amplitude != 0) return refuse(msg, n, "terrain.amplitude: must be 0 unless the kind is random");
+    if (t->seed != 0) return refuse(msg, n, "terrain.seed: must be 0 unless the kind is random");
+    if (t->key) return refuse(msg, n, "terrain.key: must be NULL unless the kind is random");
+  }
+  if (grid) {
+    if (!t->heights) return refuse(msg, n, "terrain.heights: NULL for the grid kind");
+    if (t->rows < 2 || t->rows > RG_SRB_TERRAIN_MAX_DIM) {
+      snprintf(buf, sizeof(buf), "terrain.rows: %d outside [2, %d]", t->rows, RG_SRB_TERRAIN_MAX_DIM);
+      return refuse(msg, n, buf);
+    }
+    if (t->cols < 2 || t->cols > RG_SRB_TERRAIN_MAX_DIM) {
+      snprintf(buf, sizeof(buf), "terrain.cols: %d outside [2, %d]", t->cols, RG_SRB_TERRAIN_MAX_DIM);
+      return refuse(msg, n, buf);
+    }
+  } else {
+    if (t->heights) return refuse(msg, n, "terrain.heights: must be NULL unless the kind is grid");
+    if (t->rows != 0) return refuse(msg, n, "terrain.rows: must be 0 unless the kind is grid");
+    if (t->cols != 0) return refuse(msg, n, "terrain.cols: must be 0 unless the kind is grid");
+    if (t->x0 != 0) return refuse(msg, n, "terrain.x0: must be 0 unless the kind is grid");
+    if (t->y0 != 0) return refuse(msg, n, "terrain.y0: must be 0 unless the kind is grid");
+  }
+  return true;
+}
+
+}  // namespace
+
+int rg_srb_terrain_step_launch(rg_srb_handle *h, double *state, const float *grf, const float *foot_target, const int32_t *desired_state,
+                               const double *ext, const rg_srb_obs_ptrs *obs, hipStream_t s) {
+  const unsigned lanes = 4u * (unsigned)h->B;
+  hipLaunchKernelGGL(rg_srb_terrain_step_kernel, dim3((lanes + kBlock - 1) / kBlock), dim3(kBlock), 0, s, h->dcfg, h->c, h->ground, h->body,
+                     state, grf, foot_target, desired_state, ext, to_obs(obs));
+  return launch_status(h, "rg_srb_terrain_step_kernel launch");
+}
+
+int rg_srb_terrain_settle_launch(rg_srb_handle *h, double *state, const int32_t *mask, const rg_srb_obs_ptrs *obs, hipStream_t s) {
+  const unsigned lanes = 4u * (unsigned)h->B;
+  hipLaunchKernelGGL(rg_srb_terrain_settle_kernel, dim3((lanes + kBlock - 1) / kBlock), dim3(kBlock), 0, s, h->dcfg, h->c, h->ground,
+                     h->ground.kind == RG_SRB_TERRAIN_FLAT ? 1 : 0, state, mask, to_obs(obs));
+  return launch_status(h, "rg_srb_terrain_settle_kernel launch");
+}
+
+extern "C" {
+
+int32_t rg_srb_terrain_size(void) { return (int32_t)sizeof(rg_srb_terrain); }
+
+int rg_srb_terrain_check(const rg_srb_terrain *t, char *msg, int32_t n) {
+  if (msg && n > 0) msg[0] = 0;
+  return terrain_valid(t, msg, n) ? RG_SRB_OK : RG_SRB_ERR_INVALID;
+}
+
+int rg_srb_set_terrain(rg_srb_handle *h, const rg_srb_terrain *t) {
+  if (!h) { rg_srb_thread_error("set_terrain: null handle"); return RG_SRB_ERR_INVALID; }
+  if (!t || t->kind == RG_SRB_TERRAIN_FLAT) {
+    char msg[200];
+    if (t && !terrain_valid(t, msg, sizeof(msg))) { h->err = std::string("set_terrain: ") + msg; return RG_SRB_ERR_INVALID; }
+    h->ground = rg_srb_ground();
+    return RG_SRB_OK;
+  }
+  char msg[200];
+  if (!terrain_valid(t, msg, sizeof(msg))) { h->err = std::string("set_terrain: ") + msg; return RG_SRB_ERR_INVALID; }
+  if (!h->reset_mask) {
+    DeviceScope dev(h->device);
+    if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+    const hipError_t e = hipMalloc((void **)&h->reset_mask, (size_t)h->B * sizeof(int32_t));
+    if (e != hipSuccess) { h->reset_mask = nullptr; h->err = std::string("set_terrain: hipMalloc failed: ") + hipGetErrorString(e); return RG_SRB_ERR_ALLOC; }
+  }
+  rg_srb_ground g;
+  g.kind = t->kind; g.rows = t->rows; g.cols = t->cols;
+  g.cell = t->cell; g.amplitude = t->amplitude; g.x0 = t->x0; g.y0 = t->y0;
+  g.seed = (unsigned long long)t->seed;
+  g.key = (const long long *)t->key; g.heights = t->heights;
+  h->ground = g;
+  return RG_SRB_OK;
+}
+
+int rg_srb_ground_height(rg_srb_handle *h, const double *xy, const int32_t *robot, int32_t n, double *out, void *stream) {
+  if (!h) { rg_srb_thread_error("ground_height: null handle"); return RG_SRB_ERR_INVALID; }
+  if (!xy || !out) { h->err = "ground_height: null xy or out"; return RG_SRB_ERR_INVALID; }
+  if (n < 1 || n > RG_SRB_MAX_BATCH) { h->err = "ground_height: n outside [1, RG_SRB_MAX_BATCH]"; return RG_SRB_ERR_INVALID; }
+  if (!robot && n > h->B) { h->err = "ground_height: without a robot list entry k is robot k, so n must not exceed the batch"; return RG_SRB_ERR_INVALID; }
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  hipLaunchKernelGGL(rg_srb_terrain_height_kernel, dim3(((unsigned)n + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, h->ground,
+                     h->B, xy, robot, n, out);
+  return launch_status(h, "rg_srb_terrain_height_kernel launch");
+}
+
+int rg_srb_settle(rg_srb_handle *h, double *state, const int32_t *mask, const rg_srb_obs_ptrs *obs, void *stream) {
+  if (!h) { rg_srb_thread_error("settle: null handle"); return RG_SRB_ERR_INVALID; }
+  if (!state || !obs_ok(obs)) { h->err = "settle: null state or observation pointer"; return RG_SRB_ERR_INVALID; }
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  return rg_srb_terrain_settle_launch(h, state, mask, obs, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -35,7 +35,7 @@ class BatchedGoEnv:
     reset_on_device reset).  episode_settings: planner settings of episode_abi.DEFAULTS other than the seed."""
 
     def __init__(self, batch, cfg: MPCConfig = None, targets=None, obstacles=None, seed=0, device=None, sim_settings=None, auto_reset=False,
-                 episode_settings=None, **task):
+                 episode_settings=None, terrain=None, **task):
         # The default robot is ghost WITH ITS COMMAND OFFSETS ZEROED: vy_offset / wz_offset trim a drift of the reference's
         # PyBullet robot that the reduced model does not have, and with them a straight command walks a curve off the path.
         # A cfg passed in is taken as it is, offsets included.
@@ -43,7 +43,9 @@ class BatchedGoEnv:
         self.batch = B = int(batch)
         self.ctl = BatchedMPCController(B, self.cfg, device=device)
         self.device = dev = self.ctl.device
-        self.sim = BatchedSRBSim(B, self.cfg, device=dev, **(sim_settings or {}))
+        # terrain: a RandomTerrain / GridTerrain (robot_gym_amd/sim/terrain.py) or None, the plane.  The planner, the path and the
+        # task see x and y only; the simulator stands every reset robot on the ground (sim.settle) before the task observes.
+        self.sim = BatchedSRBSim(B, self.cfg, device=dev, terrain=terrain, **(sim_settings or {}))
         task.setdefault("dt_sim", self.sim.dt_sim)
         task.setdefault("substeps", self.sim.substeps)
         self._handle = goto_abi.GotoHandle(B, self.cfg, dev, **task)
@@ -212,6 +214,10 @@ class BatchedGoEnv:
         self._episode.reset(mask.data_ptr(), None if targets is None else targets.data_ptr(), self.episode_state.data_ptr(), self.task_state.data_ptr(),
                             self.sim.state.data_ptr(), self.sim._obs_ptrs, self._paths, self._obs_cm.data_ptr(), self._final_obs_cm.data_ptr(),
                             self.reset_mask.data_ptr())
+        if self.sim.terrain is not None:
+            # the episode reset stands the robot on the plane; the task observation it wrote reads x, y and heading only, which
+            # settle leaves as they are
+            self.sim.settle(self.reset_mask)
         if not self._mirrors_stale:
             self.paths = [None] * B
             self.targets[:] = np.nan

@@ -5,6 +5,12 @@ warm-up, one synchronisation at the end of each measurement.  For the record, no
 
     python tools/srb_bench.py [--robot ghost] [--batches 1,1024,4096,32768] [--seconds 1.0] [--out profiles/srb_tick.json]
 
+    python tools/srb_bench.py --terrain [--batches 1,64,1024,4096,32768] [--out profiles/srb_terrain_tick.json]
+
+--terrain times the tick on the reference's random terrain next to the tick on the plane, in the same run and on the same
+held controller outputs (the plane before and after the terrain, so that the file carries the plane's own run-to-run spread),
+and a settle of the whole batch.
+
 Kernel statistics come from a run of their own:  rocprofv3 --kernel-trace --stats -d DIR -- python tools/srb_bench.py --batches 4096
 """
 import argparse
@@ -52,15 +58,54 @@ def srb_hash():
     """sha256 (16 hex digits) over the simulator's own sources: bench.source_hash() covers the MPC kernels only."""
     import hashlib
     h = hashlib.sha256()
-    for rel in ("robot_gym_amd/csrc/rg_srb.hip", "include/rg_srb.h"):
+    for rel in ("robot_gym_amd/csrc/rg_srb.hip", "robot_gym_amd/csrc/rg_srb_dev.inc", "robot_gym_amd/csrc/rg_srb_handle.h",
+                "robot_gym_amd/csrc/rg_srb_terrain.hip", "include/rg_srb.h", "include/rg_srb_terrain.h"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]
+
+
+def terrain_rows(args, dev, cfg):
+    """Per batch: the plane's tick, the terrain's tick, the plane's again, and settle(None), us per call."""
+    from robot_gym_amd.sim.terrain import RandomTerrain
+    rows = []
+    for B in [int(x) for x in args.batches.split(",")]:
+        rng = np.random.default_rng(B)
+        ctl = BatchedMPCController(B, cfg, device=dev)
+        flat, rough = BatchedSRBSim(B, cfg, device=dev), BatchedSRBSim(B, cfg, device=dev, terrain=RandomTerrain())
+        cmd = np.stack([rng.uniform(-0.35, 0.35, B), rng.uniform(-0.2, 0.2, B), rng.uniform(-0.4, 0.4, B)], 1).astype(np.float32)
+        hs = cfg.body_height * rng.uniform(0.9, 1.1, B)
+        flat.reset(height=hs)
+        rough.reset(height=hs)
+        ctl.reset()
+        ctl.update_controller_params(torch.as_tensor(cmd, device=dev))
+        rollout(ctl, rough, None, args.warmup)                  # into the trot on the terrain: feet landing at their own heights
+        fallen = int(rough.fallen().sum())
+        flat.state.copy_(rough.state)                           # the same robots, the same held controller outputs, either ground
+        keep = rough.state.clone()
+        flat_a, n = timed(lambda: flat.step(ctl), args.seconds)
+        rough_us, _ = timed(lambda: rough.step(ctl), args.seconds)
+        flat.state.copy_(keep)
+        flat_b, _ = timed(lambda: flat.step(ctl), args.seconds)
+        # settle of a freshly reset batch: the state is put back before every call (a settle raises the body each time), and the
+        # copy's own time is taken off
+        rough.reset(height=hs)
+        fresh = rough.state.clone()
+        both_us, _ = timed(lambda: (rough.state.copy_(fresh), rough.settle()), args.seconds)
+        copy_us, _ = timed(lambda: rough.state.copy_(fresh), args.seconds)
+        settle_us = both_us - copy_us
+        rows.append(dict(batch=B, ticks=n, flat_us=round(flat_a, 2), terrain_us=round(rough_us, 2), flat_again_us=round(flat_b, 2),
+                         settle_us=round(settle_us, 2), fallen_in_warmup=fallen))
+        print(json.dumps(rows[-1]), flush=True)
+        for h in (ctl, flat, rough):
+            h.close()
+    return rows
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--robot", default="ghost")
-    ap.add_argument("--batches", default="1,1024,4096,32768")
+    ap.add_argument("--batches", default=None, help="default 1,1024,4096,32768 (--terrain: 1,64,1024,4096,32768)")
+    ap.add_argument("--terrain", action="store_true", help="the tick on the random terrain next to the tick on the plane, and settle")
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--out", default=None)
@@ -68,7 +113,20 @@ def main():
     dev = torch.device("cuda", 0)
     cfg = MPCConfig.for_robot(args.robot)
     commit, dirty = bench.git_head()
+    args.batches = args.batches or ("1,64,1024,4096,32768" if args.terrain else "1,1024,4096,32768")
     rows = []
+    if args.terrain:
+        result = dict(what="simulator tick on the random terrain (amplitude 0.06, cell 0.05, one world per robot) next to the tick on the plane, "
+                           "same run, same held controller outputs; settle of the whole batch", robot=args.robot, commit=commit, dirty=dirty,
+                      source_hash=bench.source_hash(), srb_source_sha256=srb_hash(), device=torch.cuda.get_device_name(0),
+                      seconds_per_measurement=args.seconds, rows=terrain_rows(args, dev, cfg))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+        print(json.dumps(result))
+        return
     for B in [int(x) for x in args.batches.split(",")]:
         rng = np.random.default_rng(B)
         ctl, sim = BatchedMPCController(B, cfg, device=dev), BatchedSRBSim(B, cfg, device=dev)
