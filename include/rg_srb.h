@@ -6,10 +6,13 @@
  * forward with the controller's own first-step forces and kinematic feet, for B robots per call with no host in the
  * loop.  It is for closed-loop validation of the controller, branched (cloned) rollouts and RL on the reduced model.
  *
- * Stated limits: feet that neither slip nor bounce; massless legs; touch-down and lift-off by the gait schedule (the
- * controller's desired_state), not by measured contact; first-order (semi-implicit Euler) integration.  The ground is the
- * plane z = 0 or a heightfield (rg_srb_set_terrain, below): kinematic feet, schedule contact, no slip.  Slip, early / late
- * contact and contact by measurement are out of scope on either.
+ * Stated limits: feet that neither slip nor bounce; massless legs; first-order (semi-implicit Euler) integration.  The
+ * ground is the plane z = 0 or a heightfield (rg_srb_set_terrain, below): kinematic feet, no slip.  In rg_srb_step touch-down
+ * and lift-off follow the gait schedule (the controller's desired_state), not a measurement.  rg_srb_step_contact
+ * (rg_srb_contact.h, which states its rule) measures ONE thing on either ground: the early touch-down of a swinging foot, which
+ * stops at the ground and reports contact.  Still not measured by any entry: late contact, slip, a reach limit of the leg,
+ * collision of the body with the ground.  Late contact is left out on purpose: a commanded-stance foot that descends at a
+ * finite speed and carries no force until it arrives made every robot of the CPU model fall, on the plane too (rg_srb_contact.h).
  *
  * Conventions (those of rg_posctl.h)
  *   - return 0 on success, a negative rg_srb_status otherwise; nothing throws across the ABI; rg_srb_last_error() gives
@@ -76,7 +79,7 @@
  *     lower bound, no conversion is undefined, and any state value has a defined ground.
  *   With a terrain set, three rules of the tick change and nothing else:
  *     landing   foot_w.z = h(foot_w.x, foot_w.y) instead of 0.  A swinging foot still follows its target and is not tested
- *               against the ground (no early or late contact): with amplitude 0 every value is the plane's, bit for bit.
+ *               against the ground (rg_srb_step_contact tests it): with amplitude 0 every value is the plane's, bit for bit.
  *     fall      p.z - h(p.x, p.y) < fall_height_scale * body_height
  *     reset     the flat reset followed by rg_srb_settle of the robots reset
  *   Settle (rg_srb_settle), for the robots of a mask whose status is 0: foot_w.z = h_l = h(foot_w.xy) for each foot l,
@@ -197,5 +200,8 @@ int rg_srb_step(rg_srb_handle *h, double *state, const float *grf, const float *
 
 /* The terrain entries (the ground struct, set_terrain, ground_height, settle): part of this ABI, declared in their own file. */
 #include "rg_srb_terrain.h"
+
+/* The tick with measured foot contact (rg_srb_step_contact) and the text of its rule: part of this ABI, declared in its own file. */
+#include "rg_srb_contact.h"
 
 #endif /* RG_SRB_H */

@@ -57,6 +57,10 @@ TERRAIN_MAX_DIM = 4096   # RG_SRB_TERRAIN_MAX_DIM
 # the terrain entries, declared in include/rg_srb_terrain.h
 TERRAIN_EXPORTS = ("rg_srb_terrain_size", "rg_srb_terrain_check", "rg_srb_set_terrain", "rg_srb_ground_height", "rg_srb_settle")
 
+# the tick with measured contact, declared in include/rg_srb_contact.h
+CONTACT_EXPORTS = ("rg_srb_step_contact",)
+LEG_SWING, LEG_STANCE, LEG_EARLY_CONTACT, LEG_LOSE_CONTACT = 0, 1, 2, 3     # rg_leg_state of rg_mpc.h
+
 EXPORTS = ("rg_srb_create", "rg_srb_destroy", "rg_srb_last_error", "rg_srb_abi_version", "rg_srb_config_size", "rg_srb_state_rows",
            "rg_srb_set_body", "rg_srb_reset", "rg_srb_step")
 
@@ -101,6 +105,8 @@ def load_library(path=None):
     L.rg_srb_ground_height.restype = i32
     L.rg_srb_settle.argtypes = [fp, fp, fp, C.POINTER(CObsPtrs), fp]
     L.rg_srb_settle.restype = i32
+    L.rg_srb_step_contact.argtypes = [fp, fp, fp, fp, fp, fp, C.POINTER(CObsPtrs), fp, fp]
+    L.rg_srb_step_contact.restype = i32
     if L.rg_srb_abi_version() != ABI_VERSION:
         raise ImportError("librg_mpc.so rg_srb ABI version mismatch")
     if L.rg_srb_config_size() != C.sizeof(CConfig):
@@ -182,6 +188,41 @@ def create_status(cfg, batch, device=0, **sim):
     return rc, text
 
 
+def checked_ptr(t, name, dtype, shape, device, entry="step_contact", optional=False):
+    """The device address of the tensor argument `name` of `entry` once it is what the library will take it for: a torch
+    tensor of `dtype` and `shape`, contiguous, on `device`.  Anything else raises a ValueError naming the argument; None is
+    the C-ABI's NULL where `optional`.  Looks at the tensor only: no device is probed and the library is not called."""
+    import torch
+    if t is None:
+        if optional:
+            return None
+        raise ValueError(f"{entry}: {name} is required (None would be a NULL pointer)")
+    what = f"{entry}: {name} must be a contiguous {dtype} {list(shape)} tensor on {device}"
+    if not torch.is_tensor(t):
+        raise ValueError(f"{what}, got a {type(t).__name__}")
+    if t.dtype != dtype:
+        raise ValueError(f"{what}, got dtype {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}, got shape {list(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}, got a non-contiguous view")
+    if t.device != device:
+        raise ValueError(f"{what}, got one on {t.device}")
+    return t.data_ptr()
+
+
+def step_contact_ptrs(batch, device, state, grf, foot_target, leg_state, ext=None, touch=None):
+    """(state, grf, foot_target, leg_state, ext, touch) addresses for rg_srb_step_contact, every tensor checked first."""
+    import torch
+    B = int(batch)
+    return (checked_ptr(state, "state", torch.float64, (STATE_ROWS, B), device),
+            checked_ptr(grf, "grf", torch.float32, (B, 12), device),
+            checked_ptr(foot_target, "foot_target", torch.float32, (B, 12), device),
+            checked_ptr(leg_state, "leg_state", torch.int32, (B, 4), device),
+            checked_ptr(ext, "ext", torch.float64, (6, B), device, optional=True),
+            checked_ptr(touch, "touch", torch.int32, (4, B), device, optional=True))
+
+
 def _stream(device):
     import torch
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
@@ -251,6 +292,13 @@ class SrbHandle:
     def step(self, state_ptr, grf_ptr, foot_target_ptr, desired_ptr, ext_ptr, obs: CObsPtrs):
         self._check(self._lib.rg_srb_step(self._h, state_ptr, grf_ptr, foot_target_ptr, desired_ptr, ext_ptr, C.byref(obs),
                                           _stream(self.device)))
+
+    def step_contact(self, state, grf, foot_target, leg_state, ext, obs: CObsPtrs, touch=None):
+        """rg_srb_step_contact on TENSORS (ext and touch may be None): each is checked by step_contact_ptrs before the
+        library sees its address."""
+        ptrs = step_contact_ptrs(self.batch, self.device, state, grf, foot_target, leg_state, ext, touch)
+        self._check(self._lib.rg_srb_step_contact(self._h, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], C.byref(obs), ptrs[5],
+                                                  _stream(self.device)))
 
     def set_terrain(self, t: CTerrain = None):
         """t None: back to the plane.  The caller keeps the device arrays t points at alive."""

@@ -1,4 +1,4 @@
-// rg_srb_handle.h -- what the two translation units of the simulator share on the HOST side: the handle of include/rg_srb.h,
+// rg_srb_handle.h -- what the translation units of the simulator (rg_srb.hip, rg_srb_terrain.hip, rg_srb_contact.hip) share on the HOST side: the handle of include/rg_srb.h,
 // the small helpers of its entry points, and the calls by which rg_srb.hip (the plane) hands a tick, a reset or the end of
 // a handle's life over to rg_srb_terrain.hip once a terrain is set.  Private to robot_gym_amd/csrc.  Included after
 // rg_srb_dev.inc (SrbCfg, Obs and DevCfg are the including file's), outside its anonymous namespace.

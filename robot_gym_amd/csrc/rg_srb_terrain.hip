@@ -1,5 +1,6 @@
-// rg_srb_terrain.hip -- the heightfield ground of include/rg_srb.h: the ground function, the tick on it, settle and the
-// height query.  Its own translation unit of librg_mpc.so, so that rg_srb.hip keeps reporting exactly its two kernels.
+// rg_srb_terrain.hip -- the heightfield ground of include/rg_srb.h: the tick on it, settle and the height query (the ground
+// function itself is rg_srb_ground.inc, shared with the measured-contact tick of rg_srb_contact.hip).  Its own translation
+// unit of librg_mpc.so, so that rg_srb.hip keeps reporting exactly its two kernels.
 //
 // Layout: that of rg_srb.hip.  The step kernel is rg_srb_step_kernel with the ground function below where the plane has
 // the literal 0: lane = (robot, leg), float64, no LDS, every lane guarded at its stores only, lanes past the batch
@@ -34,7 +35,6 @@ namespace {
 namespace {
 
 constexpr int kBlock = kSrbBlock;
-constexpr double kCoordBound = 1099511627776.0;   // 2^40: lattice coordinates are clamped to it before they become integers
 
 // sum over the four lanes of a robot: (x_0 + x_1) + (x_2 + x_3) in every lane
 __device__ __forceinline__ double sum4(double x) {
@@ -42,48 +42,8 @@ __device__ __forceinline__ double sum4(double x) {
   return x + __shfl_xor(x, 2);
 }
 
-// the chain of rg_episode.h
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-__device__ __forceinline__ unsigned long long mix_word(unsigned long long h, unsigned long long w) { return mix64((h ^ w) + 0x9E3779B97F4A7C15ull); }
-__device__ __forceinline__ double unit53(unsigned long long h) { return (double)(h >> 11) * 0x1.0p-53; }
-
-// h(x, y; robot b) of rg_srb.h.  g.kind is RANDOM or GRID (wave-uniform).
-struct Ground {
-  rg_srb_ground g;
-  __device__ __forceinline__ double operator()(int b, double x, double y) const {
-    double s, t;
-    if (g.kind == RG_SRB_TERRAIN_GRID) { s = (x - g.x0) / g.cell; t = (y - g.y0) / g.cell; }
-    else { s = x / g.cell; t = y / g.cell; }
-    s = fmin(fmax(s, -kCoordBound), kCoordBound);   // a NaN becomes the lower bound
-    t = fmin(fmax(t, -kCoordBound), kCoordBound);
-    const double fi = floor(s), fj = floor(t);
-    const double u = s - fi, v = t - fj;
-    const long long i = (long long)fi, j = (long long)fj;
-    double h00, h10, h01, h11;
-    if (g.kind == RG_SRB_TERRAIN_GRID) {
-      const long long rm = g.rows - 1, cm = g.cols - 1;
-      const size_t i0 = (size_t)(i < 0 ? 0 : (i > rm ? rm : i)), i1 = (size_t)(i + 1 < 0 ? 0 : (i + 1 > rm ? rm : i + 1));
-      const size_t j0 = (size_t)(j < 0 ? 0 : (j > cm ? cm : j)), j1 = (size_t)(j + 1 < 0 ? 0 : (j + 1 > cm ? cm : j + 1));
-      const size_t C = (size_t)g.cols;
-      h00 = g.heights[i0 * C + j0]; h10 = g.heights[i1 * C + j0];
-      h01 = g.heights[i0 * C + j1]; h11 = g.heights[i1 * C + j1];
-    } else {
-      const unsigned long long key = g.key ? (unsigned long long)g.key[b] : 0ull;
-      const unsigned long long hk = mix_word(g.seed, key);
-      const unsigned long long a0 = mix_word(hk, (unsigned long long)(i >> 1)), a1 = mix_word(hk, (unsigned long long)((i + 1) >> 1));
-      const unsigned long long J0 = (unsigned long long)(j >> 1), J1 = (unsigned long long)((j + 1) >> 1);
-      h00 = g.amplitude * unit53(mix_word(a0, J0)); h10 = g.amplitude * unit53(mix_word(a1, J0));
-      h01 = g.amplitude * unit53(mix_word(a0, J1)); h11 = g.amplitude * unit53(mix_word(a1, J1));
-    }
-    if (u >= v) return h00 + u * (h10 - h00) + v * (h11 - h10);
-    return h00 + u * (h11 - h01) + v * (h01 - h00);
-  }
-};
+// kCoordBound, the hash chain and Ground, h(x, y; robot) of rg_srb.h: shared with rg_srb_contact.hip
+#include "rg_srb_ground.inc"
 
 // One control tick on the ground g: rg_srb_step_kernel (rg_srb.hip) with its two ground rules replaced -- where a foot lands and
 // the clearance of the fall test -- and otherwise its text, statement for statement.  A copy, not a shared body: moved into

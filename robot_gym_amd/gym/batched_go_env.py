@@ -35,7 +35,7 @@ class BatchedGoEnv:
     reset_on_device reset).  episode_settings: planner settings of episode_abi.DEFAULTS other than the seed."""
 
     def __init__(self, batch, cfg: MPCConfig = None, targets=None, obstacles=None, seed=0, device=None, sim_settings=None, auto_reset=False,
-                 episode_settings=None, terrain=None, **task):
+                 episode_settings=None, terrain=None, contact="schedule", **task):
         # The default robot is ghost WITH ITS COMMAND OFFSETS ZEROED: vy_offset / wz_offset trim a drift of the reference's
         # PyBullet robot that the reduced model does not have, and with them a straight command walks a curve off the path.
         # A cfg passed in is taken as it is, offsets included.
@@ -45,7 +45,9 @@ class BatchedGoEnv:
         self.device = dev = self.ctl.device
         # terrain: a RandomTerrain / GridTerrain (robot_gym_amd/sim/terrain.py) or None, the plane.  The planner, the path and the
         # task see x and y only; the simulator stands every reset robot on the ground (sim.settle) before the task observes.
-        self.sim = BatchedSRBSim(B, self.cfg, device=dev, terrain=terrain, **(sim_settings or {}))
+        # contact: "schedule" or "measured" (BatchedSRBSim): measured stops a swinging foot at the ground; a reset robot stands on
+        # four feet either way, so the reset paths are the same.
+        self.sim = BatchedSRBSim(B, self.cfg, device=dev, terrain=terrain, contact=contact, **(sim_settings or {}))
         task.setdefault("dt_sim", self.sim.dt_sim)
         task.setdefault("substeps", self.sim.substeps)
         self._handle = goto_abi.GotoHandle(B, self.cfg, dev, **task)

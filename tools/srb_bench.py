@@ -11,6 +11,12 @@ warm-up, one synchronisation at the end of each measurement.  For the record, no
 held controller outputs (the plane before and after the terrain, so that the file carries the plane's own run-to-run spread),
 and a settle of the whole batch.
 
+    python tools/srb_bench.py --contact [--batches 4096] [--out profiles/srb_contact_tick.json]
+
+--contact times the tick with measured foot contact (contact="measured", rg_srb_step_contact) on the random terrain next to the
+schedule tick on the same terrain and the tick on the plane, in the same run, from the same state and on the same held
+controller outputs (the plane before and after, for the run-to-run spread).
+
 Kernel statistics come from a run of their own:  rocprofv3 --kernel-trace --stats -d DIR -- python tools/srb_bench.py --batches 4096
 """
 import argparse
@@ -59,7 +65,8 @@ def srb_hash():
     import hashlib
     h = hashlib.sha256()
     for rel in ("robot_gym_amd/csrc/rg_srb.hip", "robot_gym_amd/csrc/rg_srb_dev.inc", "robot_gym_amd/csrc/rg_srb_handle.h",
-                "robot_gym_amd/csrc/rg_srb_terrain.hip", "include/rg_srb.h", "include/rg_srb_terrain.h"):
+                "robot_gym_amd/csrc/rg_srb_terrain.hip", "robot_gym_amd/csrc/rg_srb_ground.inc", "robot_gym_amd/csrc/rg_srb_contact.hip",
+                "include/rg_srb.h", "include/rg_srb_terrain.h", "include/rg_srb_contact.h"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]
 
@@ -101,11 +108,43 @@ def terrain_rows(args, dev, cfg):
     return rows
 
 
+def contact_rows(args, dev, cfg):
+    """Per batch: the plane's tick, the terrain's schedule tick, the measured-contact tick on the terrain, the plane's again, us per
+    call; every measurement starts from the state the warm-up (closed loop with measured contact on the terrain) ended in."""
+    from robot_gym_amd.sim.terrain import RandomTerrain
+    rows = []
+    for B in [int(x) for x in args.batches.split(",")]:
+        rng = np.random.default_rng(B)
+        ctl = BatchedMPCController(B, cfg, device=dev)
+        flat, rough = BatchedSRBSim(B, cfg, device=dev), BatchedSRBSim(B, cfg, device=dev, terrain=RandomTerrain())
+        measured = BatchedSRBSim(B, cfg, device=dev, terrain=RandomTerrain(), contact="measured")
+        cmd = np.stack([rng.uniform(-0.35, 0.35, B), rng.uniform(-0.2, 0.2, B), rng.uniform(-0.4, 0.4, B)], 1).astype(np.float32)
+        hs = cfg.body_height * rng.uniform(0.9, 1.1, B)
+        for sim in (flat, rough, measured):
+            sim.reset(height=hs)
+        ctl.reset()
+        ctl.update_controller_params(torch.as_tensor(cmd, device=dev))
+        rollout(ctl, measured, None, args.warmup)               # into the trot with measured contact: feet stopping at the ground
+        fallen = int(measured.fallen().sum())
+        touching = int(measured.touch.sum())
+        keep = measured.state.clone()
+        out = {}
+        for name, sim in (("flat_us", flat), ("terrain_us", rough), ("contact_us", measured), ("flat_again_us", flat)):
+            sim.state.copy_(keep)
+            out[name], n = timed(lambda: sim.step(ctl), args.seconds)
+        rows.append(dict(batch=B, ticks=n, **{k: round(v, 2) for k, v in out.items()}, fallen_in_warmup=fallen, feet_touching_at_start=touching))
+        print(json.dumps(rows[-1]), flush=True)
+        for h in (ctl, flat, rough, measured):
+            h.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--robot", default="ghost")
     ap.add_argument("--batches", default=None, help="default 1,1024,4096,32768 (--terrain: 1,64,1024,4096,32768)")
     ap.add_argument("--terrain", action="store_true", help="the tick on the random terrain next to the tick on the plane, and settle")
+    ap.add_argument("--contact", action="store_true", help="the measured-contact tick next to the terrain tick and the plane tick (batch 4096)")
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--out", default=None)
@@ -113,8 +152,22 @@ def main():
     dev = torch.device("cuda", 0)
     cfg = MPCConfig.for_robot(args.robot)
     commit, dirty = bench.git_head()
+    args.batches_given = args.batches is not None
     args.batches = args.batches or ("1,64,1024,4096,32768" if args.terrain else "1,1024,4096,32768")
     rows = []
+    if args.contact:
+        args.batches = args.batches if args.batches_given else "4096"
+        result = dict(what="simulator tick with measured foot contact on the random terrain (amplitude 0.06, cell 0.05, one world per robot) next to "
+                           "the schedule tick on the same terrain and the tick on the plane: same run, same start state, same held controller outputs",
+                      robot=args.robot, commit=commit, dirty=dirty, source_hash=bench.source_hash(), srb_source_sha256=srb_hash(),
+                      device=torch.cuda.get_device_name(0), seconds_per_measurement=args.seconds, rows=contact_rows(args, dev, cfg))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+        print(json.dumps(result))
+        return
     if args.terrain:
         result = dict(what="simulator tick on the random terrain (amplitude 0.06, cell 0.05, one world per robot) next to the tick on the plane, "
                            "same run, same held controller outputs; settle of the whole batch", robot=args.robot, commit=commit, dirty=dirty,
