@@ -50,9 +50,10 @@
  *      nearest obstacle is <= robot_radius; of equally near obstacles the last wins], evaluated at the cells it visits,
  *      cell coordinates ix * grid + minx with minx, xw, ... formed as _potential_map forms them (no obstacle: its dummy one at
  *      (area_width + 1, area_width + 1)).  Stops when hypot(target - cell) < grid or the last `oscillation_length` cells
- *      hold a repeat; the target is appended.  hypot is the device's, not libm's: potentials are only compared with each
- *      other and their gaps are far above an ulp, but the stop test can go the other way where the distance is within
- *      an ulp or two of the grid step.
+ *      hold a repeat; the target is appended.  hypot is the device's, not libm's, called with the larger magnitude first so that
+ *      hypot(x, y) == hypot(y, x) as in numpy and cells mirrored about an axis or the diagonal through the target tie exactly:
+ *      potentials are only compared with each other and the gaps of unequal ones are far above an ulp, but the stop test
+ *      can go the other way where the distance is within an ulp or two of the grid step.
  *   c. Path.  goto_path.build_path: n = int(length of the way points / spacing) points at i * (length / (n - 1)) by
  *      interpolate_along's segment rule, none past length + 1e-6; s by arc_table's IN-ORDER sum; first_same_x; the header
  *      (n, length of the interpolated polyline, target).  sqrt, division, multiplication and addition are correctly

@@ -77,6 +77,14 @@ __device__ __forceinline__ double draw_coord(unsigned long long seed, unsigned l
   return (c + 0.0) / 100.0;
 }
 
+// hypot with the larger magnitude first.  The library's hypot forms fma(a, a, b * b) from its arguments in the order given, so
+// hypot(x, y) and hypot(y, x) can differ in the last bit; numpy's are equal.  Two cells mirrored about the diagonal through
+// the target have equal potentials in plan_path and the first in MOTION order wins: ordered arguments keep that tie a tie.
+__device__ __forceinline__ double hypot_sym(double x, double y) {
+  x = fabs(x); y = fabs(y);
+  return x >= y ? hypot(x, y) : hypot(y, x);
+}
+
 __device__ __forceinline__ double min3(double a, double b, double c) { a = b < a ? b : a; return c < a ? c : a; }   // Python's min(a, b, c)
 __device__ __forceinline__ double max3(double a, double b, double c) { a = b > a ? b : a; return c > a ? c : a; }
 
@@ -136,7 +144,7 @@ __global__ void __launch_bounds__(kWave) rg_episode_plan_kernel(const EpCfg c, c
     const double maxx = max3(hix, 0.0, gx) + c.half_area, maxy = max3(hiy, 0.0, gy) + c.half_area;
     const double fxw = rint((maxx - minx) / reso), fyw = rint((maxy - miny) / reso);
     const int xw = fxw < 1e9 ? (int)fxw : 1000000000, yw = fyw < 1e9 ? (int)fyw : 1000000000;
-    double d = hypot(0.0 - gx, 0.0 - gy);
+    double d = hypot_sym(0.0 - gx, 0.0 - gy);
     const double fix = rint((0.0 - minx) / reso), fiy = rint((0.0 - miny) / reso);
     int ix = fix < 1e9 ? (int)fix : 1000000000, iy = fiy < 1e9 ? (int)fiy : 1000000000;
     const int m = lane & 7;
@@ -151,11 +159,11 @@ __global__ void __launch_bounds__(kWave) rg_episode_plan_kernel(const EpCfg c, c
       double p = inf;
       if (inx >= 0 && iny >= 0 && inx < xw && iny < yw) {
         const double x = (double)inx * reso + minx, y = (double)iny * reso + miny;
-        p = c.half_kp * hypot(x - gx, y - gy);
+        p = c.half_kp * hypot_sym(x - gx, y - gy);
         double dmin = inf;
         #pragma unroll 1
         for (int k = 0; k < c.nobs; k++) {
-          const double dk = hypot(x - obx[k], y - oby[k]);
+          const double dk = hypot_sym(x - obx[k], y - oby[k]);
           dmin = dmin >= dk ? dk : dmin;
         }
         if (dmin <= c.radius) {
@@ -175,7 +183,7 @@ __global__ void __launch_bounds__(kWave) rg_episode_plan_kernel(const EpCfg c, c
       ix = __shfl(inx, best);
       iy = __shfl(iny, best);
       const double xp = (double)ix * reso + minx, yp = (double)iy * reso + miny;
-      d = hypot(gx - xp, gy - yp);
+      d = hypot_sym(gx - xp, gy - yp);
       if (lane == 0) { wpx[nway] = xp; wpy[nway] = yp; }
       nway++;
       // previous.append; pop(0) past oscillation_length; stop on a repeat among them

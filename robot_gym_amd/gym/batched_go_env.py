@@ -32,7 +32,8 @@ class BatchedGoEnv:
     task_state float64 [50, B], the path slab (path_x / path_y / path_s float64 [B, n_max], path_first_same_x int32
     [B, n_max], path_hdr float64 [4, B]) and the outputs; and the episode reset on the device (episode_abi.EpisodeHandle)
     with episode_state float64 [12, B] (rows: rg_episode.h), final_obs and reset_mask int32 [B] (the robots the last
-    reset_on_device reset).  episode_settings: planner settings of episode_abi.DEFAULTS other than the seed."""
+    reset_on_device reset).  episode_settings: planner settings of episode_abi.DEFAULTS other than the seed; they govern BOTH
+    resets: reset() plans on the host with them (goto_path.plan_path / build_path), reset_on_device() on the device."""
 
     def __init__(self, batch, cfg: MPCConfig = None, targets=None, obstacles=None, seed=0, device=None, sim_settings=None, auto_reset=False,
                  episode_settings=None, terrain=None, contact="schedule", **task):
@@ -137,8 +138,9 @@ class BatchedGoEnv:
 
     def reset(self, idx=None, targets=None):
         """Robots idx (None: all): plan and build a path to targets [n,2] (None: the constructor's targets, cycled over the
-        robots, or random ones as go_env.py:163-175), upload it, put the robot at the path's start facing along it, reset
-        the controller, and observe.  Host work and blocking copies; returns obs [B, 2 * num_cam_pts]."""
+        robots, or random ones as go_env.py:163-175) under the planner settings of episode_settings, upload it, put the robot
+        at the path's start facing along it, reset the controller, and observe.  A plan the device would refuse (rg_episode.h,
+        d.) is a ValueError here, before anything is written.  Host work and blocking copies; returns obs [B, 2 * num_cam_pts]."""
         B = self.batch
         idx = np.arange(B) if idx is None else np.asarray(idx.cpu() if torch.is_tensor(idx) else idx, dtype=np.int64).reshape(-1)
         n = len(idx)
@@ -154,10 +156,13 @@ class BatchedGoEnv:
             tg = np.array([goto_path.random_target(self._rng) for _ in range(n)])
         cache = {}
         built = []
+        ef = self._episode.fields   # the planner settings the device reset plans with: both resets plan the same path
+        plan = {k: ef[k] for k in ("kp", "eta", "area_width", "grid", "robot_radius", "oscillation_length", "max_waypoints")}
         for t in tg:
             key = (float(t[0]), float(t[1]))
             if key not in cache:
-                cache[key] = goto_path.build_path(goto_path.plan_path(key, self.obstacles), int(self.fields["num_checkpoints"]), target=key)
+                cache[key] = goto_path.build_path(goto_path.plan_path(key, self.obstacles, **plan), int(self.fields["num_checkpoints"]), target=key,
+                                                  spacing=ef["spacing"], n_max=self.n_max)
             built.append(cache[key])
         for k, b in enumerate(idx):
             self.paths[b], self.targets[b] = built[k], tg[k]

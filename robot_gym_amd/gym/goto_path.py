@@ -28,16 +28,19 @@ CONTINUITY_BREAK = 30e-3
 Path = namedtuple("Path", "x y s first_same_x n length checkpoints start_xy start_angle target")
 
 
-def _potential_map(gx, gy, ox, oy, reso, rr, sx, sy):
-    minx = min(min(ox), sx, gx) - AREA_WIDTH / 2.0
-    miny = min(min(oy), sy, gy) - AREA_WIDTH / 2.0
-    maxx = max(max(ox), sx, gx) + AREA_WIDTH / 2.0
-    maxy = max(max(oy), sy, gy) + AREA_WIDTH / 2.0
+MAX_WAYPOINTS = 64  # way points of a plan at most, start and target included (RG_EPISODE_MAX_WAYPOINTS)
+
+
+def _potential_map(gx, gy, ox, oy, reso, rr, sx, sy, kp=KP, eta=ETA, area_width=AREA_WIDTH):
+    minx = min(min(ox), sx, gx) - area_width / 2.0
+    miny = min(min(oy), sy, gy) - area_width / 2.0
+    maxx = max(max(ox), sx, gx) + area_width / 2.0
+    maxy = max(max(oy), sy, gy) + area_width / 2.0
     xw = int(round((maxx - minx) / reso))
     yw = int(round((maxy - miny) / reso))
     X = (np.arange(xw) * reso + minx)[:, None]
     Y = (np.arange(yw) * reso + miny)[None, :]
-    pmap = 0.5 * KP * np.hypot(X - gx, Y - gy)
+    pmap = 0.5 * kp * np.hypot(X - gx, Y - gy)
     # the nearest obstacle of every cell; `dmin >= d` lets the last of equally near obstacles win
     dmin = np.full((xw, yw), np.inf)
     for k in range(len(ox)):
@@ -47,28 +50,34 @@ def _potential_map(gx, gy, ox, oy, reso, rr, sx, sy):
         dq = dmin[ix, iy]
         if dq <= 0.1:
             dq = 0.1
-        pmap[ix, iy] = pmap[ix, iy] + 0.5 * ETA * (1.0 / dq - 1.0 / rr) ** 2
+        pmap[ix, iy] = pmap[ix, iy] + 0.5 * eta * (1.0 / dq - 1.0 / rr) ** 2
     return pmap, minx, miny
 
 
-def plan_path(target_xy, obstacles=()):
+def plan_path(target_xy, obstacles=(), *, kp=KP, eta=ETA, area_width=AREA_WIDTH, grid=GRID, robot_radius=ROBOT_RADIUS,
+              oscillation_length=OSCILLATION_LENGTH, max_waypoints=MAX_WAYPOINTS):
     """Way points from the origin to target_xy: steepest descent on the potential grid over the 8 neighbours (the first of
-    equally low neighbours wins), stopped within one cell of the target or when the last three cells repeat, with the
-    target appended.  obstacles: [(x, y), ...]; none puts the reference's dummy obstacle outside the area.  Returns [k,2]."""
+    equally low neighbours wins), stopped within one cell of the target or when the last `oscillation_length` cells hold a
+    repeat, with the target appended.  obstacles: [(x, y), ...]; none puts the reference's dummy obstacle outside the area.
+    The keyword settings are the planner's fields of rg_episode_config (include/rg_episode.h), their defaults this module's
+    constants.  Returns [k,2].  Raises ValueError in the two cases that are RG_EPISODE_PLAN_WAYPOINTS on the device: the plan
+    would hold more than max_waypoints way points, or no neighbour of a cell has a finite potential."""
     gx, gy = float(target_xy[0]), float(target_xy[1])
     obstacles = np.asarray(obstacles, dtype=np.float64).reshape(-1, 2)
     if len(obstacles) == 0:
-        ox, oy = [AREA_WIDTH + 1.0], [AREA_WIDTH + 1.0]
+        ox, oy = [area_width + 1.0], [area_width + 1.0]
     else:
         ox, oy = list(obstacles[:, 0]), list(obstacles[:, 1])
-    sx, sy, reso = 0.0, 0.0, GRID
-    pmap, minx, miny = _potential_map(gx, gy, ox, oy, reso, ROBOT_RADIUS, sx, sy)
+    sx, sy, reso = 0.0, 0.0, grid
+    pmap, minx, miny = _potential_map(gx, gy, ox, oy, reso, robot_radius, sx, sy, kp, eta, area_width)
     d = np.hypot(sx - gx, sy - gy)
     ix = round((sx - minx) / reso)
     iy = round((sy - miny) / reso)
     rx, ry = [sx], [sy]
     previous = []
     while d >= reso:
+        if len(rx) + 2 > max_waypoints:   # the next cell and the target would not fit
+            raise ValueError(f"plan_path: more than max_waypoints = {max_waypoints} way points to {(gx, gy)}")
         minp, minix, miniy = float("inf"), -1, -1
         for mx, my in MOTION:
             inx, iny = int(ix + mx), int(iy + my)
@@ -78,6 +87,8 @@ def plan_path(target_xy, obstacles=()):
                 p = pmap[inx, iny]
             if minp > p:
                 minp, minix, miniy = p, inx, iny
+        if minix < 0:
+            raise ValueError(f"plan_path: no finite neighbour of cell {(int(ix), int(iy))} on the way to {(gx, gy)}")
         ix, iy = minix, miniy
         xp = ix * reso + minx
         yp = iy * reso + miny
@@ -85,7 +96,7 @@ def plan_path(target_xy, obstacles=()):
         rx.append(xp)
         ry.append(yp)
         previous.append((ix, iy))
-        if len(previous) > OSCILLATION_LENGTH:
+        if len(previous) > oscillation_length:
             previous.pop(0)
         if len(set(previous)) < len(previous):
             break
@@ -168,15 +179,18 @@ def chain_sort(points, origin=(0.0, 0.0), continuity_break=CONTINUITY_BREAK):
     return points[order], order
 
 
-def build_path(points, num_checkpoints=NUM_CHECKPOINTS, target=None, spacing=SPACING):
+def build_path(points, num_checkpoints=NUM_CHECKPOINTS, target=None, spacing=SPACING, n_max=None):
     """Path.__init__: n = int(len / spacing) points (the reference's 1e-2) at equal arc length along the way points,
     `length` of the INTERPOLATED polyline, checkpoints at i * length / num_checkpoints, start_xy, start_angle in [0, 2 pi)
     from the first segment -- and the tables the kernel reads: cumulative arc length s and first_same_x[i], the first j
-    with x[j] == x[i]."""
+    with x[j] == x[i].  ValueError for n < 2 and, with n_max given, for n > n_max (RG_EPISODE_PLAN_SHORT / _LONG on the
+    device)."""
     points = np.asarray(points, dtype=np.float64).reshape(-1, 2)
     n = int(arc_table(points)[-1] / spacing)
     if n < 2:
         raise ValueError(f"build_path: the way points span {n} path points, at least 2 are needed")
+    if n_max is not None and n > n_max:
+        raise ValueError(f"build_path: the way points span {n} path points, n_max is {n_max}")
     pts = interpolate_points(points, n)
     x, y = np.ascontiguousarray(pts[:, 0]), np.ascontiguousarray(pts[:, 1])
     s = arc_table(pts)

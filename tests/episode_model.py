@@ -64,27 +64,56 @@ def draw_target(seed, key, episode):
     return t
 
 
-def plan_build(target, obstacles=(), num_checkpoints=100):
+PLAN_KEYS = ("kp", "eta", "area_width", "grid", "robot_radius", "oscillation_length", "max_waypoints")
+
+
+def _split(settings):
+    """(plan_path's keywords, spacing) of a dict of rg_episode_config fields; anything else is a TypeError."""
+    settings = dict(settings)
+    spacing = settings.pop("spacing", goto_path.SPACING)
+    unknown = set(settings) - set(PLAN_KEYS)
+    if unknown:
+        raise TypeError(f"unknown planner setting(s) {sorted(unknown)}")
+    return settings, spacing
+
+
+def plan_build(target, obstacles=(), num_checkpoints=100, **settings):
     """build_path(plan_path(target)) of goto_path, the reference of the device's plan."""
+    plan, spacing = _split(settings)
     key = (float(target[0]), float(target[1]))
-    return goto_path.build_path(goto_path.plan_path(key, obstacles), num_checkpoints, target=key)
+    return goto_path.build_path(goto_path.plan_path(key, obstacles, **plan), num_checkpoints, target=key, spacing=spacing)
 
 
-def plan_path_forced(target_xy, obstacles=(), forced=()):
-    """goto_path.plan_path with its stop test `d >= reso` instrumented.  Returns (way points [k,2], flagged): flagged lists
-    the evaluations (0 = before the first step, k = after step k) where |d - reso| < FLAG_REL * reso and neither component of
-    the distance is exactly 0 (see FLAG_REL).  forced: the outcomes
-    (True: go on, False: stop) to take at the flagged evaluations, in order, in place of the comparison; evaluations past
-    its end are compared as usual."""
+def plan_path_forced(target_xy, obstacles=(), forced=(), info=None, **settings):
+    """goto_path.plan_path (its keyword settings included, and its two ValueErrors) with its stop test `d >= reso`
+    instrumented.  Returns (way points [k,2], flagged): flagged lists the evaluations (0 = before the first step, k = after
+    step k) where |d - reso| < FLAG_REL * reso and neither component of the distance is exactly 0 (see FLAG_REL).  forced: the
+    outcomes (True: go on, False: stop) to take at the flagged evaluations, in order, in place of the comparison; evaluations
+    past its end are compared as usual.
+    info: a dict that is filled, also when the plan raises, with
+      near_tie  the steps (1 = the first) at which the lowest neighbour potential and the next DISTINCT one differ by less than
+                FLAG_REL relative: the potentials are hypot's, the device's is not libm's, so the argmin may go either way
+                there.  Equal potentials are no near tie: they come from mirrored cells, whose hypot has the same arguments up
+                to sign and order, and the first in MOTION order wins on both sides.
+      edge      how many neighbour reads fell outside the grid (potential +inf)
+      repeat    whether the descent stopped on a repeated cell
+      cause     of a ValueError: "max_waypoints" or "neighbour"; None when a plan was made
+      flagged   the list that is returned"""
+    plan, _ = _split(settings)
+    kp, eta, area_width = plan.get("kp", goto_path.KP), plan.get("eta", goto_path.ETA), plan.get("area_width", goto_path.AREA_WIDTH)
+    rr, osc = plan.get("robot_radius", goto_path.ROBOT_RADIUS), plan.get("oscillation_length", goto_path.OSCILLATION_LENGTH)
+    max_way = plan.get("max_waypoints", goto_path.MAX_WAYPOINTS)
+    info = {} if info is None else info
+    info.update(near_tie=[], edge=0, repeat=False, cause=None, flagged=[])
     gx, gy = float(target_xy[0]), float(target_xy[1])
     obstacles = np.asarray(obstacles, dtype=np.float64).reshape(-1, 2)
     if len(obstacles) == 0:
-        ox, oy = [goto_path.AREA_WIDTH + 1.0], [goto_path.AREA_WIDTH + 1.0]
+        ox, oy = [area_width + 1.0], [area_width + 1.0]
     else:
         ox, oy = list(obstacles[:, 0]), list(obstacles[:, 1])
-    sx, sy, reso = 0.0, 0.0, goto_path.GRID
-    pmap, minx, miny = goto_path._potential_map(gx, gy, ox, oy, reso, goto_path.ROBOT_RADIUS, sx, sy)
-    flagged, forced = [], list(forced)
+    sx, sy, reso = 0.0, 0.0, plan.get("grid", goto_path.GRID)
+    pmap, minx, miny = goto_path._potential_map(gx, gy, ox, oy, reso, rr, sx, sy, kp, eta, area_width)
+    flagged, forced = info["flagged"], list(forced)
 
     def goes_on(d, k, dx, dy):
         if abs(d - reso) < FLAG_REL * reso and dx != 0.0 and dy != 0.0:
@@ -98,68 +127,153 @@ def plan_path_forced(target_xy, obstacles=(), forced=()):
     rx, ry, previous, k = [sx], [sy], [], 0
     dx, dy = sx - gx, sy - gy
     while goes_on(d, k, dx, dy):
+        if len(rx) + 2 > max_way:
+            info["cause"] = "max_waypoints"
+            raise ValueError(f"plan_path_forced: more than max_waypoints = {max_way} way points")
         minp, minix, miniy = float("inf"), -1, -1
+        seen = []
         for mx, my in goto_path.MOTION:
             inx, iny = int(ix + mx), int(iy + my)
-            p = float("inf") if (inx >= pmap.shape[0] or iny >= pmap.shape[1] or inx < 0 or iny < 0) else pmap[inx, iny]
+            outside = inx >= pmap.shape[0] or iny >= pmap.shape[1] or inx < 0 or iny < 0
+            info["edge"] += outside
+            p = float("inf") if outside else pmap[inx, iny]
+            seen.append(float(p))
             if minp > p:
                 minp, minix, miniy = p, inx, iny
+        if minix < 0:
+            info["cause"] = "neighbour"
+            raise ValueError("plan_path_forced: no finite neighbour")
+        k += 1
+        others = [p for p in seen if p != minp and p != float("inf")]
+        if others and min(others) - minp < FLAG_REL * max(abs(minp), abs(min(others))):
+            info["near_tie"].append(k)
         ix, iy = minix, miniy
         xp, yp = ix * reso + minx, iy * reso + miny
         dx, dy = gx - xp, gy - yp
         d = np.hypot(gx - xp, gy - yp)
         rx.append(xp)
         ry.append(yp)
-        k += 1
         previous.append((ix, iy))
-        if len(previous) > goto_path.OSCILLATION_LENGTH:
+        if len(previous) > osc:
             previous.pop(0)
         if len(set(previous)) < len(previous):
+            info["repeat"] = True
             break
     rx.append(gx)
     ry.append(gy)
     return np.stack((np.asarray(rx, dtype=np.float64), np.asarray(ry, dtype=np.float64)), axis=-1), flagged
 
 
-def plan_variants(target, obstacles=(), num_checkpoints=100):
-    """(plain path, flagged?, [paths under every outcome of the flagged stop tests]).  An unflagged target has one variant,
-    the plain path."""
-    key = (float(target[0]), float(target[1]))
-    pts, flagged = plan_path_forced(key, obstacles)
-    plain = goto_path.build_path(pts, num_checkpoints, target=key)
-    if not flagged:
-        return plain, False, [plain]
-    variants, seen = [], set()
-    for n in range(1, 4):   # up to three flagged evaluations in one descent
+def _outcomes(key, obstacles, plan):
+    """The way points under every outcome of up to three flagged stop tests (None where that descent raises), without
+    duplicates, the plain one first."""
+    out, seen = [], set()
+    for n in range(0, 4):
         for outcome in itertools.product((True, False), repeat=n):
-            p, _ = plan_path_forced(key, obstacles, outcome)
-            sig = p.tobytes()
-            if sig in seen:
-                continue
-            seen.add(sig)
+            info = {}
             try:
-                variants.append(goto_path.build_path(p, num_checkpoints, target=key))
+                p, _ = plan_path_forced(key, obstacles, outcome, info, **plan)
             except ValueError:
-                pass
-    return plain, True, variants
+                p = None
+            sig = None if p is None else p.tobytes()
+            if sig not in seen:
+                seen.add(sig)
+                out.append((p, info))
+        if n == 0 and not out[0][1]["flagged"]:
+            break
+    return out
+
+
+def _status_of(pts, spacing, n_max):
+    """(RG_EPISODE_PLAN_* status, n) of way points (None: the descent was refused), as rg_episode.h, d., prescribes."""
+    if pts is None:
+        return PLAN_WAYPOINTS, 0
+    n = int(goto_path.arc_table(pts)[-1] / spacing)
+    return (PLAN_SHORT if n < 2 else PLAN_LONG if n > n_max else PLAN_OK), n
+
+
+def plan_status(target, obstacles=(), n_max=1024, **settings):
+    """The RG_EPISODE_PLAN_* code the header prescribes for a target: _TARGET for a non-finite one, _WAYPOINTS where
+    goto_path.plan_path raises, _SHORT / _LONG by n = int(length / spacing) against 2 and n_max, else _OK."""
+    plan, spacing = _split(settings)
+    gx, gy = float(target[0]), float(target[1])
+    if not (math.isfinite(gx) and math.isfinite(gy)):
+        return PLAN_TARGET
+    try:
+        pts = goto_path.plan_path((gx, gy), obstacles, **plan)
+    except ValueError:
+        pts = None
+    return _status_of(pts, spacing, n_max)[0]
+
+
+def plan_case(target, obstacles=(), n_max=1024, num_checkpoints=100, **settings):
+    """Everything the edge tests need of one target: dict(target, status, path (goto_path.Path, None on a failure), nway, n
+    (int(length / spacing), whatever the status), flagged (a stop test too close to call), near_tie (an argmin too close to
+    call), edge, repeat, cause (see plan_path_forced), variants: [(status, path, nway)] under every outcome of the flagged
+    stop tests, the plain one first)."""
+    plan, spacing = _split(settings)
+    key = (float(target[0]), float(target[1]))
+    if not (math.isfinite(key[0]) and math.isfinite(key[1])):
+        return dict(target=key, status=PLAN_TARGET, path=None, nway=0, n=0, flagged=False, near_tie=False, edge=0, repeat=False, cause=None,
+                    variants=[(PLAN_TARGET, None, 0)])
+    variants, first, near = [], None, False
+    for pts, info in _outcomes(key, obstacles, plan):
+        status, n = _status_of(pts, spacing, n_max)
+        path = goto_path.build_path(pts, num_checkpoints, target=key, spacing=spacing) if status == PLAN_OK else None
+        variants.append((status, path, 0 if pts is None else len(pts)))
+        near = near or bool(info["near_tie"])
+        if first is None:
+            first = dict(n=n, edge=info["edge"], repeat=info["repeat"], cause=info["cause"], flagged=bool(info["flagged"]))
+    status, path, nway = variants[0]
+    return dict(target=key, status=status, path=path, nway=nway, near_tie=near, variants=variants, **first)
+
+
+def plan_variants(target, obstacles=(), num_checkpoints=100, **settings):
+    """(plain path, flagged?, [paths under every outcome of the flagged stop tests]), from plan_case with no upper limit on the
+    path points.  An unflagged target has one variant, the plain path.  ValueError where the plain plan cannot be made."""
+    c = plan_case(target, obstacles, 2 ** 62, num_checkpoints, **settings)
+    if c["path"] is None:
+        raise ValueError(f"plan_variants: no plan to {c['target']} ({('ok', 'target', 'waypoints', 'short', 'long')[c['status']]})")
+    return c["path"], c["flagged"], [path for _, path, _ in c["variants"] if path is not None]
+
+
+def _cases_chunk(args):
+    targets, obstacles, settings, n_max = args
+    return [plan_case(t, obstacles, n_max, **settings) for t in targets]
 
 
 def _variants_chunk(args):
-    targets, obstacles = args
-    return [plan_variants(t, obstacles) for t in targets]
+    targets, obstacles, settings, _ = args
+    return [plan_variants(t, obstacles, **settings) for t in targets]
 
 
-def plan_many(targets, obstacles=(), workers=None):
-    """plan_variants of every target, in spawned worker processes (none of them opens a GPU)."""
+def _pooled(chunk, jobs, workers):
+    """chunk over every job (targets, obstacles, settings, n_max), all jobs in ONE pool of spawned worker processes (none of
+    them opens a GPU); per job the list of results in the order of its targets."""
     workers = workers or min(8, os.cpu_count() or 1)
-    targets = [(float(t[0]), float(t[1])) for t in targets]
-    chunks = [targets[k::workers] for k in range(workers)]
+    work, where = [], []
+    for j, (targets, obstacles, settings, n_max) in enumerate(jobs):
+        targets = [(float(t[0]), float(t[1])) for t in targets]
+        for k in range(workers):
+            if targets[k::workers]:
+                work.append((targets[k::workers], tuple(map(tuple, obstacles)), dict(settings), n_max))
+                where.append((j, k))
     with ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("spawn")) as pool:
-        parts = list(pool.map(_variants_chunk, [(c, tuple(map(tuple, obstacles))) for c in chunks]))
-    out = [None] * len(targets)
-    for k, part in enumerate(parts):
-        out[k::workers] = part
+        parts = list(pool.map(chunk, work))
+    out = [[None] * len(job[0]) for job in jobs]
+    for (j, k), part in zip(where, parts):
+        out[j][k::workers] = part
     return out
+
+
+def plan_jobs(jobs, workers=None):
+    """[(targets, obstacles, settings, n_max)] -> per job the list of plan_case of its targets."""
+    return _pooled(_cases_chunk, jobs, workers)
+
+
+def plan_many(targets, obstacles=(), workers=None, **settings):
+    """plan_variants of every target, in spawned worker processes."""
+    return _pooled(_variants_chunk, [(targets, obstacles, settings, None)], workers)[0]
 
 
 def path_equal(path, n, length, target, x, y, s, fsx):
