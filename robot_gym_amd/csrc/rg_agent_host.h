@@ -1,0 +1,156 @@
+// rg_agent_host.h -- the host helpers that rg_policy.hip, rg_ppo.hip and rg_ddpg.hip share: the device scope, the workspace
+// arithmetic, the layer-layout rule, the checks of a configuration's fields and the error helpers.  Every message is formed
+// here once; the callers give the prefix ("config.", "policy_cfg.", "ppo_cfg.") and their API's status codes.
+// rg_mpc.hip does not include it, so the source hash behind profiles/ does not move.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+
+namespace {
+
+struct DeviceScope {
+  int prev = -1;
+  bool switched = false;
+  hipError_t err = hipSuccess;
+  explicit DeviceScope(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess && prev >= 0; }
+  }
+  ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
+};
+
+inline size_t round8(size_t n) { return (n + 7) & ~(size_t)7; }
+
+template <typename T>
+T *ws_at(void *workspace, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(workspace) + off); }
+
+// the layout rule of rg_policy.h for one network: W[in][out] then b[out] per layer, the nh hidden layers then the head.
+// Returns the floats the network takes; entries past layer nh are left as they are.
+inline int layer_layout(int first, const int32_t *widths, int nh, int head, int32_t *in, int32_t *out, int32_t *w, int32_t *b) {
+  int off = 0, prev = first;
+  for (int l = 0; l <= nh; l++) {
+    const int width = l < nh ? widths[l] : head;
+    in[l] = prev; out[l] = width;
+    w[l] = off; off += prev * width;
+    b[l] = off; off += width;
+    prev = width;
+  }
+  return off;
+}
+
+// ---- the checks of a configuration ----------------------------------------------------------------------------------------
+
+inline bool check_abi(const char *prefix, int got, int want, std::string &err) {
+  if (got == want) return true;
+  char msg[200];
+  snprintf(msg, sizeof(msg), "%sabi_version: %d, this library is version %d", prefix, got, want);
+  err = msg;
+  return false;
+}
+
+struct IntField { const char *name; int v, lo, hi; };
+
+template <size_t N>
+bool check_ints(const char *prefix, const IntField (&fields)[N], std::string &err) {
+  for (const IntField &f : fields)
+    if (f.v < f.lo || f.v > f.hi) {
+      char msg[200];
+      snprintf(msg, sizeof(msg), "%s%s: %d outside [%d, %d]", prefix, f.name, f.v, f.lo, f.hi);
+      err = msg;
+      return false;
+    }
+  return true;
+}
+
+// the width list of one network: the n layers in use within [1, max_width], the entries past them 0
+inline bool check_widths(const char *prefix, const char *name, const int32_t *w, int n, int max_layers, int max_width, std::string &err) {
+  char msg[200];
+  for (int k = 0; k < max_layers; k++) {
+    if (k < n && (w[k] < 1 || w[k] > max_width)) {
+      snprintf(msg, sizeof(msg), "%s%s[%d]: %d outside [1, %d]", prefix, name, k, w[k], max_width);
+      err = msg;
+      return false;
+    }
+    if (k >= n && w[k] != 0) {
+      snprintf(msg, sizeof(msg), "%s%s[%d]: %d must be 0 past the %d layers in use", prefix, name, k, w[k], n);
+      err = msg;
+      return false;
+    }
+  }
+  return true;
+}
+
+enum RealKind { kNonNegative, kBelowOne, kPositive, kUnit, kUnitPositive, kFinite };   // >= 0; [0, 1); > 0; [0, 1]; (0, 1]; any finite
+struct RealField { const char *name; double v; RealKind kind; };
+
+template <size_t N>
+bool check_reals(const char *prefix, const RealField (&fields)[N], std::string &err) {
+  const char *want[] = {">= 0", "in [0, 1)", "> 0", "in [0, 1]", "in (0, 1]", "finite"};
+  for (const RealField &f : fields) {
+    bool ok = std::isfinite(f.v);
+    if (ok && f.kind != kFinite) ok = f.v >= 0;
+    if (ok && f.kind == kBelowOne) ok = f.v < 1;
+    if (ok && (f.kind == kPositive || f.kind == kUnitPositive)) ok = f.v > 0;
+    if (ok && (f.kind == kUnit || f.kind == kUnitPositive)) ok = f.v <= 1;
+    if (!ok) {
+      char msg[200];
+      snprintf(msg, sizeof(msg), "%s%s: %g must be finite%s%s", prefix, f.name, f.v, f.kind == kFinite ? "" : " and ", f.kind == kFinite ? "" : want[f.kind]);
+      err = msg;
+      return false;
+    }
+  }
+  return true;
+}
+
+#ifdef RG_POLICY_ABI_VERSION
+// what rg_policy_create and rg_ppo_create check alike of an rg_policy_config (where rg_policy.h has been included): the
+// version, the dimensions, both width lists and obs_clip.  The fields only the acting side reads are the caller's.
+inline bool check_policy_config(const char *prefix, const rg_policy_config *cfg, std::string &err) {
+  if (!check_abi(prefix, cfg->abi_version, RG_POLICY_ABI_VERSION, err)) return false;
+  if (cfg->reserved0 != 0) { err = std::string(prefix) + "reserved0: must be 0"; return false; }
+  const IntField ints[] = {{"obs_dim", cfg->obs_dim, 1, RG_POLICY_MAX_OBS}, {"act_dim", cfg->act_dim, 1, RG_POLICY_MAX_ACT},
+                           {"n_policy_layers", cfg->n_policy_layers, 0, RG_POLICY_MAX_LAYERS}, {"n_value_layers", cfg->n_value_layers, 0, RG_POLICY_MAX_LAYERS}};
+  const RealField reals[] = {{"obs_clip", cfg->obs_clip, kNonNegative}};
+  return check_ints(prefix, ints, err) &&
+         check_widths(prefix, "policy_layers", cfg->policy_layers, cfg->n_policy_layers, RG_POLICY_MAX_LAYERS, RG_POLICY_MAX_WIDTH, err) &&
+         check_widths(prefix, "value_layers", cfg->value_layers, cfg->n_value_layers, RG_POLICY_MAX_LAYERS, RG_POLICY_MAX_WIDTH, err) &&
+         check_reals(prefix, reals, err);
+}
+#endif
+
+// ---- errors: h->err and the status of the caller's API ----------------------------------------------------------------------
+
+template <typename H>
+int hip_fail(H *h, int status, const char *what, hipError_t e) {
+  h->err = std::string(what) + ": " + hipGetErrorString(e);
+  return status;
+}
+
+// api: "RG_POLICY", "RG_PPO", "RG_DDPG"
+template <typename H>
+int no_device(H *h, int status, const char *api) {
+  h->err = std::string("host-only handle (") + api + "_DEVICE_NONE): the arguments are valid, there is no device to run on";
+  return status;
+}
+
+// 0, every API's OK, where the launch before went through
+template <typename H>
+int launch_status(H *h, int status, const char *what) {
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(h, status, what, e) : 0;
+}
+
+template <typename H>
+int null_arg(H *h, int status, const char *call, const char *name) {
+  h->err = std::string(call) + ": null " + name;
+  return status;
+}
+
+// in a function whose handle is h and whose file gives null_arg(h, call, name)
+#define RG_NEED(call, ptr, name) \
+  do { if (!(ptr)) return null_arg(h, call, name); } while (0)
+
+}  // namespace

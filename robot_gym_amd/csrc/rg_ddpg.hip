@@ -1,6 +1,7 @@
-// rg_ddpg.hip -- the DDPG agent of include/rg_ddpg.h.  Its own translation unit of librg_mpc.so: it shares no device code with
-// the others (the neuron arithmetic, the backward pass and the block sums of rg_ppo.hip and the noise stream of rg_policy.hip
-// are restated here, line for line).
+// rg_ddpg.hip -- the DDPG agent of include/rg_ddpg.h.  Its own translation unit of librg_mpc.so.  The noise stream, a layer's
+// forward and backward pass over a tile, the workgroup sums and the bodies of the transpose and slab-finish kernels
+// are those of rg_agent_dev.inc, which the PPO agent's files include too, and the host helpers those of rg_agent_host.h;
+// rg_mpc.hip includes neither, so the source hash behind profiles/ is unaffected.
 //
 // Sweeps (rg_ddpg_critic_sweep_kernel, rg_ddpg_actor_sweep_kernel): G workgroups of 256 threads, workgroup g walks the tiles
 // g, g + G, ... of kTile samples.  LDS (dynamic): the tile's activations of every layer of the critic, then of the actor, as
@@ -18,13 +19,16 @@
 #include <cstring>
 #include <string>
 #include "../../include/rg_ddpg.h"
+#include "rg_agent_host.h"
 
 #pragma clang fp contract(off)
+
+#include "rg_agent_dev.inc"
 
 namespace {
 
 constexpr int kTile = RG_DDPG_TILE;
-constexpr int kThreads = 256;
+constexpr int kThreads = kAgentThreads;
 constexpr int kMaxGroups = RG_DDPG_MAX_GROUPS;
 constexpr int kMaxAct = RG_DDPG_MAX_ACT;
 constexpr int kMaxIn = RG_DDPG_MAX_INPUT;
@@ -36,14 +40,12 @@ static_assert(kMaxLds == 148032 && kMaxLds <= 160 * 1024, "a sweep's tile fits a
 constexpr int kActFloats = (kMaxIn + kMaxHidden + kMaxAct) * kTile;
 static_assert(kActFloats * 4 <= 60 * 1024, "the act kernel's activations fit the static LDS of a workgroup");
 
-static_assert(kTile == 16, "the sweeps read a neuron's tile as four float4");
+static_assert(kTile == kAgentTile, "the sweeps run the shared layers, whose tile is four float4");
 static_assert(RG_DDPG_MAX_WIDTH <= kThreads && kMaxAct + kMaxIn <= kThreads, "one neuron per thread");
 static_assert(kMaxGroups <= kThreads && kTile * kMaxAct <= 64, "thread maps");
 static_assert(RG_DDPG_MAX_OBS * RG_DDPG_MAX_WINDOW >= kMaxIn, "the input limit is the tighter one");
 
-struct Net {
-  int n;                       // layers, the head included
-  int in[4], out[4], w[4], b[4];
+struct Net : NetDesc {
   int count, asum;             // floats in the buffer; floats per sample of the activations, the input included
 };
 
@@ -58,30 +60,6 @@ struct Geo {
   double gamma;
 };
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-
-__device__ __forceinline__ unsigned long long noise_hash(unsigned long long seed, unsigned long long key, unsigned long long counter,
-                                                         unsigned long long axis, unsigned long long draw) {
-  unsigned long long h = seed;
-  h = mix64((h ^ key) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ counter) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ axis) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ draw) + 0x9E3779B97F4A7C15ull);
-  return h;
-}
-
-// the standard normal of (seed, key, counter, axis): rg_policy.h, Noise
-__device__ __forceinline__ float noise_eps(unsigned long long seed, unsigned long long key, unsigned long long counter, unsigned long long axis) {
-  const double u1 = (double)((noise_hash(seed, key, counter, axis, 0) >> 11) + 1ull) * 0x1.0p-53;
-  const double u2 = (double)(noise_hash(seed, key, counter, axis, 1) >> 11) * 0x1.0p-53;
-  return (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
-}
-
 // the sample stream: rg_ddpg.h, rg_ddpg_sample
 __device__ __forceinline__ unsigned long long sample_hash(unsigned long long seed, unsigned long long updates, unsigned long long m,
                                                           unsigned long long draw) {
@@ -90,23 +68,6 @@ __device__ __forceinline__ unsigned long long sample_hash(unsigned long long see
   h = mix64((h ^ m) + 0x9E3779B97F4A7C15ull);
   h = mix64((h ^ draw) + 0x9E3779B97F4A7C15ull);
   return h;
-}
-
-// the sum of v over the workgroup of 256, the same in every thread: a shuffle tree in each wave, the four waves in order
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off);
-  __syncthreads();   // sh may still be read from the call before
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
-// sum over idx = 0 .. n-1 of p[idx]: thread t takes t, t + 256, ... in order, then block_sum
-__device__ __forceinline__ double strided_sum(const double *__restrict__ p, int n, double *sh) {
-  double s = 0.0;
-  for (int idx = threadIdx.x; idx < n; idx += kThreads) s = s + p[idx];
-  return block_sum(s, sh);
 }
 
 __device__ __forceinline__ bool short_ring(const long long *__restrict__ state) { return state[1] < 2; }
@@ -147,114 +108,7 @@ __device__ __forceinline__ void fill_state(const Geo &g, const float *__restrict
   }
 }
 
-// ---- the layers (rg_ppo.hip's) ------------------------------------------------------------------------------------------
-
-// y[j][s] = act(sum_i W[i][j] x[i][s] + b[j]).  mode 0 relu, 1 tanhf, 2 linear
-__device__ __forceinline__ void forward_layer(const float *__restrict__ P, const int nin, const int nout, const int woff, const int boff,
-                                              const float *x, float *y, const int mode) {
-  const int j = threadIdx.x;
-  if (j < nout) {
-    const float *__restrict__ W = P + woff + j;
-    float acc[kTile];
-#pragma unroll
-    for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
-#pragma unroll 4
-    for (int i = 0; i < nin; i++) {
-      const float w = W[(size_t)i * nout];
-      const float4 xa = *reinterpret_cast<const float4 *>(x + i * kTile);
-      const float4 xb = *reinterpret_cast<const float4 *>(x + i * kTile + 4);
-      const float4 xc = *reinterpret_cast<const float4 *>(x + i * kTile + 8);
-      const float4 xd = *reinterpret_cast<const float4 *>(x + i * kTile + 12);
-      acc[0] = __builtin_fmaf(w, xa.x, acc[0]); acc[1] = __builtin_fmaf(w, xa.y, acc[1]);
-      acc[2] = __builtin_fmaf(w, xa.z, acc[2]); acc[3] = __builtin_fmaf(w, xa.w, acc[3]);
-      acc[4] = __builtin_fmaf(w, xb.x, acc[4]); acc[5] = __builtin_fmaf(w, xb.y, acc[5]);
-      acc[6] = __builtin_fmaf(w, xb.z, acc[6]); acc[7] = __builtin_fmaf(w, xb.w, acc[7]);
-      acc[8] = __builtin_fmaf(w, xc.x, acc[8]); acc[9] = __builtin_fmaf(w, xc.y, acc[9]);
-      acc[10] = __builtin_fmaf(w, xc.z, acc[10]); acc[11] = __builtin_fmaf(w, xc.w, acc[11]);
-      acc[12] = __builtin_fmaf(w, xd.x, acc[12]); acc[13] = __builtin_fmaf(w, xd.y, acc[13]);
-      acc[14] = __builtin_fmaf(w, xd.z, acc[14]); acc[15] = __builtin_fmaf(w, xd.w, acc[15]);
-    }
-    const float bias = P[boff + j];
-    float *yj = y + j * kTile;
-#pragma unroll
-    for (int r = 0; r < kTile; r++) {
-      float v = acc[r] + bias;
-      if (mode == 0) v = v > 0.0f ? v : 0.0f;
-      else if (mode == 1) v = tanhf(v);
-      yj[r] = v;
-    }
-  }
-}
-
-// slab[W[i][j]] += sum_s x[i][s] delta[j][s], slab[b[j]] += sum_s delta[j][s]
-__device__ __forceinline__ void backward_weights(float *__restrict__ slab, const int nin, const int nout, const int woff, const int boff,
-                                                 const float *x, const float *dl) {
-  const int j = threadIdx.x;
-  if (j < nout) {
-    float d[kTile];
-#pragma unroll
-    for (int q = 0; q < kTile / 4; q++) {
-      const float4 v = *reinterpret_cast<const float4 *>(dl + j * kTile + 4 * q);
-      d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w;
-    }
-    float bs = d[0];
-#pragma unroll
-    for (int r = 1; r < kTile; r++) bs = bs + d[r];
-    slab[boff + j] = slab[boff + j] + bs;
-    float *__restrict__ sw = slab + woff + j;
-#pragma unroll 4
-    for (int i = 0; i < nin; i++) {
-      const float4 xa = *reinterpret_cast<const float4 *>(x + i * kTile);
-      const float4 xb = *reinterpret_cast<const float4 *>(x + i * kTile + 4);
-      const float4 xc = *reinterpret_cast<const float4 *>(x + i * kTile + 8);
-      const float4 xd = *reinterpret_cast<const float4 *>(x + i * kTile + 12);
-      float v = xa.x * d[0];
-      v = __builtin_fmaf(xa.y, d[1], v); v = __builtin_fmaf(xa.z, d[2], v); v = __builtin_fmaf(xa.w, d[3], v);
-      v = __builtin_fmaf(xb.x, d[4], v); v = __builtin_fmaf(xb.y, d[5], v); v = __builtin_fmaf(xb.z, d[6], v); v = __builtin_fmaf(xb.w, d[7], v);
-      v = __builtin_fmaf(xc.x, d[8], v); v = __builtin_fmaf(xc.y, d[9], v); v = __builtin_fmaf(xc.z, d[10], v); v = __builtin_fmaf(xc.w, d[11], v);
-      v = __builtin_fmaf(xd.x, d[12], v); v = __builtin_fmaf(xd.y, d[13], v); v = __builtin_fmaf(xd.z, d[14], v); v = __builtin_fmaf(xd.w, d[15], v);
-      const size_t o = (size_t)i * nout;
-      sw[o] = sw[o] + v;
-    }
-  }
-}
-
-// acc[s] = sum_j Wt[j][i] dl[j][s] for this thread's input i (an fma chain over j in order)
-__device__ __forceinline__ void input_chain(const float *__restrict__ Wt, const int nin, const int nout, const int woff, const float *dl, float *acc) {
-  const float *__restrict__ W = Wt + woff + threadIdx.x;
-#pragma unroll
-  for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
-#pragma unroll 4
-  for (int j = 0; j < nout; j++) {
-    const float w = W[(size_t)j * nin];
-    const float4 da = *reinterpret_cast<const float4 *>(dl + j * kTile);
-    const float4 db = *reinterpret_cast<const float4 *>(dl + j * kTile + 4);
-    const float4 dc = *reinterpret_cast<const float4 *>(dl + j * kTile + 8);
-    const float4 dd = *reinterpret_cast<const float4 *>(dl + j * kTile + 12);
-    acc[0] = __builtin_fmaf(w, da.x, acc[0]); acc[1] = __builtin_fmaf(w, da.y, acc[1]);
-    acc[2] = __builtin_fmaf(w, da.z, acc[2]); acc[3] = __builtin_fmaf(w, da.w, acc[3]);
-    acc[4] = __builtin_fmaf(w, db.x, acc[4]); acc[5] = __builtin_fmaf(w, db.y, acc[5]);
-    acc[6] = __builtin_fmaf(w, db.z, acc[6]); acc[7] = __builtin_fmaf(w, db.w, acc[7]);
-    acc[8] = __builtin_fmaf(w, dc.x, acc[8]); acc[9] = __builtin_fmaf(w, dc.y, acc[9]);
-    acc[10] = __builtin_fmaf(w, dc.z, acc[10]); acc[11] = __builtin_fmaf(w, dc.w, acc[11]);
-    acc[12] = __builtin_fmaf(w, dd.x, acc[12]); acc[13] = __builtin_fmaf(w, dd.y, acc[13]);
-    acc[14] = __builtin_fmaf(w, dd.z, acc[14]); acc[15] = __builtin_fmaf(w, dd.w, acc[15]);
-  }
-}
-
-// dn[i][s] = x[i][s] > 0 ? sum_j Wt[j][i] dl[j][s] : 0
-__device__ __forceinline__ void backward_inputs(const float *__restrict__ Wt, const int nin, const int nout, const int woff, const float *x,
-                                                const float *dl, float *dn) {
-  const int i = threadIdx.x;
-  if (i < nin) {
-    float acc[kTile];
-    input_chain(Wt, nin, nout, woff, dl, acc);
-    const float *xi = x + i * kTile;
-    float *di = dn + i * kTile;
-#pragma unroll
-    for (int r = 0; r < kTile; r++) di[r] = xi[r] > 0.0f ? acc[r] : 0.0f;
-  }
-}
+// ---- the layers (rg_agent_dev.inc's) and what only this agent needs of them -------------------------------------------------
 
 // the critic's input layer toward the action: dn[k][s] = (float)((double)(sum_j Wt[j][k] dl[j][s]) * (1 - mu[k][s]^2)) for k < act_dim; no gate
 __device__ __forceinline__ void backward_action(const float *__restrict__ Wt, const int nin, const int nout, const int woff, const int act_dim,
@@ -334,17 +188,7 @@ __device__ __forceinline__ void stage_nets(const Net &actor, const Net &critic, 
 __global__ void __launch_bounds__(kThreads) rg_ddpg_transpose_kernel(const Net nd, const float *__restrict__ P, float *__restrict__ Wt,
                                                                      const long long *__restrict__ gate) {
   if (short_ring(gate)) return;
-  const int e = blockIdx.x * kThreads + (int)threadIdx.x;
-#pragma unroll
-  for (int l = 0; l < 4; l++) {
-    if (l < nd.n) {
-      const int k = e - nd.w[l];
-      if (k >= 0 && k < nd.in[l] * nd.out[l]) {
-        const int i = k / nd.out[l], j = k - i * nd.out[l];
-        Wt[nd.w[l] + j * nd.in[l] + i] = P[e];
-      }
-    }
-  }
+  transpose_element(nd, P, Wt, blockIdx.x * kThreads + (int)threadIdx.x);
 }
 
 // ---- act, store, sample -----------------------------------------------------------------------------------------------
@@ -584,9 +428,7 @@ __global__ void __launch_bounds__(kThreads) rg_ddpg_grad_finish_kernel(const int
   if (short_ring(gate)) return;
   const int e = blockIdx.x * kThreads + (int)threadIdx.x;
   if (e >= count) return;
-  double s = 0.0;
-  for (int g = 0; g < G; g++) s = s + (double)slabs[(size_t)g * count + e];
-  grad[e] = (float)s;
+  grad[e] = slab_sum(slabs, count, G, e);
 }
 
 // loss = sign * (sum of the partials) / M; out2, out3 (optional) receive the loss and its negative
@@ -595,7 +437,7 @@ __global__ void __launch_bounds__(kThreads) rg_ddpg_loss_finish_kernel(const int
                                                                        const long long *__restrict__ gate) {
   __shared__ double sh[4];
   if (short_ring(gate)) return;   // uniform
-  const double s = strided_sum(part, n, sh);
+  const double s = strided_sum(part, n, 1, sh);
   if (threadIdx.x == 0) {
     const double mean = s / (double)M;
     *out = sign * mean;
@@ -626,7 +468,7 @@ __global__ void __launch_bounds__(kThreads) rg_ddpg_adam_kernel(const AdamCfg c,
                                                                 double *__restrict__ norm_out, const long long *__restrict__ gate) {
   __shared__ double sh[4];
   if (gate && short_ring(gate)) return;   // uniform
-  const double norm = sqrt(strided_sum(part, c.GN, sh));
+  const double norm = sqrt(strided_sum(part, c.GN, 1, sh));
   if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = norm;
   const int e = blockIdx.x * kThreads + (int)threadIdx.x;
   if (e >= c.count) return;
@@ -665,20 +507,7 @@ __global__ void rg_ddpg_stats_kernel(double *__restrict__ stats) {
   if (blockIdx.x == 0 && threadIdx.x < RG_DDPG_STATS) stats[threadIdx.x] = nan("");
 }
 
-struct DeviceScope {
-  int prev = -1;
-  bool switched = false;
-  hipError_t err = hipSuccess;
-  explicit DeviceScope(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess && prev >= 0; }
-  }
-  ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
-};
-
 thread_local std::string g_create_err;
-
-size_t round8(size_t n) { return (n + 7) & ~(size_t)7; }
 
 }  // namespace
 
@@ -697,84 +526,32 @@ struct rg_ddpg_handle {
 namespace {
 
 bool validate(const rg_ddpg_config *cfg, std::string &err) {
-  char msg[200];
-  if (cfg->abi_version != RG_DDPG_ABI_VERSION) {
-    snprintf(msg, sizeof(msg), "config.abi_version: %d, this library is version %d", cfg->abi_version, RG_DDPG_ABI_VERSION);
-    err = msg;
-    return false;
-  }
-  struct I { const char *name; int v, lo, hi; };
-  const I ints[] = {{"obs_dim", cfg->obs_dim, 1, RG_DDPG_MAX_OBS}, {"act_dim", cfg->act_dim, 1, RG_DDPG_MAX_ACT}, {"window", cfg->window, 1, RG_DDPG_MAX_WINDOW},
-                    {"n_actor_layers", cfg->n_actor_layers, 0, RG_DDPG_MAX_LAYERS}, {"n_critic_layers", cfg->n_critic_layers, 0, RG_DDPG_MAX_LAYERS},
-                    {"capacity", cfg->capacity, 2, RG_DDPG_MAX_CAPACITY}, {"minibatch", cfg->minibatch, 1, RG_DDPG_MAX_MINIBATCH}};
-  for (const I &f : ints)
-    if (f.v < f.lo || f.v > f.hi) {
-      snprintf(msg, sizeof(msg), "config.%s: %d outside [%d, %d]", f.name, f.v, f.lo, f.hi);
-      err = msg;
-      return false;
-    }
+  const IntField ints[] = {{"obs_dim", cfg->obs_dim, 1, RG_DDPG_MAX_OBS}, {"act_dim", cfg->act_dim, 1, RG_DDPG_MAX_ACT}, {"window", cfg->window, 1, RG_DDPG_MAX_WINDOW},
+                           {"n_actor_layers", cfg->n_actor_layers, 0, RG_DDPG_MAX_LAYERS}, {"n_critic_layers", cfg->n_critic_layers, 0, RG_DDPG_MAX_LAYERS},
+                           {"capacity", cfg->capacity, 2, RG_DDPG_MAX_CAPACITY}, {"minibatch", cfg->minibatch, 1, RG_DDPG_MAX_MINIBATCH}};
+  if (!check_abi("config.", cfg->abi_version, RG_DDPG_ABI_VERSION, err) || !check_ints("config.", ints, err)) return false;
   if (cfg->window * cfg->obs_dim > RG_DDPG_MAX_INPUT) {
+    char msg[200];
     snprintf(msg, sizeof(msg), "config.window: window * obs_dim = %d above %d", cfg->window * cfg->obs_dim, RG_DDPG_MAX_INPUT);
     err = msg;
     return false;
   }
-  for (int net = 0; net < 2; net++) {
-    const char *name = net ? "critic_layers" : "actor_layers";
-    const int32_t *w = net ? cfg->critic_layers : cfg->actor_layers;
-    const int n = net ? cfg->n_critic_layers : cfg->n_actor_layers;
-    for (int k = 0; k < RG_DDPG_MAX_LAYERS; k++) {
-      if (k < n && (w[k] < 1 || w[k] > RG_DDPG_MAX_WIDTH)) {
-        snprintf(msg, sizeof(msg), "config.%s[%d]: %d outside [1, %d]", name, k, w[k], RG_DDPG_MAX_WIDTH);
-        err = msg;
-        return false;
-      }
-      if (k >= n && w[k] != 0) {
-        snprintf(msg, sizeof(msg), "config.%s[%d]: %d must be 0 past the %d layers in use", name, k, w[k], n);
-        err = msg;
-        return false;
-      }
-    }
-  }
-  // kind 0: >= 0; 1: in [0, 1); 2: > 0; 3: in [0, 1]; 4: in (0, 1]; 5: finite
-  struct F { const char *name; double v; int kind; };
-  const F fields[] = {{"gamma", cfg->gamma, 3}, {"tau", cfg->tau, 4}, {"actor_lr", cfg->actor_lr, 0}, {"critic_lr", cfg->critic_lr, 0},
-                      {"beta1", cfg->beta1, 1}, {"beta2", cfg->beta2, 1}, {"adam_eps", cfg->adam_eps, 2}, {"clipnorm", cfg->clipnorm, 0},
-                      {"ou_theta", cfg->ou_theta, 0}, {"ou_mu", cfg->ou_mu, 5}, {"ou_sigma", cfg->ou_sigma, 0}, {"ou_dt", cfg->ou_dt, 2}};
-  const char *want[] = {">= 0", "in [0, 1)", "> 0", "in [0, 1]", "in (0, 1]", "finite"};
-  for (const F &f : fields) {
-    bool ok = std::isfinite(f.v);
-    if (ok && f.kind != 5) ok = f.v >= 0;
-    if (ok && f.kind == 1) ok = f.v < 1;
-    if (ok && (f.kind == 2 || f.kind == 4)) ok = f.v > 0;
-    if (ok && (f.kind == 3 || f.kind == 4)) ok = f.v <= 1;
-    if (!ok) {
-      snprintf(msg, sizeof(msg), "config.%s: %g must be finite%s%s", f.name, f.v, f.kind == 5 ? "" : " and ", f.kind == 5 ? "" : want[f.kind]);
-      err = msg;
-      return false;
-    }
-  }
-  return true;
+  const RealField reals[] = {{"gamma", cfg->gamma, kUnit}, {"tau", cfg->tau, kUnitPositive}, {"actor_lr", cfg->actor_lr, kNonNegative},
+                             {"critic_lr", cfg->critic_lr, kNonNegative}, {"beta1", cfg->beta1, kBelowOne}, {"beta2", cfg->beta2, kBelowOne},
+                             {"adam_eps", cfg->adam_eps, kPositive}, {"clipnorm", cfg->clipnorm, kNonNegative}, {"ou_theta", cfg->ou_theta, kNonNegative},
+                             {"ou_mu", cfg->ou_mu, kFinite}, {"ou_sigma", cfg->ou_sigma, kNonNegative}, {"ou_dt", cfg->ou_dt, kPositive}};
+  return check_widths("config.", "actor_layers", cfg->actor_layers, cfg->n_actor_layers, RG_DDPG_MAX_LAYERS, RG_DDPG_MAX_WIDTH, err) &&
+         check_widths("config.", "critic_layers", cfg->critic_layers, cfg->n_critic_layers, RG_DDPG_MAX_LAYERS, RG_DDPG_MAX_WIDTH, err) &&
+         check_reals("config.", reals, err);
 }
 
 void fill_layout(const rg_ddpg_config *cfg, rg_ddpg_layout &L) {
   std::memset(&L, 0, sizeof(L));
   const int in_s = cfg->window * cfg->obs_dim;
-  for (int net = 0; net < 2; net++) {
-    const int32_t *widths = net ? cfg->critic_layers : cfg->actor_layers;
-    const int nh = net ? cfg->n_critic_layers : cfg->n_actor_layers;
-    int32_t *in = net ? L.critic_in : L.actor_in, *out = net ? L.critic_out : L.actor_out;
-    int32_t *w = net ? L.critic_w : L.actor_w, *b = net ? L.critic_b : L.actor_b;
-    int off = 0, prev = net ? cfg->act_dim + in_s : in_s;
-    for (int l = 0; l <= nh; l++) {
-      const int width = l < nh ? widths[l] : (net ? 1 : cfg->act_dim);
-      in[l] = prev; out[l] = width;
-      w[l] = off; off += prev * width;
-      b[l] = off; off += width;
-      prev = width;
-    }
-    if (net) { L.n_critic = nh + 1; L.critic_count = off; }
-    else { L.n_actor = nh + 1; L.actor_count = off; }
-  }
+  L.n_actor = cfg->n_actor_layers + 1;
+  L.actor_count = layer_layout(in_s, cfg->actor_layers, cfg->n_actor_layers, cfg->act_dim, L.actor_in, L.actor_out, L.actor_w, L.actor_b);
+  L.n_critic = cfg->n_critic_layers + 1;
+  L.critic_count = layer_layout(cfg->act_dim + in_s, cfg->critic_layers, cfg->n_critic_layers, 1, L.critic_in, L.critic_out, L.critic_w, L.critic_b);
 }
 
 void fill_net(const rg_ddpg_layout &L, int net, Net &nd) {
@@ -789,28 +566,10 @@ void fill_net(const rg_ddpg_layout &L, int net, Net &nd) {
   for (int l = 0; l < nd.n; l++) nd.asum += nd.out[l];
 }
 
-int hip_fail(rg_ddpg_handle *h, const char *what, hipError_t e) {
-  h->err = std::string(what) + ": " + hipGetErrorString(e);
-  return RG_DDPG_ERR_HIP;
-}
-
-int no_device(rg_ddpg_handle *h) {
-  h->err = "host-only handle (RG_DDPG_DEVICE_NONE): the arguments are valid, there is no device to run on";
-  return RG_DDPG_ERR_NO_DEVICE;
-}
-
-int launch_status(rg_ddpg_handle *h, const char *what) {
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? hip_fail(h, what, e) : RG_DDPG_OK;
-}
-
-int null_arg(rg_ddpg_handle *h, const char *call, const char *name) {
-  h->err = std::string(call) + ": null " + name;
-  return RG_DDPG_ERR_INVALID;
-}
-
-#define RG_NEED(call, ptr, name) \
-  do { if (!(ptr)) return null_arg(h, call, name); } while (0)
+int hip_fail(rg_ddpg_handle *h, const char *what, hipError_t e) { return hip_fail(h, RG_DDPG_ERR_HIP, what, e); }
+int no_device(rg_ddpg_handle *h) { return no_device(h, RG_DDPG_ERR_NO_DEVICE, "RG_DDPG"); }
+int launch_status(rg_ddpg_handle *h, const char *what) { return launch_status(h, RG_DDPG_ERR_HIP, what); }
+int null_arg(rg_ddpg_handle *h, const char *call, const char *name) { return null_arg(h, RG_DDPG_ERR_INVALID, call, name); }
 
 int check_ring(rg_ddpg_handle *h, const char *call, const rg_ddpg_ring *ring, bool obs, bool action, bool reward, bool done) {
   RG_NEED(call, ring, "ring");
@@ -823,9 +582,6 @@ int check_ring(rg_ddpg_handle *h, const char *call, const rg_ddpg_ring *ring, bo
 }
 
 RingDev ring_dev(const rg_ddpg_ring *r) { return RingDev{r->obs, r->action, r->reward, (int *)r->done, (long long *)r->state}; }
-
-template <typename T>
-T *ws_at(void *workspace, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(workspace) + off); }
 
 unsigned blocks_of(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 

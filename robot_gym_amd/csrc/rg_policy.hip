@@ -1,5 +1,8 @@
 // rg_policy.hip -- the acting and collecting side of the PPO agent of include/rg_policy.h.  Its own translation unit of
-// librg_mpc.so; it shares no device code with the others and rg_mpc.hip does not include it.
+// librg_mpc.so.  The noise stream, the normaliser's arithmetic, the workgroup sum and the layer descriptor are those of
+// rg_agent_dev.inc, which the agents' update files include too, and the host helpers those of rg_agent_host.h; rg_mpc.hip
+// includes neither, so the source hash behind profiles/ is unaffected.  The act kernel's neuron (8 samples wide, where the
+// shared layer is 16) stays here.
 //
 // rg_policy_act_kernel: kTile robots per workgroup of 512 threads.  Threads 0..255 (waves 0..3) run the policy network,
 // threads 256..511 (waves 4..7) the value network: every branch on the network is uniform over a wave, and both halves meet
@@ -23,8 +26,11 @@
 #include <cstring>
 #include <string>
 #include "../../include/rg_policy.h"
+#include "rg_agent_host.h"
 
 #pragma clang fp contract(off)
+
+#include "rg_agent_dev.inc"
 
 namespace {
 
@@ -33,7 +39,7 @@ constexpr int kMaxW = RG_POLICY_MAX_WIDTH;
 constexpr int kMaxAct = RG_POLICY_MAX_ACT;
 constexpr int kHalf = 256;
 constexpr int kActThreads = 2 * kHalf;
-constexpr int kRed = 256;          // threads of a record / returns workgroup
+constexpr int kRed = kAgentThreads;   // threads of a record / returns workgroup: block_sum's four waves
 constexpr int kMaxGroups = 256;    // workgroups per column of rg_policy_record
 constexpr int kCols = RG_POLICY_NORM_COLS;
 constexpr int kRewardCol = RG_POLICY_NORM_REWARD;
@@ -43,48 +49,12 @@ static_assert(kTile == 8, "the act kernel reads the activations of an input as t
 static_assert(kTile * RG_POLICY_MAX_OBS <= kActThreads && kTile * kMaxAct <= 64, "act kernel thread maps");
 static_assert(RG_POLICY_NORM_ROWS == 3 * kCols && kRewardCol == RG_POLICY_MAX_OBS, "norm_state layout");
 
-struct NetDesc {
-  int n;                       // layers, the head included
-  int in[4], out[4], w[4], b[4];
-};
-
 struct ActDev {
   int B, obs_dim, act_dim, logstd_off;
   double obs_clip;
   unsigned long long seed;
   NetDesc pol, val;
 };
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-
-__device__ __forceinline__ unsigned long long noise_hash(unsigned long long seed, unsigned long long key, unsigned long long counter,
-                                                         unsigned long long axis, unsigned long long draw) {
-  unsigned long long h = seed;
-  h = mix64((h ^ key) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ counter) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ axis) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ draw) + 0x9E3779B97F4A7C15ull);
-  return h;
-}
-
-// the standard normal of (seed, key, counter, axis): rg_policy.h, Noise
-__device__ __forceinline__ float noise_eps(unsigned long long seed, unsigned long long key, unsigned long long counter, unsigned long long axis) {
-  const double u1 = (double)((noise_hash(seed, key, counter, axis, 0) >> 11) + 1ull) * 0x1.0p-53;
-  const double u2 = (double)(noise_hash(seed, key, counter, axis, 1) >> 11) * 0x1.0p-53;
-  return (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
-}
-
-// 1 / the divisor of StreamingNormalize.transform is never formed: the value is divided, as the reference divides it
-__device__ __forceinline__ double norm_scale(double count, double var_sum) {
-  return count > 1.0 ? sqrt(var_sum / (count - 1.0) + 1e-4) + 1e-8 : 1.0;
-}
-
-__device__ __forceinline__ double clip_sym(double v, double c) { return c > 0.0 ? (v < -c ? -c : (v > c ? c : v)) : v; }
 
 __global__ void __launch_bounds__(kActThreads) rg_policy_act_kernel(const ActDev *__restrict__ d, const float *__restrict__ obs,
                                                                     const double *__restrict__ norm, const float *__restrict__ pp,
@@ -191,17 +161,6 @@ __global__ void __launch_bounds__(kActThreads) rg_policy_act_kernel(const ActDev
 struct RecCfg {
   int B, obs_dim, G;
 };
-
-// the sum of v over the workgroup, the same in every thread: a shuffle tree in each wave, the four waves in order.
-// Every thread of the workgroup calls it.
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off);
-  __syncthreads();   // sh may still be read from the call before
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
 
 // part[col][g][kParts]: the sum over g of entry k, thread g holding workgroup g's partial
 __device__ __forceinline__ double finish_sum(const double *__restrict__ part, int col, int G, int k, double *sh) {
@@ -315,17 +274,6 @@ __global__ void __launch_bounds__(kRed) rg_policy_returns_kernel(const RetCfg c,
   }
 }
 
-struct DeviceScope {
-  int prev = -1;
-  bool switched = false;
-  hipError_t err = hipSuccess;
-  explicit DeviceScope(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess && prev >= 0; }
-  }
-  ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
-};
-
 thread_local std::string g_create_err;
 
 }  // namespace
@@ -343,85 +291,22 @@ struct rg_policy_handle {
 namespace {
 
 bool validate(const rg_policy_config *cfg, std::string &err) {
-  char msg[200];
-  if (cfg->abi_version != RG_POLICY_ABI_VERSION) {
-    snprintf(msg, sizeof(msg), "config.abi_version: %d, this library is version %d", cfg->abi_version, RG_POLICY_ABI_VERSION);
-    err = msg;
-    return false;
-  }
-  if (cfg->reserved0 != 0) { err = "config.reserved0: must be 0"; return false; }
-  struct I { const char *name; int v, lo, hi; };
-  const I ints[] = {{"obs_dim", cfg->obs_dim, 1, RG_POLICY_MAX_OBS}, {"act_dim", cfg->act_dim, 1, RG_POLICY_MAX_ACT},
-                    {"n_policy_layers", cfg->n_policy_layers, 0, RG_POLICY_MAX_LAYERS}, {"n_value_layers", cfg->n_value_layers, 0, RG_POLICY_MAX_LAYERS}};
-  for (const I &f : ints)
-    if (f.v < f.lo || f.v > f.hi) {
-      snprintf(msg, sizeof(msg), "config.%s: %d outside [%d, %d]", f.name, f.v, f.lo, f.hi);
-      err = msg;
-      return false;
-    }
-  for (int net = 0; net < 2; net++) {
-    const char *name = net ? "value_layers" : "policy_layers";
-    const int32_t *w = net ? cfg->value_layers : cfg->policy_layers;
-    const int n = net ? cfg->n_value_layers : cfg->n_policy_layers;
-    for (int k = 0; k < RG_POLICY_MAX_LAYERS; k++) {
-      if (k < n && (w[k] < 1 || w[k] > RG_POLICY_MAX_WIDTH)) {
-        snprintf(msg, sizeof(msg), "config.%s[%d]: %d outside [1, %d]", name, k, w[k], RG_POLICY_MAX_WIDTH);
-        err = msg;
-        return false;
-      }
-      if (k >= n && w[k] != 0) {
-        snprintf(msg, sizeof(msg), "config.%s[%d]: %d must be 0 past the %d layers in use", name, k, w[k], n);
-        err = msg;
-        return false;
-      }
-    }
-  }
-  struct F { const char *name; double v; bool unit; };
-  const F fields[] = {{"obs_clip", cfg->obs_clip, false}, {"reward_clip", cfg->reward_clip, false}, {"discount", cfg->discount, true},
-                      {"gae_lambda", cfg->gae_lambda, true}};
-  for (const F &f : fields)
-    if (!std::isfinite(f.v) || f.v < 0 || (f.unit && f.v > 1)) {
-      snprintf(msg, sizeof(msg), "config.%s: %g must be finite and %s", f.name, f.v, f.unit ? "in [0, 1]" : ">= 0");
-      err = msg;
-      return false;
-    }
-  return true;
+  const RealField reals[] = {{"reward_clip", cfg->reward_clip, kNonNegative}, {"discount", cfg->discount, kUnit}, {"gae_lambda", cfg->gae_lambda, kUnit}};
+  return check_policy_config("config.", cfg, err) && check_reals("config.", reals, err);
 }
 
 void fill_layout(const rg_policy_config *cfg, rg_policy_layout &L) {
   std::memset(&L, 0, sizeof(L));
-  for (int net = 0; net < 2; net++) {
-    const int32_t *widths = net ? cfg->value_layers : cfg->policy_layers;
-    const int nh = net ? cfg->n_value_layers : cfg->n_policy_layers;
-    int32_t *in = net ? L.value_in : L.policy_in, *out = net ? L.value_out : L.policy_out;
-    int32_t *w = net ? L.value_w : L.policy_w, *b = net ? L.value_b : L.policy_b;
-    int off = 0, prev = cfg->obs_dim;
-    for (int l = 0; l <= nh; l++) {
-      const int width = l < nh ? widths[l] : (net ? 1 : cfg->act_dim);
-      in[l] = prev; out[l] = width;
-      w[l] = off; off += prev * width;
-      b[l] = off; off += width;
-      prev = width;
-    }
-    if (net) { L.n_value = nh + 1; L.value_count = off; }
-    else { L.n_policy = nh + 1; L.logstd_offset = off; L.policy_count = off + cfg->act_dim; }
-  }
+  L.n_policy = cfg->n_policy_layers + 1;
+  L.logstd_offset = layer_layout(cfg->obs_dim, cfg->policy_layers, cfg->n_policy_layers, cfg->act_dim, L.policy_in, L.policy_out, L.policy_w, L.policy_b);
+  L.policy_count = L.logstd_offset + cfg->act_dim;
+  L.n_value = cfg->n_value_layers + 1;
+  L.value_count = layer_layout(cfg->obs_dim, cfg->value_layers, cfg->n_value_layers, 1, L.value_in, L.value_out, L.value_w, L.value_b);
 }
 
-int hip_fail(rg_policy_handle *h, const char *what, hipError_t e) {
-  h->err = std::string(what) + ": " + hipGetErrorString(e);
-  return RG_POLICY_ERR_HIP;
-}
-
-int no_device(rg_policy_handle *h) {
-  h->err = "host-only handle (RG_POLICY_DEVICE_NONE): the arguments are valid, there is no device to run on";
-  return RG_POLICY_ERR_NO_DEVICE;
-}
-
-int launch_status(rg_policy_handle *h, const char *what) {
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? hip_fail(h, what, e) : RG_POLICY_OK;
-}
+int hip_fail(rg_policy_handle *h, const char *what, hipError_t e) { return hip_fail(h, RG_POLICY_ERR_HIP, what, e); }
+int no_device(rg_policy_handle *h) { return no_device(h, RG_POLICY_ERR_NO_DEVICE, "RG_POLICY"); }
+int launch_status(rg_policy_handle *h, const char *what) { return launch_status(h, RG_POLICY_ERR_HIP, what); }
 
 }  // namespace
 

@@ -1,6 +1,8 @@
-// rg_ppo.hip -- the PPO update of include/rg_ppo.h.  Its own translation unit of librg_mpc.so: it shares no device code with
-// the others (the neuron arithmetic and the observation transform of rg_policy.hip are restated here, line for line, so that
-// the forward pass gives rg_policy_act's mean to the bit).
+// rg_ppo.hip -- the PPO update of include/rg_ppo.h.  Its own translation unit of librg_mpc.so.  A layer's forward and backward
+// pass over a tile, the normaliser's arithmetic, the workgroup sums and the bodies of the transpose and slab-finish
+// kernels are those of rg_agent_dev.inc, which the acting side includes too (so the forward pass gives rg_policy_act's mean
+// to the bit from one text), and the host helpers those of rg_agent_host.h; rg_mpc.hip includes neither, so the source hash
+// behind profiles/ is unaffected.
 //
 // Sweeps (rg_ppo_policy_forward_kernel, rg_ppo_policy_backward_kernel, rg_ppo_value_backward_kernel): G workgroups of 256
 // threads, workgroup g walks the tiles g, g + G, ... of kTile samples.  LDS (dynamic): the tile's activations of every layer
@@ -22,13 +24,16 @@
 #include <cstring>
 #include <string>
 #include "../../include/rg_ppo.h"
+#include "rg_agent_host.h"
 
 #pragma clang fp contract(off)
+
+#include "rg_agent_dev.inc"
 
 namespace {
 
 constexpr int kTile = RG_PPO_TILE;
-constexpr int kThreads = 256;
+constexpr int kThreads = kAgentThreads;
 constexpr int kMaxGroups = RG_PPO_MAX_GROUPS;
 constexpr int kMaxAct = RG_POLICY_MAX_ACT;
 constexpr int kCols = RG_POLICY_NORM_COLS;
@@ -39,14 +44,9 @@ constexpr int kMaxLds = (RG_POLICY_MAX_OBS + RG_POLICY_MAX_LAYERS * RG_POLICY_MA
 static_assert(kMaxLds == 86272 && kMaxLds <= 160 * 1024, "a sweep's tile fits a compute unit's LDS at every configuration");
 constexpr int kScal = 8;             // workspace scalars: n (clamped), m, sd, n
 
-static_assert(kTile == 16, "the sweeps read a neuron's tile as four float4");
+static_assert(kTile == kAgentTile, "the sweeps run the shared layers, whose tile is four float4");
 static_assert(RG_POLICY_MAX_WIDTH <= kThreads && RG_POLICY_MAX_OBS <= kThreads, "one neuron per thread");
 static_assert(kMaxGroups <= kThreads, "finish_sum holds one workgroup's partial per thread");
-
-struct NetDesc {
-  int n;                       // layers, the head included
-  int in[4], out[4], w[4], b[4];
-};
 
 struct SweepCfg {
   int T, B, N, G, ntiles;
@@ -68,29 +68,6 @@ struct Desc {                  // in the workspace: what a sweep reads of its ca
   double *scal, *klr, *kls, *part;   // the workspace's regions
   float *wt, *slabs;
 };
-
-__device__ __forceinline__ double norm_scale(double count, double var_sum) {
-  return count > 1.0 ? sqrt(var_sum / (count - 1.0) + 1e-4) + 1e-8 : 1.0;
-}
-
-__device__ __forceinline__ double clip_sym(double v, double c) { return c > 0.0 ? (v < -c ? -c : (v > c ? c : v)) : v; }
-
-// the sum of v over the workgroup of 256, the same in every thread: a shuffle tree in each wave, the four waves in order
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off);
-  __syncthreads();   // sh may still be read from the call before
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
-// sum over idx = 0 .. n-1 of p[idx * stride]: thread t takes t, t + 256, ... in order, then block_sum
-__device__ __forceinline__ double strided_sum(const double *__restrict__ p, int n, int stride, double *sh) {
-  double s = 0.0;
-  for (int idx = threadIdx.x; idx < n; idx += kThreads) s = s + p[(size_t)idx * stride];
-  return block_sum(s, sh);
-}
 
 // ---- prepare --------------------------------------------------------------------------------------------------------
 
@@ -135,17 +112,7 @@ __global__ void __launch_bounds__(kThreads) rg_ppo_prepare_finish_kernel(const i
 // ---- the transposed copy of the weights -------------------------------------------------------------------------------
 
 __global__ void __launch_bounds__(kThreads) rg_ppo_transpose_kernel(const NetDesc nd, const float *__restrict__ P, float *__restrict__ Wt) {
-  const int e = blockIdx.x * kThreads + (int)threadIdx.x;
-#pragma unroll
-  for (int l = 0; l < 4; l++) {
-    if (l < nd.n) {
-      const int k = e - nd.w[l];
-      if (k >= 0 && k < nd.in[l] * nd.out[l]) {
-        const int i = k / nd.out[l], j = k - i * nd.out[l];
-        Wt[nd.w[l] + j * nd.in[l] + i] = P[e];
-      }
-    }
-  }
+  transpose_element(nd, P, Wt, blockIdx.x * kThreads + (int)threadIdx.x);
 }
 
 // the two descriptors and the rollout's pointers into the workspace, where the sweeps index them (dynamic indexing of a by-value kernel argument
@@ -168,108 +135,6 @@ __global__ void rg_ppo_describe_kernel(const SweepCfg pol, const SweepCfg val, c
 }
 
 // ---- the sweeps -------------------------------------------------------------------------------------------------------
-
-// y[j][s] = act(sum_i W[i][j] x[i][s] + b[j]): rg_policy_act_kernel's neuron, kTile samples wide.  mode 0 relu, 1 tanhf, 2 linear
-__device__ __forceinline__ void forward_layer(const float *__restrict__ P, const int nin, const int nout, const int woff, const int boff,
-                                              const float *x, float *y, const int mode) {
-  const int j = threadIdx.x;
-  if (j < nout) {
-    const float *__restrict__ W = P + woff + j;
-    float acc[kTile];
-#pragma unroll
-    for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
-#pragma unroll 4
-    for (int i = 0; i < nin; i++) {
-      const float w = W[(size_t)i * nout];
-      const float4 xa = *reinterpret_cast<const float4 *>(x + i * kTile);
-      const float4 xb = *reinterpret_cast<const float4 *>(x + i * kTile + 4);
-      const float4 xc = *reinterpret_cast<const float4 *>(x + i * kTile + 8);
-      const float4 xd = *reinterpret_cast<const float4 *>(x + i * kTile + 12);
-      acc[0] = __builtin_fmaf(w, xa.x, acc[0]); acc[1] = __builtin_fmaf(w, xa.y, acc[1]);
-      acc[2] = __builtin_fmaf(w, xa.z, acc[2]); acc[3] = __builtin_fmaf(w, xa.w, acc[3]);
-      acc[4] = __builtin_fmaf(w, xb.x, acc[4]); acc[5] = __builtin_fmaf(w, xb.y, acc[5]);
-      acc[6] = __builtin_fmaf(w, xb.z, acc[6]); acc[7] = __builtin_fmaf(w, xb.w, acc[7]);
-      acc[8] = __builtin_fmaf(w, xc.x, acc[8]); acc[9] = __builtin_fmaf(w, xc.y, acc[9]);
-      acc[10] = __builtin_fmaf(w, xc.z, acc[10]); acc[11] = __builtin_fmaf(w, xc.w, acc[11]);
-      acc[12] = __builtin_fmaf(w, xd.x, acc[12]); acc[13] = __builtin_fmaf(w, xd.y, acc[13]);
-      acc[14] = __builtin_fmaf(w, xd.z, acc[14]); acc[15] = __builtin_fmaf(w, xd.w, acc[15]);
-    }
-    const float bias = P[boff + j];
-    float *yj = y + j * kTile;
-#pragma unroll
-    for (int r = 0; r < kTile; r++) {
-      float v = acc[r] + bias;
-      if (mode == 0) v = v > 0.0f ? v : 0.0f;
-      else if (mode == 1) v = tanhf(v);
-      yj[r] = v;
-    }
-  }
-}
-
-// slab[W[i][j]] += sum_s x[i][s] delta[j][s], slab[b[j]] += sum_s delta[j][s]
-__device__ __forceinline__ void backward_weights(float *__restrict__ slab, const int nin, const int nout, const int woff, const int boff,
-                                                 const float *x, const float *dl) {
-  const int j = threadIdx.x;
-  if (j < nout) {
-    float d[kTile];
-#pragma unroll
-    for (int q = 0; q < kTile / 4; q++) {
-      const float4 v = *reinterpret_cast<const float4 *>(dl + j * kTile + 4 * q);
-      d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w;
-    }
-    float bs = d[0];
-#pragma unroll
-    for (int r = 1; r < kTile; r++) bs = bs + d[r];
-    slab[boff + j] = slab[boff + j] + bs;
-    float *__restrict__ sw = slab + woff + j;
-#pragma unroll 4
-    for (int i = 0; i < nin; i++) {
-      const float4 xa = *reinterpret_cast<const float4 *>(x + i * kTile);
-      const float4 xb = *reinterpret_cast<const float4 *>(x + i * kTile + 4);
-      const float4 xc = *reinterpret_cast<const float4 *>(x + i * kTile + 8);
-      const float4 xd = *reinterpret_cast<const float4 *>(x + i * kTile + 12);
-      float v = xa.x * d[0];
-      v = __builtin_fmaf(xa.y, d[1], v); v = __builtin_fmaf(xa.z, d[2], v); v = __builtin_fmaf(xa.w, d[3], v);
-      v = __builtin_fmaf(xb.x, d[4], v); v = __builtin_fmaf(xb.y, d[5], v); v = __builtin_fmaf(xb.z, d[6], v); v = __builtin_fmaf(xb.w, d[7], v);
-      v = __builtin_fmaf(xc.x, d[8], v); v = __builtin_fmaf(xc.y, d[9], v); v = __builtin_fmaf(xc.z, d[10], v); v = __builtin_fmaf(xc.w, d[11], v);
-      v = __builtin_fmaf(xd.x, d[12], v); v = __builtin_fmaf(xd.y, d[13], v); v = __builtin_fmaf(xd.z, d[14], v); v = __builtin_fmaf(xd.w, d[15], v);
-      const size_t o = (size_t)i * nout;
-      sw[o] = sw[o] + v;
-    }
-  }
-}
-
-// dn[i][s] = x[i][s] > 0 ? sum_j Wt[j][i] dl[j][s] : 0
-__device__ __forceinline__ void backward_inputs(const float *__restrict__ Wt, const int nin, const int nout, const int woff, const float *x,
-                                                const float *dl, float *dn) {
-  const int i = threadIdx.x;
-  if (i < nin) {
-    const float *__restrict__ W = Wt + woff + i;
-    float acc[kTile];
-#pragma unroll
-    for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
-#pragma unroll 4
-    for (int j = 0; j < nout; j++) {
-      const float w = W[(size_t)j * nin];
-      const float4 da = *reinterpret_cast<const float4 *>(dl + j * kTile);
-      const float4 db = *reinterpret_cast<const float4 *>(dl + j * kTile + 4);
-      const float4 dc = *reinterpret_cast<const float4 *>(dl + j * kTile + 8);
-      const float4 dd = *reinterpret_cast<const float4 *>(dl + j * kTile + 12);
-      acc[0] = __builtin_fmaf(w, da.x, acc[0]); acc[1] = __builtin_fmaf(w, da.y, acc[1]);
-      acc[2] = __builtin_fmaf(w, da.z, acc[2]); acc[3] = __builtin_fmaf(w, da.w, acc[3]);
-      acc[4] = __builtin_fmaf(w, db.x, acc[4]); acc[5] = __builtin_fmaf(w, db.y, acc[5]);
-      acc[6] = __builtin_fmaf(w, db.z, acc[6]); acc[7] = __builtin_fmaf(w, db.w, acc[7]);
-      acc[8] = __builtin_fmaf(w, dc.x, acc[8]); acc[9] = __builtin_fmaf(w, dc.y, acc[9]);
-      acc[10] = __builtin_fmaf(w, dc.z, acc[10]); acc[11] = __builtin_fmaf(w, dc.w, acc[11]);
-      acc[12] = __builtin_fmaf(w, dd.x, acc[12]); acc[13] = __builtin_fmaf(w, dd.y, acc[13]);
-      acc[14] = __builtin_fmaf(w, dd.z, acc[14]); acc[15] = __builtin_fmaf(w, dd.w, acc[15]);
-    }
-    const float *xi = x + i * kTile;
-    float *di = dn + i * kTile;
-#pragma unroll
-    for (int r = 0; r < kTile; r++) di[r] = xi[r] > 0.0f ? acc[r] : 0.0f;
-  }
-}
 
 template <bool kPolicy, bool kBackward>
 __device__ __forceinline__ void sweep(const Desc *__restrict__ dp, const float *__restrict__ P) {
@@ -426,9 +291,7 @@ __global__ void __launch_bounds__(kThreads) rg_ppo_grad_finish_kernel(const int 
                                                                       float *__restrict__ grad) {
   const int e = blockIdx.x * kThreads + (int)threadIdx.x;
   if (e >= n) return;
-  double s = 0.0;
-  for (int g = 0; g < G; g++) s = s + (double)slabs[(size_t)g * count + e];
-  grad[e] = (float)s;
+  grad[e] = slab_sum(slabs, count, G, e);
 }
 
 struct LossCfg {
@@ -516,20 +379,7 @@ __global__ void __launch_bounds__(kThreads) rg_ppo_penalty_kernel(const int B, c
   }
 }
 
-struct DeviceScope {
-  int prev = -1;
-  bool switched = false;
-  hipError_t err = hipSuccess;
-  explicit DeviceScope(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess && prev >= 0; }
-  }
-  ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
-};
-
 thread_local std::string g_create_err;
-
-size_t round8(size_t n) { return (n + 7) & ~(size_t)7; }
 
 }  // namespace
 
@@ -546,121 +396,21 @@ struct rg_ppo_handle {
 
 namespace {
 
-bool validate_policy(const rg_policy_config *cfg, std::string &err) {
-  char msg[200];
-  if (cfg->abi_version != RG_POLICY_ABI_VERSION) {
-    snprintf(msg, sizeof(msg), "policy_cfg.abi_version: %d, this library is version %d", cfg->abi_version, RG_POLICY_ABI_VERSION);
-    err = msg;
-    return false;
-  }
-  if (cfg->reserved0 != 0) { err = "policy_cfg.reserved0: must be 0"; return false; }
-  struct I { const char *name; int v, lo, hi; };
-  const I ints[] = {{"obs_dim", cfg->obs_dim, 1, RG_POLICY_MAX_OBS}, {"act_dim", cfg->act_dim, 1, RG_POLICY_MAX_ACT},
-                    {"n_policy_layers", cfg->n_policy_layers, 0, RG_POLICY_MAX_LAYERS}, {"n_value_layers", cfg->n_value_layers, 0, RG_POLICY_MAX_LAYERS}};
-  for (const I &f : ints)
-    if (f.v < f.lo || f.v > f.hi) {
-      snprintf(msg, sizeof(msg), "policy_cfg.%s: %d outside [%d, %d]", f.name, f.v, f.lo, f.hi);
-      err = msg;
-      return false;
-    }
-  for (int net = 0; net < 2; net++) {
-    const char *name = net ? "value_layers" : "policy_layers";
-    const int32_t *w = net ? cfg->value_layers : cfg->policy_layers;
-    const int n = net ? cfg->n_value_layers : cfg->n_policy_layers;
-    for (int k = 0; k < RG_POLICY_MAX_LAYERS; k++) {
-      if (k < n && (w[k] < 1 || w[k] > RG_POLICY_MAX_WIDTH)) {
-        snprintf(msg, sizeof(msg), "policy_cfg.%s[%d]: %d outside [1, %d]", name, k, w[k], RG_POLICY_MAX_WIDTH);
-        err = msg;
-        return false;
-      }
-      if (k >= n && w[k] != 0) {
-        snprintf(msg, sizeof(msg), "policy_cfg.%s[%d]: %d must be 0 past the %d layers in use", name, k, w[k], n);
-        err = msg;
-        return false;
-      }
-    }
-  }
-  if (!std::isfinite(cfg->obs_clip) || cfg->obs_clip < 0) {
-    snprintf(msg, sizeof(msg), "policy_cfg.obs_clip: %g must be finite and >= 0", cfg->obs_clip);
-    err = msg;
-    return false;
-  }
-  return true;
-}
-
 bool validate_ppo(const rg_ppo_config *cfg, std::string &err) {
-  char msg[200];
-  if (cfg->abi_version != RG_PPO_ABI_VERSION) {
-    snprintf(msg, sizeof(msg), "ppo_cfg.abi_version: %d, this library is version %d", cfg->abi_version, RG_PPO_ABI_VERSION);
-    err = msg;
-    return false;
-  }
-  struct I { const char *name; int v, lo, hi; };
-  const I ints[] = {{"epochs_policy", cfg->epochs_policy, 0, RG_PPO_MAX_EPOCHS}, {"epochs_value", cfg->epochs_value, 0, RG_PPO_MAX_EPOCHS},
-                    {"conv_logpdf", cfg->conv_logpdf, RG_PPO_LOGPDF_EXACT, RG_PPO_LOGPDF_REFERENCE}};
-  for (const I &f : ints)
-    if (f.v < f.lo || f.v > f.hi) {
-      snprintf(msg, sizeof(msg), "ppo_cfg.%s: %d outside [%d, %d]", f.name, f.v, f.lo, f.hi);
-      err = msg;
-      return false;
-    }
-  struct F { const char *name; double v; int kind; };   // kind 0: >= 0; 1: in [0, 1); 2: > 0
-  const F fields[] = {{"policy_lr", cfg->policy_lr, 0}, {"value_lr", cfg->value_lr, 0}, {"beta1", cfg->beta1, 1}, {"beta2", cfg->beta2, 1},
-                      {"adam_eps", cfg->adam_eps, 2}, {"kl_target", cfg->kl_target, 2}, {"kl_cutoff_factor", cfg->kl_cutoff_factor, 0},
-                      {"kl_cutoff_coef", cfg->kl_cutoff_coef, 0}};
-  for (const F &f : fields)
-    if (!std::isfinite(f.v) || f.v < 0 || (f.kind == 1 && f.v >= 1) || (f.kind == 2 && f.v <= 0)) {
-      snprintf(msg, sizeof(msg), "ppo_cfg.%s: %g must be finite and %s", f.name, f.v, f.kind == 0 ? ">= 0" : (f.kind == 1 ? "in [0, 1)" : "> 0"));
-      err = msg;
-      return false;
-    }
-  return true;
+  const IntField ints[] = {{"epochs_policy", cfg->epochs_policy, 0, RG_PPO_MAX_EPOCHS}, {"epochs_value", cfg->epochs_value, 0, RG_PPO_MAX_EPOCHS},
+                           {"conv_logpdf", cfg->conv_logpdf, RG_PPO_LOGPDF_EXACT, RG_PPO_LOGPDF_REFERENCE}};
+  const RealField reals[] = {{"policy_lr", cfg->policy_lr, kNonNegative}, {"value_lr", cfg->value_lr, kNonNegative}, {"beta1", cfg->beta1, kBelowOne},
+                             {"beta2", cfg->beta2, kBelowOne}, {"adam_eps", cfg->adam_eps, kPositive}, {"kl_target", cfg->kl_target, kPositive},
+                             {"kl_cutoff_factor", cfg->kl_cutoff_factor, kNonNegative}, {"kl_cutoff_coef", cfg->kl_cutoff_coef, kNonNegative}};
+  return check_abi("ppo_cfg.", cfg->abi_version, RG_PPO_ABI_VERSION, err) && check_ints("ppo_cfg.", ints, err) && check_reals("ppo_cfg.", reals, err);
 }
 
-// the layout rule of rg_policy.h for one network: W[in][out] then b[out] per layer, the head last
-void fill_net(const rg_policy_config *cfg, int net, NetDesc &nd, int &count) {
-  const int32_t *widths = net ? cfg->value_layers : cfg->policy_layers;
-  const int nh = net ? cfg->n_value_layers : cfg->n_policy_layers;
-  std::memset(&nd, 0, sizeof(nd));
-  int off = 0, prev = cfg->obs_dim;
-  for (int l = 0; l <= nh; l++) {
-    const int width = l < nh ? widths[l] : (net ? 1 : cfg->act_dim);
-    nd.in[l] = prev; nd.out[l] = width;
-    nd.w[l] = off; off += prev * width;
-    nd.b[l] = off; off += width;
-    prev = width;
-  }
-  nd.n = nh + 1;
-  count = off;
-}
-
-int hip_fail(rg_ppo_handle *h, const char *what, hipError_t e) {
-  h->err = std::string(what) + ": " + hipGetErrorString(e);
-  return RG_PPO_ERR_HIP;
-}
-
-int no_device(rg_ppo_handle *h) {
-  h->err = "host-only handle (RG_PPO_DEVICE_NONE): the arguments are valid, there is no device to run on";
-  return RG_PPO_ERR_NO_DEVICE;
-}
-
-int launch_status(rg_ppo_handle *h, const char *what) {
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? hip_fail(h, what, e) : RG_PPO_OK;
-}
-
-int null_arg(rg_ppo_handle *h, const char *call, const char *name) {
-  h->err = std::string(call) + ": null " + name;
-  return RG_PPO_ERR_INVALID;
-}
-
-#define RG_NEED(call, ptr, name) \
-  do { if (!(ptr)) return null_arg(h, call, name); } while (0)
+int hip_fail(rg_ppo_handle *h, const char *what, hipError_t e) { return hip_fail(h, RG_PPO_ERR_HIP, what, e); }
+int no_device(rg_ppo_handle *h) { return no_device(h, RG_PPO_ERR_NO_DEVICE, "RG_PPO"); }
+int launch_status(rg_ppo_handle *h, const char *what) { return launch_status(h, RG_PPO_ERR_HIP, what); }
+int null_arg(rg_ppo_handle *h, const char *call, const char *name) { return null_arg(h, RG_PPO_ERR_INVALID, call, name); }
 
 RoDev ro_dev(const rg_ppo_rollout *ro) { return RoDev{ro->obs, ro->action, ro->mean, ro->logstd, ro->adv, ro->ret, (const int *)ro->mask}; }
-
-template <typename T>
-T *ws_at(void *workspace, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(workspace) + off); }
 
 const double *penalty_of(const void *opt_state) { return reinterpret_cast<const double *>(static_cast<const char *>(opt_state) + 16); }
 
@@ -779,7 +529,7 @@ int rg_ppo_create(const rg_policy_config *policy_cfg, const rg_ppo_config *ppo_c
   *out = nullptr;
   char msg[128];
   std::string err;
-  if (!validate_policy(policy_cfg, err) || !validate_ppo(ppo_cfg, err)) { g_create_err = err; return RG_PPO_ERR_INVALID; }
+  if (!check_policy_config("policy_cfg.", policy_cfg, err) || !validate_ppo(ppo_cfg, err)) { g_create_err = err; return RG_PPO_ERR_INVALID; }
   if (T < 1 || T > RG_POLICY_MAX_T) {
     snprintf(msg, sizeof(msg), "T: %d outside [1, %d]", T, RG_POLICY_MAX_T);
     g_create_err = msg;
@@ -805,7 +555,9 @@ int rg_ppo_create(const rg_policy_config *policy_cfg, const rg_ppo_config *ppo_c
   if (h->GP > kMaxGroups) h->GP = kMaxGroups;
   for (int net = 0; net < 2; net++) {
     SweepCfg &c = net ? h->val : h->pol;
-    fill_net(policy_cfg, net, c.nd, c.count);
+    c.nd.n = (net ? policy_cfg->n_value_layers : policy_cfg->n_policy_layers) + 1;
+    c.count = layer_layout(policy_cfg->obs_dim, net ? policy_cfg->value_layers : policy_cfg->policy_layers, c.nd.n - 1, net ? 1 : policy_cfg->act_dim,
+                           c.nd.in, c.nd.out, c.nd.w, c.nd.b);
     c.T = T; c.B = B; c.N = h->N; c.G = h->G; c.ntiles = ntiles;
     c.obs_dim = policy_cfg->obs_dim; c.act_dim = policy_cfg->act_dim;
     c.logstd_off = c.count;

@@ -39,7 +39,7 @@ LOG_2PI = math.log(2.0 * math.pi)
 
 def policy_hash():
     h = hashlib.sha256()
-    for rel in ("robot_gym_amd/csrc/rg_policy.hip", "include/rg_policy.h"):
+    for rel in ("robot_gym_amd/csrc/rg_policy.hip", "robot_gym_amd/csrc/rg_agent_dev.inc", "robot_gym_amd/csrc/rg_agent_host.h", "include/rg_policy.h"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]
 
@@ -124,7 +124,7 @@ def main():
     result = dict(what="PPO agent kernels next to BatchedGoEnv.step, one process and run, us per call: act / record / returns (T = 32) alone, the "
                        "torch path of act alone, env.step alone (auto-reset, limits out of reach), and the collector's tick with the act kernel "
                        "and with the torch path (median of alternated repeats, [min, max] in spread).  `commit` is the commit the measured tree "
-                       "was based on; policy_source_sha256 is the hash of rg_policy.hip and rg_policy.h as measured",
+                       "was based on; policy_source_sha256 is the hash of rg_policy.hip, the two rg_agent_* files it includes and rg_policy.h as measured",
                   robot=args.robot, commit=commit, dirty=dirty, source_hash=bench.source_hash(), policy_source_sha256=policy_hash(),
                   device=torch.cuda.get_device_name(0), seconds_per_measurement=args.seconds, repeats=args.repeats, rows=rows)
     if args.out:

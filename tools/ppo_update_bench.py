@@ -38,12 +38,15 @@ def _hash(paths):
     return h.hexdigest()[:16]
 
 
+SHARED = ("robot_gym_amd/csrc/rg_agent_dev.inc", "robot_gym_amd/csrc/rg_agent_host.h")   # what the agents' files include
+
+
 def policy_hash():
-    return _hash(("robot_gym_amd/csrc/rg_policy.hip", "include/rg_policy.h"))
+    return _hash(("robot_gym_amd/csrc/rg_policy.hip",) + SHARED + ("include/rg_policy.h",))
 
 
 def ppo_hash():
-    return _hash(("robot_gym_amd/csrc/rg_ppo.hip", "include/rg_ppo.h"))
+    return _hash(("robot_gym_amd/csrc/rg_ppo.hip",) + SHARED + ("include/rg_ppo.h",))
 
 
 def _once(fn, restore):
