@@ -58,7 +58,8 @@
  *   x = (x + (theta * (mu - x)) * dt) + (sigma * sqrt(dt)) * eps, stored as float32; action = mean + x (float32); counter += 1.
  *   MEAN: action = mean; ou_state and the counter are left alone (both may be NULL).  The action is not clipped: the task clips it.
  * rg_ddpg_store: writes obs, action, reward, done of all B robots at slot head, zeroes the ou_state rows of the robots with
- *   done != 0 (keras-rl's reset_states), then head = (head + 1) mod C, count = min(count + 1, C).
+ *   done != 0 (keras-rl's reset_states), then head = (head + 1) mod C, count = min(count + 1, C).  A head outside [0, C) (a ring
+ *   state the caller spoilt) is first clamped to the nearest slot, 0 or C - 1, so that no write leaves the ring.
  * rg_ddpg_sample: idx int32 [M][2] = (age, robot), with replacement:
  *   h(draw) = seed; for w in (updates, m, draw): h = mix((h ^ w) + 0x9E3779B97F4A7C15);  age = 1 + h(0) mod (count - 1),
  *   robot = h(1) mod B (unsigned).

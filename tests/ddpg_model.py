@@ -108,11 +108,24 @@ def _f64(v):
     return np.asarray(v).astype(np.float64)
 
 
-def critic_grad(ring, idx, critic, target_actor, target_critic, lay, window, gamma=0.99, dtype=np.float64, q_shift=0.0, pre=None):
+def _live(idx, live):
+    """(idx with the dead samples pointed at transition (1, 0), which exists in every ring that holds one; live as float64)."""
+    idx = np.asarray(idx)
+    if live is None:
+        return idx, np.ones(len(idx))
+    live = np.asarray(live, dtype=bool)
+    idx = idx.copy()
+    idx[~live] = (1, 0)
+    return idx, live.astype(np.float64)
+
+
+def critic_grad(ring, idx, critic, target_actor, target_critic, lay, window, gamma=0.99, dtype=np.float64, q_shift=0.0, pre=None, live=None,
+                tiles=None):
     """The critic's loss (sum 0.5 (y - Q)^2) / M over the transitions idx [M, 2] and its gradient with respect to the critic
     buffer.  q_shift is added to every Q after the forward pass; pre receives the critic's pre-activations on [action, s0].
-    Returns dict(grad, mag, loss, q, y)."""
-    idx = np.asarray(idx)
+    live (bool [M]): a sample whose entry is False contributes nothing to the loss or the gradient while M stays M (an index
+    outside the ring, rg_ddpg.h); its index is not looked at.  tiles: UM.backward's.  Returns dict(grad, mag, loss, q, y)."""
+    idx, lv = _live(idx, live)
     ages, robots = idx[:, 0], idx[:, 1]
     M = len(idx)
     s1, s0 = ring.states(ages - 1, robots, window), ring.states(ages, robots, window)
@@ -124,17 +137,18 @@ def critic_grad(ring, idx, critic, target_actor, target_critic, lay, window, gam
     layers = PM.split(critic, lay["critic"], dtype)
     acts = UM.forward_all(np.concatenate([ring.action[slots, robots].astype(dtype), s0.astype(dtype)], axis=1), layers, "linear", dtype, pre=pre)
     q = _f64(acts[-1][:, 0]) + q_shift
-    e = q - y
+    e = (q - y) * lv
     mag = np.zeros(lay["critic_count"])
-    grad = UM.backward(acts, layers, (e / M)[:, None].astype(dtype), lay["critic_count"], lay["critic"], dtype, mag)
+    grad = UM.backward(acts, layers, (e / M)[:, None].astype(dtype), lay["critic_count"], lay["critic"], dtype, mag, tiles)
     return dict(grad=_f64(grad), mag=mag, loss=float(np.sum(0.5 * e * e) / M), q=q, y=y)
 
 
-def actor_grad(ring, idx, actor, critic, lay, window, dtype=np.float64, mu_shift=0.0, pre_actor=None, pre_critic=None):
+def actor_grad(ring, idx, actor, critic, lay, window, dtype=np.float64, mu_shift=0.0, pre_actor=None, pre_critic=None, live=None, tiles=None):
     """The actor's loss -(sum Q([mu(s0), s0])) / M and its gradient with respect to the actor buffer: backward through the
     critic's inputs (relu gates on its hidden layers, none on the input), the action's components times (1 - mu^2) in float64,
-    then through the actor.  mu_shift is added to every mean after the actor's forward pass.  Returns dict(grad, mag, loss, mean_q, mu)."""
-    idx = np.asarray(idx)
+    then through the actor.  mu_shift is added to every mean after the actor's forward pass.  live, tiles: critic_grad's.
+    Returns dict(grad, mag, loss, mean_q, mu)."""
+    idx, lv = _live(idx, live)
     ages, robots = idx[:, 0], idx[:, 1]
     M, A = len(idx), lay["actor"][-1][1]
     s0 = ring.states(ages, robots, window)
@@ -142,15 +156,15 @@ def actor_grad(ring, idx, actor, critic, lay, window, dtype=np.float64, mu_shift
     acts_a = UM.forward_all(s0, la, "tanh", dtype, pre=pre_actor)
     mu = _f64(acts_a[-1]) + mu_shift
     acts_c = UM.forward_all(np.concatenate([mu.astype(dtype), s0.astype(dtype)], axis=1), lc, "linear", dtype, pre=pre_critic)
-    q = _f64(acts_c[-1][:, 0])
-    d = np.full((M, 1), dtype(-1.0 / M), dtype=dtype)
+    q = _f64(acts_c[-1][:, 0]) * lv
+    d = (np.full((M, 1), dtype(-1.0 / M), dtype=dtype) * lv[:, None]).astype(dtype)
     for k in range(len(lc) - 1, -1, -1):
         d = d @ lc[k][0].T
         if k > 0:
             d = d * (acts_c[k] > 0)
     delta = (_f64(d[:, :A]) * (1.0 - mu * mu)).astype(dtype)
     mag = np.zeros(lay["actor_count"])
-    grad = UM.backward(acts_a, la, delta, lay["actor_count"], lay["actor"], dtype, mag)
+    grad = UM.backward(acts_a, la, delta, lay["actor_count"], lay["actor"], dtype, mag, tiles)
     return dict(grad=_f64(grad), mag=mag, loss=float(-np.sum(q) / M), mean_q=float(np.sum(q) / M), mu=acts_a[-1])
 
 
@@ -163,6 +177,20 @@ def clip(grad, clipnorm):
     if clipnorm > 0 and norm >= clipnorm:
         g = (g.astype(np.float64) * (clipnorm / norm)).astype(np.float32)
     return g, norm
+
+
+def adam_header(p, g, m, v, t, lr, beta1=0.9, beta2=0.999, eps=1e-8):
+    """One step of rg_ddpg_adam's formula with the header's roundings (rg_ddpg.h): float32 p, g, m, v; t is the step count before
+    it.  m and v in float32 with one rounding per operation, p in float64 with one rounding.  Returns (p, m, v) as float32."""
+    p, g, m, v = (np.asarray(a, dtype=np.float32) for a in (p, g, m, v))
+    f = np.float32
+    t = float(t + 1)
+    m = f(beta1) * m + f(1.0 - beta1) * g
+    v = f(beta2) * v + f(1.0 - beta2) * (g * g)
+    assert m.dtype == np.float32 and v.dtype == np.float32
+    bc1, bc2s = 1.0 - math.pow(beta1, t), math.sqrt(1.0 - math.pow(beta2, t))
+    denom = np.sqrt(v.astype(np.float64)) / bc2s + eps
+    return (p.astype(np.float64) - (lr / bc1) * m.astype(np.float64) / denom).astype(np.float32), m, v
 
 
 def soft_update(target, online, tau):

@@ -46,16 +46,43 @@ def forward_all(x, layers, head, dtype=np.float64, pre=None):
     return acts
 
 
-def backward(acts, layers, delta, count, spec, dtype=np.float64, mag=None):
+def tile_sum(x, d, tile, groups):
+    """x.T @ d for float32 x [M, in] and d [M, out] summed in the order of rg_ppo.h / rg_ddpg.h: a float32 chain over the `tile`
+    samples of a tile in order (padded samples are zeros), a float32 running sum over the tiles g, g + groups, ... of a
+    workgroup, a float64 sum over the workgroups in order, rounded to float32 once.  Products are rounded before they are added
+    (no fused multiply-add), as everywhere in the float32 model."""
+    x, d = np.asarray(x, dtype=np.float32), np.asarray(d, dtype=np.float32)
+    M = x.shape[0]
+    ntiles = -(-M // tile)
+    pad = ntiles * tile - M
+    xt = np.concatenate([x, np.zeros((pad, x.shape[1]), dtype=np.float32)]).reshape(ntiles, tile, -1)
+    dt = np.concatenate([d, np.zeros((pad, d.shape[1]), dtype=np.float32)]).reshape(ntiles, tile, -1)
+    t = np.zeros((ntiles, x.shape[1], d.shape[1]), dtype=np.float32)
+    for s in range(tile):
+        t += xt[:, s, :, None] * dt[:, s, None, :]
+    G = min(ntiles, groups)
+    slab = np.zeros((G,) + t.shape[1:], dtype=np.float32)
+    for first in range(0, ntiles, G):
+        n = min(G, ntiles - first)
+        slab[:n] += t[first:first + n]
+    total = np.zeros(t.shape[1:], dtype=np.float64)
+    for g in range(G):
+        total += slab[g]
+    return total.astype(np.float32)
+
+
+def backward(acts, layers, delta, count, spec, dtype=np.float64, mag=None, tiles=None):
     """The gradient of sum(delta * pre-activation of the head) with respect to every W and b, laid out as the buffer `spec`
     ([(in, out, w_offset, b_offset)]) of `count` entries.  relu'(0) = 0.  mag (an array of `count` entries) receives the sum of
-    the absolute values of the terms each entry is the sum of: what a rounding error of that sum scales with."""
+    the absolute values of the terms each entry is the sum of: what a rounding error of that sum scales with.  tiles = (tile,
+    groups), with dtype float32: the sums over the samples run in the kernels' order (tile_sum) instead of numpy's."""
     grad = np.zeros(count, dtype=dtype)
     d = np.asarray(delta, dtype=dtype)
+    ordered = tiles is not None and dtype == np.float32
     for k in range(len(layers) - 1, -1, -1):
         i, o, w, b = spec[k]
-        grad[w:w + i * o] = (acts[k].T @ d).reshape(-1)
-        grad[b:b + o] = d.sum(axis=0)
+        grad[w:w + i * o] = (tile_sum(acts[k], d, *tiles) if ordered else acts[k].T @ d).reshape(-1)
+        grad[b:b + o] = tile_sum(np.ones((len(d), 1), dtype=np.float32), d, *tiles)[0] if ordered else d.sum(axis=0)
         if mag is not None:
             mag[w:w + i * o] = (np.abs(acts[k]).T @ np.abs(d)).reshape(-1)
             mag[b:b + o] = np.abs(d).sum(axis=0)
