@@ -56,13 +56,17 @@ class PPO:
         return dict(x=x, valid=valid, adv=adv, action=rollout.action.to(p.dtype), old_mean=rollout.mean.to(p.dtype),
                     old_logstd=rollout.logstd.to(p.dtype), ret=rollout.ret.to(p.dtype))
 
+    def _evaluate(self, b):
+        """(mean, value) of the batch under the current parameters; a recurrent policy's update overrides it."""
+        return self.policy.evaluate(b["x"])
+
     def kl(self, b):
         """KL(behaviour || current) per robot [B], averaged over time."""
-        mean, _ = self.policy.evaluate(b["x"])
+        mean, _ = self._evaluate(b)
         return (diag_normal_kl(b["old_mean"], b["old_logstd"], mean, self.policy.logstd) * b["valid"]).mean(0)
 
     def policy_loss(self, b):
-        mean, _ = self.policy.evaluate(b["x"])
+        mean, _ = self._evaluate(b)
         logstd = self.policy.logstd
         kl = (diag_normal_kl(b["old_mean"], b["old_logstd"], mean, logstd) * b["valid"]).mean(0)
         ratio = torch.exp(diag_normal_logpdf(mean, logstd, b["action"], self.conv_logpdf)
@@ -73,7 +77,7 @@ class PPO:
         return (surrogate + self.penalty * kl + cutoff).mean()
 
     def value_loss(self, b):
-        _, value = self.policy.evaluate(b["x"])
+        _, value = self._evaluate(b)
         return (0.5 * (b["ret"] - value) ** 2 * b["valid"]).mean()
 
     def adjust_penalty(self, kl_change):

@@ -1,0 +1,471 @@
+// rg_rnn.hip -- the recurrent Gaussian policy of include/rg_rnn.h: one tick (rg_rnn_act) and T ticks with the state kept on
+// the chip (rg_rnn_unroll).  Its own translation unit of librg_mpc.so.  The noise stream, the normaliser's arithmetic and the
+// layer descriptor are those of rg_agent_dev.inc and the host helpers those of rg_agent_host.h; rg_mpc.hip includes neither
+// this file nor them, so the source hash behind profiles/ is unaffected.
+//
+// A tile of kTile robots per workgroup.  One output neuron per thread with kTile accumulators in registers; the activations
+// of a layer lie in LDS as x[i][robot] (a thread reads the kTile values of input i as two 16-byte broadcasts); the weight
+// W[i][j] is read once per (workgroup, neuron), coalesced along j, and used kTile times.  The sum over i runs in order with
+// explicit fmaf: over the x inputs, then over the h (or r*h) inputs.
+//
+// The policy's tick is policy_stage(s) for s = 0 .. n_dense + 2, a barrier in front of each:
+//   s < n_dense       dense relu layer s, ping-pong between the two x buffers
+//   s = n_dense       the 2H gates: threads 0 .. H-1 leave r*h, threads H .. 2H-1 leave u
+//   s = n_dense + 1   the H candidates; thread j forms h'[j] from its own h[j] and u[j], writes it over h[j] and to memory
+//   s = n_dense + 2   the head from h', into the x buffer the cell did not read
+// rg_rnn_act_kernel: 512 threads, threads 0..255 (waves 0..3) the policy's stages, threads 256..511 (waves 4..7) the value
+// network's layers (rg_policy_act_kernel's neuron, so the value is that kernel's to the bit); every branch on the network is
+// uniform over a wave and both halves meet at the same barriers.  A workgroup reads its robots' rows of hidden_in before
+// the first barrier and writes hidden_out after it: hidden_out may be hidden_in.
+// rg_rnn_unroll_kernel: 256 threads, the same policy_stage calls T times; h stays in LDS between ticks.
+// LDS, floats: act (4 * RG_RNN_MAX_WIDTH + 3 * RG_RNN_MAX_UNITS + RG_RNN_MAX_ACT) * RG_RNN_TILE = 45184 bytes;
+//              unroll (2 * RG_RNN_MAX_WIDTH + 3 * RG_RNN_MAX_UNITS) * RG_RNN_TILE = 28672 bytes, and its copy of the descriptor
+//              (at most 256 bytes).
+// The descriptor is read from device memory (dynamic indexing of a by-value kernel argument could end on the stack); the
+// unroll kernel copies it to LDS first.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include "../../include/rg_policy.h"
+#include "../../include/rg_rnn.h"
+#include "rg_agent_host.h"
+
+#pragma clang fp contract(off)
+
+#include "rg_agent_dev.inc"
+
+namespace {
+
+constexpr int kTile = RG_RNN_TILE;
+constexpr int kMaxW = RG_RNN_MAX_WIDTH;
+constexpr int kMaxH = RG_RNN_MAX_UNITS;
+constexpr int kMaxAct = RG_RNN_MAX_ACT;
+constexpr int kHalf = 256;
+constexpr int kActThreads = 2 * kHalf;
+constexpr int kCols = RG_POLICY_NORM_COLS;
+
+static_assert(kTile == 8, "a neuron reads the activations of an input as two float4");
+static_assert(2 * kMaxH <= kHalf && kMaxW <= kHalf, "one output neuron per thread of the policy's half");
+static_assert(kTile * kMaxAct <= 64 && kMaxAct <= kMaxW, "sampling thread map; the head's output fits an x buffer");
+static_assert(RG_RNN_MAX_OBS <= RG_POLICY_MAX_OBS && RG_RNN_MAX_OBS <= kMaxW, "norm_state columns");
+static_assert(RG_RNN_MODE_SAMPLE == RG_POLICY_MODE_SAMPLE && RG_RNN_MODE_MEAN == RG_POLICY_MODE_MEAN, "modes");
+
+struct RnnDev {
+  int B, obs_dim, act_dim, H, n_dense, n_x;
+  int dense_in[2], dense_out[2], dense_w[2], dense_b[2];
+  int w_ru, b_ru, w_c, b_c, head_w, head_b, logstd_off, pad0;
+  double obs_clip;
+  unsigned long long seed;
+  NetDesc val;
+};
+
+// acc[r] = fma(W[i][j], x[i][r], acc[r]) for i = 0 .. nin-1 in order; W points at W[0][j], stride = the layer's `out`
+__device__ __forceinline__ void chain8(const float *__restrict__ W, const int stride, const float *x, const int nin, float (&acc)[kTile]) {
+#pragma unroll 8
+  for (int i = 0; i < nin; i++) {
+    const float w = W[(size_t)i * stride];
+    const float4 xa = *reinterpret_cast<const float4 *>(x + i * kTile);
+    const float4 xb = *reinterpret_cast<const float4 *>(x + i * kTile + 4);
+    acc[0] = __builtin_fmaf(w, xa.x, acc[0]); acc[1] = __builtin_fmaf(w, xa.y, acc[1]);
+    acc[2] = __builtin_fmaf(w, xa.z, acc[2]); acc[3] = __builtin_fmaf(w, xa.w, acc[3]);
+    acc[4] = __builtin_fmaf(w, xb.x, acc[4]); acc[5] = __builtin_fmaf(w, xb.y, acc[5]);
+    acc[6] = __builtin_fmaf(w, xb.z, acc[6]); acc[7] = __builtin_fmaf(w, xb.w, acc[7]);
+  }
+}
+
+__device__ __forceinline__ float sigmoidf(const float a) { return 1.0f / (1.0f + expf(-a)); }
+
+// observation component i of robot b through the normaliser: float64, rounded to float32 (rg_policy.h, transform)
+__device__ __forceinline__ float normalised(const float *__restrict__ obs, const double *__restrict__ norm, const int i, const int b, const int B,
+                                            const double clip) {
+  double v = (double)obs[(size_t)i * B + b] - norm[kCols + i];
+  v = v / norm_scale(norm[i], norm[2 * kCols + i]);
+  return (float)clip_sym(v, clip);
+}
+
+// stage s of the policy's tick for output neuron j (0 .. 255).  xs: the two x buffers, x0 in xs[0]; hs, rh, us [H][kTile].
+// hout_a, hout_b: where h' goes in memory ([B][H] each), either may be null.
+__device__ __forceinline__ void policy_stage(const RnnDev *d, const float *__restrict__ pp, const int s, const int j, const int b0,
+                                             float (*xs)[kMaxW * kTile], float *hs, float *rh, float *us, float *hout_a, float *hout_b) {
+  const int n_dense = d->n_dense, H = d->H, n_x = d->n_x;
+  float acc[kTile];
+#pragma unroll
+  for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
+  if (s < n_dense) {
+    const int nin = d->dense_in[s], nout = d->dense_out[s];
+    if (j < nout) {
+      chain8(pp + d->dense_w[s] + j, nout, xs[s & 1], nin, acc);
+      const float bias = pp[d->dense_b[s] + j];
+      float *y = xs[(s & 1) ^ 1] + j * kTile;
+#pragma unroll
+      for (int r = 0; r < kTile; r++) {
+        const float v = acc[r] + bias;
+        y[r] = v > 0.0f ? v : 0.0f;
+      }
+    }
+  } else if (s == n_dense) {
+    if (j < 2 * H) {
+      const float *__restrict__ W = pp + d->w_ru + j;
+      chain8(W, 2 * H, xs[n_dense & 1], n_x, acc);
+      chain8(W + (size_t)n_x * 2 * H, 2 * H, hs, H, acc);
+      const float bias = pp[d->b_ru + j];
+      if (j < H) {
+#pragma unroll
+        for (int r = 0; r < kTile; r++) rh[j * kTile + r] = sigmoidf(acc[r] + bias) * hs[j * kTile + r];
+      } else {
+#pragma unroll
+        for (int r = 0; r < kTile; r++) us[(j - H) * kTile + r] = sigmoidf(acc[r] + bias);
+      }
+    }
+  } else if (s == n_dense + 1) {
+    if (j < H) {
+      const float *__restrict__ W = pp + d->w_c + j;
+      chain8(W, H, xs[n_dense & 1], n_x, acc);
+      chain8(W + (size_t)n_x * H, H, rh, H, acc);
+      const float bias = pp[d->b_c + j];
+#pragma unroll
+      for (int r = 0; r < kTile; r++) {
+        const float c = tanhf(acc[r] + bias);
+        const float u = us[j * kTile + r], h = hs[j * kTile + r];
+        const float hn = __builtin_fmaf(u, h, __builtin_fmaf(-u, c, c));
+        hs[j * kTile + r] = hn;   // only this thread reads or writes h[j] in this stage
+        const int b = b0 + r;
+        if (b < d->B) {
+          if (hout_a) hout_a[(size_t)b * H + j] = hn;
+          if (hout_b) hout_b[(size_t)b * H + j] = hn;
+        }
+      }
+    }
+  } else if (s == n_dense + 2) {
+    const int act_dim = d->act_dim;
+    if (j < act_dim) {
+      chain8(pp + d->head_w + j, act_dim, hs, H, acc);
+      const float bias = pp[d->head_b + j];
+      float *y = xs[(n_dense & 1) ^ 1] + j * kTile;
+#pragma unroll
+      for (int r = 0; r < kTile; r++) y[r] = tanhf(acc[r] + bias);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kActThreads) rg_rnn_act_kernel(const RnnDev *__restrict__ d, const float *__restrict__ obs,
+                                                                 const double *__restrict__ norm, const float *__restrict__ pp,
+                                                                 const float *__restrict__ vp, long long *__restrict__ act_state,
+                                                                 const int *__restrict__ reset, const float *hidden_in, float *hidden_out,
+                                                                 const int mode, float *__restrict__ action, float *__restrict__ mean,
+                                                                 float *__restrict__ value, float *__restrict__ logprob) {
+  __shared__ __attribute__((aligned(16))) float xp[2][kMaxW * kTile];   // the policy's x buffers, [input * kTile + robot]
+  __shared__ __attribute__((aligned(16))) float xv[2][kMaxW * kTile];   // the value network's
+  __shared__ __attribute__((aligned(16))) float hs[kMaxH * kTile];
+  __shared__ __attribute__((aligned(16))) float rh[kMaxH * kTile];
+  __shared__ __attribute__((aligned(16))) float us[kMaxH * kTile];
+  __shared__ float eps_s[kTile * kMaxAct];
+  const int tid = threadIdx.x;
+  const int net = tid >> 8;          // uniform over a wave
+  const int j = tid & (kHalf - 1);
+  const int B = d->B, obs_dim = d->obs_dim, act_dim = d->act_dim, H = d->H;
+  const int b0 = blockIdx.x * kTile;
+  if (tid < obs_dim * kTile) {
+    const int i = tid / kTile, r = tid % kTile, b = b0 + r;
+    const float xn = b < B ? normalised(obs, norm, i, b, B, d->obs_clip) : 0.0f;
+    xp[0][tid] = xn;
+    xv[0][tid] = xn;
+  }
+  for (int idx = tid; idx < H * kTile; idx += kActThreads) {   // along j: a robot's row is read contiguously
+    const int r = idx / H, k = idx - r * H, b = b0 + r;
+    float h = 0.0f;
+    if (b < B && !(reset && reset[b] != 0)) h = hidden_in[(size_t)b * H + k];
+    hs[k * kTile + r] = h;
+  }
+  const int n_pol = d->n_dense + 3, n_val = d->val.n;
+  const int n_max = n_pol > n_val ? n_pol : n_val;
+  for (int s = 0; s < n_max; s++) {
+    __syncthreads();
+    if (net == 0) {
+      if (s < n_pol) policy_stage(d, pp, s, j, b0, xp, hs, rh, us, hidden_out, nullptr);
+    } else if (s < n_val) {
+      const int nin = d->val.in[s], nout = d->val.out[s];
+      if (j < nout) {
+        float acc[kTile];
+#pragma unroll
+        for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
+        chain8(vp + d->val.w[s] + j, nout, xv[s & 1], nin, acc);
+        const float bias = vp[d->val.b[s] + j];
+        float *y = xv[(s & 1) ^ 1] + j * kTile;
+#pragma unroll
+        for (int r = 0; r < kTile; r++) {
+          float v = acc[r] + bias;
+          if (s < n_val - 1) v = v > 0.0f ? v : 0.0f;
+          y[r] = v;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const float *mean_s = xp[(d->n_dense & 1) ^ 1];   // [component * kTile + robot]
+  const float *value_s = xv[n_val & 1];             // [robot]
+  // sample: thread r * act_dim + a, so that a tile's actions are one contiguous store (rg_policy_act_kernel's epilogue)
+  if (tid < kTile * act_dim) {
+    const int r = tid / act_dim, a = tid % act_dim, b = b0 + r;
+    float e = 0.0f;
+    if (b < B) {
+      const float m = mean_s[a * kTile + r];
+      float act = m;
+      if (mode == RG_RNN_MODE_SAMPLE) {
+        e = noise_eps(d->seed, (unsigned long long)act_state[b], (unsigned long long)act_state[(size_t)B + b], (unsigned long long)a);
+        const float se = expf(pp[d->logstd_off + a]) * e;
+        act = m + se;
+      }
+      action[(size_t)b * act_dim + a] = act;
+      if (mean) mean[(size_t)b * act_dim + a] = m;
+    }
+    eps_s[r * kMaxAct + a] = e;
+  }
+  __syncthreads();   // every counter has been read
+  if (tid < kTile && b0 + tid < B) {
+    const int b = b0 + tid;
+    if (logprob) {
+      double s = 0.0, sl = 0.0;
+      for (int a = 0; a < act_dim; a++) {
+        const double e = (double)eps_s[tid * kMaxAct + a];
+        s = s + e * e;
+        sl = sl + (double)pp[d->logstd_off + a];
+      }
+      logprob[b] = (float)(-0.5 * s - sl - 0.5 * (double)act_dim * 1.8378770664093453);   // ln(2 pi)
+    }
+    if (value) value[b] = value_s[tid];
+    if (mode == RG_RNN_MODE_SAMPLE) act_state[(size_t)B + b] = act_state[(size_t)B + b] + 1;
+  }
+}
+
+__global__ void __launch_bounds__(kHalf) rg_rnn_unroll_kernel(const RnnDev *__restrict__ dg, const float *__restrict__ obs,
+                                                              const int *__restrict__ reset, const float *h0, const double *__restrict__ norm,
+                                                              const float *__restrict__ pp, const int T, float *__restrict__ mean_out,
+                                                              float *__restrict__ hidden_seq, float *hidden_last) {
+  // the descriptor from LDS: as scalar registers its fields, live through the loop over t, do not fit beside the pointers
+  __shared__ RnnDev dsh;
+  for (int idx = threadIdx.x; idx < (int)(sizeof(RnnDev) / sizeof(int)); idx += kHalf)
+    reinterpret_cast<int *>(&dsh)[idx] = reinterpret_cast<const int *>(dg)[idx];
+  __syncthreads();
+  const RnnDev *d = &dsh;
+  __shared__ __attribute__((aligned(16))) float xs[2][kMaxW * kTile];
+  __shared__ __attribute__((aligned(16))) float hs[kMaxH * kTile];
+  __shared__ __attribute__((aligned(16))) float rh[kMaxH * kTile];
+  __shared__ __attribute__((aligned(16))) float us[kMaxH * kTile];
+  const int tid = threadIdx.x;
+  const int B = d->B, obs_dim = d->obs_dim, act_dim = d->act_dim, H = d->H;
+  const int b0 = blockIdx.x * kTile;
+  const int n_pol = d->n_dense + 3;
+  const float *mean_s = xs[(d->n_dense & 1) ^ 1];
+  for (int idx = tid; idx < H * kTile; idx += kHalf) {
+    const int r = idx / H, k = idx - r * H, b = b0 + r;
+    hs[k * kTile + r] = b < B ? h0[(size_t)b * H + k] : 0.0f;
+  }
+  for (int t = 0; t < T; t++) {
+    const float *__restrict__ obs_t = obs + (size_t)t * obs_dim * B;
+    const int *__restrict__ reset_t = reset + (size_t)t * B;
+    for (int idx = tid; idx < obs_dim * kTile; idx += kHalf) {
+      const int i = idx / kTile, r = idx % kTile, b = b0 + r;
+      xs[0][idx] = b < B ? normalised(obs_t, norm, i, b, B, d->obs_clip) : 0.0f;
+    }
+    for (int idx = tid; idx < H * kTile; idx += kHalf) {   // the thread that wrote h0's element zeroes it
+      const int r = idx / H, k = idx - r * H, b = b0 + r;
+      if (b < B && reset_t[b] != 0) hs[k * kTile + r] = 0.0f;
+    }
+    float *hseq_t = hidden_seq ? hidden_seq + (size_t)t * B * H : nullptr;
+    float *hlast = t == T - 1 ? hidden_last : nullptr;
+    for (int s = 0; s < n_pol; s++) {
+      __syncthreads();
+      policy_stage(d, pp, s, tid, b0, xs, hs, rh, us, hseq_t, hlast);
+    }
+    __syncthreads();
+    if (tid < kTile * act_dim) {
+      const int r = tid / act_dim, a = tid % act_dim, b = b0 + r;
+      if (b < B) mean_out[((size_t)t * B + b) * act_dim + a] = mean_s[a * kTile + r];
+    }
+    __syncthreads();   // the next tick's observation may land in the buffer the mean was read from
+  }
+}
+
+thread_local std::string g_create_err;
+
+}  // namespace
+
+struct rg_rnn_handle {
+  rg_rnn_config cfg{};
+  rg_rnn_layout lay{};
+  RnnDev dv{};
+  int B = 0, device = 0;
+  RnnDev *dev_cfg = nullptr;
+  std::string err;
+};
+
+namespace {
+
+bool validate(const rg_rnn_config *cfg, std::string &err) {
+  const char *prefix = "config.";
+  if (!check_abi(prefix, cfg->abi_version, RG_RNN_ABI_VERSION, err)) return false;
+  if (cfg->reserved0 != 0) { err = std::string(prefix) + "reserved0: must be 0"; return false; }
+  const IntField ints[] = {{"obs_dim", cfg->obs_dim, 1, RG_RNN_MAX_OBS}, {"act_dim", cfg->act_dim, 1, RG_RNN_MAX_ACT},
+                           {"n_policy_layers", cfg->n_policy_layers, 0, RG_RNN_MAX_DENSE}, {"gru_units", cfg->gru_units, 1, RG_RNN_MAX_UNITS},
+                           {"n_value_layers", cfg->n_value_layers, 0, RG_RNN_MAX_VALUE_LAYERS}};
+  const RealField reals[] = {{"obs_clip", cfg->obs_clip, kNonNegative}};
+  return check_ints(prefix, ints, err) &&
+         check_widths(prefix, "policy_layers", cfg->policy_layers, cfg->n_policy_layers, RG_RNN_MAX_DENSE, RG_RNN_MAX_WIDTH, err) &&
+         check_widths(prefix, "value_layers", cfg->value_layers, cfg->n_value_layers, RG_RNN_MAX_VALUE_LAYERS, RG_RNN_MAX_WIDTH, err) &&
+         check_reals(prefix, reals, err);
+}
+
+void fill_layout(const rg_rnn_config *cfg, rg_rnn_layout &L) {
+  std::memset(&L, 0, sizeof(L));
+  const int H = cfg->gru_units, nd = cfg->n_policy_layers;
+  int off = 0, prev = cfg->obs_dim;
+  for (int l = 0; l < nd; l++) {
+    const int width = cfg->policy_layers[l];
+    L.dense_in[l] = prev; L.dense_out[l] = width;
+    L.dense_w[l] = off; off += prev * width;
+    L.dense_b[l] = off; off += width;
+    prev = width;
+  }
+  L.n_dense = nd; L.n_x = prev; L.gru_units = H;
+  L.w_ru = off; off += (prev + H) * 2 * H;
+  L.b_ru = off; off += 2 * H;
+  L.w_c = off; off += (prev + H) * H;
+  L.b_c = off; off += H;
+  L.head_w = off; off += H * cfg->act_dim;
+  L.head_b = off; off += cfg->act_dim;
+  L.logstd_offset = off;
+  L.policy_count = off + cfg->act_dim;
+  L.n_value = cfg->n_value_layers + 1;
+  L.value_count = layer_layout(cfg->obs_dim, cfg->value_layers, cfg->n_value_layers, 1, L.value_in, L.value_out, L.value_w, L.value_b);
+}
+
+int hip_fail(rg_rnn_handle *h, const char *what, hipError_t e) { return hip_fail(h, RG_RNN_ERR_HIP, what, e); }
+int no_device(rg_rnn_handle *h) { return no_device(h, RG_RNN_ERR_NO_DEVICE, "RG_RNN"); }
+int launch_status(rg_rnn_handle *h, const char *what) { return launch_status(h, RG_RNN_ERR_HIP, what); }
+int null_arg(rg_rnn_handle *h, const char *call, const char *name) { return null_arg(h, RG_RNN_ERR_INVALID, call, name); }
+
+}  // namespace
+
+extern "C" {
+
+int32_t rg_rnn_abi_version(void) { return RG_RNN_ABI_VERSION; }
+int32_t rg_rnn_config_size(void) { return (int32_t)sizeof(rg_rnn_config); }
+int32_t rg_rnn_layout_size(void) { return (int32_t)sizeof(rg_rnn_layout); }
+int32_t rg_rnn_tile(void) { return RG_RNN_TILE; }
+const char *rg_rnn_last_error(const rg_rnn_handle *h) { return h ? h->err.c_str() : g_create_err.c_str(); }
+
+int rg_rnn_param_layout(const rg_rnn_config *cfg, rg_rnn_layout *out) {
+  if (!cfg || !out) { g_create_err = "param_layout: null config or out"; return RG_RNN_ERR_INVALID; }
+  std::string err;
+  if (!validate(cfg, err)) { g_create_err = err; return RG_RNN_ERR_INVALID; }
+  fill_layout(cfg, *out);
+  return RG_RNN_OK;
+}
+
+int rg_rnn_create(const rg_rnn_config *cfg, int32_t batch, int32_t device, rg_rnn_handle **out) {
+  if (!cfg || !out) { g_create_err = "create: null config or out"; return RG_RNN_ERR_INVALID; }
+  *out = nullptr;
+  std::string err;
+  if (batch < 1 || batch > RG_RNN_MAX_BATCH) {
+    char msg[96];
+    snprintf(msg, sizeof(msg), "batch: %d outside [1, %d]", batch, RG_RNN_MAX_BATCH);
+    g_create_err = msg;
+    return RG_RNN_ERR_INVALID;
+  }
+  if (!validate(cfg, err)) { g_create_err = err; return RG_RNN_ERR_INVALID; }
+  rg_rnn_handle *h = new rg_rnn_handle();
+  h->cfg = *cfg;
+  h->B = batch;
+  h->device = device;
+  fill_layout(cfg, h->lay);
+  const rg_rnn_layout &L = h->lay;
+  RnnDev &d = h->dv;
+  d.B = batch; d.obs_dim = cfg->obs_dim; d.act_dim = cfg->act_dim; d.H = L.gru_units; d.n_dense = L.n_dense; d.n_x = L.n_x;
+  for (int l = 0; l < 2; l++) { d.dense_in[l] = L.dense_in[l]; d.dense_out[l] = L.dense_out[l]; d.dense_w[l] = L.dense_w[l]; d.dense_b[l] = L.dense_b[l]; }
+  d.w_ru = L.w_ru; d.b_ru = L.b_ru; d.w_c = L.w_c; d.b_c = L.b_c; d.head_w = L.head_w; d.head_b = L.head_b; d.logstd_off = L.logstd_offset;
+  d.obs_clip = cfg->obs_clip; d.seed = cfg->seed;
+  d.val.n = L.n_value;
+  for (int l = 0; l < 4; l++) { d.val.in[l] = L.value_in[l]; d.val.out[l] = L.value_out[l]; d.val.w[l] = L.value_w[l]; d.val.b[l] = L.value_b[l]; }
+  if (device == RG_RNN_DEVICE_NONE) {   // a host-only handle: the configuration, for argument checks on any machine
+    *out = h;
+    return RG_RNN_OK;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_err = "no HIP device available"; delete h; return RG_RNN_ERR_NO_DEVICE; }
+  if (device < 0 || device >= ndev) { g_create_err = "device index out of range"; delete h; return RG_RNN_ERR_INVALID; }
+  DeviceScope dev(device);
+  if (dev.err != hipSuccess) { g_create_err = std::string("hipSetDevice failed: ") + hipGetErrorString(dev.err); delete h; return RG_RNN_ERR_HIP; }
+  hipError_t e = hipMalloc((void **)&h->dev_cfg, sizeof(RnnDev));
+  if (e != hipSuccess) {
+    g_create_err = std::string("hipMalloc failed: ") + hipGetErrorString(e);
+    rg_rnn_destroy(h);
+    return RG_RNN_ERR_ALLOC;
+  }
+  e = hipMemcpy(h->dev_cfg, &h->dv, sizeof(RnnDev), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    g_create_err = std::string("hipMemcpy failed: ") + hipGetErrorString(e);
+    rg_rnn_destroy(h);
+    return RG_RNN_ERR_HIP;
+  }
+  *out = h;
+  return RG_RNN_OK;
+}
+
+void rg_rnn_destroy(rg_rnn_handle *h) {
+  if (!h) return;
+  if (h->device >= 0) {
+    DeviceScope dev(h->device);
+    if (h->dev_cfg) (void)hipFree(h->dev_cfg);
+  }
+  delete h;
+}
+
+int rg_rnn_act(rg_rnn_handle *h, const float *obs, const double *norm_state, const float *policy_params, const float *value_params,
+               int64_t *act_state, const int32_t *reset, const float *hidden_in, float *hidden_out, int32_t mode, float *action, float *mean,
+               float *value, float *logprob, void *stream) {
+  if (!h) { g_create_err = "act: null handle"; return RG_RNN_ERR_INVALID; }
+  RG_NEED("act", obs, "obs");
+  RG_NEED("act", norm_state, "norm_state");
+  RG_NEED("act", policy_params, "policy_params");
+  RG_NEED("act", value_params, "value_params");
+  if (mode != RG_RNN_MODE_SAMPLE && mode != RG_RNN_MODE_MEAN) { h->err = "act: mode is neither RG_RNN_MODE_SAMPLE nor RG_RNN_MODE_MEAN"; return RG_RNN_ERR_INVALID; }
+  if (!act_state && mode == RG_RNN_MODE_SAMPLE) return null_arg(h, "act", "act_state");
+  RG_NEED("act", hidden_in, "hidden_in");
+  RG_NEED("act", hidden_out, "hidden_out");
+  RG_NEED("act", action, "action");
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  hipLaunchKernelGGL(rg_rnn_act_kernel, dim3(((unsigned)h->B + kTile - 1) / kTile), dim3(kActThreads), 0, (hipStream_t)stream, h->dev_cfg, obs,
+                     norm_state, policy_params, value_params, (long long *)act_state, reset, hidden_in, hidden_out, mode, action, mean, value,
+                     logprob);
+  return launch_status(h, "rg_rnn_act_kernel launch");
+}
+
+int rg_rnn_unroll(rg_rnn_handle *h, const float *obs, const int32_t *reset, const float *h0, const double *norm_state, const float *policy_params,
+                  int32_t T, float *mean_out, float *hidden_seq, float *hidden_last, void *stream) {
+  if (!h) { g_create_err = "unroll: null handle"; return RG_RNN_ERR_INVALID; }
+  RG_NEED("unroll", obs, "obs");
+  RG_NEED("unroll", reset, "reset");
+  RG_NEED("unroll", h0, "h0");
+  RG_NEED("unroll", norm_state, "norm_state");
+  RG_NEED("unroll", policy_params, "policy_params");
+  if (T < 1 || T > RG_RNN_MAX_T) {
+    char msg[96];
+    snprintf(msg, sizeof(msg), "unroll: T %d outside [1, %d]", T, RG_RNN_MAX_T);
+    h->err = msg;
+    return RG_RNN_ERR_INVALID;
+  }
+  RG_NEED("unroll", mean_out, "mean_out");
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  hipLaunchKernelGGL(rg_rnn_unroll_kernel, dim3(((unsigned)h->B + kTile - 1) / kTile), dim3(kHalf), 0, (hipStream_t)stream, h->dev_cfg, obs, reset,
+                     h0, norm_state, policy_params, T, mean_out, hidden_seq, hidden_last);
+  return launch_status(h, "rg_rnn_unroll_kernel launch");
+}
+
+}  // extern "C"
