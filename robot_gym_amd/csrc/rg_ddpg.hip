@@ -1,6 +1,6 @@
 // rg_ddpg.hip -- the DDPG agent of include/rg_ddpg.h.  Its own translation unit of librg_mpc.so.  The noise stream, a layer's
 // forward and backward pass over a tile, the workgroup sums and the bodies of the transpose and slab-finish kernels
-// are those of rg_agent_dev.inc, which the PPO agent's files include too, and the host helpers those of rg_agent_host.h;
+// are those of rg_agent_dev.inc, which the PPO agent's files include too, and the host helpers those of rg_host.h;
 // rg_mpc.hip includes neither, so the source hash behind profiles/ is unaffected.
 //
 // Sweeps (rg_ddpg_critic_sweep_kernel, rg_ddpg_actor_sweep_kernel): G workgroups of 256 threads, workgroup g walks the tiles
@@ -19,7 +19,7 @@
 #include <cstring>
 #include <string>
 #include "../../include/rg_ddpg.h"
-#include "rg_agent_host.h"
+#include "rg_host.h"
 
 #pragma clang fp contract(off)
 
@@ -536,10 +536,11 @@ bool validate(const rg_ddpg_config *cfg, std::string &err) {
     err = msg;
     return false;
   }
-  const RealField reals[] = {{"gamma", cfg->gamma, kUnit}, {"tau", cfg->tau, kUnitPositive}, {"actor_lr", cfg->actor_lr, kNonNegative},
-                             {"critic_lr", cfg->critic_lr, kNonNegative}, {"beta1", cfg->beta1, kBelowOne}, {"beta2", cfg->beta2, kBelowOne},
-                             {"adam_eps", cfg->adam_eps, kPositive}, {"clipnorm", cfg->clipnorm, kNonNegative}, {"ou_theta", cfg->ou_theta, kNonNegative},
-                             {"ou_mu", cfg->ou_mu, kFinite}, {"ou_sigma", cfg->ou_sigma, kNonNegative}, {"ou_dt", cfg->ou_dt, kPositive}};
+  const RealField reals[] = {{"gamma", &cfg->gamma, 1, kUnit}, {"tau", &cfg->tau, 1, kUnitPositive}, {"actor_lr", &cfg->actor_lr, 1, kNonNegative},
+                             {"critic_lr", &cfg->critic_lr, 1, kNonNegative}, {"beta1", &cfg->beta1, 1, kBelowOne}, {"beta2", &cfg->beta2, 1, kBelowOne},
+                             {"adam_eps", &cfg->adam_eps, 1, kPositive}, {"clipnorm", &cfg->clipnorm, 1, kNonNegative},
+                             {"ou_theta", &cfg->ou_theta, 1, kNonNegative}, {"ou_mu", &cfg->ou_mu, 1, kFinite}, {"ou_sigma", &cfg->ou_sigma, 1, kNonNegative},
+                             {"ou_dt", &cfg->ou_dt, 1, kPositive}};
   return check_widths("config.", "actor_layers", cfg->actor_layers, cfg->n_actor_layers, RG_DDPG_MAX_LAYERS, RG_DDPG_MAX_WIDTH, err) &&
          check_widths("config.", "critic_layers", cfg->critic_layers, cfg->n_critic_layers, RG_DDPG_MAX_LAYERS, RG_DDPG_MAX_WIDTH, err) &&
          check_reals("config.", reals, err);
@@ -697,13 +698,7 @@ int rg_ddpg_create(const rg_ddpg_config *cfg, int32_t batch, int32_t device, rg_
   if (!cfg || !out) { g_create_err = "create: null config or out"; return RG_DDPG_ERR_INVALID; }
   *out = nullptr;
   std::string err;
-  if (!validate(cfg, err)) { g_create_err = err; return RG_DDPG_ERR_INVALID; }
-  if (batch < 1 || batch > RG_DDPG_MAX_BATCH) {
-    char msg[96];
-    snprintf(msg, sizeof(msg), "batch: %d outside [1, %d]", batch, RG_DDPG_MAX_BATCH);
-    g_create_err = msg;
-    return RG_DDPG_ERR_INVALID;
-  }
+  if (!validate(cfg, err) || !check_batch(batch, RG_DDPG_MAX_BATCH, err)) { g_create_err = err; return RG_DDPG_ERR_INVALID; }
   rg_ddpg_handle *h = new rg_ddpg_handle();
   h->cfg = *cfg;
   h->B = batch;
@@ -737,11 +732,8 @@ int rg_ddpg_create(const rg_ddpg_config *cfg, int32_t batch, int32_t device, rg_
     *out = h;
     return RG_DDPG_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_err = "no HIP device available"; delete h; return RG_DDPG_ERR_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { g_create_err = "device index out of range"; delete h; return RG_DDPG_ERR_INVALID; }
-  DeviceScope dev(device);
-  if (dev.err != hipSuccess) { g_create_err = std::string("hipSetDevice failed: ") + hipGetErrorString(dev.err); delete h; return RG_DDPG_ERR_HIP; }
+  std::optional<DeviceScope> dev;
+  if (const int rc = enter_device(device, &dev, RG_DDPG_ERR_NO_DEVICE, RG_DDPG_ERR_INVALID, RG_DDPG_ERR_HIP, g_create_err)) { delete h; return rc; }
   // the sweeps' tiles need more dynamic LDS than the default limit of a launch.  The attribute belongs to the function and the
   // device, not to the handle: it is set to the most any configuration of the ABI needs, so handles do not undo each other
   hipError_t e = hipFuncSetAttribute((const void *)rg_ddpg_critic_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);

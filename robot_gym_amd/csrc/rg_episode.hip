@@ -26,6 +26,7 @@
 #include <string>
 #include <vector>
 #include "../../include/rg_episode.h"
+#include "rg_host.h"
 
 #pragma clang fp contract(off)
 
@@ -349,17 +350,6 @@ __global__ void __launch_bounds__(kAccBlock) rg_episode_accumulate_kernel(int B,
   if (done[b] != 0) ep[RG_EPISODE_ROW_ENDED * sB + b] = 1.0;
 }
 
-struct DeviceScope {
-  int prev = -1;
-  bool switched = false;
-  hipError_t err = hipSuccess;
-  explicit DeviceScope(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess && prev >= 0; }
-  }
-  ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
-};
-
 thread_local std::string g_create_err;
 
 }  // namespace
@@ -393,33 +383,16 @@ namespace {
 
 bool validate(const rg_episode_config *cfg, std::string &err) {
   char msg[200];
-  if (cfg->abi_version != RG_EPISODE_ABI_VERSION) {
-    snprintf(msg, sizeof(msg), "config.abi_version: %d, this library is version %d", cfg->abi_version, RG_EPISODE_ABI_VERSION);
-    err = msg;
+  const RealField reals[] = {{"kp", &cfg->kp, 1, kPositive}, {"eta", &cfg->eta, 1, kFinite}, {"area_width", &cfg->area_width, 1, kPositive},
+                             {"grid", &cfg->grid, 1, kPositive}, {"robot_radius", &cfg->robot_radius, 1, kPositive}, {"spacing", &cfg->spacing, 1, kPositive}};
+  if (!check_abi("config.", cfg->abi_version, RG_EPISODE_ABI_VERSION, err) || !check_reserved("config.", "reserved0", cfg->reserved0, err) ||
+      !check_reserved("config.", "reserved1", cfg->reserved1, err) || !check_reals("config.", reals, err))
     return false;
-  }
-  if (cfg->reserved0 != 0) { err = "config.reserved0: must be 0"; return false; }
-  if (cfg->reserved1 != 0) { err = "config.reserved1: must be 0"; return false; }
-  struct F { const char *name; double v; bool positive; };
-  const F fields[] = {{"kp", cfg->kp, true}, {"eta", cfg->eta, false}, {"area_width", cfg->area_width, true}, {"grid", cfg->grid, true},
-                      {"robot_radius", cfg->robot_radius, true}, {"spacing", cfg->spacing, true}};
-  for (const F &f : fields)
-    if (!std::isfinite(f.v) || (f.positive && !(f.v > 0))) {
-      snprintf(msg, sizeof(msg), "config.%s: %g must be finite%s", f.name, f.v, f.positive ? " and > 0" : "");
-      err = msg;
-      return false;
-    }
   if (cfg->eta < 0) { snprintf(msg, sizeof(msg), "config.eta: %g must be >= 0", cfg->eta); err = msg; return false; }
-  struct I { const char *name; int v, lo, hi; };
-  const I ints[] = {{"oscillation_length", cfg->oscillation_length, 1, RG_EPISODE_MAX_OSCILLATION},
-                    {"max_waypoints", cfg->max_waypoints, 2, RG_EPISODE_MAX_WAYPOINTS},
-                    {"num_obstacles", cfg->num_obstacles, 0, RG_EPISODE_MAX_OBSTACLES}};
-  for (const I &f : ints)
-    if (f.v < f.lo || f.v > f.hi) {
-      snprintf(msg, sizeof(msg), "config.%s: %d outside [%d, %d]", f.name, f.v, f.lo, f.hi);
-      err = msg;
-      return false;
-    }
+  const IntField ints[] = {{"oscillation_length", cfg->oscillation_length, 1, RG_EPISODE_MAX_OSCILLATION},
+                           {"max_waypoints", cfg->max_waypoints, 2, RG_EPISODE_MAX_WAYPOINTS},
+                           {"num_obstacles", cfg->num_obstacles, 0, RG_EPISODE_MAX_OBSTACLES}};
+  if (!check_ints("config.", ints, err)) return false;
   for (int k = 0; k < RG_EPISODE_MAX_OBSTACLES; k++)
     for (int a = 0; a < 2; a++)
       if (!std::isfinite(cfg->obstacles[k][a])) {
@@ -430,20 +403,10 @@ bool validate(const rg_episode_config *cfg, std::string &err) {
   return true;
 }
 
-int hip_fail(rg_episode_handle *h, const char *what, hipError_t e) {
-  h->err = std::string(what) + ": " + hipGetErrorString(e);
-  return RG_EPISODE_ERR_HIP;
-}
-
-int no_device(rg_episode_handle *h) {
-  h->err = "host-only handle (RG_EPISODE_DEVICE_NONE): the arguments are valid, there is no device to run on";
-  return RG_EPISODE_ERR_NO_DEVICE;
-}
-
-int launch_status(rg_episode_handle *h, const char *what) {
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? hip_fail(h, what, e) : RG_EPISODE_OK;
-}
+int hip_fail(rg_episode_handle *h, const char *what, hipError_t e) { return hip_fail(h, RG_EPISODE_ERR_HIP, what, e); }
+int no_device(rg_episode_handle *h) { return no_device(h, RG_EPISODE_ERR_NO_DEVICE, "RG_EPISODE"); }
+int launch_status(rg_episode_handle *h, const char *what) { return launch_status(h, RG_EPISODE_ERR_HIP, what); }
+int null_arg(rg_episode_handle *h, const char *call, const char *name) { return null_arg(h, RG_EPISODE_ERR_INVALID, call, name); }
 
 }  // namespace
 
@@ -460,13 +423,7 @@ int rg_episode_create(const rg_episode_config *ecfg, const rg_srb_config *scfg, 
   *out = nullptr;
   std::string err;
   double Iinv[9];
-  if (batch < 1 || batch > RG_EPISODE_MAX_BATCH) {
-    char msg[96];
-    snprintf(msg, sizeof(msg), "batch: %d outside [1, %d]", batch, RG_EPISODE_MAX_BATCH);
-    g_create_err = msg;
-    return RG_EPISODE_ERR_INVALID;
-  }
-  if (!validate(ecfg, err)) { g_create_err = err; return RG_EPISODE_ERR_INVALID; }
+  if (!check_batch(batch, RG_EPISODE_MAX_BATCH, err) || !validate(ecfg, err)) { g_create_err = err; return RG_EPISODE_ERR_INVALID; }
   if (!srb_validate(scfg, batch, Iinv, err)) { g_create_err = "srb " + err; return RG_EPISODE_ERR_INVALID; }
   if (!goto_validate(gcfg, batch, err)) { g_create_err = "goto " + err; return RG_EPISODE_ERR_INVALID; }
   rg_episode_handle *h = new rg_episode_handle();
@@ -486,11 +443,8 @@ int rg_episode_create(const rg_episode_config *ecfg, const rg_srb_config *scfg, 
     *out = h;
     return RG_EPISODE_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_err = "no HIP device available"; delete h; return RG_EPISODE_ERR_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { g_create_err = "device index out of range"; delete h; return RG_EPISODE_ERR_INVALID; }
-  DeviceScope dev(device);
-  if (dev.err != hipSuccess) { g_create_err = std::string("hipSetDevice failed: ") + hipGetErrorString(dev.err); delete h; return RG_EPISODE_ERR_HIP; }
+  std::optional<DeviceScope> dev;
+  if (const int rc = enter_device(device, &dev, RG_EPISODE_ERR_NO_DEVICE, RG_EPISODE_ERR_INVALID, RG_EPISODE_ERR_HIP, g_create_err)) { delete h; return rc; }
   DevCfg *kin = new DevCfg();
   srb_fill_kinematics(scfg, kin);
   hipError_t e = hipMalloc((void **)&h->dcfg, sizeof(DevCfg));
@@ -527,16 +481,15 @@ int rg_episode_reset(rg_episode_handle *h, const int32_t *mask, const double *ta
                      double *sim_state, const rg_srb_obs_ptrs *sim_obs, const rg_goto_path_ptrs *paths, float *obs, float *final_obs,
                      int32_t *reset_mask_out, void *stream) {
   if (!h) { g_create_err = "reset: null handle"; return RG_EPISODE_ERR_INVALID; }
-  if (!mask) { h->err = "reset: null mask"; return RG_EPISODE_ERR_INVALID; }
-  if (!episode_state) { h->err = "reset: null episode_state"; return RG_EPISODE_ERR_INVALID; }
-  if (!task_state) { h->err = "reset: null task_state"; return RG_EPISODE_ERR_INVALID; }
-  if (!sim_state) { h->err = "reset: null sim_state"; return RG_EPISODE_ERR_INVALID; }
-  if (!(sim_obs && sim_obs->rpy && sim_obs->rpy_rate && sim_obs->v_world && sim_obs->quat && sim_obs->q && sim_obs->foot_pos && sim_obs->jac &&
-        sim_obs->contact && sim_obs->t_robot)) { h->err = "reset: null sim_obs pointer"; return RG_EPISODE_ERR_INVALID; }
-  if (!(paths && paths->x && paths->y && paths->s && paths->first_same_x && paths->hdr)) { h->err = "reset: null paths pointer"; return RG_EPISODE_ERR_INVALID; }
-  if (!obs) { h->err = "reset: null obs"; return RG_EPISODE_ERR_INVALID; }
-  if (!final_obs) { h->err = "reset: null final_obs"; return RG_EPISODE_ERR_INVALID; }
-  if (!reset_mask_out) { h->err = "reset: null reset_mask_out"; return RG_EPISODE_ERR_INVALID; }
+  RG_NEED("reset", mask, "mask");
+  RG_NEED("reset", episode_state, "episode_state");
+  RG_NEED("reset", task_state, "task_state");
+  RG_NEED("reset", sim_state, "sim_state");
+  RG_NEED("reset", obs_ok(sim_obs), "sim_obs pointer");
+  RG_NEED("reset", paths_ok(paths), "paths pointer");
+  RG_NEED("reset", obs, "obs");
+  RG_NEED("reset", final_obs, "final_obs");
+  RG_NEED("reset", reset_mask_out, "reset_mask_out");
   if (reset_mask_out == mask) { h->err = "reset: reset_mask_out must not alias mask"; return RG_EPISODE_ERR_INVALID; }
   if (h->device < 0) return no_device(h);
   DeviceScope dev(h->device);
@@ -547,19 +500,16 @@ int rg_episode_reset(rg_episode_handle *h, const int32_t *mask, const double *ta
   hipLaunchKernelGGL(rg_episode_plan_kernel, dim3((unsigned)h->B), dim3(kWave), 0, s, h->c, pp);
   int rc = launch_status(h, "rg_episode_plan_kernel launch");
   if (rc) return rc;
-  const Obs o{sim_obs->rpy, sim_obs->rpy_rate, sim_obs->v_world, sim_obs->quat, sim_obs->q, sim_obs->foot_pos, sim_obs->jac, sim_obs->contact,
-              sim_obs->t_robot};
-  const Paths P{paths->x, paths->y, paths->s, paths->first_same_x, paths->hdr};
   hipLaunchKernelGGL(rg_episode_reset_kernel, dim3((unsigned)h->B), dim3(kWave), 0, s, h->dcfg, h->dev_cfg, h->gc, reset_mask_out, task_state, sim_state,
-                     o, P, obs);
+                     to_obs(sim_obs), to_paths(paths), obs);
   return launch_status(h, "rg_episode_reset_kernel launch");
 }
 
 int rg_episode_accumulate(rg_episode_handle *h, double *episode_state, const float *reward, const int32_t *done, void *stream) {
   if (!h) { g_create_err = "accumulate: null handle"; return RG_EPISODE_ERR_INVALID; }
-  if (!episode_state) { h->err = "accumulate: null episode_state"; return RG_EPISODE_ERR_INVALID; }
-  if (!reward) { h->err = "accumulate: null reward"; return RG_EPISODE_ERR_INVALID; }
-  if (!done) { h->err = "accumulate: null done"; return RG_EPISODE_ERR_INVALID; }
+  RG_NEED("accumulate", episode_state, "episode_state");
+  RG_NEED("accumulate", reward, "reward");
+  RG_NEED("accumulate", done, "done");
   if (h->device < 0) return no_device(h);
   DeviceScope dev(h->device);
   if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);

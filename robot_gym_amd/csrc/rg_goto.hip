@@ -21,6 +21,7 @@
 #include <vector>
 #include "../../include/rg_goto.h"
 #include "../../include/rg_srb.h"
+#include "rg_host.h"
 
 #pragma clang fp contract(off)
 
@@ -157,17 +158,6 @@ __global__ void __launch_bounds__(kPreBlock) rg_goto_set_kernel(int B, int n, co
   for (int r = 0; r < RG_GOTO_STATE_ROWS; r++) task[r * sB + b] = 0.0;
 }
 
-struct DeviceScope {
-  int prev = -1;
-  bool switched = false;
-  hipError_t err = hipSuccess;
-  explicit DeviceScope(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess && prev >= 0; }
-  }
-  ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
-};
-
 thread_local std::string g_create_err;
 
 }  // namespace
@@ -183,34 +173,19 @@ struct rg_goto_handle {
 
 namespace {
 
-
-int hip_fail(rg_goto_handle *h, const char *what, hipError_t e) {
-  h->err = std::string(what) + ": " + hipGetErrorString(e);
-  return RG_GOTO_ERR_HIP;
-}
-
-int no_device(rg_goto_handle *h) {
-  h->err = "host-only handle (RG_GOTO_DEVICE_NONE): the arguments are valid, there is no device to run on";
-  return RG_GOTO_ERR_NO_DEVICE;
-}
-
-int launch_status(rg_goto_handle *h, const char *what) {
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? hip_fail(h, what, e) : RG_GOTO_OK;
-}
-
-bool paths_ok(const rg_goto_path_ptrs *p) { return p && p->x && p->y && p->s && p->first_same_x && p->hdr; }
-
-Paths to_paths(const rg_goto_path_ptrs *p) { return {p->x, p->y, p->s, p->first_same_x, p->hdr}; }
+int hip_fail(rg_goto_handle *h, const char *what, hipError_t e) { return hip_fail(h, RG_GOTO_ERR_HIP, what, e); }
+int no_device(rg_goto_handle *h) { return no_device(h, RG_GOTO_ERR_NO_DEVICE, "RG_GOTO"); }
+int launch_status(rg_goto_handle *h, const char *what) { return launch_status(h, RG_GOTO_ERR_HIP, what); }
+int null_arg(rg_goto_handle *h, const char *call, const char *name) { return null_arg(h, RG_GOTO_ERR_INVALID, call, name); }
 
 int post(rg_goto_handle *h, const char *who, int observe_only, double *task_state, const double *sim_state, const rg_goto_path_ptrs *paths,
          float *obs, float *reward, int32_t *done, void *stream) {
   if (!h) { g_create_err = std::string(who) + ": null handle"; return RG_GOTO_ERR_INVALID; }
-  if (!task_state) { h->err = std::string(who) + ": null task_state"; return RG_GOTO_ERR_INVALID; }
-  if (!sim_state) { h->err = std::string(who) + ": null sim_state"; return RG_GOTO_ERR_INVALID; }
-  if (!paths_ok(paths)) { h->err = std::string(who) + ": null paths pointer"; return RG_GOTO_ERR_INVALID; }
-  if (!obs) { h->err = std::string(who) + ": null obs"; return RG_GOTO_ERR_INVALID; }
-  if (!observe_only && (!reward || !done)) { h->err = std::string(who) + ": null reward or done"; return RG_GOTO_ERR_INVALID; }
+  RG_NEED(who, task_state, "task_state");
+  RG_NEED(who, sim_state, "sim_state");
+  RG_NEED(who, paths_ok(paths), "paths pointer");
+  RG_NEED(who, obs, "obs");
+  if (!observe_only) RG_NEED(who, reward && done, "reward or done");
   if (h->device < 0) return no_device(h);
   DeviceScope dev(h->device);
   if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
@@ -233,27 +208,18 @@ int rg_goto_create(const rg_goto_config *cfg, int32_t batch, int32_t device, rg_
   *out = nullptr;
   std::string err;
   if (!goto_validate(cfg, batch, err)) { g_create_err = err; return RG_GOTO_ERR_INVALID; }
-  if (device == RG_GOTO_DEVICE_NONE) {   // a host-only handle: the configuration, for argument checks on any machine
-    rg_goto_handle *h = new rg_goto_handle();
-    h->B = batch;
-    h->device = device;
-    h->cfg = *cfg;
-    h->c.B = batch; h->c.n_max = cfg->n_max;
-    h->stage_host.resize((size_t)kStageRows * batch);
-    *out = h;
-    return RG_GOTO_OK;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_err = "no HIP device available"; return RG_GOTO_ERR_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { g_create_err = "device index out of range"; return RG_GOTO_ERR_INVALID; }
-  DeviceScope dev(device);
-  if (dev.err != hipSuccess) { g_create_err = std::string("hipSetDevice failed: ") + hipGetErrorString(dev.err); return RG_GOTO_ERR_HIP; }
   rg_goto_handle *h = new rg_goto_handle();
   h->B = batch;
   h->device = device;
   h->cfg = *cfg;
   goto_fill_cfg(cfg, batch, h->c);
   h->stage_host.resize((size_t)kStageRows * batch);
+  if (device == RG_GOTO_DEVICE_NONE) {   // a host-only handle: the configuration, for argument checks on any machine
+    *out = h;
+    return RG_GOTO_OK;
+  }
+  std::optional<DeviceScope> dev;
+  if (const int rc = enter_device(device, &dev, RG_GOTO_ERR_NO_DEVICE, RG_GOTO_ERR_INVALID, RG_GOTO_ERR_HIP, g_create_err)) { delete h; return rc; }
   const hipError_t e = hipMalloc((void **)&h->stage, (size_t)kStageRows * batch * sizeof(double));
   if (e != hipSuccess) {
     g_create_err = std::string("hipMalloc failed: ") + hipGetErrorString(e);
@@ -277,9 +243,9 @@ int rg_goto_set_path(rg_goto_handle *h, const int32_t *idx_host, int32_t n, cons
                      const double *target, const double *x, const double *y, const double *s, const int32_t *first_same_x,
                      const rg_goto_path_ptrs *paths, double *task_state, void *stream) {
   if (!h) { g_create_err = "set_path: null handle"; return RG_GOTO_ERR_INVALID; }
-  if (!npts || !length || !target || !x || !y || !s || !first_same_x) { h->err = "set_path: null host array"; return RG_GOTO_ERR_INVALID; }
-  if (!paths_ok(paths)) { h->err = "set_path: null paths pointer"; return RG_GOTO_ERR_INVALID; }
-  if (!task_state) { h->err = "set_path: null task_state"; return RG_GOTO_ERR_INVALID; }
+  RG_NEED("set_path", npts && length && target && x && y && s && first_same_x, "host array");
+  RG_NEED("set_path", paths_ok(paths), "paths pointer");
+  RG_NEED("set_path", task_state, "task_state");
   const int B = h->B, n_max = h->c.n_max;
   if (idx_host ? (n < 1 || n > B) : n != B) { h->err = "set_path: n must be the batch without an index list, 1..batch with one"; return RG_GOTO_ERR_INVALID; }
   const size_t sn = (size_t)n;
@@ -340,11 +306,11 @@ int rg_goto_set_path(rg_goto_handle *h, const int32_t *idx_host, int32_t n, cons
 int rg_goto_pre_step(rg_goto_handle *h, const double *task_state, const double *sim_state, const rg_goto_path_ptrs *paths,
                      const float *action, float *cmd_out, void *stream) {
   if (!h) { g_create_err = "pre_step: null handle"; return RG_GOTO_ERR_INVALID; }
-  if (!task_state) { h->err = "pre_step: null task_state"; return RG_GOTO_ERR_INVALID; }
-  if (!sim_state) { h->err = "pre_step: null sim_state"; return RG_GOTO_ERR_INVALID; }
-  if (!paths_ok(paths)) { h->err = "pre_step: null paths pointer"; return RG_GOTO_ERR_INVALID; }
-  if (!action) { h->err = "pre_step: null action"; return RG_GOTO_ERR_INVALID; }
-  if (!cmd_out) { h->err = "pre_step: null cmd_out"; return RG_GOTO_ERR_INVALID; }
+  RG_NEED("pre_step", task_state, "task_state");
+  RG_NEED("pre_step", sim_state, "sim_state");
+  RG_NEED("pre_step", paths_ok(paths), "paths pointer");
+  RG_NEED("pre_step", action, "action");
+  RG_NEED("pre_step", cmd_out, "cmd_out");
   if (h->device < 0) return no_device(h);
   DeviceScope dev(h->device);
   if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);

@@ -1,7 +1,7 @@
 // rg_goto_dev.inc -- device code of the go-to-target task shared by rg_goto.hip (the tick) and rg_episode.hip (the
 // observation of a reset on the device): the kernel-side configuration, the path view, and steps 1 and 2 of the tick of
-// include/rg_goto.h -- window, visible points, chain, interpolation -- for one robot on one 64-lane wave.
-// Included after `#pragma clang fp contract(off)`, inside the including file's anonymous namespace.
+// include/rg_goto.h -- window, visible points, chain, interpolation -- for one robot on one 64-lane wave; and the host-side
+// checks and fills of rg_goto_config (on the helpers of rg_host.h).  Included after `#pragma clang fp contract(off)`, inside the including file's anonymous namespace.
 
 constexpr int kWave = 64;
 constexpr int kMaxVis = RG_GOTO_MAX_VISIBLE;
@@ -19,6 +19,10 @@ struct Paths {
   const int *fsx;
   const double *hdr;
 };
+
+inline bool paths_ok(const rg_goto_path_ptrs *p) { return p && p->x && p->y && p->s && p->first_same_x && p->hdr; }
+
+inline Paths to_paths(const rg_goto_path_ptrs *p) { return {p->x, p->y, p->s, p->first_same_x, p->hdr}; }
 
 // (d, i) <- the lexicographic minimum over the wave, in every lane
 __device__ __forceinline__ void wave_argmin(double &d, int &i) {
@@ -171,53 +175,27 @@ inline void goto_fill_cfg(const rg_goto_config *cfg, int batch, GotoCfg &c) {
 
 // The checks of rg_goto_create on the configuration and the batch; false: err names the field (host)
 inline bool goto_validate(const rg_goto_config *cfg, int32_t batch, std::string &err) {
-  char msg[200];
-  if (cfg->abi_version != RG_GOTO_ABI_VERSION) {
-    snprintf(msg, sizeof(msg), "config.abi_version: %d, this library is version %d", cfg->abi_version, RG_GOTO_ABI_VERSION);
-    err = msg;
+  const RealField reals[] = {{"window_height", &cfg->window_height, 1, kPositive}, {"window_top_width", &cfg->window_top_width, 1, kPositive},
+                             {"window_bottom_width", &cfg->window_bottom_width, 1, kPositive}, {"window_distance", &cfg->window_distance, 1, kFinite},
+                             {"max_track_err", &cfg->max_track_err, 1, kPositive}, {"progress_window", &cfg->progress_window, 1, kPositive},
+                             {"progress_limit", &cfg->progress_limit, 1, kPositive}, {"target_radius", &cfg->target_radius, 1, kPositive},
+                             {"time_penalty", &cfg->time_penalty, 1, kFinite}, {"checkpoint_reward_total", &cfg->checkpoint_reward_total, 1, kFinite},
+                             {"max_time", &cfg->max_time, 1, kPositive}, {"continuity_break", &cfg->continuity_break, 1, kPositive},
+                             {"action_low", cfg->action_low, 2, kFinite}, {"action_high", cfg->action_high, 2, kFinite},
+                             {"cmd_offset", cfg->cmd_offset, 3, kFinite}, {"dt_sim", &cfg->dt_sim, 1, kPositive}};
+  if (!check_abi("config.", cfg->abi_version, RG_GOTO_ABI_VERSION, err) || !check_reserved("config.", "reserved0", cfg->reserved0, err) ||
+      !check_reserved("config.", "reserved1", cfg->reserved1, err) || !check_batch(batch, RG_GOTO_MAX_BATCH, err) ||
+      !check_reals("config.", reals, err))
     return false;
-  }
-  if (cfg->reserved0 != 0) { err = "config.reserved0: must be 0"; return false; }
-  if (cfg->reserved1 != 0) { err = "config.reserved1: must be 0"; return false; }
-  if (batch < 1 || batch > RG_GOTO_MAX_BATCH) {
-    snprintf(msg, sizeof(msg), "batch: %d outside [1, %d]", batch, RG_GOTO_MAX_BATCH);
-    err = msg;
-    return false;
-  }
-  struct F { const char *name; const double *p; int n; bool positive; };
-  const F fields[] = {{"window_height", &cfg->window_height, 1, true}, {"window_top_width", &cfg->window_top_width, 1, true},
-                      {"window_bottom_width", &cfg->window_bottom_width, 1, true}, {"window_distance", &cfg->window_distance, 1, false},
-                      {"max_track_err", &cfg->max_track_err, 1, true}, {"progress_window", &cfg->progress_window, 1, true},
-                      {"progress_limit", &cfg->progress_limit, 1, true}, {"target_radius", &cfg->target_radius, 1, true},
-                      {"time_penalty", &cfg->time_penalty, 1, false}, {"checkpoint_reward_total", &cfg->checkpoint_reward_total, 1, false},
-                      {"max_time", &cfg->max_time, 1, true}, {"continuity_break", &cfg->continuity_break, 1, true},
-                      {"action_low", cfg->action_low, 2, false}, {"action_high", cfg->action_high, 2, false},
-                      {"cmd_offset", cfg->cmd_offset, 3, false}, {"dt_sim", &cfg->dt_sim, 1, true}};
-  for (const F &f : fields)
-    for (int i = 0; i < f.n; i++) {
-      const double v = f.p[i];
-      if (!std::isfinite(v) || (f.positive && !(v > 0))) {
-        if (f.n > 1) snprintf(msg, sizeof(msg), "config.%s[%d]: %g is not finite", f.name, i, v);
-        else snprintf(msg, sizeof(msg), "config.%s: %g must be finite%s", f.name, v, f.positive ? " and > 0" : "");
-        err = msg;
-        return false;
-      }
-    }
   for (int i = 0; i < 2; i++)
     if (cfg->action_low[i] > cfg->action_high[i]) {
+      char msg[200];
       snprintf(msg, sizeof(msg), "config.action_low[%d]: %g above action_high[%d] = %g", i, cfg->action_low[i], i, cfg->action_high[i]);
       err = msg;
       return false;
     }
-  struct I { const char *name; int v, lo, hi; };
-  const I ints[] = {{"substeps", cfg->substeps, 1, RG_SRB_MAX_SUBSTEPS}, {"num_cam_pts", cfg->num_cam_pts, 1, RG_GOTO_MAX_CAM_PTS},
-                    {"num_checkpoints", cfg->num_checkpoints, 1, RG_GOTO_MAX_CHECKPOINTS}, {"n_max", cfg->n_max, 2, RG_GOTO_MAX_PATH},
-                    {"max_visible", cfg->max_visible, 2, RG_GOTO_MAX_VISIBLE}};
-  for (const I &f : ints)
-    if (f.v < f.lo || f.v > f.hi) {
-      snprintf(msg, sizeof(msg), "config.%s: %d outside [%d, %d]", f.name, f.v, f.lo, f.hi);
-      err = msg;
-      return false;
-    }
-  return true;
+  const IntField ints[] = {{"substeps", cfg->substeps, 1, RG_SRB_MAX_SUBSTEPS}, {"num_cam_pts", cfg->num_cam_pts, 1, RG_GOTO_MAX_CAM_PTS},
+                           {"num_checkpoints", cfg->num_checkpoints, 1, RG_GOTO_MAX_CHECKPOINTS}, {"n_max", cfg->n_max, 2, RG_GOTO_MAX_PATH},
+                           {"max_visible", cfg->max_visible, 2, RG_GOTO_MAX_VISIBLE}};
+  return check_ints("config.", ints, err);
 }

@@ -1,16 +1,19 @@
-// rg_agent_host.h -- the host helpers that rg_policy.hip, rg_ppo.hip and rg_ddpg.hip share: the device scope, the workspace
-// arithmetic, the layer-layout rule, the checks of a configuration's fields and the error helpers.  Every message is formed
-// here once; the callers give the prefix ("config.", "policy_cfg.", "ppo_cfg.") and their API's status codes.
+// rg_host.h -- the host helpers that every translation unit of the library but the controller's shares: the device scope and
+// the device preamble of a create, the workspace arithmetic, the layer-layout rule, the checks of a configuration's fields
+// and the error helpers.  Every message is formed here once; the callers give the prefix ("config.", "policy_cfg.",
+// "ppo_cfg.") and their API's status codes.
 // rg_mpc.hip does not include it, so the source hash behind profiles/ does not move.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <optional>
 #include <string>
 
 namespace {
 
+// The calling thread's current device is restored on scope exit (rg_mpc.h conventions).
 struct DeviceScope {
   int prev = -1;
   bool switched = false;
@@ -21,6 +24,19 @@ struct DeviceScope {
   }
   ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
 };
+
+// The device preamble of a create: a device exists, `device` is one of them and, where the caller gives a scope to enter (its
+// own, because it lives to the end of the create), the switch went through.  0, every API's OK, or the status of the caller's
+// that applies, with the text in err.
+inline int enter_device(int device, std::optional<DeviceScope> *scope, int st_no_device, int st_invalid, int st_hip, std::string &err) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { err = "no HIP device available"; return st_no_device; }
+  if (device < 0 || device >= ndev) { err = "device index out of range"; return st_invalid; }
+  if (!scope) return 0;
+  scope->emplace(device);
+  if ((*scope)->err != hipSuccess) { err = std::string("hipSetDevice failed: ") + hipGetErrorString((*scope)->err); return st_hip; }
+  return 0;
+}
 
 inline size_t round8(size_t n) { return (n + 7) & ~(size_t)7; }
 
@@ -47,6 +63,20 @@ inline bool check_abi(const char *prefix, int got, int want, std::string &err) {
   if (got == want) return true;
   char msg[200];
   snprintf(msg, sizeof(msg), "%sabi_version: %d, this library is version %d", prefix, got, want);
+  err = msg;
+  return false;
+}
+
+inline bool check_reserved(const char *prefix, const char *name, int value, std::string &err) {
+  if (value == 0) return true;
+  err = std::string(prefix) + name + ": must be 0";
+  return false;
+}
+
+inline bool check_batch(int batch, int max, std::string &err) {
+  if (batch >= 1 && batch <= max) return true;
+  char msg[96];
+  snprintf(msg, sizeof(msg), "batch: %d outside [1, %d]", batch, max);
   err = msg;
   return false;
 }
@@ -84,24 +114,27 @@ inline bool check_widths(const char *prefix, const char *name, const int32_t *w,
 }
 
 enum RealKind { kNonNegative, kBelowOne, kPositive, kUnit, kUnitPositive, kFinite };   // >= 0; [0, 1); > 0; [0, 1]; (0, 1]; any finite
-struct RealField { const char *name; double v; RealKind kind; };
+struct RealField { const char *name; const double *p; int n; RealKind kind; };   // a scalar: &cfg->x, 1; an array (n > 1) is kFinite
 
 template <size_t N>
 bool check_reals(const char *prefix, const RealField (&fields)[N], std::string &err) {
   const char *want[] = {">= 0", "in [0, 1)", "> 0", "in [0, 1]", "in (0, 1]", "finite"};
-  for (const RealField &f : fields) {
-    bool ok = std::isfinite(f.v);
-    if (ok && f.kind != kFinite) ok = f.v >= 0;
-    if (ok && f.kind == kBelowOne) ok = f.v < 1;
-    if (ok && (f.kind == kPositive || f.kind == kUnitPositive)) ok = f.v > 0;
-    if (ok && (f.kind == kUnit || f.kind == kUnitPositive)) ok = f.v <= 1;
-    if (!ok) {
-      char msg[200];
-      snprintf(msg, sizeof(msg), "%s%s: %g must be finite%s%s", prefix, f.name, f.v, f.kind == kFinite ? "" : " and ", f.kind == kFinite ? "" : want[f.kind]);
-      err = msg;
-      return false;
+  for (const RealField &f : fields)
+    for (int i = 0; i < f.n; i++) {
+      const double v = f.p[i];
+      bool ok = std::isfinite(v);
+      if (ok && f.kind != kFinite) ok = v >= 0;
+      if (ok && f.kind == kBelowOne) ok = v < 1;
+      if (ok && (f.kind == kPositive || f.kind == kUnitPositive)) ok = v > 0;
+      if (ok && (f.kind == kUnit || f.kind == kUnitPositive)) ok = v <= 1;
+      if (!ok) {
+        char msg[200];
+        if (f.n > 1) snprintf(msg, sizeof(msg), "%s%s[%d]: %g is not finite", prefix, f.name, i, v);
+        else snprintf(msg, sizeof(msg), "%s%s: %g must be finite%s%s", prefix, f.name, v, f.kind == kFinite ? "" : " and ", f.kind == kFinite ? "" : want[f.kind]);
+        err = msg;
+        return false;
+      }
     }
-  }
   return true;
 }
 
@@ -110,10 +143,10 @@ bool check_reals(const char *prefix, const RealField (&fields)[N], std::string &
 // version, the dimensions, both width lists and obs_clip.  The fields only the acting side reads are the caller's.
 inline bool check_policy_config(const char *prefix, const rg_policy_config *cfg, std::string &err) {
   if (!check_abi(prefix, cfg->abi_version, RG_POLICY_ABI_VERSION, err)) return false;
-  if (cfg->reserved0 != 0) { err = std::string(prefix) + "reserved0: must be 0"; return false; }
+  if (!check_reserved(prefix, "reserved0", cfg->reserved0, err)) return false;
   const IntField ints[] = {{"obs_dim", cfg->obs_dim, 1, RG_POLICY_MAX_OBS}, {"act_dim", cfg->act_dim, 1, RG_POLICY_MAX_ACT},
                            {"n_policy_layers", cfg->n_policy_layers, 0, RG_POLICY_MAX_LAYERS}, {"n_value_layers", cfg->n_value_layers, 0, RG_POLICY_MAX_LAYERS}};
-  const RealField reals[] = {{"obs_clip", cfg->obs_clip, kNonNegative}};
+  const RealField reals[] = {{"obs_clip", &cfg->obs_clip, 1, kNonNegative}};
   return check_ints(prefix, ints, err) &&
          check_widths(prefix, "policy_layers", cfg->policy_layers, cfg->n_policy_layers, RG_POLICY_MAX_LAYERS, RG_POLICY_MAX_WIDTH, err) &&
          check_widths(prefix, "value_layers", cfg->value_layers, cfg->n_value_layers, RG_POLICY_MAX_LAYERS, RG_POLICY_MAX_WIDTH, err) &&
@@ -129,7 +162,7 @@ int hip_fail(H *h, int status, const char *what, hipError_t e) {
   return status;
 }
 
-// api: "RG_POLICY", "RG_PPO", "RG_DDPG"
+// api: "RG_POLICY", "RG_GOTO", ...
 template <typename H>
 int no_device(H *h, int status, const char *api) {
   h->err = std::string("host-only handle (") + api + "_DEVICE_NONE): the arguments are valid, there is no device to run on";

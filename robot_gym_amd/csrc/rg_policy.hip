@@ -1,6 +1,6 @@
 // rg_policy.hip -- the acting and collecting side of the PPO agent of include/rg_policy.h.  Its own translation unit of
 // librg_mpc.so.  The noise stream, the normaliser's arithmetic, the workgroup sum and the layer descriptor are those of
-// rg_agent_dev.inc, which the agents' update files include too, and the host helpers those of rg_agent_host.h; rg_mpc.hip
+// rg_agent_dev.inc, which the agents' update files include too, and the host helpers those of rg_host.h; rg_mpc.hip
 // includes neither, so the source hash behind profiles/ is unaffected.  The act kernel's neuron (8 samples wide, where the
 // shared layer is 16) stays here.
 //
@@ -26,7 +26,7 @@
 #include <cstring>
 #include <string>
 #include "../../include/rg_policy.h"
-#include "rg_agent_host.h"
+#include "rg_host.h"
 
 #pragma clang fp contract(off)
 
@@ -291,7 +291,7 @@ struct rg_policy_handle {
 namespace {
 
 bool validate(const rg_policy_config *cfg, std::string &err) {
-  const RealField reals[] = {{"reward_clip", cfg->reward_clip, kNonNegative}, {"discount", cfg->discount, kUnit}, {"gae_lambda", cfg->gae_lambda, kUnit}};
+  const RealField reals[] = {{"reward_clip", &cfg->reward_clip, 1, kNonNegative}, {"discount", &cfg->discount, 1, kUnit}, {"gae_lambda", &cfg->gae_lambda, 1, kUnit}};
   return check_policy_config("config.", cfg, err) && check_reals("config.", reals, err);
 }
 
@@ -331,13 +331,7 @@ int rg_policy_create(const rg_policy_config *cfg, int32_t batch, int32_t device,
   if (!cfg || !out) { g_create_err = "create: null config or out"; return RG_POLICY_ERR_INVALID; }
   *out = nullptr;
   std::string err;
-  if (batch < 1 || batch > RG_POLICY_MAX_BATCH) {
-    char msg[96];
-    snprintf(msg, sizeof(msg), "batch: %d outside [1, %d]", batch, RG_POLICY_MAX_BATCH);
-    g_create_err = msg;
-    return RG_POLICY_ERR_INVALID;
-  }
-  if (!validate(cfg, err)) { g_create_err = err; return RG_POLICY_ERR_INVALID; }
+  if (!check_batch(batch, RG_POLICY_MAX_BATCH, err) || !validate(cfg, err)) { g_create_err = err; return RG_POLICY_ERR_INVALID; }
   rg_policy_handle *h = new rg_policy_handle();
   h->cfg = *cfg;
   h->B = batch;
@@ -357,11 +351,8 @@ int rg_policy_create(const rg_policy_config *cfg, int32_t batch, int32_t device,
     *out = h;
     return RG_POLICY_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_err = "no HIP device available"; delete h; return RG_POLICY_ERR_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { g_create_err = "device index out of range"; delete h; return RG_POLICY_ERR_INVALID; }
-  DeviceScope dev(device);
-  if (dev.err != hipSuccess) { g_create_err = std::string("hipSetDevice failed: ") + hipGetErrorString(dev.err); delete h; return RG_POLICY_ERR_HIP; }
+  std::optional<DeviceScope> dev;
+  if (const int rc = enter_device(device, &dev, RG_POLICY_ERR_NO_DEVICE, RG_POLICY_ERR_INVALID, RG_POLICY_ERR_HIP, g_create_err)) { delete h; return rc; }
   hipError_t e = hipMalloc((void **)&h->dev_cfg, sizeof(ActDev));
   if (e == hipSuccess) e = hipMalloc((void **)&h->part, sizeof(double) * (size_t)(cfg->obs_dim + 1) * h->G * kParts);
   if (e != hipSuccess) {

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <string>
 #include "../../include/rg_posctl.h"
+#include "rg_host.h"
 
 #pragma clang fp contract(off)
 
@@ -256,18 +257,6 @@ __global__ void __launch_bounds__(256) rg_posctl_torque_kernel(PosCfg c, int B, 
   }
 }
 
-// The calling thread's current device is restored on scope exit (rg_mpc.h conventions).
-struct DeviceScope {
-  int prev = -1;
-  bool switched = false;
-  hipError_t err = hipSuccess;
-  explicit DeviceScope(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess && prev >= 0; }
-  }
-  ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
-};
-
 thread_local std::string g_create_err;
 
 }  // namespace
@@ -281,36 +270,17 @@ struct rg_posctl_handle {
 namespace {
 
 bool validate(const rg_posctl_config *cfg, int32_t batch, std::string &err) {
-  char msg[160];
-  if (cfg->abi_version != RG_POSCTL_ABI_VERSION) {
-    snprintf(msg, sizeof(msg), "config.abi_version: %d, this library is version %d", cfg->abi_version, RG_POSCTL_ABI_VERSION);
-    err = msg;
+  const RealField reals[] = {{"hip", &cfg->hip, 1, kPositive}, {"leg", &cfg->leg, 1, kPositive}, {"foot", &cfg->foot, 1, kPositive},
+                             {"hip_v", cfg->hip_v, 12, kFinite}, {"pose_frames", cfg->pose_frames, 12, kFinite},
+                             {"start_frames", cfg->start_frames, 12, kFinite}, {"leg_offset", cfg->leg_offset, 4, kFinite},
+                             {"step_offset", &cfg->step_offset, 1, kFinite}, {"motor_kp", cfg->motor_kp, 12, kFinite},
+                             {"motor_kd", cfg->motor_kd, 12, kFinite}};
+  if (!check_abi("config.", cfg->abi_version, RG_POSCTL_ABI_VERSION, err) || !check_reserved("config.", "reserved0", cfg->reserved0, err) ||
+      !check_batch(batch, RG_POSCTL_MAX_BATCH, err) || !check_reals("config.", reals, err))
     return false;
-  }
-  if (cfg->reserved0 != 0) { err = "config.reserved0: must be 0"; return false; }
-  if (batch < 1 || batch > RG_POSCTL_MAX_BATCH) {
-    snprintf(msg, sizeof(msg), "batch: %d outside [1, %d]", batch, RG_POSCTL_MAX_BATCH);
-    err = msg;
-    return false;
-  }
-  struct F { const char *name; const double *p; int n; bool positive; };
-  const F fields[] = {{"hip", &cfg->hip, 1, true}, {"leg", &cfg->leg, 1, true}, {"foot", &cfg->foot, 1, true},
-                      {"hip_v", cfg->hip_v, 12, false}, {"pose_frames", cfg->pose_frames, 12, false},
-                      {"start_frames", cfg->start_frames, 12, false}, {"leg_offset", cfg->leg_offset, 4, false},
-                      {"step_offset", &cfg->step_offset, 1, false}, {"motor_kp", cfg->motor_kp, 12, false},
-                      {"motor_kd", cfg->motor_kd, 12, false}};
-  for (const F &f : fields)
-    for (int i = 0; i < f.n; i++) {
-      const double v = f.p[i];
-      if (!std::isfinite(v) || (f.positive && !(v > 0))) {
-        if (f.n > 1) snprintf(msg, sizeof(msg), "config.%s[%d]: %g is not finite", f.name, i, v);
-        else snprintf(msg, sizeof(msg), "config.%s: %g must be finite%s", f.name, v, f.positive ? " and > 0" : "");
-        err = msg;
-        return false;
-      }
-    }
   // phi_swing divides by 1 - step_offset and phi_stance by step_offset
   if (!(cfg->step_offset > 0 && cfg->step_offset < 1)) {
+    char msg[160];
     snprintf(msg, sizeof(msg), "config.step_offset: %g outside (0, 1)", cfg->step_offset);
     err = msg;
     return false;
@@ -318,11 +288,8 @@ bool validate(const rg_posctl_config *cfg, int32_t batch, std::string &err) {
   return true;
 }
 
-int launch_status(rg_posctl_handle *h, const char *what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { h->err = std::string(what) + ": " + hipGetErrorString(e); return RG_POSCTL_ERR_HIP; }
-  return RG_POSCTL_OK;
-}
+int hip_fail(rg_posctl_handle *h, const char *what, hipError_t e) { return hip_fail(h, RG_POSCTL_ERR_HIP, what, e); }
+int launch_status(rg_posctl_handle *h, const char *what) { return launch_status(h, RG_POSCTL_ERR_HIP, what); }
 
 }  // namespace
 
@@ -337,9 +304,8 @@ int rg_posctl_create(const rg_posctl_config *cfg, int32_t batch, int32_t device,
   *out = nullptr;
   std::string err;
   if (!validate(cfg, batch, err)) { g_create_err = err; return RG_POSCTL_ERR_INVALID; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_err = "no HIP device available"; return RG_POSCTL_ERR_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { g_create_err = "device index out of range"; return RG_POSCTL_ERR_INVALID; }
+  // no scope: create runs nothing on the device
+  if (const int rc = enter_device(device, nullptr, RG_POSCTL_ERR_NO_DEVICE, RG_POSCTL_ERR_INVALID, RG_POSCTL_ERR_HIP, g_create_err)) return rc;
   rg_posctl_handle *h = new rg_posctl_handle();
   h->B = batch;
   h->device = device;
@@ -367,7 +333,7 @@ int rg_posctl_bezier_step(rg_posctl_handle *h, double t, const double *t_robot, 
   if (!h) { g_create_err = "bezier_step: null handle"; return RG_POSCTL_ERR_INVALID; }
   if (!state || !angles) { h->err = "bezier_step: null state or angles"; return RG_POSCTL_ERR_INVALID; }
   DeviceScope dev(h->device);
-  if (dev.err != hipSuccess) { h->err = std::string("hipSetDevice failed: ") + hipGetErrorString(dev.err); return RG_POSCTL_ERR_HIP; }
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
   hipLaunchKernelGGL(rg_posctl_bezier_kernel, dim3((h->B + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, h->c, h->B, t,
                      t_robot, params, state, angles);
   return launch_status(h, "rg_posctl_bezier_kernel launch");
@@ -377,7 +343,7 @@ int rg_posctl_pose(rg_posctl_handle *h, const float *pose, float *angles, void *
   if (!h) { g_create_err = "pose: null handle"; return RG_POSCTL_ERR_INVALID; }
   if (!pose || !angles) { h->err = "pose: null pose or angles"; return RG_POSCTL_ERR_INVALID; }
   DeviceScope dev(h->device);
-  if (dev.err != hipSuccess) { h->err = std::string("hipSetDevice failed: ") + hipGetErrorString(dev.err); return RG_POSCTL_ERR_HIP; }
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
   hipLaunchKernelGGL(rg_posctl_pose_kernel, dim3((h->B + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, h->c, h->B, pose,
                      angles);
   return launch_status(h, "rg_posctl_pose_kernel launch");
@@ -389,7 +355,7 @@ int rg_posctl_position_to_torque(rg_posctl_handle *h, const float *angles, const
   if (!angles || !q || !qd || !tau) { h->err = "position_to_torque: null pointer"; return RG_POSCTL_ERR_INVALID; }
   if (substeps < 1 || substeps > RG_POSCTL_MAX_SUBSTEPS) { h->err = "position_to_torque: substeps outside [1, 1024]"; return RG_POSCTL_ERR_INVALID; }
   DeviceScope dev(h->device);
-  if (dev.err != hipSuccess) { h->err = std::string("hipSetDevice failed: ") + hipGetErrorString(dev.err); return RG_POSCTL_ERR_HIP; }
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
   const size_t total = (size_t)h->B * 12;
   hipLaunchKernelGGL(rg_posctl_torque_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->c, h->B,
                      substeps, angles, q, qd, tau);

@@ -1,7 +1,7 @@
 // rg_ppo.hip -- the PPO update of include/rg_ppo.h.  Its own translation unit of librg_mpc.so.  A layer's forward and backward
 // pass over a tile, the normaliser's arithmetic, the workgroup sums and the bodies of the transpose and slab-finish
 // kernels are those of rg_agent_dev.inc, which the acting side includes too (so the forward pass gives rg_policy_act's mean
-// to the bit from one text), and the host helpers those of rg_agent_host.h; rg_mpc.hip includes neither, so the source hash
+// to the bit from one text), and the host helpers those of rg_host.h; rg_mpc.hip includes neither, so the source hash
 // behind profiles/ is unaffected.
 //
 // Sweeps (rg_ppo_policy_forward_kernel, rg_ppo_policy_backward_kernel, rg_ppo_value_backward_kernel): G workgroups of 256
@@ -24,7 +24,7 @@
 #include <cstring>
 #include <string>
 #include "../../include/rg_ppo.h"
-#include "rg_agent_host.h"
+#include "rg_host.h"
 
 #pragma clang fp contract(off)
 
@@ -399,9 +399,9 @@ namespace {
 bool validate_ppo(const rg_ppo_config *cfg, std::string &err) {
   const IntField ints[] = {{"epochs_policy", cfg->epochs_policy, 0, RG_PPO_MAX_EPOCHS}, {"epochs_value", cfg->epochs_value, 0, RG_PPO_MAX_EPOCHS},
                            {"conv_logpdf", cfg->conv_logpdf, RG_PPO_LOGPDF_EXACT, RG_PPO_LOGPDF_REFERENCE}};
-  const RealField reals[] = {{"policy_lr", cfg->policy_lr, kNonNegative}, {"value_lr", cfg->value_lr, kNonNegative}, {"beta1", cfg->beta1, kBelowOne},
-                             {"beta2", cfg->beta2, kBelowOne}, {"adam_eps", cfg->adam_eps, kPositive}, {"kl_target", cfg->kl_target, kPositive},
-                             {"kl_cutoff_factor", cfg->kl_cutoff_factor, kNonNegative}, {"kl_cutoff_coef", cfg->kl_cutoff_coef, kNonNegative}};
+  const RealField reals[] = {{"policy_lr", &cfg->policy_lr, 1, kNonNegative}, {"value_lr", &cfg->value_lr, 1, kNonNegative}, {"beta1", &cfg->beta1, 1, kBelowOne},
+                             {"beta2", &cfg->beta2, 1, kBelowOne}, {"adam_eps", &cfg->adam_eps, 1, kPositive}, {"kl_target", &cfg->kl_target, 1, kPositive},
+                             {"kl_cutoff_factor", &cfg->kl_cutoff_factor, 1, kNonNegative}, {"kl_cutoff_coef", &cfg->kl_cutoff_coef, 1, kNonNegative}};
   return check_abi("ppo_cfg.", cfg->abi_version, RG_PPO_ABI_VERSION, err) && check_ints("ppo_cfg.", ints, err) && check_reals("ppo_cfg.", reals, err);
 }
 
@@ -591,11 +591,8 @@ int rg_ppo_create(const rg_policy_config *policy_cfg, const rg_ppo_config *ppo_c
     *out = h;
     return RG_PPO_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_err = "no HIP device available"; delete h; return RG_PPO_ERR_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { g_create_err = "device index out of range"; delete h; return RG_PPO_ERR_INVALID; }
-  DeviceScope dev(device);
-  if (dev.err != hipSuccess) { g_create_err = std::string("hipSetDevice failed: ") + hipGetErrorString(dev.err); delete h; return RG_PPO_ERR_HIP; }
+  std::optional<DeviceScope> dev;
+  if (const int rc = enter_device(device, &dev, RG_PPO_ERR_NO_DEVICE, RG_PPO_ERR_INVALID, RG_PPO_ERR_HIP, g_create_err)) { delete h; return rc; }
   // the sweeps' tiles may need more dynamic LDS than the default limit of a launch.  The attribute belongs to the function and
   // the device, not to the handle: it is set to the most any configuration of the ABI needs, so handles do not undo each other
   hipError_t e = hipFuncSetAttribute((const void *)rg_ppo_policy_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);

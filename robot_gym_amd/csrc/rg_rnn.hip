@@ -1,6 +1,6 @@
 // rg_rnn.hip -- the recurrent Gaussian policy of include/rg_rnn.h: one tick (rg_rnn_act) and T ticks with the state kept on
 // the chip (rg_rnn_unroll).  Its own translation unit of librg_mpc.so.  The noise stream, the normaliser's arithmetic and the
-// layer descriptor are those of rg_agent_dev.inc and the host helpers those of rg_agent_host.h; rg_mpc.hip includes neither
+// layer descriptor are those of rg_agent_dev.inc and the host helpers those of rg_host.h; rg_mpc.hip includes neither
 // this file nor them, so the source hash behind profiles/ is unaffected.
 //
 // A tile of kTile robots per workgroup.  One output neuron per thread with kTile accumulators in registers; the activations
@@ -30,7 +30,7 @@
 #include <string>
 #include "../../include/rg_policy.h"
 #include "../../include/rg_rnn.h"
-#include "rg_agent_host.h"
+#include "rg_host.h"
 
 #pragma clang fp contract(off)
 
@@ -307,11 +307,11 @@ namespace {
 bool validate(const rg_rnn_config *cfg, std::string &err) {
   const char *prefix = "config.";
   if (!check_abi(prefix, cfg->abi_version, RG_RNN_ABI_VERSION, err)) return false;
-  if (cfg->reserved0 != 0) { err = std::string(prefix) + "reserved0: must be 0"; return false; }
+  if (!check_reserved(prefix, "reserved0", cfg->reserved0, err)) return false;
   const IntField ints[] = {{"obs_dim", cfg->obs_dim, 1, RG_RNN_MAX_OBS}, {"act_dim", cfg->act_dim, 1, RG_RNN_MAX_ACT},
                            {"n_policy_layers", cfg->n_policy_layers, 0, RG_RNN_MAX_DENSE}, {"gru_units", cfg->gru_units, 1, RG_RNN_MAX_UNITS},
                            {"n_value_layers", cfg->n_value_layers, 0, RG_RNN_MAX_VALUE_LAYERS}};
-  const RealField reals[] = {{"obs_clip", cfg->obs_clip, kNonNegative}};
+  const RealField reals[] = {{"obs_clip", &cfg->obs_clip, 1, kNonNegative}};
   return check_ints(prefix, ints, err) &&
          check_widths(prefix, "policy_layers", cfg->policy_layers, cfg->n_policy_layers, RG_RNN_MAX_DENSE, RG_RNN_MAX_WIDTH, err) &&
          check_widths(prefix, "value_layers", cfg->value_layers, cfg->n_value_layers, RG_RNN_MAX_VALUE_LAYERS, RG_RNN_MAX_WIDTH, err) &&
@@ -369,13 +369,7 @@ int rg_rnn_create(const rg_rnn_config *cfg, int32_t batch, int32_t device, rg_rn
   if (!cfg || !out) { g_create_err = "create: null config or out"; return RG_RNN_ERR_INVALID; }
   *out = nullptr;
   std::string err;
-  if (batch < 1 || batch > RG_RNN_MAX_BATCH) {
-    char msg[96];
-    snprintf(msg, sizeof(msg), "batch: %d outside [1, %d]", batch, RG_RNN_MAX_BATCH);
-    g_create_err = msg;
-    return RG_RNN_ERR_INVALID;
-  }
-  if (!validate(cfg, err)) { g_create_err = err; return RG_RNN_ERR_INVALID; }
+  if (!check_batch(batch, RG_RNN_MAX_BATCH, err) || !validate(cfg, err)) { g_create_err = err; return RG_RNN_ERR_INVALID; }
   rg_rnn_handle *h = new rg_rnn_handle();
   h->cfg = *cfg;
   h->B = batch;
@@ -393,11 +387,8 @@ int rg_rnn_create(const rg_rnn_config *cfg, int32_t batch, int32_t device, rg_rn
     *out = h;
     return RG_RNN_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_err = "no HIP device available"; delete h; return RG_RNN_ERR_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { g_create_err = "device index out of range"; delete h; return RG_RNN_ERR_INVALID; }
-  DeviceScope dev(device);
-  if (dev.err != hipSuccess) { g_create_err = std::string("hipSetDevice failed: ") + hipGetErrorString(dev.err); delete h; return RG_RNN_ERR_HIP; }
+  std::optional<DeviceScope> dev;
+  if (const int rc = enter_device(device, &dev, RG_RNN_ERR_NO_DEVICE, RG_RNN_ERR_INVALID, RG_RNN_ERR_HIP, g_create_err)) { delete h; return rc; }
   hipError_t e = hipMalloc((void **)&h->dev_cfg, sizeof(RnnDev));
   if (e != hipSuccess) {
     g_create_err = std::string("hipMalloc failed: ") + hipGetErrorString(e);

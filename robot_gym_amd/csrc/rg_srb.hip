@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 #include "../../include/rg_srb.h"
+#include "rg_host.h"
 
 #pragma clang fp contract(off)
 
@@ -202,11 +203,8 @@ int rg_srb_create(const rg_srb_config *cfg, int32_t batch, int32_t device, rg_sr
   std::string err;
   double Iinv[9];
   if (!srb_validate(cfg, batch, Iinv, err)) { g_create_err = err; return RG_SRB_ERR_INVALID; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_err = "no HIP device available"; return RG_SRB_ERR_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { g_create_err = "device index out of range"; return RG_SRB_ERR_INVALID; }
-  DeviceScope dev(device);
-  if (dev.err != hipSuccess) { g_create_err = std::string("hipSetDevice failed: ") + hipGetErrorString(dev.err); return RG_SRB_ERR_HIP; }
+  std::optional<DeviceScope> dev;
+  if (const int rc = enter_device(device, &dev, RG_SRB_ERR_NO_DEVICE, RG_SRB_ERR_INVALID, RG_SRB_ERR_HIP, g_create_err)) return rc;
   rg_srb_handle *h = new rg_srb_handle();
   h->B = batch;
   h->device = device;

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 #include "../../include/rg_srb.h"
+#include "rg_host.h"
 
 #pragma clang fp contract(off)
 

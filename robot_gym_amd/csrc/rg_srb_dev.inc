@@ -1,7 +1,7 @@
 // rg_srb_dev.inc -- code of the single-rigid-body simulator shared by rg_srb.hip and rg_episode.hip (the reset on the
 // device): the kernel-side configuration, the observation writer (step 4 of include/rg_srb.h), the body of a reset for
-// one (robot, leg) lane, and the host-side checks and fills of rg_srb_config.  Included after `#pragma clang fp
-// contract(off)` and rg_mpc_dev.h, inside the including file's anonymous namespace.
+// one (robot, leg) lane, and the host-side checks and fills of rg_srb_config (on the helpers of rg_host.h).  Included after
+// `#pragma clang fp contract(off)` and rg_mpc_dev.h, inside the including file's anonymous namespace.
 
 constexpr double kIkDone = 1e-18;      // squared foot error (1e-9 m) below which the reset stops repeating the IK
 
@@ -16,6 +16,12 @@ struct Obs {
   int *contact;
   double *t_robot;
 };
+
+inline bool obs_ok(const rg_srb_obs_ptrs *o) {
+  return o && o->rpy && o->rpy_rate && o->v_world && o->quat && o->q && o->foot_pos && o->jac && o->contact && o->t_robot;
+}
+
+inline Obs to_obs(const rg_srb_obs_ptrs *o) { return {o->rpy, o->rpy_rate, o->v_world, o->quat, o->q, o->foot_pos, o->jac, o->contact, o->t_robot}; }
 
 // rotation of the quaternion (x, y, z, w), row-major
 __device__ __forceinline__ void quat_rot(const double *qt, double *R) {
@@ -151,35 +157,16 @@ inline const char *check_inertia(const double *I, double *inv) {
 // The checks of rg_srb_create on the configuration and the batch; false: err names the field.  Iinv: the inverse inertia.
 inline bool srb_validate(const rg_srb_config *cfg, int32_t batch, double *Iinv, std::string &err) {
   char msg[200];
-  if (cfg->abi_version != RG_SRB_ABI_VERSION) {
-    snprintf(msg, sizeof(msg), "config.abi_version: %d, this library is version %d", cfg->abi_version, RG_SRB_ABI_VERSION);
-    err = msg;
+  const RealField reals[] = {{"mass", &cfg->mass, 1, kPositive}, {"inertia", cfg->inertia, 9, kFinite}, {"gravity", &cfg->gravity, 1, kPositive},
+                             {"body_height", &cfg->body_height, 1, kPositive}, {"hip", cfg->hip, 12, kFinite}, {"motor_dir", cfg->motor_dir, 12, kFinite},
+                             {"motor_off", cfg->motor_off, 12, kFinite}, {"jxyz", cfg->jxyz, 36, kFinite}, {"jrpy", cfg->jrpy, 36, kFinite},
+                             {"jaxis", cfg->jaxis, 36, kFinite}, {"toe_xyz", cfg->toe_xyz, 12, kFinite}, {"toe_com", cfg->toe_com, 12, kFinite},
+                             {"base_com", cfg->base_com, 3, kFinite}, {"init_q", cfg->init_q, 12, kFinite}, {"ik_damping", &cfg->ik_damping, 1, kFinite},
+                             {"ik_max_step", &cfg->ik_max_step, 1, kPositive}, {"dt_sim", &cfg->dt_sim, 1, kPositive},
+                             {"fall_height_scale", &cfg->fall_height_scale, 1, kFinite}, {"fall_tilt", &cfg->fall_tilt, 1, kPositive}};
+  if (!check_abi("config.", cfg->abi_version, RG_SRB_ABI_VERSION, err) || !check_reserved("config.", "reserved0", cfg->reserved0, err) ||
+      !check_batch(batch, RG_SRB_MAX_BATCH, err) || !check_reals("config.", reals, err))
     return false;
-  }
-  if (cfg->reserved0 != 0) { err = "config.reserved0: must be 0"; return false; }
-  if (batch < 1 || batch > RG_SRB_MAX_BATCH) {
-    snprintf(msg, sizeof(msg), "batch: %d outside [1, %d]", batch, RG_SRB_MAX_BATCH);
-    err = msg;
-    return false;
-  }
-  struct F { const char *name; const double *p; int n; bool positive; };
-  const F fields[] = {{"mass", &cfg->mass, 1, true}, {"inertia", cfg->inertia, 9, false}, {"gravity", &cfg->gravity, 1, true},
-                      {"body_height", &cfg->body_height, 1, true}, {"hip", cfg->hip, 12, false}, {"motor_dir", cfg->motor_dir, 12, false},
-                      {"motor_off", cfg->motor_off, 12, false}, {"jxyz", cfg->jxyz, 36, false}, {"jrpy", cfg->jrpy, 36, false},
-                      {"jaxis", cfg->jaxis, 36, false}, {"toe_xyz", cfg->toe_xyz, 12, false}, {"toe_com", cfg->toe_com, 12, false},
-                      {"base_com", cfg->base_com, 3, false}, {"init_q", cfg->init_q, 12, false}, {"ik_damping", &cfg->ik_damping, 1, false},
-                      {"ik_max_step", &cfg->ik_max_step, 1, true}, {"dt_sim", &cfg->dt_sim, 1, true},
-                      {"fall_height_scale", &cfg->fall_height_scale, 1, false}, {"fall_tilt", &cfg->fall_tilt, 1, true}};
-  for (const F &f : fields)
-    for (int i = 0; i < f.n; i++) {
-      const double v = f.p[i];
-      if (!std::isfinite(v) || (f.positive && !(v > 0))) {
-        if (f.n > 1) snprintf(msg, sizeof(msg), "config.%s[%d]: %g is not finite", f.name, i, v);
-        else snprintf(msg, sizeof(msg), "config.%s: %g must be finite%s", f.name, v, f.positive ? " and > 0" : "");
-        err = msg;
-        return false;
-      }
-    }
   if (const char *what = check_inertia(cfg->inertia, Iinv)) { err = std::string("config.inertia: ") + what; return false; }
   for (int i = 0; i < 12; i++) {
     if (!(cfg->motor_dir[i] == 1.0 || cfg->motor_dir[i] == -1.0)) {
@@ -194,12 +181,8 @@ inline bool srb_validate(const rg_srb_config *cfg, int32_t batch, double *Iinv, 
       return false;
     }
   }
-  if (cfg->ik_iters < 1 || cfg->ik_iters > 64) { snprintf(msg, sizeof(msg), "config.ik_iters: %d outside [1, 64]", cfg->ik_iters); err = msg; return false; }
-  if (cfg->substeps < 1 || cfg->substeps > RG_SRB_MAX_SUBSTEPS) {
-    snprintf(msg, sizeof(msg), "config.substeps: %d outside [1, %d]", cfg->substeps, RG_SRB_MAX_SUBSTEPS);
-    err = msg;
-    return false;
-  }
+  const IntField ints[] = {{"ik_iters", cfg->ik_iters, 1, 64}, {"substeps", cfg->substeps, 1, RG_SRB_MAX_SUBSTEPS}};
+  if (!check_ints("config.", ints, err)) return false;
   if (cfg->ik_damping < 0) { snprintf(msg, sizeof(msg), "config.ik_damping: %g must be >= 0", cfg->ik_damping); err = msg; return false; }
   if (!(cfg->fall_height_scale >= 0 && cfg->fall_height_scale < 1)) {
     snprintf(msg, sizeof(msg), "config.fall_height_scale: %g outside [0, 1)", cfg->fall_height_scale);

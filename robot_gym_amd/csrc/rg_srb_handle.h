@@ -1,7 +1,7 @@
 // rg_srb_handle.h -- what the translation units of the simulator (rg_srb.hip, rg_srb_terrain.hip, rg_srb_contact.hip) share on the HOST side: the handle of include/rg_srb.h,
 // the small helpers of its entry points, and the calls by which rg_srb.hip (the plane) hands a tick, a reset or the end of
 // a handle's life over to rg_srb_terrain.hip once a terrain is set.  Private to robot_gym_amd/csrc.  Included after
-// rg_srb_dev.inc (SrbCfg, Obs and DevCfg are the including file's), outside its anonymous namespace.
+// rg_host.h and rg_srb_dev.inc (SrbCfg, Obs and DevCfg are the including file's), outside its anonymous namespace.
 #ifndef RG_SRB_HANDLE_H
 #define RG_SRB_HANDLE_H
 
@@ -44,33 +44,8 @@ void rg_srb_thread_error(const char *text);
 
 namespace {
 
-// The calling thread's current device is restored on scope exit (rg_mpc.h conventions).
-struct DeviceScope {
-  int prev = -1;
-  bool switched = false;
-  hipError_t err = hipSuccess;
-  explicit DeviceScope(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) { err = hipSetDevice(dev); switched = err == hipSuccess && prev >= 0; }
-  }
-  ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
-};
-
-inline int hip_fail(rg_srb_handle *h, const char *what, hipError_t e) {
-  h->err = std::string(what) + ": " + hipGetErrorString(e);
-  return RG_SRB_ERR_HIP;
-}
-
-inline int launch_status(rg_srb_handle *h, const char *what) {
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? hip_fail(h, what, e) : RG_SRB_OK;
-}
-
-inline bool obs_ok(const rg_srb_obs_ptrs *o) {
-  return o && o->rpy && o->rpy_rate && o->v_world && o->quat && o->q && o->foot_pos && o->jac && o->contact && o->t_robot;
-}
-
-inline Obs to_obs(const rg_srb_obs_ptrs *o) { return {o->rpy, o->rpy_rate, o->v_world, o->quat, o->q, o->foot_pos, o->jac, o->contact, o->t_robot}; }
+inline int hip_fail(rg_srb_handle *h, const char *what, hipError_t e) { return hip_fail(h, RG_SRB_ERR_HIP, what, e); }
+inline int launch_status(rg_srb_handle *h, const char *what) { return launch_status(h, RG_SRB_ERR_HIP, what); }
 
 }  // namespace
 

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include "../../include/rg_srb.h"
+#include "rg_host.h"
 
 #pragma clang fp contract(off)
 
@@ -229,10 +230,8 @@ bool refuse(char *msg, int n, const char *text) {
 bool terrain_valid(const rg_srb_terrain *t, char *msg, int n) {
   char buf[200];
   if (!t) return refuse(msg, n, "terrain: null");
-  if (t->abi_version != RG_SRB_ABI_VERSION) {
-    snprintf(buf, sizeof(buf), "terrain.abi_version: %d, this library is version %d", t->abi_version, RG_SRB_ABI_VERSION);
-    return refuse(msg, n, buf);
-  }
+  std::string err;
+  if (!check_abi("terrain.", t->abi_version, RG_SRB_ABI_VERSION, err)) return refuse(msg, n, err.c_str());
   if (t->kind != RG_SRB_TERRAIN_FLAT && t->kind != RG_SRB_TERRAIN_RANDOM && t->kind != RG_SRB_TERRAIN_GRID) {
     snprintf(buf, sizeof(buf), "terrain.kind: %d is not 0 (flat), 1 (random) or 2 (grid)", t->kind);
     return refuse(msg, n, buf);
