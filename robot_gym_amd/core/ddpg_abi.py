@@ -5,9 +5,8 @@ status codes into exceptions and owns one rg_ddpg_handle.  There is NO CPU fallb
 raises.  Every buffer is a caller-owned tensor (layouts: rg_ddpg.h).
 """
 import ctypes as C
-import os
 
-from robot_gym_amd.core import goto_abi, mpc_abi
+from robot_gym_amd.core.c_abi import Handle, RgError, create_status as _create_status, d, fp, i32, i64, load, merged, resolve_device
 
 ABI_VERSION = 1
 MAX_OBS, MAX_ACT, MAX_WINDOW, MAX_INPUT, MAX_LAYERS, MAX_WIDTH = 64, 4, 8, 128, 3, 256
@@ -20,17 +19,11 @@ DEVICE_NONE = -1
 MODE_SAMPLE, MODE_MEAN = 0, 1
 ACTOR, CRITIC = 0, 1
 STAT_NAMES = ("critic_loss_first", "critic_loss_last", "actor_loss_first", "actor_loss_last", "mean_q_last", "critic_grad_norm_last")
-d = C.c_double
-i32 = C.c_int32
-fp = C.c_void_p
-
-STATUS = {0: "OK", -1: "INVALID", -2: "HIP", -3: "NO_DEVICE"}
+STATUS = {0: "OK", -1: "INVALID", -2: "HIP", -3: "NO_DEVICE"}     # rg_ddpg_status has no ALLOC
 
 
-class RgDdpgError(RuntimeError):
-    def __init__(self, status, text):
-        super().__init__(f"rg_ddpg status {status} ({STATUS.get(status, '?')}): {text}")
-        self.status = status
+class RgDdpgError(RgError):
+    unit, names = "rg_ddpg", STATUS
 
 
 class CConfig(C.Structure):
@@ -66,67 +59,36 @@ DEFAULTS = dict(obs_dim=16, act_dim=2, window=5, actor_layers=(128, 128, 64), cr
                 ou_dt=1e-2, seed=0)
 _FLOATS = ("gamma", "tau", "actor_lr", "critic_lr", "beta1", "beta2", "adam_eps", "clipnorm", "ou_theta", "ou_mu", "ou_sigma", "ou_dt")
 
-_lib = None
+_RING = C.POINTER(CRing)
+# rg_ddpg.h's entries past those every unit has; the int32 getters are declared with the checks they serve
+SIGNATURES = {
+    "create": (i32, [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]),
+    "workspace_bytes": (i64, [fp]),
+    "opt_state_bytes": (i64, [fp]),
+    "groups": (i32, [fp]),
+    "lds_bytes": (i32, [fp]),
+    "param_layout": (i32, [C.POINTER(CConfig), C.POINTER(CLayout)]),
+    "act": (i32, [fp, _RING, fp, fp, fp, fp, i32, fp, fp, fp]),
+    "store": (i32, [fp, _RING, fp, fp, fp, fp, fp, fp]),
+    "sample": (i32, [fp, _RING, fp, fp]),
+    "critic_grad": (i32, [fp, _RING, fp, fp, fp, fp, fp, fp, fp, fp]),
+    "actor_grad": (i32, [fp, _RING, fp, fp, fp, fp, fp, fp, fp]),
+    "adam": (i32, [fp, i32, fp, fp, fp, fp, fp, fp, fp]),
+    "soft_update": (i32, [fp, i32, fp, fp, fp, fp]),
+    "advance": (i32, [fp, _RING, fp]),
+    "update": (i32, [fp, _RING, fp, fp, fp, fp, fp, fp, i32, fp, fp]),
+}
 
 
 def load_library(path=None):
-    """The rg_ddpg_* entries of librg_mpc.so (mpc_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    p = path or mpc_abi.LIB_PATH
-    if not os.path.exists(p):
-        raise ImportError(f"{p} not found: build it with `make -C robot_gym_amd/csrc` (or __graft_entry__.build()); "
-                          "the DDPG agent has no CPU fallback")
-    L = C.CDLL(p)
-    L.rg_ddpg_create.argtypes = [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]
-    L.rg_ddpg_create.restype = i32
-    L.rg_ddpg_destroy.argtypes = [fp]
-    L.rg_ddpg_destroy.restype = None
-    L.rg_ddpg_last_error.argtypes = [fp]
-    L.rg_ddpg_last_error.restype = C.c_char_p
-    for name in ("abi_version", "config_size", "layout_size", "ring_size", "tile"):
-        getattr(L, f"rg_ddpg_{name}").argtypes = []
-        getattr(L, f"rg_ddpg_{name}").restype = i32
-    for name in ("workspace_bytes", "opt_state_bytes"):
-        getattr(L, f"rg_ddpg_{name}").argtypes = [fp]
-        getattr(L, f"rg_ddpg_{name}").restype = C.c_int64
-    for name in ("groups", "lds_bytes"):
-        getattr(L, f"rg_ddpg_{name}").argtypes = [fp]
-        getattr(L, f"rg_ddpg_{name}").restype = i32
-    L.rg_ddpg_param_layout.argtypes = [C.POINTER(CConfig), C.POINTER(CLayout)]
-    ring = C.POINTER(CRing)
-    L.rg_ddpg_act.argtypes = [fp, ring, fp, fp, fp, fp, i32, fp, fp, fp]
-    L.rg_ddpg_store.argtypes = [fp, ring, fp, fp, fp, fp, fp, fp]
-    L.rg_ddpg_sample.argtypes = [fp, ring, fp, fp]
-    L.rg_ddpg_critic_grad.argtypes = [fp, ring, fp, fp, fp, fp, fp, fp, fp, fp]
-    L.rg_ddpg_actor_grad.argtypes = [fp, ring, fp, fp, fp, fp, fp, fp, fp]
-    L.rg_ddpg_adam.argtypes = [fp, i32, fp, fp, fp, fp, fp, fp, fp]
-    L.rg_ddpg_soft_update.argtypes = [fp, i32, fp, fp, fp, fp]
-    L.rg_ddpg_advance.argtypes = [fp, ring, fp]
-    L.rg_ddpg_update.argtypes = [fp, ring, fp, fp, fp, fp, fp, fp, i32, fp, fp]
-    for name in ("param_layout", "act", "store", "sample", "critic_grad", "actor_grad", "adam", "soft_update", "advance", "update"):
-        getattr(L, f"rg_ddpg_{name}").restype = i32
-    if L.rg_ddpg_abi_version() != ABI_VERSION:
-        raise ImportError("librg_mpc.so rg_ddpg ABI version mismatch")
-    for what, lib_size, mine in (("config", L.rg_ddpg_config_size(), C.sizeof(CConfig)), ("layout", L.rg_ddpg_layout_size(), C.sizeof(CLayout)),
-                                 ("ring", L.rg_ddpg_ring_size(), C.sizeof(CRing))):
-        if lib_size != mine:
-            raise ImportError(f"rg_ddpg_{what} size mismatch: lib {lib_size} vs binding {mine}")
-    if L.rg_ddpg_tile() != TILE:
-        raise ImportError(f"rg_ddpg tile mismatch: lib {L.rg_ddpg_tile()} vs binding {TILE}")
-    if path is None:
-        _lib = L
-    return L
+    """The rg_ddpg_* entries of librg_mpc.so (c_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
+    return load("rg_ddpg", "the DDPG agent has no CPU fallback", SIGNATURES, {"config": CConfig, "layout": CLayout, "ring": CRing},
+                {"tile": TILE}, ABI_VERSION, path)
 
 
 def ddpg_fields(**settings):
     """The value of every rg_ddpg_config setting as a dict: DEFAULTS overridden by `settings`."""
-    unknown = set(settings) - set(DEFAULTS)
-    if unknown:
-        raise TypeError(f"unknown ddpg setting(s) {sorted(unknown)}")
-    out = dict(DEFAULTS)
-    out.update(settings)
+    out = merged(DEFAULTS, settings, "ddpg")
     for name in ("actor_layers", "critic_layers"):
         out[name] = tuple(int(w) for w in out[name])
         if len(out[name]) > MAX_LAYERS:
@@ -172,52 +134,28 @@ def param_layout(cconfig=None, **settings):
 
 def create_status(cconfig=None, batch=1, device=DEVICE_NONE):
     """(status, text) of rg_ddpg_create; destroys the handle when one is made."""
-    lib = load_library()
     cc = make_cconfig() if cconfig is None else cconfig
-    h = fp()
-    rc = lib.rg_ddpg_create(C.byref(cc), int(batch), int(device), C.byref(h))
-    text = lib.rg_ddpg_last_error(None).decode() if rc else ""
-    if h:
-        lib.rg_ddpg_destroy(h)
-    return rc, text
+    return _create_status(load_library(), "rg_ddpg", C.byref(cc), int(batch), int(device))
 
 
-class DdpgHandle:
+class DdpgHandle(Handle):
     """Owns one rg_ddpg_handle and launches on torch's current stream of its device.  device=DEVICE_NONE makes the host-only
     handle of rg_ddpg_create: it needs no GPU, every call checks its arguments and then raises NO_DEVICE."""
 
+    unit, error = "rg_ddpg", RgDdpgError
+
     def __init__(self, batch, device=None, **settings):
-        self._h = fp()
-        self._lib = load_library()
+        lib = load_library()
         self.batch = int(batch)
         self.fields = ddpg_fields(**settings)
-        if device == DEVICE_NONE:
-            self.device, index = None, DEVICE_NONE
-        else:
-            import torch
-            if not torch.cuda.is_available():
-                raise RgDdpgError(-3, "no GPU: the DDPG kernels have no CPU fallback")
-            index = None if device is None else torch.device(device).index
-            self.device = torch.device("cuda", torch.cuda.current_device() if index is None else index)
-            index = self.device.index
+        self.device, index = resolve_device(device, RgDdpgError, "the DDPG kernels have no CPU fallback", DEVICE_NONE)
         cc = make_cconfig(**settings)
-        rc = self._lib.rg_ddpg_create(C.byref(cc), self.batch, index, C.byref(self._h))
-        if rc != 0:
-            msg = self._lib.rg_ddpg_last_error(None)
-            self._h = fp()
-            raise RgDdpgError(rc, msg.decode() if msg else "create failed")
+        self._create(lib, C.byref(cc), self.batch, index)
         self.layout = param_layout(cc)
-        self.workspace_bytes = int(self._lib.rg_ddpg_workspace_bytes(self._h))
-        self.opt_state_bytes = int(self._lib.rg_ddpg_opt_state_bytes(self._h))
-        self.groups = int(self._lib.rg_ddpg_groups(self._h))
-        self.lds_bytes = int(self._lib.rg_ddpg_lds_bytes(self._h))
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RgDdpgError(rc, self._lib.rg_ddpg_last_error(self._h).decode())
-
-    def _s(self):
-        return None if self.device is None else goto_abi._stream(self.device)
+        self.workspace_bytes = int(lib.rg_ddpg_workspace_bytes(self._h))
+        self.opt_state_bytes = int(lib.rg_ddpg_opt_state_bytes(self._h))
+        self.groups = int(lib.rg_ddpg_groups(self._h))
+        self.lds_bytes = int(lib.rg_ddpg_lds_bytes(self._h))
 
     def act(self, ring, obs_ptr, actor_ptr, ou_ptr, act_state_ptr, mode, action_ptr, mean_ptr=None):
         self._check(self._lib.rg_ddpg_act(self._h, C.byref(ring), obs_ptr, actor_ptr, ou_ptr, act_state_ptr, int(mode), action_ptr, mean_ptr, self._s()))
@@ -247,14 +185,3 @@ class DdpgHandle:
     def update(self, ring, actor_ptr, critic_ptr, target_actor_ptr, target_critic_ptr, opt_state_ptr, workspace_ptr, n_updates, stats_ptr):
         self._check(self._lib.rg_ddpg_update(self._h, C.byref(ring), actor_ptr, critic_ptr, target_actor_ptr, target_critic_ptr, opt_state_ptr,
                                              workspace_ptr, int(n_updates), stats_ptr, self._s()))
-
-    def close(self):
-        if self._h:
-            self._lib.rg_ddpg_destroy(self._h)
-            self._h = fp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

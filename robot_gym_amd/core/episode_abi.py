@@ -5,9 +5,9 @@ exceptions and owns one rg_episode_handle.  There is NO CPU fallback: without th
 Every buffer is a caller-owned tensor (layouts: rg_episode.h).
 """
 import ctypes as C
-import os
 
-from robot_gym_amd.core import goto_abi, mpc_abi, srb_abi
+from robot_gym_amd.core import goto_abi, srb_abi
+from robot_gym_amd.core.c_abi import STATUS, Handle, RgError, create_status as _create_status, d, fill_config, fp, i32, load, merged, resolve_device  # noqa: F401 -- STATUS stays a name of this module
 
 ABI_VERSION = 1
 ROWS = 12                # RG_EPISODE_ROWS
@@ -16,17 +16,10 @@ ROWS = 12                # RG_EPISODE_ROWS
 MAX_WAYPOINTS, MAX_OBSTACLES, MAX_OSCILLATION = 64, 16, 8
 DEVICE_NONE = -1         # RG_EPISODE_DEVICE_NONE: a host-only handle
 PLAN_STATUS = ("ok", "target", "waypoints", "short", "long")   # RG_EPISODE_PLAN_*
-d = C.c_double
-i32 = C.c_int32
-fp = C.c_void_p
-
-STATUS = {0: "OK", -1: "INVALID", -2: "HIP", -3: "NO_DEVICE", -4: "ALLOC"}
 
 
-class RgEpisodeError(RuntimeError):
-    def __init__(self, status, text):
-        super().__init__(f"rg_episode status {status} ({STATUS.get(status, '?')}): {text}")
-        self.status = status
+class RgEpisodeError(RgError):
+    unit = "rg_episode"
 
 
 class CConfig(C.Structure):
@@ -45,50 +38,22 @@ DEFAULTS = dict(kp=5.0, eta=100.0, area_width=5.0, grid=0.5, robot_radius=0.25, 
                 max_waypoints=64)
 INT_FIELDS = ("seed", "oscillation_length", "max_waypoints")
 
-_lib = None
+# rg_episode.h's entries past those every unit has; the int32 getters are declared with the checks they serve
+SIGNATURES = {
+    "create": (i32, [C.POINTER(CConfig), C.POINTER(srb_abi.CConfig), C.POINTER(goto_abi.CConfig), i32, i32, C.POINTER(fp)]),
+    "reset": (i32, [fp, fp, fp, fp, fp, fp, C.POINTER(srb_abi.CObsPtrs), C.POINTER(goto_abi.CPathPtrs), fp, fp, fp, fp]),
+    "accumulate": (i32, [fp, fp, fp, fp, fp]),
+}
 
 
 def load_library(path=None):
-    """The rg_episode_* entries of librg_mpc.so (mpc_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    p = path or mpc_abi.LIB_PATH
-    if not os.path.exists(p):
-        raise ImportError(f"{p} not found: build it with `make -C robot_gym_amd/csrc` (or __graft_entry__.build()); "
-                          "the episode reset has no CPU fallback")
-    L = C.CDLL(p)
-    L.rg_episode_create.argtypes = [C.POINTER(CConfig), C.POINTER(srb_abi.CConfig), C.POINTER(goto_abi.CConfig), i32, i32, C.POINTER(fp)]
-    L.rg_episode_create.restype = i32
-    L.rg_episode_destroy.argtypes = [fp]
-    L.rg_episode_destroy.restype = None
-    L.rg_episode_last_error.argtypes = [fp]
-    L.rg_episode_last_error.restype = C.c_char_p
-    L.rg_episode_abi_version.restype = i32
-    L.rg_episode_config_size.restype = i32
-    L.rg_episode_state_rows.restype = i32
-    L.rg_episode_reset.argtypes = [fp, fp, fp, fp, fp, fp, C.POINTER(srb_abi.CObsPtrs), C.POINTER(goto_abi.CPathPtrs), fp, fp, fp, fp]
-    L.rg_episode_reset.restype = i32
-    L.rg_episode_accumulate.argtypes = [fp, fp, fp, fp, fp]
-    L.rg_episode_accumulate.restype = i32
-    if L.rg_episode_abi_version() != ABI_VERSION:
-        raise ImportError("librg_mpc.so rg_episode ABI version mismatch")
-    if L.rg_episode_config_size() != C.sizeof(CConfig):
-        raise ImportError(f"rg_episode_config size mismatch: lib {L.rg_episode_config_size()} vs binding {C.sizeof(CConfig)}")
-    if L.rg_episode_state_rows() != ROWS:
-        raise ImportError(f"rg_episode state rows mismatch: lib {L.rg_episode_state_rows()} vs binding {ROWS}")
-    if path is None:
-        _lib = L
-    return L
+    """The rg_episode_* entries of librg_mpc.so (c_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
+    return load("rg_episode", "the episode reset has no CPU fallback", SIGNATURES, {"config": CConfig}, {"state_rows": ROWS}, ABI_VERSION, path)
 
 
 def episode_fields(obstacles=(), **settings):
     """The value of every rg_episode_config field as a dict: DEFAULTS overridden by `settings`, and the obstacles [(x, y), ...]."""
-    unknown = set(settings) - set(DEFAULTS)
-    if unknown:
-        raise TypeError(f"unknown episode setting(s) {sorted(unknown)}")
-    out = dict(DEFAULTS)
-    out.update(settings)
+    out = merged(DEFAULTS, settings, "episode")
     obs = [(float(o[0]), float(o[1])) for o in (() if obstacles is None else obstacles)]
     if len(obs) > MAX_OBSTACLES:
         raise ValueError(f"at most {MAX_OBSTACLES} obstacles, got {len(obs)}")
@@ -101,16 +66,11 @@ def make_cconfig(obstacles=(), **settings):
     c.abi_version = ABI_VERSION
     c.reserved0 = c.reserved1 = 0
     f = episode_fields(obstacles, **settings)
-    for name, v in f.items():
-        if name == "obstacles":
-            c.num_obstacles = len(v)
-            for k, (x, y) in enumerate(v):
-                c.obstacles[k][0], c.obstacles[k][1] = x, y
-        elif name in INT_FIELDS:
-            setattr(c, name, int(v))
-        else:
-            setattr(c, name, float(v))
-    return c
+    obs = f.pop("obstacles")
+    c.num_obstacles = len(obs)
+    for k, (x, y) in enumerate(obs):
+        c.obstacles[k][0], c.obstacles[k][1] = x, y
+    return fill_config(c, f, INT_FIELDS)
 
 
 def create_status(ecfg=None, scfg=None, gcfg=None, batch=1, device=DEVICE_NONE, mpc_cfg=None):
@@ -123,49 +83,26 @@ def create_status(ecfg=None, scfg=None, gcfg=None, batch=1, device=DEVICE_NONE, 
     ecfg = make_cconfig() if ecfg is None else ecfg
     scfg = srb_abi.make_cconfig(mpc_cfg) if scfg is None else scfg
     gcfg = goto_abi.make_cconfig(mpc_cfg) if gcfg is None else gcfg
-    h = fp()
-    rc = lib.rg_episode_create(C.byref(ecfg), C.byref(scfg), C.byref(gcfg), int(batch), int(device), C.byref(h))
-    text = lib.rg_episode_last_error(None).decode() if rc else ""
-    if h:
-        lib.rg_episode_destroy(h)
-    return rc, text
+    return _create_status(lib, "rg_episode", C.byref(ecfg), C.byref(scfg), C.byref(gcfg), int(batch), int(device))
 
 
-class EpisodeHandle:
+class EpisodeHandle(Handle):
     """Owns one rg_episode_handle and launches on torch's current stream of its device.  sim_settings / task_settings are the
     keyword settings the simulator (srb_abi.make_cconfig) and the task (goto_abi.make_cconfig) were created with.
     device=DEVICE_NONE makes the host-only handle of rg_episode_create: it needs no GPU, every call checks its arguments and
     then raises NO_DEVICE."""
 
+    unit, error = "rg_episode", RgEpisodeError
+
     def __init__(self, batch, mpc_cfg, device=None, obstacles=(), sim_settings=None, task_settings=None, **settings):
-        self._h = fp()
-        self._lib = load_library()
+        lib = load_library()
         self.batch = int(batch)
         self.fields = episode_fields(obstacles, **settings)
-        if device == DEVICE_NONE:
-            self.device, index = None, DEVICE_NONE
-        else:
-            import torch
-            if not torch.cuda.is_available():
-                raise RgEpisodeError(-3, "no GPU: the episode reset has no CPU fallback")
-            index = None if device is None else torch.device(device).index
-            self.device = torch.device("cuda", torch.cuda.current_device() if index is None else index)
-            index = self.device.index
+        self.device, index = resolve_device(device, RgEpisodeError, "the episode reset has no CPU fallback", DEVICE_NONE)
         ec = make_cconfig(obstacles, **settings)
         sc = srb_abi.make_cconfig(mpc_cfg, **(sim_settings or {}))
         gc = goto_abi.make_cconfig(mpc_cfg, **(task_settings or {}))
-        rc = self._lib.rg_episode_create(C.byref(ec), C.byref(sc), C.byref(gc), self.batch, index, C.byref(self._h))
-        if rc != 0:
-            msg = self._lib.rg_episode_last_error(None)
-            self._h = fp()
-            raise RgEpisodeError(rc, msg.decode() if msg else "create failed")
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RgEpisodeError(rc, self._lib.rg_episode_last_error(self._h).decode())
-
-    def _s(self):
-        return None if self.device is None else goto_abi._stream(self.device)
+        self._create(lib, C.byref(ec), C.byref(sc), C.byref(gc), self.batch, index)
 
     def reset(self, mask_ptr, targets_ptr, episode_state_ptr, task_state_ptr, sim_state_ptr, sim_obs, paths, obs_ptr, final_obs_ptr,
               reset_mask_ptr):
@@ -176,14 +113,3 @@ class EpisodeHandle:
 
     def accumulate(self, episode_state_ptr, reward_ptr, done_ptr):
         self._check(self._lib.rg_episode_accumulate(self._h, episode_state_ptr, reward_ptr, done_ptr, self._s()))
-
-    def close(self):
-        if self._h:
-            self._lib.rg_episode_destroy(self._h)
-            self._h = fp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

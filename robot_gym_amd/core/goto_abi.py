@@ -5,11 +5,11 @@ status codes into exceptions and owns one rg_goto_handle.  There is NO CPU fallb
 handle raises.  Task state, path slab and outputs are caller-owned tensors (layouts: rg_goto.h).
 """
 import ctypes as C
-import os
 
 import numpy as np
 
-from robot_gym_amd.core import mpc_abi
+from robot_gym_amd.core.c_abi import (STATUS, Handle, RgError, create_status as _create_status, d, fill_config, fp, host_array, host_ptr, i32,  # noqa: F401 -- STATUS stays a name of this module
+                                      index_array, load, merged, resolve_device)
 
 ABI_VERSION = 1
 STATE_ROWS = 50          # RG_GOTO_STATE_ROWS
@@ -20,17 +20,10 @@ MAX_CAM_PTS, MAX_VISIBLE, MAX_PATH, MAX_CHECKPOINTS = 16, 128, 65536, 65536
 LIMIT_REWARD = -100.0
 DEVICE_NONE = -1         # RG_GOTO_DEVICE_NONE: a host-only handle
 REASONS = ("none", "fallen", "path_done", "on_target", "progress", "track", "time")   # RG_GOTO_REASON_*
-d = C.c_double
-i32 = C.c_int32
-fp = C.c_void_p
-
-STATUS = {0: "OK", -1: "INVALID", -2: "HIP", -3: "NO_DEVICE", -4: "ALLOC"}
 
 
-class RgGotoError(RuntimeError):
-    def __init__(self, status, text):
-        super().__init__(f"rg_goto status {status} ({STATUS.get(status, '?')}): {text}")
-        self.status = status
+class RgGotoError(RgError):
+    unit = "rg_goto"
 
 
 class CConfig(C.Structure):
@@ -61,57 +54,28 @@ DEFAULTS = dict(window_height=0.160, window_top_width=0.270, window_bottom_width
                 dt_sim=0.001, substeps=10, num_cam_pts=8, num_checkpoints=100, n_max=1024, max_visible=128)
 INT_FIELDS = ("substeps", "num_cam_pts", "num_checkpoints", "n_max", "max_visible")
 
-_lib = None
+# rg_goto.h's entries past those every unit has; the int32 getters are declared with the checks they serve
+SIGNATURES = {
+    "create": (i32, [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]),
+    "set_path": (i32, [fp, fp, i32, fp, fp, fp, fp, fp, fp, fp, C.POINTER(CPathPtrs), fp, fp]),
+    "pre_step": (i32, [fp, fp, fp, C.POINTER(CPathPtrs), fp, fp, fp]),
+    "post_step": (i32, [fp, fp, fp, C.POINTER(CPathPtrs), fp, fp, fp, fp]),
+    "observe": (i32, [fp, fp, fp, C.POINTER(CPathPtrs), fp, fp]),
+}
 
 
 def load_library(path=None):
-    """The rg_goto_* entries of librg_mpc.so (mpc_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    p = path or mpc_abi.LIB_PATH
-    if not os.path.exists(p):
-        raise ImportError(f"{p} not found: build it with `make -C robot_gym_amd/csrc` (or __graft_entry__.build()); "
-                          "the go-to-target task has no CPU fallback")
-    L = C.CDLL(p)
-    L.rg_goto_create.argtypes = [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]
-    L.rg_goto_create.restype = i32
-    L.rg_goto_destroy.argtypes = [fp]
-    L.rg_goto_destroy.restype = None
-    L.rg_goto_last_error.argtypes = [fp]
-    L.rg_goto_last_error.restype = C.c_char_p
-    L.rg_goto_abi_version.restype = i32
-    L.rg_goto_config_size.restype = i32
-    L.rg_goto_state_rows.restype = i32
-    L.rg_goto_set_path.argtypes = [fp, fp, i32, fp, fp, fp, fp, fp, fp, fp, C.POINTER(CPathPtrs), fp, fp]
-    L.rg_goto_set_path.restype = i32
-    L.rg_goto_pre_step.argtypes = [fp, fp, fp, C.POINTER(CPathPtrs), fp, fp, fp]
-    L.rg_goto_pre_step.restype = i32
-    L.rg_goto_post_step.argtypes = [fp, fp, fp, C.POINTER(CPathPtrs), fp, fp, fp, fp]
-    L.rg_goto_post_step.restype = i32
-    L.rg_goto_observe.argtypes = [fp, fp, fp, C.POINTER(CPathPtrs), fp, fp]
-    L.rg_goto_observe.restype = i32
-    if L.rg_goto_abi_version() != ABI_VERSION:
-        raise ImportError("librg_mpc.so rg_goto ABI version mismatch")
-    if L.rg_goto_config_size() != C.sizeof(CConfig):
-        raise ImportError(f"rg_goto_config size mismatch: lib {L.rg_goto_config_size()} vs binding {C.sizeof(CConfig)}")
-    if L.rg_goto_state_rows() != STATE_ROWS:
-        raise ImportError(f"rg_goto state rows mismatch: lib {L.rg_goto_state_rows()} vs binding {STATE_ROWS}")
-    if path is None:
-        _lib = L
-    return L
+    """The rg_goto_* entries of librg_mpc.so (c_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
+    return load("rg_goto", "the go-to-target task has no CPU fallback", SIGNATURES, {"config": CConfig}, {"state_rows": STATE_ROWS},
+                ABI_VERSION, path)
 
 
 def task_fields(mpc_cfg=None, **task):
     """The value of every rg_goto_config field as a dict: DEFAULTS, cmd_offset from the MPCConfig `mpc_cfg` (if given),
     overridden by `task`."""
-    unknown = set(task) - set(DEFAULTS)
-    if unknown:
-        raise TypeError(f"unknown task setting(s) {sorted(unknown)}")
-    out = dict(DEFAULTS)
-    if mpc_cfg is not None:
+    out = merged(DEFAULTS, task, "task")
+    if mpc_cfg is not None and "cmd_offset" not in task:
         out["cmd_offset"] = (mpc_cfg.vx_offset, mpc_cfg.vy_offset, mpc_cfg.wz_offset)
-    out.update(task)
     return out
 
 
@@ -119,87 +83,40 @@ def make_cconfig(mpc_cfg=None, **task):
     c = CConfig()
     c.abi_version = ABI_VERSION
     c.reserved0 = c.reserved1 = 0
-    for name, v in task_fields(mpc_cfg, **task).items():
-        if hasattr(v, "__len__"):
-            arr = getattr(c, name)
-            if len(v) != len(arr):
-                raise ValueError(f"config field {name}: expected {len(arr)} values, got {len(v)}")
-            for k, x in enumerate(v):
-                arr[k] = float(x)
-        elif name in INT_FIELDS:
-            setattr(c, name, int(v))
-        else:
-            setattr(c, name, float(v))
-    return c
+    return fill_config(c, task_fields(mpc_cfg, **task), INT_FIELDS)
 
 
 def create_status(cfg=None, batch=1, device=0, **task):
     """(status, text) of rg_goto_create; destroys the handle when one is made.  cfg: a CConfig, an MPCConfig or None."""
     lib = load_library()
-    h = fp()
     cc = cfg if isinstance(cfg, CConfig) else make_cconfig(cfg, **task)
-    rc = lib.rg_goto_create(C.byref(cc), int(batch), int(device), C.byref(h))
-    text = lib.rg_goto_last_error(None).decode() if rc else ""
-    if h:
-        lib.rg_goto_destroy(h)
-    return rc, text
+    return _create_status(lib, "rg_goto", C.byref(cc), int(batch), int(device))
 
 
-def _stream(device):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _arr(a, dtype, shape, name):
-    a = np.ascontiguousarray(np.asarray(a, dtype=dtype))
-    if a.shape != shape:
-        raise ValueError(f"{name} must have shape {list(shape)}, got {list(a.shape)}")
-    return a
-
-
-class GotoHandle:
+class GotoHandle(Handle):
     """Owns one rg_goto_handle and launches on torch's current stream of its device.  device=DEVICE_NONE makes the host-only
     handle of rg_goto_create: it needs no GPU, every call checks its arguments and then raises NO_DEVICE."""
 
+    unit, error = "rg_goto", RgGotoError
+
     def __init__(self, batch, mpc_cfg=None, device=None, **task):
-        self._h = fp()
-        self._lib = load_library()
+        lib = load_library()
         self.batch = int(batch)
         self.fields = task_fields(mpc_cfg, **task)
         self.n_max = int(self.fields["n_max"])
-        if device == DEVICE_NONE:
-            self.device, index = None, DEVICE_NONE
-        else:
-            import torch
-            if not torch.cuda.is_available():
-                raise RgGotoError(-3, "no GPU: the go-to-target task has no CPU fallback")
-            index = None if device is None else torch.device(device).index
-            self.device = torch.device("cuda", torch.cuda.current_device() if index is None else index)
-            index = self.device.index
-        cc = make_cconfig(mpc_cfg, **task)
-        rc = self._lib.rg_goto_create(C.byref(cc), self.batch, index, C.byref(self._h))
-        if rc != 0:
-            msg = self._lib.rg_goto_last_error(None)
-            self._h = fp()
-            raise RgGotoError(rc, msg.decode() if msg else "create failed")
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RgGotoError(rc, self._lib.rg_goto_last_error(self._h).decode())
-
-    def _s(self):
-        return None if self.device is None else _stream(self.device)
+        self.device, index = resolve_device(device, RgGotoError, "the go-to-target task has no CPU fallback", DEVICE_NONE)
+        self._create(lib, C.byref(make_cconfig(mpc_cfg, **task)), self.batch, index)
 
     def set_path(self, paths: CPathPtrs, task_state_ptr, idx, npts, length, target, x, y, s, first_same_x):
         """Host arrays as rg_goto_set_path takes them (robot_gym_amd.gym.goto_path.pack_paths makes them)."""
-        ia = None if idx is None else np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(-1))
+        ia = index_array(idx)
         n = self.batch if ia is None else len(ia)
-        npts = _arr(npts, np.int32, (n,), "npts")
-        length = _arr(length, np.float64, (n,), "length")
-        target = _arr(target, np.float64, (2, n), "target")
-        x, y, s = (_arr(a, np.float64, (n, self.n_max), k) for a, k in ((x, "x"), (y, "y"), (s, "s")))
-        first_same_x = _arr(first_same_x, np.int32, (n, self.n_max), "first_same_x")
-        self._check(self._lib.rg_goto_set_path(self._h, None if ia is None else ia.ctypes.data, n, npts.ctypes.data, length.ctypes.data,
+        npts = host_array(npts, np.int32, (n,), "npts")
+        length = host_array(length, np.float64, (n,), "length")
+        target = host_array(target, np.float64, (2, n), "target")
+        x, y, s = (host_array(a, np.float64, (n, self.n_max), k) for a, k in ((x, "x"), (y, "y"), (s, "s")))
+        first_same_x = host_array(first_same_x, np.int32, (n, self.n_max), "first_same_x")
+        self._check(self._lib.rg_goto_set_path(self._h, host_ptr(ia), n, npts.ctypes.data, length.ctypes.data,
                                                target.ctypes.data, x.ctypes.data, y.ctypes.data, s.ctypes.data, first_same_x.ctypes.data,
                                                C.byref(paths), task_state_ptr, self._s()))
 
@@ -211,14 +128,3 @@ class GotoHandle:
 
     def observe(self, task_state_ptr, sim_state_ptr, paths: CPathPtrs, obs_ptr):
         self._check(self._lib.rg_goto_observe(self._h, task_state_ptr, sim_state_ptr, C.byref(paths), obs_ptr, self._s()))
-
-    def close(self):
-        if self._h:
-            self._lib.rg_goto_destroy(self._h)
-            self._h = fp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

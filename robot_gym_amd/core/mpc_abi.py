@@ -6,22 +6,18 @@ negative status codes into exceptions.  There is NO CPU fallback: if the library
 or no GPU is present the constructor raises.
 """
 import ctypes as C
-import os
 
-_CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "csrc")
-# RG_MPC_LIB: load another build of the same C-ABI (kernel A/B experiments); never a fallback
-LIB_PATH = os.environ.get("RG_MPC_LIB") or os.path.abspath(os.path.join(_CSRC, "librg_mpc.so"))
+from robot_gym_amd.core.c_abi import LIB_PATH, Handle, RgError, d, fp, i32, i64, load  # noqa: F401 -- LIB_PATH: read by tools and tests
 
 ABI_VERSION = 5
 AUDIT_PERIOD = 8   # RG_MPC_AUDIT_PERIOD: the audit lane picks on the first tick and then on every 8th one (ticks 4, 12, 20 ...)
-d = C.c_double
-i32 = C.c_int32
-fp = C.c_void_p
 
 
-class RgMpcError(RuntimeError):
-    def __init__(self, status, text):
-        super().__init__(f"rg_mpc status {status}: {text}")
+class RgMpcError(RgError):
+    unit = "rg_mpc"
+
+    def __init__(self, status, text):     # its own, shorter text: no status name
+        RuntimeError.__init__(self, f"rg_mpc status {status}: {text}")
         self.status = status
 
 
@@ -57,88 +53,43 @@ EXPORTS = ("rg_mpc_create", "rg_mpc_reset", "rg_mpc_reset_at", "rg_mpc_reset_mas
            "rg_mpc_last_bin_counts", "rg_mpc_last_solver_stats", "rg_mpc_last_iterations", "rg_mpc_audit_stats", "rg_mpc_last_direct_count", "rg_mpc_profile_begin", "rg_mpc_profile_stride", "rg_mpc_profile_end", "rg_mpc_kernel_names", "rg_mpc_plan_description", "rg_mpc_profile_window_names", "rg_mpc_debug_poison_lds", "rg_mpc_destroy", "rg_mpc_last_error",
            "rg_mpc_abi_version", "rg_mpc_config_size")
 
-_lib = None
+_I32P, _I64P, _DP = C.POINTER(i32), C.POINTER(i64), C.POINTER(d)
+# rg_mpc.h's entries past those every unit has; the int32 getters are declared with the checks they serve
+SIGNATURES = {
+    "create": (i32, [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]),
+    "reset": (i32, [fp, _I32P, i32, d, fp]),
+    "reset_at": (i32, [fp, _I32P, _DP, i32, fp]),
+    "reset_masked": (i32, [fp, fp, d, fp]),
+    "set_command": (i32, [fp, fp, fp]),
+    "set_gait": (i32, [fp, fp, fp, fp, fp, fp]),
+    "set_body": (i32, [fp, _I32P, i32, fp, fp, fp, fp, fp, fp]),
+    "state_layout": (i32, [C.POINTER(CConfig), _I64P, C.POINTER(C.c_char_p)]),
+    "state_check": (i32, [C.POINTER(CConfig), fp, i32, i64, _I32P, i32]),
+    "save_state": (i32, [fp, _I32P, i32, fp, fp]),
+    "load_state": (i32, [fp, _I32P, i32, fp, _DP, fp]),
+    "copy_state": (i32, [fp, _I32P, _I32P, i32, fp]),
+    "step": (i32, [fp, d, C.POINTER(CStatePtrs), C.POINTER(COutPtrs), fp]),
+    "step_host": (i32, [fp, d, fp, fp, i64, C.POINTER(CStatePtrs), C.POINTER(COutPtrs), fp, fp]),
+    "hybrid_to_torque": (i32, [fp, fp, fp, fp, fp, fp]),
+    "hybrid_to_torque_substeps": (i32, [fp, fp, fp, fp, fp, i32, fp]),
+    "last_bin_counts": (i32, [fp, C.POINTER(i32 * 5), fp]),
+    "last_solver_stats": (i32, [fp, _I64P, _I32P, _I32P, _I32P, _I32P, fp]),
+    "last_iterations": (i32, [fp, _I32P, _I32P, fp]),
+    "audit_stats": (i32, [fp, _I64P, _I64P, _DP, _DP, _I64P, _I64P, i32, fp]),
+    "last_direct_count": (i32, [fp, _I32P, _I64P, fp]),
+    "profile_begin": (i32, [fp, i32]),
+    "profile_stride": (i32, [fp, i32]),
+    "profile_end": (i32, [fp, C.POINTER(C.c_float * 6), C.POINTER(i32 * 5), fp]),
+    "kernel_names": (C.c_char_p, []),
+    "plan_description": (C.c_char_p, [fp]),
+    "profile_window_names": (C.c_char_p, [fp]),
+    "debug_poison_lds": (i32, [fp, fp]),
+}
 
 
 def load_library(path=None):
     """Load librg_mpc.so.  Raises (never falls back) when the HIP extension is missing."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    p = path or LIB_PATH
-    if not os.path.exists(p):
-        raise ImportError(f"{p} not found: build it with `make -C robot_gym_amd/csrc` (or __graft_entry__.build()); "
-                          "the MPC path has no CPU fallback")
-    L = C.CDLL(p)
-    L.rg_mpc_create.argtypes = [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]
-    L.rg_mpc_create.restype = i32
-    L.rg_mpc_reset.argtypes = [fp, C.POINTER(i32), i32, d, fp]
-    L.rg_mpc_reset.restype = i32
-    L.rg_mpc_reset_at.argtypes = [fp, C.POINTER(i32), C.POINTER(d), i32, fp]
-    L.rg_mpc_reset_at.restype = i32
-    L.rg_mpc_reset_masked.argtypes = [fp, fp, d, fp]
-    L.rg_mpc_reset_masked.restype = i32
-    L.rg_mpc_set_command.argtypes = [fp, fp, fp]
-    L.rg_mpc_set_command.restype = i32
-    L.rg_mpc_step.argtypes = [fp, d, C.POINTER(CStatePtrs), C.POINTER(COutPtrs), fp]
-    L.rg_mpc_step.restype = i32
-    L.rg_mpc_step_host.argtypes = [fp, d, fp, fp, C.c_int64, C.POINTER(CStatePtrs), C.POINTER(COutPtrs), fp, fp]
-    L.rg_mpc_step_host.restype = i32
-    L.rg_mpc_hybrid_to_torque.argtypes = [fp, fp, fp, fp, fp, fp]
-    L.rg_mpc_hybrid_to_torque.restype = i32
-    L.rg_mpc_hybrid_to_torque_substeps.argtypes = [fp, fp, fp, fp, fp, i32, fp]
-    L.rg_mpc_hybrid_to_torque_substeps.restype = i32
-    L.rg_mpc_set_gait.argtypes = [fp, fp, fp, fp, fp, fp]
-    L.rg_mpc_set_gait.restype = i32
-    L.rg_mpc_set_body.argtypes = [fp, C.POINTER(i32), i32, fp, fp, fp, fp, fp, fp]
-    L.rg_mpc_set_body.restype = i32
-    L.rg_mpc_state_layout.argtypes = [C.POINTER(CConfig), C.POINTER(C.c_int64), C.POINTER(C.c_char_p)]
-    L.rg_mpc_state_layout.restype = i32
-    L.rg_mpc_state_check.argtypes = [C.POINTER(CConfig), fp, i32, C.c_int64, C.POINTER(i32), i32]
-    L.rg_mpc_state_check.restype = i32
-    L.rg_mpc_save_state.argtypes = [fp, C.POINTER(i32), i32, fp, fp]
-    L.rg_mpc_save_state.restype = i32
-    L.rg_mpc_load_state.argtypes = [fp, C.POINTER(i32), i32, fp, C.POINTER(d), fp]
-    L.rg_mpc_load_state.restype = i32
-    L.rg_mpc_copy_state.argtypes = [fp, C.POINTER(i32), C.POINTER(i32), i32, fp]
-    L.rg_mpc_copy_state.restype = i32
-    L.rg_mpc_last_bin_counts.argtypes = [fp, C.POINTER(i32 * 5), fp]
-    L.rg_mpc_last_bin_counts.restype = i32
-    L.rg_mpc_last_solver_stats.argtypes = [fp, C.POINTER(C.c_int64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), fp]
-    L.rg_mpc_last_solver_stats.restype = i32
-    L.rg_mpc_audit_stats.argtypes = [fp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(d), C.POINTER(d), C.POINTER(C.c_int64),
-                                     C.POINTER(C.c_int64), i32, fp]
-    L.rg_mpc_audit_stats.restype = i32
-    L.rg_mpc_last_direct_count.argtypes = [fp, C.POINTER(i32), C.POINTER(C.c_int64), fp]
-    L.rg_mpc_last_direct_count.restype = i32
-    L.rg_mpc_profile_begin.argtypes = [fp, i32]
-    L.rg_mpc_profile_begin.restype = i32
-    L.rg_mpc_profile_end.argtypes = [fp, C.POINTER(C.c_float * 6), C.POINTER(i32 * 5), fp]
-    L.rg_mpc_profile_end.restype = i32
-    L.rg_mpc_kernel_names.restype = C.c_char_p
-    L.rg_mpc_plan_description.argtypes = [C.c_void_p]
-    L.rg_mpc_plan_description.restype = C.c_char_p
-    L.rg_mpc_last_iterations.argtypes = [fp, C.POINTER(i32), C.POINTER(i32), fp]
-    L.rg_mpc_last_iterations.restype = i32
-    L.rg_mpc_profile_stride.argtypes = [fp, i32]
-    L.rg_mpc_profile_stride.restype = i32
-    L.rg_mpc_debug_poison_lds.argtypes = [fp, fp]
-    L.rg_mpc_debug_poison_lds.restype = i32
-    L.rg_mpc_profile_window_names.argtypes = [C.c_void_p]
-    L.rg_mpc_profile_window_names.restype = C.c_char_p
-    L.rg_mpc_destroy.argtypes = [fp]
-    L.rg_mpc_destroy.restype = None
-    L.rg_mpc_last_error.argtypes = [fp]
-    L.rg_mpc_last_error.restype = C.c_char_p
-    L.rg_mpc_abi_version.restype = i32
-    L.rg_mpc_config_size.restype = i32
-    if L.rg_mpc_abi_version() != ABI_VERSION:
-        raise ImportError("librg_mpc.so ABI version mismatch")
-    if L.rg_mpc_config_size() != C.sizeof(CConfig):
-        raise ImportError(f"rg_mpc_config size mismatch: lib {L.rg_mpc_config_size()} vs binding {C.sizeof(CConfig)}")
-    if path is None:
-        _lib = L
-    return L
+    return load("rg_mpc", "the MPC path has no CPU fallback", SIGNATURES, {"config": CConfig}, {}, ABI_VERSION, path)
 
 
 def _i32_array(idx):
@@ -198,24 +149,16 @@ def make_cconfig(cfg):
     return c
 
 
-class MpcHandle:
+class MpcHandle(Handle):
     """Owns one rg_mpc_handle (one device, one stream)."""
 
+    unit, error = "rg_mpc", RgMpcError
+
     def __init__(self, cfg, batch, device=0):
-        self._lib = load_library()
-        self._h = fp()
+        lib = load_library()
         self.batch = int(batch)
         self.device = int(device)
-        cc = make_cconfig(cfg)
-        rc = self._lib.rg_mpc_create(C.byref(cc), self.batch, self.device, C.byref(self._h))
-        if rc != 0:
-            msg = self._lib.rg_mpc_last_error(None)
-            self._h = fp()
-            raise RgMpcError(rc, msg.decode() if msg else "create failed")
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RgMpcError(rc, self._lib.rg_mpc_last_error(self._h).decode())
+        self._create(lib, C.byref(make_cconfig(cfg)), self.batch, self.device)
 
     def reset(self, idx=None, t0=0.0, stream=None):
         if idx is None:
@@ -345,14 +288,3 @@ class MpcHandle:
 
     def kernel_names(self):
         return self._lib.rg_mpc_kernel_names().decode().split(",")
-
-    def close(self):
-        if self._h:
-            self._lib.rg_mpc_destroy(self._h)
-            self._h = fp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -5,9 +5,8 @@ status codes into exceptions and owns one rg_policy_handle.  There is NO CPU fal
 handle raises.  Every buffer is a caller-owned tensor (layouts: rg_policy.h).
 """
 import ctypes as C
-import os
 
-from robot_gym_amd.core import goto_abi, mpc_abi
+from robot_gym_amd.core.c_abi import STATUS, Handle, RgError, create_status as _create_status, d, fp, i32, load, merged, resolve_device  # noqa: F401 -- STATUS stays a name of this module
 
 ABI_VERSION = 1
 MAX_OBS, MAX_ACT, MAX_LAYERS, MAX_WIDTH = 64, 4, 3, 256
@@ -17,17 +16,10 @@ NORM_REWARD = 64         # RG_POLICY_NORM_REWARD: the reward's column
 NORM_ROWS = 195          # RG_POLICY_NORM_ROWS = [count, mean, var_sum][NORM_COLS]
 DEVICE_NONE = -1         # RG_POLICY_DEVICE_NONE: a host-only handle
 MODE_SAMPLE, MODE_MEAN = 0, 1
-d = C.c_double
-i32 = C.c_int32
-fp = C.c_void_p
-
-STATUS = {0: "OK", -1: "INVALID", -2: "HIP", -3: "NO_DEVICE", -4: "ALLOC"}
 
 
-class RgPolicyError(RuntimeError):
-    def __init__(self, status, text):
-        super().__init__(f"rg_policy status {status} ({STATUS.get(status, '?')}): {text}")
-        self.status = status
+class RgPolicyError(RgError):
+    unit = "rg_policy"
 
 
 class CConfig(C.Structure):
@@ -54,57 +46,25 @@ EXPORTS = ("rg_policy_create", "rg_policy_destroy", "rg_policy_last_error", "rg_
 DEFAULTS = dict(obs_dim=16, act_dim=2, policy_layers=(200, 100), value_layers=(200, 100), obs_clip=5.0, reward_clip=10.0, discount=0.985,
                 gae_lambda=1.0, seed=0)
 
-_lib = None
+# rg_policy.h's entries past those every unit has; the int32 getters are declared with the checks they serve
+SIGNATURES = {
+    "create": (i32, [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]),
+    "param_layout": (i32, [C.POINTER(CConfig), C.POINTER(CLayout)]),
+    "act": (i32, [fp, fp, fp, fp, fp, fp, i32, fp, fp, fp, fp, fp]),
+    "record": (i32, [fp, fp, fp, fp, fp, fp, fp, fp, fp, fp]),
+    "returns": (i32, [fp, fp, fp, fp, fp, fp, i32, i32, fp, fp, fp]),
+}
 
 
 def load_library(path=None):
-    """The rg_policy_* entries of librg_mpc.so (mpc_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    p = path or mpc_abi.LIB_PATH
-    if not os.path.exists(p):
-        raise ImportError(f"{p} not found: build it with `make -C robot_gym_amd/csrc` (or __graft_entry__.build()); "
-                          "the policy has no CPU fallback")
-    L = C.CDLL(p)
-    L.rg_policy_create.argtypes = [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]
-    L.rg_policy_create.restype = i32
-    L.rg_policy_destroy.argtypes = [fp]
-    L.rg_policy_destroy.restype = None
-    L.rg_policy_last_error.argtypes = [fp]
-    L.rg_policy_last_error.restype = C.c_char_p
-    for name in ("abi_version", "config_size", "layout_size", "norm_rows", "tile"):
-        getattr(L, f"rg_policy_{name}").restype = i32
-    L.rg_policy_param_layout.argtypes = [C.POINTER(CConfig), C.POINTER(CLayout)]
-    L.rg_policy_param_layout.restype = i32
-    L.rg_policy_act.argtypes = [fp, fp, fp, fp, fp, fp, i32, fp, fp, fp, fp, fp]
-    L.rg_policy_act.restype = i32
-    L.rg_policy_record.argtypes = [fp, fp, fp, fp, fp, fp, fp, fp, fp, fp]
-    L.rg_policy_record.restype = i32
-    L.rg_policy_returns.argtypes = [fp, fp, fp, fp, fp, fp, i32, i32, fp, fp, fp]
-    L.rg_policy_returns.restype = i32
-    if L.rg_policy_abi_version() != ABI_VERSION:
-        raise ImportError("librg_mpc.so rg_policy ABI version mismatch")
-    if L.rg_policy_config_size() != C.sizeof(CConfig):
-        raise ImportError(f"rg_policy_config size mismatch: lib {L.rg_policy_config_size()} vs binding {C.sizeof(CConfig)}")
-    if L.rg_policy_layout_size() != C.sizeof(CLayout):
-        raise ImportError(f"rg_policy_layout size mismatch: lib {L.rg_policy_layout_size()} vs binding {C.sizeof(CLayout)}")
-    if L.rg_policy_norm_rows() != NORM_ROWS:
-        raise ImportError(f"rg_policy norm rows mismatch: lib {L.rg_policy_norm_rows()} vs binding {NORM_ROWS}")
-    if L.rg_policy_tile() != TILE:
-        raise ImportError(f"rg_policy tile mismatch: lib {L.rg_policy_tile()} vs binding {TILE}")
-    if path is None:
-        _lib = L
-    return L
+    """The rg_policy_* entries of librg_mpc.so (c_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
+    return load("rg_policy", "the policy has no CPU fallback", SIGNATURES, {"config": CConfig, "layout": CLayout},
+                {"norm_rows": NORM_ROWS, "tile": TILE}, ABI_VERSION, path)
 
 
 def policy_fields(**settings):
     """The value of every rg_policy_config setting as a dict: DEFAULTS overridden by `settings`."""
-    unknown = set(settings) - set(DEFAULTS)
-    if unknown:
-        raise TypeError(f"unknown policy setting(s) {sorted(unknown)}")
-    out = dict(DEFAULTS)
-    out.update(settings)
+    out = merged(DEFAULTS, settings, "policy")
     for name in ("policy_layers", "value_layers"):
         out[name] = tuple(int(w) for w in out[name])
         if len(out[name]) > MAX_LAYERS:
@@ -144,48 +104,24 @@ def param_layout(cconfig=None, **settings):
 
 def create_status(cconfig=None, batch=1, device=DEVICE_NONE):
     """(status, text) of rg_policy_create; destroys the handle when one is made."""
-    lib = load_library()
     cc = make_cconfig() if cconfig is None else cconfig
-    h = fp()
-    rc = lib.rg_policy_create(C.byref(cc), int(batch), int(device), C.byref(h))
-    text = lib.rg_policy_last_error(None).decode() if rc else ""
-    if h:
-        lib.rg_policy_destroy(h)
-    return rc, text
+    return _create_status(load_library(), "rg_policy", C.byref(cc), int(batch), int(device))
 
 
-class PolicyHandle:
+class PolicyHandle(Handle):
     """Owns one rg_policy_handle and launches on torch's current stream of its device.  device=DEVICE_NONE makes the host-only
     handle of rg_policy_create: it needs no GPU, every call checks its arguments and then raises NO_DEVICE."""
 
+    unit, error = "rg_policy", RgPolicyError
+
     def __init__(self, batch, device=None, **settings):
-        self._h = fp()
-        self._lib = load_library()
+        lib = load_library()
         self.batch = int(batch)
         self.fields = policy_fields(**settings)
-        if device == DEVICE_NONE:
-            self.device, index = None, DEVICE_NONE
-        else:
-            import torch
-            if not torch.cuda.is_available():
-                raise RgPolicyError(-3, "no GPU: the policy kernels have no CPU fallback")
-            index = None if device is None else torch.device(device).index
-            self.device = torch.device("cuda", torch.cuda.current_device() if index is None else index)
-            index = self.device.index
+        self.device, index = resolve_device(device, RgPolicyError, "the policy kernels have no CPU fallback", DEVICE_NONE)
         cc = make_cconfig(**settings)
-        rc = self._lib.rg_policy_create(C.byref(cc), self.batch, index, C.byref(self._h))
-        if rc != 0:
-            msg = self._lib.rg_policy_last_error(None)
-            self._h = fp()
-            raise RgPolicyError(rc, msg.decode() if msg else "create failed")
+        self._create(lib, C.byref(cc), self.batch, index)
         self.layout = param_layout(cc)
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RgPolicyError(rc, self._lib.rg_policy_last_error(self._h).decode())
-
-    def _s(self):
-        return None if self.device is None else goto_abi._stream(self.device)
 
     def act(self, obs_ptr, norm_ptr, policy_params_ptr, value_params_ptr, act_state_ptr, mode, action_ptr, mean_ptr=None, value_ptr=None,
             logprob_ptr=None):
@@ -199,14 +135,3 @@ class PolicyHandle:
     def returns(self, reward_ptr, value_ptr, done_ptr, last_value_ptr, norm_ptr, T, bootstrap, ret_ptr, adv_ptr):
         self._check(self._lib.rg_policy_returns(self._h, reward_ptr, value_ptr, done_ptr, last_value_ptr, norm_ptr, int(T), int(bool(bootstrap)),
                                                 ret_ptr, adv_ptr, self._s()))
-
-    def close(self):
-        if self._h:
-            self._lib.rg_policy_destroy(self._h)
-            self._h = fp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

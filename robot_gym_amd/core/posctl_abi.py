@@ -5,25 +5,17 @@ exceptions and owns one rg_posctl_handle.  There is NO CPU fallback: without the
 The Bezier gait state lives in a caller-owned float64 tensor [15][B] (rows: phi, last_time, alpha, frame[4][3]).
 """
 import ctypes as C
-import os
 
-from robot_gym_amd.core import mpc_abi
+from robot_gym_amd.core.c_abi import STATUS, Handle, RgError, create_status as _create_status, d, fill_config, fp, i32, load, resolve_device, stream  # noqa: F401 -- STATUS stays a name of this module
 
 ABI_VERSION = 1
 STATE_ROWS = 15        # RG_POSCTL_STATE_ROWS
 ROW_PHI, ROW_LAST_TIME, ROW_ALPHA, ROW_FRAME = 0, 1, 2, 3
 MAX_SUBSTEPS = 1024    # RG_POSCTL_MAX_SUBSTEPS
-d = C.c_double
-i32 = C.c_int32
-fp = C.c_void_p
-
-STATUS = {0: "OK", -1: "INVALID", -2: "HIP", -3: "NO_DEVICE", -4: "ALLOC"}
 
 
-class RgPosCtlError(RuntimeError):
-    def __init__(self, status, text):
-        super().__init__(f"rg_posctl status {status} ({STATUS.get(status, '?')}): {text}")
-        self.status = status
+class RgPosCtlError(RgError):
+    unit = "rg_posctl"
 
 
 class CConfig(C.Structure):
@@ -37,40 +29,18 @@ class CConfig(C.Structure):
 EXPORTS = ("rg_posctl_create", "rg_posctl_destroy", "rg_posctl_last_error", "rg_posctl_abi_version", "rg_posctl_config_size",
            "rg_posctl_bezier_step", "rg_posctl_pose", "rg_posctl_position_to_torque")
 
-_lib = None
+# rg_posctl.h's entries past those every unit has; the int32 getters are declared with the checks they serve
+SIGNATURES = {
+    "create": (i32, [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]),
+    "bezier_step": (i32, [fp, d, fp, fp, fp, fp, fp]),
+    "pose": (i32, [fp, fp, fp, fp]),
+    "position_to_torque": (i32, [fp, fp, fp, fp, fp, i32, fp]),
+}
 
 
 def load_library(path=None):
-    """The rg_posctl_* entries of librg_mpc.so (mpc_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    p = path or mpc_abi.LIB_PATH
-    if not os.path.exists(p):
-        raise ImportError(f"{p} not found: build it with `make -C robot_gym_amd/csrc` (or __graft_entry__.build()); "
-                          "the position-mode controllers have no CPU fallback")
-    L = C.CDLL(p)
-    L.rg_posctl_create.argtypes = [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]
-    L.rg_posctl_create.restype = i32
-    L.rg_posctl_destroy.argtypes = [fp]
-    L.rg_posctl_destroy.restype = None
-    L.rg_posctl_last_error.argtypes = [fp]
-    L.rg_posctl_last_error.restype = C.c_char_p
-    L.rg_posctl_abi_version.restype = i32
-    L.rg_posctl_config_size.restype = i32
-    L.rg_posctl_bezier_step.argtypes = [fp, d, fp, fp, fp, fp, fp]
-    L.rg_posctl_bezier_step.restype = i32
-    L.rg_posctl_pose.argtypes = [fp, fp, fp, fp]
-    L.rg_posctl_pose.restype = i32
-    L.rg_posctl_position_to_torque.argtypes = [fp, fp, fp, fp, fp, i32, fp]
-    L.rg_posctl_position_to_torque.restype = i32
-    if L.rg_posctl_abi_version() != ABI_VERSION:
-        raise ImportError("librg_mpc.so rg_posctl ABI version mismatch")
-    if L.rg_posctl_config_size() != C.sizeof(CConfig):
-        raise ImportError(f"rg_posctl_config size mismatch: lib {L.rg_posctl_config_size()} vs binding {C.sizeof(CConfig)}")
-    if path is None:
-        _lib = L
-    return L
+    """The rg_posctl_* entries of librg_mpc.so (c_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
+    return load("rg_posctl", "the position-mode controllers have no CPU fallback", SIGNATURES, {"config": CConfig}, {}, ABI_VERSION, path)
 
 
 def make_cconfig(cfg):
@@ -78,67 +48,36 @@ def make_cconfig(cfg):
     c = CConfig()
     c.abi_version = ABI_VERSION
     c.reserved0 = 0
-    for name, _ in CConfig._fields_:
-        if name in ("abi_version", "reserved0"):
-            continue
-        v = getattr(cfg, name)
-        if hasattr(v, "__len__"):
-            arr = getattr(c, name)
-            if len(v) != len(arr):
-                raise ValueError(f"config field {name}: expected {len(arr)} values, got {len(v)}")
-            for k, x in enumerate(v):
-                arr[k] = float(x)
-        else:
-            setattr(c, name, float(v))
-    return c
+    return fill_config(c, {name: getattr(cfg, name) for name, _ in CConfig._fields_ if name not in ("abi_version", "reserved0")})
 
 
 def create_status(cfg, batch, device=0):
     """(status, text) of rg_posctl_create for `cfg`; destroys the handle when one is made.  For tests of the validation."""
     lib = load_library()
-    h = fp()
     cc = cfg if isinstance(cfg, CConfig) else make_cconfig(cfg)
-    rc = lib.rg_posctl_create(C.byref(cc), int(batch), int(device), C.byref(h))
-    text = lib.rg_posctl_last_error(None).decode() if rc else ""
-    if h:
-        lib.rg_posctl_destroy(h)
-    return rc, text
+    return _create_status(lib, "rg_posctl", C.byref(cc), int(batch), int(device))
 
 
-def _stream(device):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-class PosCtlHandle:
+class PosCtlHandle(Handle):
     """Owns one rg_posctl_handle (one device) and launches on torch's current stream of that device.  The batched
     controllers of robot_gym_amd.controllers.bezier / .pose share it."""
 
+    unit, error = "rg_posctl", RgPosCtlError
+
     def __init__(self, cfg, batch, device=None):
         import torch
-        if not torch.cuda.is_available():
-            raise RgPosCtlError(-3, "no GPU: the position-mode controllers have no CPU fallback")
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else torch.device(device).index or 0)
-        self._lib = load_library()
-        self._h = fp()
+        # `or 0`: an index-less device ("cuda") is device 0 here, the current device in every other handle: kept, not endorsed
+        self.device, index = resolve_device(device if device is None else torch.device(device).index or 0, RgPosCtlError,
+                                            "the position-mode controllers have no CPU fallback")
         self.batch = int(batch)
-        cc = make_cconfig(cfg)
-        rc = self._lib.rg_posctl_create(C.byref(cc), self.batch, self.device.index, C.byref(self._h))
-        if rc != 0:
-            msg = self._lib.rg_posctl_last_error(None)
-            self._h = fp()
-            raise RgPosCtlError(rc, msg.decode() if msg else "create failed")
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RgPosCtlError(rc, self._lib.rg_posctl_last_error(self._h).decode())
+        self._create(load_library(), C.byref(make_cconfig(cfg)), self.batch, index)
 
     def bezier_step(self, t, t_robot_ptr, params_ptr, state_ptr, angles_ptr):
         self._check(self._lib.rg_posctl_bezier_step(self._h, float(t), t_robot_ptr, params_ptr, state_ptr, angles_ptr,
-                                                    _stream(self.device)))
+                                                    stream(self.device)))
 
     def pose(self, pose_ptr, angles_ptr):
-        self._check(self._lib.rg_posctl_pose(self._h, pose_ptr, angles_ptr, _stream(self.device)))
+        self._check(self._lib.rg_posctl_pose(self._h, pose_ptr, angles_ptr, stream(self.device)))
 
     def position_to_torque(self, angles, q, qd, substeps=1):
         """angles [B,12], q / qd [S,12,B] (or [12,B] for S = 1) float32 device tensors -> tau [S,B,12] float32."""
@@ -151,7 +90,7 @@ class PosCtlHandle:
         qd = self.device_f32(qd, (S, 12, B), "qd")
         tau = torch.empty(S, B, 12, dtype=torch.float32, device=self.device)
         self._check(self._lib.rg_posctl_position_to_torque(self._h, angles.data_ptr(), q.data_ptr(), qd.data_ptr(), tau.data_ptr(), S,
-                                                           _stream(self.device)))
+                                                           stream(self.device)))
         return tau
 
     def device_f32(self, x, shape, name):
@@ -161,14 +100,3 @@ class PosCtlHandle:
         if t.numel() != int(torch.Size(shape).numel()):
             raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
         return t.reshape(shape).contiguous()
-
-    def close(self):
-        if self._h:
-            self._lib.rg_posctl_destroy(self._h)
-            self._h = fp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -5,9 +5,8 @@ codes into exceptions and owns one rg_rnn_handle.  There is NO CPU fallback: wit
 raises.  Every buffer is a caller-owned tensor (layouts: rg_rnn.h).
 """
 import ctypes as C
-import os
 
-from robot_gym_amd.core import goto_abi, mpc_abi
+from robot_gym_amd.core.c_abi import STATUS, Handle, RgError, create_status as _create_status, d, fp, i32, load, merged, resolve_device  # noqa: F401 -- STATUS stays a name of this module
 
 ABI_VERSION = 1
 MAX_OBS, MAX_ACT, MAX_DENSE, MAX_VALUE_LAYERS, MAX_WIDTH, MAX_UNITS = 64, 4, 2, 3, 256, 128
@@ -15,17 +14,10 @@ TILE = 8                 # RG_RNN_TILE: robots per workgroup of both kernels
 MAX_T = 1 << 16          # RG_RNN_MAX_T
 DEVICE_NONE = -1         # RG_RNN_DEVICE_NONE: a host-only handle
 MODE_SAMPLE, MODE_MEAN = 0, 1
-d = C.c_double
-i32 = C.c_int32
-fp = C.c_void_p
-
-STATUS = {0: "OK", -1: "INVALID", -2: "HIP", -3: "NO_DEVICE", -4: "ALLOC"}
 
 
-class RgRnnError(RuntimeError):
-    def __init__(self, status, text):
-        super().__init__(f"rg_rnn status {status} ({STATUS.get(status, '?')}): {text}")
-        self.status = status
+class RgRnnError(RgError):
+    unit = "rg_rnn"
 
 
 class CConfig(C.Structure):
@@ -50,53 +42,24 @@ EXPORTS = ("rg_rnn_create", "rg_rnn_destroy", "rg_rnn_last_error", "rg_rnn_abi_v
 # the reference's agents/ppo/scripts/networks.py (RecurrentGaussianPolicy: policy_layers[:-1], GRUBlockCell(100)) and configs.py
 DEFAULTS = dict(obs_dim=16, act_dim=2, policy_layers=(200,), gru_units=100, value_layers=(200, 100), obs_clip=5.0, seed=0)
 
-_lib = None
+# rg_rnn.h's entries past those every unit has; the int32 getters are declared with the checks they serve
+SIGNATURES = {
+    "create": (i32, [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]),
+    "param_layout": (i32, [C.POINTER(CConfig), C.POINTER(CLayout)]),
+    "act": (i32, [fp, fp, fp, fp, fp, fp, fp, fp, fp, i32, fp, fp, fp, fp, fp]),
+    "unroll": (i32, [fp, fp, fp, fp, fp, fp, i32, fp, fp, fp, fp]),
+}
 
 
 def load_library(path=None):
-    """The rg_rnn_* entries of librg_mpc.so (mpc_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    p = path or mpc_abi.LIB_PATH
-    if not os.path.exists(p):
-        raise ImportError(f"{p} not found: build it with `make -C robot_gym_amd/csrc` (or __graft_entry__.build()); "
-                          "the recurrent policy has no CPU fallback")
-    L = C.CDLL(p)
-    L.rg_rnn_create.argtypes = [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]
-    L.rg_rnn_create.restype = i32
-    L.rg_rnn_destroy.argtypes = [fp]
-    L.rg_rnn_destroy.restype = None
-    L.rg_rnn_last_error.argtypes = [fp]
-    L.rg_rnn_last_error.restype = C.c_char_p
-    for name in ("abi_version", "config_size", "layout_size", "tile"):
-        getattr(L, f"rg_rnn_{name}").restype = i32
-    L.rg_rnn_param_layout.argtypes = [C.POINTER(CConfig), C.POINTER(CLayout)]
-    L.rg_rnn_param_layout.restype = i32
-    L.rg_rnn_act.argtypes = [fp, fp, fp, fp, fp, fp, fp, fp, fp, i32, fp, fp, fp, fp, fp]
-    L.rg_rnn_act.restype = i32
-    L.rg_rnn_unroll.argtypes = [fp, fp, fp, fp, fp, fp, i32, fp, fp, fp, fp]
-    L.rg_rnn_unroll.restype = i32
-    if L.rg_rnn_abi_version() != ABI_VERSION:
-        raise ImportError("librg_mpc.so rg_rnn ABI version mismatch")
-    if L.rg_rnn_config_size() != C.sizeof(CConfig):
-        raise ImportError(f"rg_rnn_config size mismatch: lib {L.rg_rnn_config_size()} vs binding {C.sizeof(CConfig)}")
-    if L.rg_rnn_layout_size() != C.sizeof(CLayout):
-        raise ImportError(f"rg_rnn_layout size mismatch: lib {L.rg_rnn_layout_size()} vs binding {C.sizeof(CLayout)}")
-    if L.rg_rnn_tile() != TILE:
-        raise ImportError(f"rg_rnn tile mismatch: lib {L.rg_rnn_tile()} vs binding {TILE}")
-    if path is None:
-        _lib = L
-    return L
+    """The rg_rnn_* entries of librg_mpc.so (c_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
+    return load("rg_rnn", "the recurrent policy has no CPU fallback", SIGNATURES, {"config": CConfig, "layout": CLayout}, {"tile": TILE},
+                ABI_VERSION, path)
 
 
 def rnn_fields(**settings):
     """The value of every rg_rnn_config setting as a dict: DEFAULTS overridden by `settings`."""
-    unknown = set(settings) - set(DEFAULTS)
-    if unknown:
-        raise TypeError(f"unknown recurrent policy setting(s) {sorted(unknown)}")
-    out = dict(DEFAULTS)
-    out.update(settings)
+    out = merged(DEFAULTS, settings, "recurrent policy")
     for name, most in (("policy_layers", MAX_DENSE), ("value_layers", MAX_VALUE_LAYERS)):
         out[name] = tuple(int(w) for w in out[name])
         if len(out[name]) > most:
@@ -139,48 +102,24 @@ def param_layout(cconfig=None, **settings):
 
 def create_status(cconfig=None, batch=1, device=DEVICE_NONE):
     """(status, text) of rg_rnn_create; destroys the handle when one is made."""
-    lib = load_library()
     cc = make_cconfig() if cconfig is None else cconfig
-    h = fp()
-    rc = lib.rg_rnn_create(C.byref(cc), int(batch), int(device), C.byref(h))
-    text = lib.rg_rnn_last_error(None).decode() if rc else ""
-    if h:
-        lib.rg_rnn_destroy(h)
-    return rc, text
+    return _create_status(load_library(), "rg_rnn", C.byref(cc), int(batch), int(device))
 
 
-class RnnHandle:
+class RnnHandle(Handle):
     """Owns one rg_rnn_handle and launches on torch's current stream of its device.  device=DEVICE_NONE makes the host-only
     handle of rg_rnn_create: it needs no GPU, every call checks its arguments and then raises NO_DEVICE."""
 
+    unit, error = "rg_rnn", RgRnnError
+
     def __init__(self, batch, device=None, **settings):
-        self._h = fp()
-        self._lib = load_library()
+        lib = load_library()
         self.batch = int(batch)
         self.fields = rnn_fields(**settings)
-        if device == DEVICE_NONE:
-            self.device, index = None, DEVICE_NONE
-        else:
-            import torch
-            if not torch.cuda.is_available():
-                raise RgRnnError(-3, "no GPU: the recurrent policy's kernels have no CPU fallback")
-            index = None if device is None else torch.device(device).index
-            self.device = torch.device("cuda", torch.cuda.current_device() if index is None else index)
-            index = self.device.index
+        self.device, index = resolve_device(device, RgRnnError, "the recurrent policy's kernels have no CPU fallback", DEVICE_NONE)
         cc = make_cconfig(**settings)
-        rc = self._lib.rg_rnn_create(C.byref(cc), self.batch, index, C.byref(self._h))
-        if rc != 0:
-            msg = self._lib.rg_rnn_last_error(None)
-            self._h = fp()
-            raise RgRnnError(rc, msg.decode() if msg else "create failed")
+        self._create(lib, C.byref(cc), self.batch, index)
         self.layout = param_layout(cc)
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RgRnnError(rc, self._lib.rg_rnn_last_error(self._h).decode())
-
-    def _s(self):
-        return None if self.device is None else goto_abi._stream(self.device)
 
     def act(self, obs_ptr, norm_ptr, policy_params_ptr, value_params_ptr, act_state_ptr, reset_ptr, hidden_in_ptr, hidden_out_ptr, mode, action_ptr,
             mean_ptr=None, value_ptr=None, logprob_ptr=None):
@@ -190,14 +129,3 @@ class RnnHandle:
     def unroll(self, obs_ptr, reset_ptr, h0_ptr, norm_ptr, policy_params_ptr, T, mean_ptr, hidden_seq_ptr=None, hidden_last_ptr=None):
         self._check(self._lib.rg_rnn_unroll(self._h, obs_ptr, reset_ptr, h0_ptr, norm_ptr, policy_params_ptr, int(T), mean_ptr, hidden_seq_ptr,
                                             hidden_last_ptr, self._s()))
-
-    def close(self):
-        if self._h:
-            self._lib.rg_rnn_destroy(self._h)
-            self._h = fp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

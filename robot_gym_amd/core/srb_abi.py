@@ -5,28 +5,21 @@ negative status codes into exceptions and owns one rg_srb_handle.  There is NO C
 GPU the constructor raises.  The simulation state lives in a caller-owned float64 tensor [43][B] (rows: rg_srb.h).
 """
 import ctypes as C
-import os
 
 import numpy as np
 
-from robot_gym_amd.core import mpc_abi
+from robot_gym_amd.core.c_abi import (STATUS, Handle, RgError, create_status as _create_status, d, fill_config, fp, host_array, host_ptr, i32,  # noqa: F401 -- STATUS stays a name of this module
+                                      index_array, load, merged, resolve_device, stream)
 
 ABI_VERSION = 1
 STATE_ROWS = 43          # RG_SRB_STATE_ROWS
 ROW_P, ROW_QUAT, ROW_V, ROW_W, ROW_FOOT, ROW_Q, ROW_STANCE, ROW_STEPS, ROW_STATUS = 0, 3, 7, 10, 13, 25, 37, 41, 42
 MAX_SUBSTEPS = 1024      # RG_SRB_MAX_SUBSTEPS
 RESET_IK_PASSES = 4      # RG_SRB_RESET_IK_PASSES
-d = C.c_double
-i32 = C.c_int32
-fp = C.c_void_p
-
-STATUS = {0: "OK", -1: "INVALID", -2: "HIP", -3: "NO_DEVICE", -4: "ALLOC"}
 
 
-class RgSrbError(RuntimeError):
-    def __init__(self, status, text):
-        super().__init__(f"rg_srb status {status} ({STATUS.get(status, '?')}): {text}")
-        self.status = status
+class RgSrbError(RgError):
+    unit = "rg_srb"
 
 
 class CConfig(C.Structure):
@@ -68,56 +61,25 @@ EXPORTS = ("rg_srb_create", "rg_srb_destroy", "rg_srb_last_error", "rg_srb_abi_v
 # core/sim_constants.py, and the two fall thresholds
 SIM_DEFAULTS = dict(dt_sim=0.001, substeps=10, fall_height_scale=0.5, fall_tilt=1.0)
 
-_lib = None
+# the entries of rg_srb.h, rg_srb_terrain.h and rg_srb_contact.h past those every unit has; the int32 getters are declared with
+# the checks they serve
+SIGNATURES = {
+    "create": (i32, [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]),
+    "set_body": (i32, [fp, fp, i32, fp, fp, fp]),
+    "reset": (i32, [fp, fp, i32, fp, fp, fp, fp, C.POINTER(CObsPtrs), fp]),
+    "step": (i32, [fp, fp, fp, fp, fp, fp, C.POINTER(CObsPtrs), fp]),
+    "terrain_check": (i32, [C.POINTER(CTerrain), C.c_char_p, i32]),
+    "set_terrain": (i32, [fp, C.POINTER(CTerrain)]),
+    "ground_height": (i32, [fp, fp, fp, i32, fp, fp]),
+    "settle": (i32, [fp, fp, fp, C.POINTER(CObsPtrs), fp]),
+    "step_contact": (i32, [fp, fp, fp, fp, fp, fp, C.POINTER(CObsPtrs), fp, fp]),
+}
 
 
 def load_library(path=None):
-    """The rg_srb_* entries of librg_mpc.so (mpc_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    p = path or mpc_abi.LIB_PATH
-    if not os.path.exists(p):
-        raise ImportError(f"{p} not found: build it with `make -C robot_gym_amd/csrc` (or __graft_entry__.build()); "
-                          "the single-rigid-body simulator has no CPU fallback")
-    L = C.CDLL(p)
-    L.rg_srb_create.argtypes = [C.POINTER(CConfig), i32, i32, C.POINTER(fp)]
-    L.rg_srb_create.restype = i32
-    L.rg_srb_destroy.argtypes = [fp]
-    L.rg_srb_destroy.restype = None
-    L.rg_srb_last_error.argtypes = [fp]
-    L.rg_srb_last_error.restype = C.c_char_p
-    L.rg_srb_abi_version.restype = i32
-    L.rg_srb_config_size.restype = i32
-    L.rg_srb_state_rows.restype = i32
-    L.rg_srb_set_body.argtypes = [fp, fp, i32, fp, fp, fp]
-    L.rg_srb_set_body.restype = i32
-    L.rg_srb_reset.argtypes = [fp, fp, i32, fp, fp, fp, fp, C.POINTER(CObsPtrs), fp]
-    L.rg_srb_reset.restype = i32
-    L.rg_srb_step.argtypes = [fp, fp, fp, fp, fp, fp, C.POINTER(CObsPtrs), fp]
-    L.rg_srb_step.restype = i32
-    L.rg_srb_terrain_size.restype = i32
-    L.rg_srb_terrain_check.argtypes = [C.POINTER(CTerrain), C.c_char_p, i32]
-    L.rg_srb_terrain_check.restype = i32
-    L.rg_srb_set_terrain.argtypes = [fp, C.POINTER(CTerrain)]
-    L.rg_srb_set_terrain.restype = i32
-    L.rg_srb_ground_height.argtypes = [fp, fp, fp, i32, fp, fp]
-    L.rg_srb_ground_height.restype = i32
-    L.rg_srb_settle.argtypes = [fp, fp, fp, C.POINTER(CObsPtrs), fp]
-    L.rg_srb_settle.restype = i32
-    L.rg_srb_step_contact.argtypes = [fp, fp, fp, fp, fp, fp, C.POINTER(CObsPtrs), fp, fp]
-    L.rg_srb_step_contact.restype = i32
-    if L.rg_srb_abi_version() != ABI_VERSION:
-        raise ImportError("librg_mpc.so rg_srb ABI version mismatch")
-    if L.rg_srb_config_size() != C.sizeof(CConfig):
-        raise ImportError(f"rg_srb_config size mismatch: lib {L.rg_srb_config_size()} vs binding {C.sizeof(CConfig)}")
-    if L.rg_srb_state_rows() != STATE_ROWS:
-        raise ImportError(f"rg_srb state rows mismatch: lib {L.rg_srb_state_rows()} vs binding {STATE_ROWS}")
-    if L.rg_srb_terrain_size() != C.sizeof(CTerrain):
-        raise ImportError(f"rg_srb_terrain size mismatch: lib {L.rg_srb_terrain_size()} vs binding {C.sizeof(CTerrain)}")
-    if path is None:
-        _lib = L
-    return L
+    """The rg_srb_* entries of librg_mpc.so (c_abi.LIB_PATH).  Raises (never falls back) when the library is missing."""
+    return load("rg_srb", "the single-rigid-body simulator has no CPU fallback", SIGNATURES, {"config": CConfig, "terrain": CTerrain},
+                {"state_rows": STATE_ROWS}, ABI_VERSION, path)
 
 
 def make_cterrain(kind=TERRAIN_FLAT, cell=0.0, amplitude=0.0, seed=0, key=None, heights=None, rows=0, cols=0, x0=0.0, y0=0.0):
@@ -141,19 +103,15 @@ def sim_fields(cfg, **sim):
     """The values of every rg_srb_config field as a dict: the body and kinematic fields of the MPCConfig `cfg`, init_q from
     the robot's INIT_MOTOR_ANGLES (or `init_q=`), and the simulator's settings (SIM_DEFAULTS, overridden by `sim`)."""
     from robot_gym_amd.model.robots.robot_constants import ROBOTS
-    unknown = set(sim) - set(SIM_DEFAULTS) - {"init_q"}
-    if unknown:
-        raise TypeError(f"unknown simulator setting(s) {sorted(unknown)}")
+    sim = merged(dict(SIM_DEFAULTS, init_q=None), sim, "simulator")
     out = {}
     for name, _ in CConfig._fields_:
         if name in ("abi_version", "reserved0"):
             continue
         if name == "init_q":
-            out[name] = tuple(sim["init_q"]) if sim.get("init_q") is not None else tuple(ROBOTS[cfg.robot].init_motor_angles)
-        elif name in SIM_DEFAULTS:
-            out[name] = sim.get(name, SIM_DEFAULTS[name])
+            out[name] = tuple(sim["init_q"]) if sim["init_q"] is not None else tuple(ROBOTS[cfg.robot].init_motor_angles)
         else:
-            out[name] = getattr(cfg, name)
+            out[name] = sim[name] if name in SIM_DEFAULTS else getattr(cfg, name)
     return out
 
 
@@ -162,30 +120,14 @@ def make_cconfig(cfg, **sim):
     c = CConfig()
     c.abi_version = ABI_VERSION
     c.reserved0 = 0
-    for name, v in sim_fields(cfg, **sim).items():
-        if hasattr(v, "__len__"):
-            arr = getattr(c, name)
-            if len(v) != len(arr):
-                raise ValueError(f"config field {name}: expected {len(arr)} values, got {len(v)}")
-            for k, x in enumerate(v):
-                arr[k] = float(x)
-        elif name in ("ik_iters", "substeps"):
-            setattr(c, name, int(v))
-        else:
-            setattr(c, name, float(v))
-    return c
+    return fill_config(c, sim_fields(cfg, **sim), ("ik_iters", "substeps"))
 
 
 def create_status(cfg, batch, device=0, **sim):
     """(status, text) of rg_srb_create for `cfg`; destroys the handle when one is made.  For tests of the validation."""
     lib = load_library()
-    h = fp()
     cc = cfg if isinstance(cfg, CConfig) else make_cconfig(cfg, **sim)
-    rc = lib.rg_srb_create(C.byref(cc), int(batch), int(device), C.byref(h))
-    text = lib.rg_srb_last_error(None).decode() if rc else ""
-    if h:
-        lib.rg_srb_destroy(h)
-    return rc, text
+    return _create_status(lib, "rg_srb", C.byref(cc), int(batch), int(device))
 
 
 def checked_ptr(t, name, dtype, shape, device, entry="step_contact", optional=False):
@@ -223,100 +165,62 @@ def step_contact_ptrs(batch, device, state, grf, foot_target, leg_state, ext=Non
             checked_ptr(touch, "touch", torch.int32, (4, B), device, optional=True))
 
 
-def _stream(device):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _f64(a, shape, name):
-    if a is None:
-        return None
-    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
-    if a.shape != shape:
-        raise ValueError(f"{name} must have shape {list(shape)}, got {list(a.shape)}")
-    return a
+    return None if a is None else host_array(a, np.float64, shape, name)
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data
-
-
-class SrbHandle:
+class SrbHandle(Handle):
     """Owns one rg_srb_handle (one device) and launches on torch's current stream of that device."""
 
-    def __init__(self, cfg, batch, device=None, **sim):
-        import torch
-        if not torch.cuda.is_available():
-            raise RgSrbError(-3, "no GPU: the single-rigid-body simulator has no CPU fallback")
-        index = None if device is None else torch.device(device).index
-        self.device = torch.device("cuda", torch.cuda.current_device() if index is None else index)
-        self._lib = load_library()
-        self._h = fp()
-        self.batch = int(batch)
-        cc = make_cconfig(cfg, **sim)
-        rc = self._lib.rg_srb_create(C.byref(cc), self.batch, self.device.index, C.byref(self._h))
-        if rc != 0:
-            msg = self._lib.rg_srb_last_error(None)
-            self._h = fp()
-            raise RgSrbError(rc, msg.decode() if msg else "create failed")
+    unit, error = "rg_srb", RgSrbError
 
-    def _check(self, rc):
-        if rc != 0:
-            raise RgSrbError(rc, self._lib.rg_srb_last_error(self._h).decode())
+    def __init__(self, cfg, batch, device=None, **sim):
+        self.device, index = resolve_device(device, RgSrbError, "the single-rigid-body simulator has no CPU fallback")
+        self.batch = int(batch)
+        self._create(load_library(), C.byref(make_cconfig(cfg, **sim)), self.batch, index)
 
     def set_body(self, idx=None, mass=None, inertia=None):
         """mass [n], inertia [9,n] or [n,3,3] host arrays for robots idx (None: all); both None returns every robot to the config."""
         if mass is None and inertia is None:
             if idx is not None:
                 raise ValueError("set_body: give mass or inertia with idx (neither, and no idx, returns every robot to the config)")
-            self._check(self._lib.rg_srb_set_body(self._h, None, 0, None, None, _stream(self.device)))
+            self._check(self._lib.rg_srb_set_body(self._h, None, 0, None, None, stream(self.device)))
             return
-        ia = None if idx is None else np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(-1))
+        ia = index_array(idx)
         n = self.batch if ia is None else len(ia)
         if inertia is not None:
             inertia = np.asarray(inertia, dtype=np.float64)
             if inertia.shape == (n, 3, 3):
                 inertia = inertia.reshape(n, 9).T
         mass, inertia = _f64(mass, (n,), "mass"), _f64(inertia, (9, n), "inertia")
-        self._check(self._lib.rg_srb_set_body(self._h, _ptr(ia), n, _ptr(mass), _ptr(inertia), _stream(self.device)))
+        self._check(self._lib.rg_srb_set_body(self._h, host_ptr(ia), n, host_ptr(mass), host_ptr(inertia), stream(self.device)))
 
     def reset(self, state_ptr, obs: CObsPtrs, idx=None, xy=None, yaw=None, height=None):
-        ia = None if idx is None else np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(-1))
+        ia = index_array(idx)
         n = self.batch if ia is None else len(ia)
         if n == 0:
             return
         xy, yaw, height = _f64(xy, (2, n), "xy"), _f64(yaw, (n,), "yaw"), _f64(height, (n,), "height")
-        self._check(self._lib.rg_srb_reset(self._h, _ptr(ia), n, _ptr(xy), _ptr(yaw), _ptr(height), state_ptr, C.byref(obs),
-                                           _stream(self.device)))
+        self._check(self._lib.rg_srb_reset(self._h, host_ptr(ia), n, host_ptr(xy), host_ptr(yaw), host_ptr(height), state_ptr, C.byref(obs),
+                                           stream(self.device)))
 
     def step(self, state_ptr, grf_ptr, foot_target_ptr, desired_ptr, ext_ptr, obs: CObsPtrs):
         self._check(self._lib.rg_srb_step(self._h, state_ptr, grf_ptr, foot_target_ptr, desired_ptr, ext_ptr, C.byref(obs),
-                                          _stream(self.device)))
+                                          stream(self.device)))
 
     def step_contact(self, state, grf, foot_target, leg_state, ext, obs: CObsPtrs, touch=None):
         """rg_srb_step_contact on TENSORS (ext and touch may be None): each is checked by step_contact_ptrs before the
         library sees its address."""
         ptrs = step_contact_ptrs(self.batch, self.device, state, grf, foot_target, leg_state, ext, touch)
         self._check(self._lib.rg_srb_step_contact(self._h, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], C.byref(obs), ptrs[5],
-                                                  _stream(self.device)))
+                                                  stream(self.device)))
 
     def set_terrain(self, t: CTerrain = None):
         """t None: back to the plane.  The caller keeps the device arrays t points at alive."""
         self._check(self._lib.rg_srb_set_terrain(self._h, None if t is None else C.byref(t)))
 
     def ground_height(self, xy_ptr, robot_ptr, n, out_ptr):
-        self._check(self._lib.rg_srb_ground_height(self._h, xy_ptr, robot_ptr, int(n), out_ptr, _stream(self.device)))
+        self._check(self._lib.rg_srb_ground_height(self._h, xy_ptr, robot_ptr, int(n), out_ptr, stream(self.device)))
 
     def settle(self, state_ptr, mask_ptr, obs: CObsPtrs):
-        self._check(self._lib.rg_srb_settle(self._h, state_ptr, mask_ptr, C.byref(obs), _stream(self.device)))
-
-    def close(self):
-        if self._h:
-            self._lib.rg_srb_destroy(self._h)
-            self._h = fp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._check(self._lib.rg_srb_settle(self._h, state_ptr, mask_ptr, C.byref(obs), stream(self.device)))
