@@ -1,0 +1,960 @@
+// rg_bptt.hip -- the recurrent PPO policy update of include/rg_bptt.h: back-propagation through time through the GRU cell of
+// rg_rnn.h, with the head, Adam and the penalty rule of rg_ppo.h.  Its own translation unit of librg_mpc.so.  The normaliser's
+// arithmetic, the workgroup sums and the transpose body are those of rg_agent_dev.inc and the host helpers those of rg_host.h;
+// rg_mpc.hip includes neither this file nor them, so the source hash behind profiles/ is unaffected.  The tick's arithmetic is
+// restated from rg_rnn.hip (whose device functions are its own): the GPU tests hold the two to the same bits.
+//
+// One gradient is four kinds of launch (rg_bptt.h):
+//   F  rg_bptt_forward_kernel: kTile robots per 256-thread workgroup through all T ticks, one output neuron per thread with
+//      kTile accumulators, x, h, r*h and u in LDS as [input * kTile + robot]; every intermediate of every sample goes to the
+//      workspace as [sample][neuron], coalesced along the neuron.
+//   H  rg_bptt_sample_kl_kernel (a thread per sample), rg_bptt_robot_kl_kernel (a thread per robot), rg_bptt_head_kernel
+//      (delta_mean per sample, the float64 partials of the loss and of the logstd gradient), rg_bptt_loss_finish_kernel.
+//   B  rg_bptt_delta_kernel: the same tile of robots with t from T - 1 down to 0.  Thread i < H owns hidden unit i: its dh for
+//      the kTile robots stays in registers, it reads r, u, c and h of its unit from the workspace, and the deltas of the tick
+//      (delta_mean, delta_c, delta_ru, the dense deltas) lie in LDS for the chains, which read the transposed weights
+//      coalesced along i.  Four barriers a tick, one more with two dense layers.
+//   W  rg_bptt_weight_kernel: grid (row tiles of kRows input rows over all blocks, G groups of chunks); thread j owns column j
+//      of the block, holds the chunk's kChunk deltas of its column in registers and kRows float64 sums; the chunk's kChunk x
+//      kRows inputs are staged in LDS (the row past a block's inputs is the constant 1: the bias).  rg_bptt_grad_finish_kernel
+//      adds the G float64 partials per element in index order.
+// LDS (static), floats of the header limits W = RG_RNN_MAX_WIDTH, H = RG_RNN_MAX_UNITS, A = RG_RNN_MAX_ACT, tile RG_RNN_TILE:
+//   F  (2 W + 3 H) * tile * 4 = 28672 bytes;  B  (2 W + 3 H + A) * tile * 4 = 28800 bytes; each with its copy of the descriptor
+//      (at most 768 bytes);  W  RG_BPTT_CHUNK * RG_BPTT_ROWS * 4 = 1024 bytes;  the sums 32 bytes.
+// The descriptor (layouts, the call's pointers, the workspace's regions) is written into the head of the workspace by a
+// one-thread kernel first in every entry that launches; F and B copy it to LDS (as scalar registers its fields, live through
+// the loop over t, do not fit beside the pointers).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include "../../include/rg_policy.h"
+#include "../../include/rg_ppo.h"
+#include "../../include/rg_rnn.h"
+#include "../../include/rg_bptt.h"
+#include "rg_host.h"
+
+#pragma clang fp contract(off)
+
+#include "rg_agent_dev.inc"
+
+namespace {
+
+constexpr int kTile = RG_RNN_TILE;
+constexpr int kMaxW = RG_RNN_MAX_WIDTH;
+constexpr int kMaxH = RG_RNN_MAX_UNITS;
+constexpr int kMaxAct = RG_RNN_MAX_ACT;
+constexpr int kThreads = kAgentThreads;
+constexpr int kCols = RG_POLICY_NORM_COLS;
+constexpr int kChunk = RG_BPTT_CHUNK;
+constexpr int kRows = RG_BPTT_ROWS;
+constexpr int kMaxGroups = RG_BPTT_MAX_GROUPS;
+constexpr int kMaxParts = 256;       // workgroups of the head kernel, at most
+constexpr int kPart = 1 + kMaxAct;   // per workgroup of the head kernel: the loss sum, then the logstd gradient
+constexpr int kBlocks = RG_RNN_MAX_DENSE + 3;
+
+static_assert(kTile == 8, "a neuron reads the activations of an input as two float4");
+static_assert(2 * kMaxH <= kThreads && kMaxW <= kThreads, "one output neuron, one column of a block per thread");
+static_assert(kTile * kMaxAct <= kThreads && kMaxAct <= kMaxW, "the mean's thread map; the head's output fits an x buffer");
+static_assert(kChunk * kRows == kThreads && kRows % 4 == 0, "a thread stages one input of a chunk; rows are read as float4");
+static_assert(kMaxParts <= kThreads && kMaxAct == RG_POLICY_MAX_ACT, "strided sums; the head's arrays");
+static_assert(RG_RNN_MAX_DENSE == 2, "the delta pass has two dense delta buffers and the transpose four blocks");
+
+struct WBlock {                // one block of policy_params for the W phase
+  const float *in0, *in1, *delta;   // the inputs [N][n0] and then [N][n1] (in1 may be null with n1 = 0), the deltas [N][out]
+  int n0, n1, out, w_off, b_off, tile0;   // tile0: the first row tile of this block in the grid
+};
+
+struct BpttDev {               // in the workspace: what the kernels read of a call
+  int T, B, N, obs_dim, act_dim, H, n_dense, n_x;
+  int dense_in[2], dense_out[2], dense_w[2], dense_b[2];
+  int w_ru, b_ru, w_c, b_c, head_w, head_b, logstd_off, count;
+  int G, per, nchunks, P, nblk, pad0;
+  double obs_clip, c, thr, coef;
+  const float *obs, *action, *mean0, *logstd0, *adv, *h0;
+  const int *mask, *reset;
+  const double *norm, *scal, *penalty;
+  float *a[3], *hin, *r, *u, *cc, *rh, *hn, *mean, *dmean, *dru, *dcs, *dd[2], *wt;
+  double *kls, *klr, *part, *gpart;
+  WBlock blk[kBlocks];
+};
+static_assert(sizeof(BpttDev) % sizeof(int) == 0 && sizeof(BpttDev) <= 768, "copied to LDS word by word");
+
+__global__ void rg_bptt_describe_kernel(const BpttDev src, BpttDev *__restrict__ dst) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *dst = src;
+}
+
+__device__ __forceinline__ const BpttDev *descriptor_to_lds(const BpttDev *__restrict__ dg, BpttDev *dsh) {
+  for (int idx = threadIdx.x; idx < (int)(sizeof(BpttDev) / sizeof(int)); idx += kThreads)
+    reinterpret_cast<int *>(dsh)[idx] = reinterpret_cast<const int *>(dg)[idx];
+  __syncthreads();
+  return dsh;
+}
+
+// acc[r] = fma(W[i * stride], x[i][r], acc[r]) for i = 0 .. nin-1 in order
+__device__ __forceinline__ void chain8(const float *__restrict__ W, const int stride, const float *x, const int nin, float (&acc)[kTile]) {
+#pragma unroll 8
+  for (int i = 0; i < nin; i++) {
+    const float w = W[(size_t)i * stride];
+    const float4 xa = *reinterpret_cast<const float4 *>(x + i * kTile);
+    const float4 xb = *reinterpret_cast<const float4 *>(x + i * kTile + 4);
+    acc[0] = __builtin_fmaf(w, xa.x, acc[0]); acc[1] = __builtin_fmaf(w, xa.y, acc[1]);
+    acc[2] = __builtin_fmaf(w, xa.z, acc[2]); acc[3] = __builtin_fmaf(w, xa.w, acc[3]);
+    acc[4] = __builtin_fmaf(w, xb.x, acc[4]); acc[5] = __builtin_fmaf(w, xb.y, acc[5]);
+    acc[6] = __builtin_fmaf(w, xb.z, acc[6]); acc[7] = __builtin_fmaf(w, xb.w, acc[7]);
+  }
+}
+
+__device__ __forceinline__ float sigmoidf(const float a) { return 1.0f / (1.0f + expf(-a)); }
+
+// ---- F: the forward pass, every intermediate kept --------------------------------------------------------------------------
+
+// stage s of the tick for output neuron j (rg_rnn.hip, policy_stage), t0 = t * B: what it forms also goes to the workspace
+__device__ __forceinline__ void forward_stage(const BpttDev *d, const float *__restrict__ pp, const int s, const int j, const int b0, const size_t t0,
+                                              float (*xs)[kMaxW * kTile], float *hs, float *rh, float *us) {
+  const int n_dense = d->n_dense, H = d->H, n_x = d->n_x, B = d->B;
+  float acc[kTile];
+#pragma unroll
+  for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
+  if (s < n_dense) {
+    const int nin = d->dense_in[s], nout = d->dense_out[s];
+    if (j < nout) {
+      chain8(pp + d->dense_w[s] + j, nout, xs[s & 1], nin, acc);
+      const float bias = pp[d->dense_b[s] + j];
+      float *y = xs[(s & 1) ^ 1] + j * kTile;
+      float *out = d->a[s + 1];
+#pragma unroll
+      for (int r = 0; r < kTile; r++) {
+        const float v = acc[r] + bias;
+        const float a = v > 0.0f ? v : 0.0f;
+        y[r] = a;
+        if (b0 + r < B) out[(t0 + b0 + r) * nout + j] = a;
+      }
+    }
+  } else if (s == n_dense) {
+    if (j < 2 * H) {
+      const float *__restrict__ W = pp + d->w_ru + j;
+      chain8(W, 2 * H, xs[n_dense & 1], n_x, acc);
+      chain8(W + (size_t)n_x * 2 * H, 2 * H, hs, H, acc);
+      const float bias = pp[d->b_ru + j];
+      if (j < H) {
+#pragma unroll
+        for (int r = 0; r < kTile; r++) {
+          const float g = sigmoidf(acc[r] + bias);
+          const float p = g * hs[j * kTile + r];
+          rh[j * kTile + r] = p;
+          if (b0 + r < B) { d->r[(t0 + b0 + r) * H + j] = g; d->rh[(t0 + b0 + r) * H + j] = p; }
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < kTile; r++) {
+          const float g = sigmoidf(acc[r] + bias);
+          us[(j - H) * kTile + r] = g;
+          if (b0 + r < B) d->u[(t0 + b0 + r) * H + (j - H)] = g;
+        }
+      }
+    }
+  } else if (s == n_dense + 1) {
+    if (j < H) {
+      const float *__restrict__ W = pp + d->w_c + j;
+      chain8(W, H, xs[n_dense & 1], n_x, acc);
+      chain8(W + (size_t)n_x * H, H, rh, H, acc);
+      const float bias = pp[d->b_c + j];
+#pragma unroll
+      for (int r = 0; r < kTile; r++) {
+        const float c = tanhf(acc[r] + bias);
+        const float u = us[j * kTile + r], h = hs[j * kTile + r];
+        const float hn = __builtin_fmaf(u, h, __builtin_fmaf(-u, c, c));
+        hs[j * kTile + r] = hn;   // only this thread reads or writes h[j] in this stage
+        if (b0 + r < B) { d->cc[(t0 + b0 + r) * H + j] = c; d->hn[(t0 + b0 + r) * H + j] = hn; }
+      }
+    }
+  } else if (s == n_dense + 2) {
+    const int act_dim = d->act_dim;
+    if (j < act_dim) {
+      chain8(pp + d->head_w + j, act_dim, hs, H, acc);
+      const float bias = pp[d->head_b + j];
+      float *y = xs[(n_dense & 1) ^ 1] + j * kTile;
+#pragma unroll
+      for (int r = 0; r < kTile; r++) y[r] = tanhf(acc[r] + bias);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) rg_bptt_forward_kernel(const BpttDev *__restrict__ dg, const float *__restrict__ pp) {
+  __shared__ BpttDev dsh;
+  __shared__ __attribute__((aligned(16))) float xs[2][kMaxW * kTile];
+  __shared__ __attribute__((aligned(16))) float hs[kMaxH * kTile];
+  __shared__ __attribute__((aligned(16))) float rh[kMaxH * kTile];
+  __shared__ __attribute__((aligned(16))) float us[kMaxH * kTile];
+  const BpttDev *d = descriptor_to_lds(dg, &dsh);
+  const int tid = threadIdx.x;
+  const int B = d->B, T = d->T, obs_dim = d->obs_dim, act_dim = d->act_dim, H = d->H;
+  const int b0 = blockIdx.x * kTile;
+  const int n_pol = d->n_dense + 3;
+  const float *mean_s = xs[(d->n_dense & 1) ^ 1];
+  const double *__restrict__ norm = d->norm;
+  for (int idx = tid; idx < H * kTile; idx += kThreads) {
+    const int r = idx / H, k = idx - r * H, b = b0 + r;
+    hs[k * kTile + r] = b < B ? d->h0[(size_t)b * H + k] : 0.0f;
+  }
+  for (int t = 0; t < T; t++) {
+    const size_t t0 = (size_t)t * B;
+    const float *__restrict__ obs_t = d->obs + t0 * obs_dim;
+    const int *__restrict__ reset_t = d->reset + t0;
+    // the observation through the normaliser: float64, rounded to float32 once (rg_policy.h, transform)
+    for (int idx = tid; idx < obs_dim * kTile; idx += kThreads) {
+      const int r = idx / obs_dim, i = idx - r * obs_dim, b = b0 + r;
+      float xn = 0.0f;
+      if (b < B) {
+        double v = (double)obs_t[(size_t)i * B + b] - norm[kCols + i];
+        v = v / norm_scale(norm[i], norm[2 * kCols + i]);
+        xn = (float)clip_sym(v, d->obs_clip);
+        d->a[0][(t0 + b) * obs_dim + i] = xn;
+      }
+      xs[0][i * kTile + r] = xn;
+    }
+    for (int idx = tid; idx < H * kTile; idx += kThreads) {   // the state this tick reads
+      const int r = idx / H, k = idx - r * H, b = b0 + r;
+      if (b < B) {
+        if (reset_t[b] != 0) hs[k * kTile + r] = 0.0f;
+        d->hin[(t0 + b) * H + k] = hs[k * kTile + r];
+      }
+    }
+    for (int s = 0; s < n_pol; s++) {
+      __syncthreads();
+      forward_stage(d, pp, s, tid, b0, t0, xs, hs, rh, us);
+    }
+    __syncthreads();
+    if (tid < kTile * act_dim) {
+      const int r = tid / act_dim, a = tid % act_dim, b = b0 + r;
+      if (b < B) d->mean[(t0 + b) * act_dim + a] = mean_s[a * kTile + r];
+    }
+    __syncthreads();   // the next tick's observation may land in the buffer the mean was read from
+  }
+}
+
+// ---- H: the head, float64 --------------------------------------------------------------------------------------------------
+
+// sample n of rg_ppo.h's policy loss.  kBackward false: kls[n]; true: delta_mean[n], and the sample's terms of the loss and of
+// the logstd gradient are added to loss and gls.
+template <bool kBackward>
+__device__ __forceinline__ void head_sample(const BpttDev *__restrict__ d, const float *__restrict__ P, const int n, double &loss, double (&gls)[kMaxAct]) {
+  const int act_dim = d->act_dim;
+  const bool valid = d->mask[n] != 0;
+  const double inv = 1.0 / ((double)d->T * (double)d->B);
+  double kl = 0.0, lp = 0.0, lp0 = 0.0;
+  double z[kMaxAct], D[kMaxAct], q[kMaxAct], sg[kMaxAct], mu[kMaxAct];
+#pragma unroll
+  for (int k = 0; k < kMaxAct; k++) {
+    z[k] = D[k] = q[k] = mu[k] = 0.0;
+    sg[k] = 1.0;
+    if (k < act_dim) {
+      const double ls = (double)P[d->logstd_off + k], ls0 = (double)d->logstd0[k];
+      const double s1 = exp(ls), s0 = exp(ls0);
+      const double m1 = (double)d->mean[(size_t)n * act_dim + k], m0 = (double)d->mean0[(size_t)n * act_dim + k];
+      const double dk = m1 - m0;
+      const double qk = (s0 * s0 + dk * dk) / (s1 * s1);
+      kl = kl + ((qk - 1.0) + 2.0 * (ls - ls0));
+      if (kBackward) {
+        const double a = (double)d->action[(size_t)n * act_dim + k];
+        const double zk = (a - m1) / s1, z0 = (a - m0) / s0;
+        lp = lp + (-d->c * ls - 0.5 * (zk * zk));
+        lp0 = lp0 + (-d->c * ls0 - 0.5 * (z0 * z0));
+        z[k] = zk;
+      }
+      D[k] = dk; q[k] = qk; sg[k] = s1; mu[k] = m1;
+    }
+  }
+  kl = 0.5 * kl;
+  if (!kBackward) {
+    d->kls[n] = valid ? kl : 0.0;
+  } else {
+    double ratio = 0.0, advn = 0.0, gb = 0.0;
+    if (valid) {
+      ratio = exp(lp - lp0);
+      advn = ((double)d->adv[n] - d->scal[1]) / d->scal[2];
+      const double klb = d->klr[n % d->B];
+      gb = *d->penalty + (klb > d->thr ? 2.0 * d->coef * (klb - d->thr) : 0.0);
+      loss = loss + ratio * advn;
+    }
+#pragma unroll
+    for (int k = 0; k < kMaxAct; k++) {
+      if (k < act_dim) {
+        float dlt = 0.0f;
+        if (valid) {
+          const double dmu = (-advn * ratio * z[k] / sg[k] + gb * D[k] / (sg[k] * sg[k])) * inv;
+          dlt = (float)(dmu * (1.0 - mu[k] * mu[k]));
+          gls[k] = gls[k] + (-advn * ratio * (z[k] * z[k] - d->c) + gb * (1.0 - q[k])) * inv;
+        }
+        d->dmean[(size_t)n * act_dim + k] = dlt;
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) rg_bptt_sample_kl_kernel(const BpttDev *__restrict__ d, const float *__restrict__ P) {
+  const long long n = (long long)blockIdx.x * kThreads + (int)threadIdx.x;
+  if (n >= d->N) return;
+  double loss = 0.0, gls[kMaxAct] = {0.0, 0.0, 0.0, 0.0};
+  head_sample<false>(d, P, (int)n, loss, gls);
+}
+
+// KL_b = (sum_t kls[t][b]) / T, t in order
+__global__ void __launch_bounds__(kThreads) rg_bptt_robot_kl_kernel(const int T, const int B, const double *__restrict__ kls, double *__restrict__ out) {
+  const int b = blockIdx.x * kThreads + (int)threadIdx.x;
+  if (b >= B) return;
+  double s = 0.0;
+  for (int t = 0; t < T; t++) s = s + kls[(size_t)t * B + b];
+  out[b] = s / (double)T;
+}
+
+__global__ void __launch_bounds__(kThreads) rg_bptt_head_kernel(const BpttDev *__restrict__ d, const float *__restrict__ P) {
+  __shared__ double sh[4];
+  double loss = 0.0, gls[kMaxAct] = {0.0, 0.0, 0.0, 0.0};
+  const long long step = (long long)d->P * kThreads;
+  for (long long n = (long long)blockIdx.x * kThreads + (int)threadIdx.x; n < d->N; n += step) head_sample<true>(d, P, (int)n, loss, gls);
+  double *p = d->part + (size_t)blockIdx.x * kPart;
+  loss = block_sum(loss, sh);
+  if (threadIdx.x == 0) p[0] = loss;
+#pragma unroll
+  for (int k = 0; k < kMaxAct; k++) {
+    const double g = block_sum(gls[k], sh);
+    if (threadIdx.x == 0) p[1 + k] = g;
+  }
+}
+
+struct LossCfg {
+  int T, B, P, act_dim, logstd_off, pad0;
+  double thr, coef;
+};
+
+__global__ void __launch_bounds__(kThreads) rg_bptt_loss_finish_kernel(const LossCfg c, const double *__restrict__ part, const double *__restrict__ klr,
+                                                                       const double *__restrict__ penalty, float *__restrict__ grad,
+                                                                       double *__restrict__ loss_out, double *__restrict__ loss_out2) {
+  __shared__ double sh[4];
+  const double s1 = strided_sum(part, c.P, kPart, sh);
+  const double inv = 1.0 / ((double)c.T * (double)c.B);
+  const double pen = *penalty;
+  double s2 = 0.0;
+  for (int b = threadIdx.x; b < c.B; b += kThreads) {
+    const double k = klr[b], over = k - c.thr;
+    s2 = s2 + (pen * k + (k > c.thr ? c.coef * (over * over) : 0.0));
+  }
+  s2 = block_sum(s2, sh);
+  const double loss = -(s1 * inv) + s2 / (double)c.B;
+#pragma unroll
+  for (int k = 0; k < kMaxAct; k++) {
+    if (k < c.act_dim) {   // uniform
+      const double gk = strided_sum(part + 1 + k, c.P, kPart, sh);
+      if (threadIdx.x == 0) grad[c.logstd_off + k] = (float)gk;
+    }
+  }
+  if (threadIdx.x == 0) {
+    *loss_out = loss;
+    if (loss_out2) *loss_out2 = loss;
+  }
+}
+
+// ---- B: the delta pass -----------------------------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(kThreads) rg_bptt_transpose_kernel(const NetDesc nd, const int count, const float *__restrict__ P, float *__restrict__ Wt) {
+  const int e = blockIdx.x * kThreads + (int)threadIdx.x;
+  if (e < count) transpose_element(nd, P, Wt, e);
+}
+
+__global__ void __launch_bounds__(kThreads) rg_bptt_delta_kernel(const BpttDev *__restrict__ dg) {
+  __shared__ BpttDev dsh;
+  __shared__ __attribute__((aligned(16))) float dm[kMaxAct * kTile];        // delta_mean of the tick, [component * kTile + robot]
+  __shared__ __attribute__((aligned(16))) float dcs[kMaxH * kTile];         // delta_c
+  __shared__ __attribute__((aligned(16))) float dru[2 * kMaxH * kTile];     // delta_r, then delta_u
+  __shared__ __attribute__((aligned(16))) float dbuf[2][kMaxW * kTile];     // the dense deltas, ping-pong
+  const BpttDev *d = descriptor_to_lds(dg, &dsh);
+  const int tid = threadIdx.x;
+  const int B = d->B, act_dim = d->act_dim, H = d->H, n_dense = d->n_dense, n_x = d->n_x;
+  const int b0 = blockIdx.x * kTile;
+  const int bl = B - 1;                // a slot past the batch mirrors the last robot: the same loads, the same values, the same stores
+  const int rows = n_x + H;            // rows of W_ru and of W_c: the stride of their transposed copies
+  const float *__restrict__ Wt = d->wt;
+  float dh[kTile], dhp[kTile], hin[kTile], rr[kTile], acc[kTile];
+#pragma unroll
+  for (int r = 0; r < kTile; r++) dh[r] = dhp[r] = hin[r] = rr[r] = 0.0f;
+  for (int t = d->T - 1; t >= 0; t--) {
+    const size_t t0 = (size_t)t * B;
+    if (tid < act_dim * kTile) {
+      const int a = tid / kTile, r = tid % kTile, b = b0 + r < bl ? b0 + r : bl;
+      dm[tid] = d->dmean[(t0 + b) * act_dim + a];
+    }
+    __syncthreads();   // and every chain of the tick before has read dcs, dru and dbuf
+    if (tid < H) {
+#pragma unroll
+      for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
+      chain8(Wt + d->head_w + tid, H, dm, act_dim, acc);
+#pragma unroll
+      for (int r = 0; r < kTile; r++) {
+        const int b = b0 + r < bl ? b0 + r : bl;
+        const size_t o = (t0 + b) * H + tid;
+        const float u = d->u[o], c = d->cc[o];
+        hin[r] = d->hin[o];
+        rr[r] = d->r[o];
+        const float g = dh[r] + acc[r];
+        const float dc = g * (1.0f - u), du = g * (hin[r] - c);
+        dhp[r] = g * u;
+        const float dcv = dc * (1.0f - c * c), duv = du * (u * (1.0f - u));
+        dcs[tid * kTile + r] = dcv;
+        dru[(H + tid) * kTile + r] = duv;
+        d->dcs[o] = dcv;
+        d->dru[(t0 + b) * 2 * H + H + tid] = duv;
+      }
+    }
+    __syncthreads();
+    if (tid < H) {
+#pragma unroll
+      for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
+      chain8(Wt + d->w_c + n_x + tid, rows, dcs, H, acc);   // Wt_c[j][n_x + i]
+#pragma unroll
+      for (int r = 0; r < kTile; r++) {
+        const int b = b0 + r < bl ? b0 + r : bl;
+        const float drh = acc[r];
+        const float dr = drh * hin[r];
+        dhp[r] = dhp[r] + drh * rr[r];
+        const float drv = dr * (rr[r] * (1.0f - rr[r]));
+        dru[tid * kTile + r] = drv;
+        d->dru[(t0 + b) * 2 * H + tid] = drv;
+      }
+    }
+    __syncthreads();
+    if (tid < H) {
+#pragma unroll
+      for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
+      chain8(Wt + d->w_ru + n_x + tid, rows, dru, 2 * H, acc);   // Wt_ru[j][n_x + i]
+#pragma unroll
+      for (int r = 0; r < kTile; r++) {
+        const int b = b0 + r < bl ? b0 + r : bl;
+        const float v = dhp[r] + acc[r];
+        dh[r] = d->reset[t0 + b] == 0 ? v : 0.0f;   // nothing crosses a reset
+      }
+    }
+    if (n_dense > 0 && tid < n_x) {
+#pragma unroll
+      for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
+      chain8(Wt + d->w_ru + tid, rows, dru, 2 * H, acc);
+      chain8(Wt + d->w_c + tid, rows, dcs, H, acc);
+      const float *act = d->a[n_dense];
+      float *out = d->dd[n_dense - 1];
+#pragma unroll
+      for (int r = 0; r < kTile; r++) {
+        const int b = b0 + r < bl ? b0 + r : bl;
+        const float v = act[(t0 + b) * n_x + tid] > 0.0f ? acc[r] : 0.0f;
+        out[(t0 + b) * n_x + tid] = v;
+        dbuf[0][tid * kTile + r] = v;
+      }
+    }
+    int cur = 0;
+    for (int l = n_dense - 1; l >= 1; l--) {
+      __syncthreads();
+      const int nin = d->dense_in[l], nout = d->dense_out[l];
+      if (tid < nin) {
+#pragma unroll
+        for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
+        chain8(Wt + d->dense_w[l] + tid, nin, dbuf[cur], nout, acc);   // Wt_l[j][k]
+        const float *act = d->a[l];
+        float *out = d->dd[l - 1];
+#pragma unroll
+        for (int r = 0; r < kTile; r++) {
+          const int b = b0 + r < bl ? b0 + r : bl;
+          const float v = act[(t0 + b) * nin + tid] > 0.0f ? acc[r] : 0.0f;
+          out[(t0 + b) * nin + tid] = v;
+          dbuf[cur ^ 1][tid * kTile + r] = v;
+        }
+      }
+      cur ^= 1;
+    }
+  }
+}
+
+// ---- W: the weight gradients -------------------------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(kThreads) rg_bptt_weight_kernel(const BpttDev *__restrict__ d) {
+  __shared__ __attribute__((aligned(16))) float xin[kChunk * kRows];   // [sample of the chunk][row of the tile]
+  const int tid = threadIdx.x, g = blockIdx.y;
+  int k = 0;
+  for (int q = 1; q < kBlocks; q++)
+    if (q < d->nblk && (int)blockIdx.x >= d->blk[q].tile0) k = q;
+  const WBlock &blk = d->blk[k];
+  const int n0 = blk.n0, nin = blk.n0 + blk.n1, out = blk.out, N = d->N;
+  const int row0 = ((int)blockIdx.x - blk.tile0) * kRows;
+  const int ss = tid / kRows, si = tid % kRows, srow = row0 + si;   // what this thread stages of a chunk
+  const float *__restrict__ delta = blk.delta;
+  double sum[kRows];
+#pragma unroll
+  for (int i = 0; i < kRows; i++) sum[i] = 0.0;
+  const int first = g * d->per;
+  const int last = first + d->per < d->nchunks ? first + d->per : d->nchunks;
+  for (int ch = first; ch < last; ch++) {
+    const long long nb = (long long)ch * kChunk;
+    __syncthreads();   // the chunk before has been read
+    {
+      const long long n = nb + ss;
+      float v = 0.0f;
+      if (n < N) {
+        if (srow < n0) v = blk.in0[(size_t)n * n0 + srow];
+        else if (srow < nin) v = blk.in1[(size_t)n * blk.n1 + (srow - n0)];
+        else if (srow == nin) v = 1.0f;
+      }
+      xin[ss * kRows + si] = v;
+    }
+    float dl[kChunk];
+#pragma unroll
+    for (int s = 0; s < kChunk; s++) {
+      const long long n = nb + s;
+      dl[s] = (tid < out && n < N) ? delta[(size_t)n * out + tid] : 0.0f;
+    }
+    __syncthreads();
+    float v[kRows];
+#pragma unroll
+    for (int i = 0; i < kRows; i++) v[i] = 0.0f;
+#pragma unroll
+    for (int s = 0; s < kChunk; s++) {
+#pragma unroll
+      for (int q = 0; q < kRows / 4; q++) {
+        const float4 x = *reinterpret_cast<const float4 *>(xin + s * kRows + 4 * q);
+        v[4 * q] = __builtin_fmaf(x.x, dl[s], v[4 * q]);
+        v[4 * q + 1] = __builtin_fmaf(x.y, dl[s], v[4 * q + 1]);
+        v[4 * q + 2] = __builtin_fmaf(x.z, dl[s], v[4 * q + 2]);
+        v[4 * q + 3] = __builtin_fmaf(x.w, dl[s], v[4 * q + 3]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < kRows; i++) sum[i] = sum[i] + (double)v[i];
+  }
+  if (tid < out) {
+    double *__restrict__ part = d->gpart + (size_t)g * d->count;
+#pragma unroll
+    for (int i = 0; i < kRows; i++) {
+      const int row = row0 + i;
+      if (row < nin) part[blk.w_off + (size_t)row * out + tid] = sum[i];
+      else if (row == nin) part[blk.b_off + tid] = sum[i];
+    }
+  }
+}
+
+// grad[e] = (float) sum_g gpart[g][e], g in order, for the first n elements (the networks; logstd is the loss kernel's)
+__global__ void __launch_bounds__(kThreads) rg_bptt_grad_finish_kernel(const int n, const int count, const int G, const double *__restrict__ gpart,
+                                                                       float *__restrict__ grad) {
+  const int e = blockIdx.x * kThreads + (int)threadIdx.x;
+  if (e >= n) return;
+  double s = 0.0;
+  for (int g = 0; g < G; g++) s = s + gpart[(size_t)g * count + e];
+  grad[e] = (float)s;
+}
+
+// ---- Adam and the penalty (rg_ppo.hip's arithmetic) --------------------------------------------------------------------------
+
+struct AdamCfg {
+  int count, pad0;
+  double lr, b1, b2, eps;
+};
+
+__global__ void __launch_bounds__(kThreads) rg_bptt_adam_kernel(const AdamCfg c, float *__restrict__ p, const float *__restrict__ grad,
+                                                                float *__restrict__ m, float *__restrict__ v, const long long *__restrict__ step) {
+  const int e = blockIdx.x * kThreads + (int)threadIdx.x;
+  if (e >= c.count) return;
+  const double t = (double)(*step + 1);
+  const double bc1 = 1.0 - pow(c.b1, t), bc2s = sqrt(1.0 - pow(c.b2, t));
+  const float b1 = (float)c.b1, b2 = (float)c.b2, o1 = (float)(1.0 - c.b1), o2 = (float)(1.0 - c.b2);
+  const float gg = grad[e];
+  const float t1 = b1 * m[e], t2 = o1 * gg;
+  const float mn = t1 + t2;
+  const float t3 = b2 * v[e], t4 = gg * gg;
+  const float t5 = o2 * t4;
+  const float vn = t3 + t5;
+  m[e] = mn;
+  v[e] = vn;
+  const double denom = sqrt((double)vn) / bc2s + c.eps;
+  p[e] = (float)((double)p[e] - (c.lr / bc1) * (double)mn / denom);
+}
+
+__global__ void rg_bptt_adam_count_kernel(long long *__restrict__ step) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *step = *step + 1;
+}
+
+// stats: kl_change, penalty; nan_out (or null): two losses that no epoch wrote
+__global__ void __launch_bounds__(kThreads) rg_bptt_penalty_kernel(const int B, const double target, const double *__restrict__ klr,
+                                                                   double *__restrict__ penalty, double *__restrict__ stats, double *__restrict__ nan_out) {
+  __shared__ double sh[4];
+  const double s = strided_sum(klr, B, 1, sh);
+  if (threadIdx.x == 0) {
+    const double change = s / (double)B;
+    double pen = *penalty;
+    if (change > 1.3 * target) pen = pen * 1.5;
+    else if (change < 0.7 * target) pen = pen / 1.5;
+    *penalty = pen;
+    stats[0] = change;
+    stats[1] = pen;
+    if (nan_out) nan_out[0] = nan_out[1] = nan("");
+  }
+}
+
+thread_local std::string g_create_err;
+
+}  // namespace
+
+struct rg_bptt_handle {
+  rg_rnn_config rcfg{};
+  rg_ppo_config cfg{};
+  BpttDev dv{};                // everything but the call's pointers and the workspace's regions
+  NetDesc tr{};                // the blocks whose transposed copy the delta pass reads
+  int T = 0, B = 0, N = 0, device = 0, tiles = 0;
+  // byte offsets into the workspace
+  size_t o_desc = 0, o_part = 0, o_klr = 0, o_kls = 0, o_grad = 0, o_wt = 0, o_gpart = 0, o_a[3] = {0, 0, 0}, o_hin = 0, o_r = 0, o_u = 0, o_c = 0, o_rh = 0,
+         o_hn = 0, o_mean = 0, o_dmean = 0, o_dru = 0, o_dcs = 0, o_dd[2] = {0, 0}, ws_bytes = 0, opt_bytes = 0;
+  std::string err;
+};
+
+namespace {
+
+bool validate_rnn(const rg_rnn_config *cfg, std::string &err) {
+  const char *prefix = "rnn_cfg.";
+  if (!check_abi(prefix, cfg->abi_version, RG_RNN_ABI_VERSION, err)) return false;
+  if (!check_reserved(prefix, "reserved0", cfg->reserved0, err)) return false;
+  const IntField ints[] = {{"obs_dim", cfg->obs_dim, 1, RG_RNN_MAX_OBS}, {"act_dim", cfg->act_dim, 1, RG_RNN_MAX_ACT},
+                           {"n_policy_layers", cfg->n_policy_layers, 0, RG_RNN_MAX_DENSE}, {"gru_units", cfg->gru_units, 1, RG_RNN_MAX_UNITS},
+                           {"n_value_layers", cfg->n_value_layers, 0, RG_RNN_MAX_VALUE_LAYERS}};
+  const RealField reals[] = {{"obs_clip", &cfg->obs_clip, 1, kNonNegative}};
+  return check_ints(prefix, ints, err) &&
+         check_widths(prefix, "policy_layers", cfg->policy_layers, cfg->n_policy_layers, RG_RNN_MAX_DENSE, RG_RNN_MAX_WIDTH, err) &&
+         check_widths(prefix, "value_layers", cfg->value_layers, cfg->n_value_layers, RG_RNN_MAX_VALUE_LAYERS, RG_RNN_MAX_WIDTH, err) &&
+         check_reals(prefix, reals, err);
+}
+
+bool validate_ppo(const rg_ppo_config *cfg, std::string &err) {
+  const IntField ints[] = {{"epochs_policy", cfg->epochs_policy, 0, RG_PPO_MAX_EPOCHS}, {"epochs_value", cfg->epochs_value, 0, RG_PPO_MAX_EPOCHS},
+                           {"conv_logpdf", cfg->conv_logpdf, RG_PPO_LOGPDF_EXACT, RG_PPO_LOGPDF_REFERENCE}};
+  const RealField reals[] = {{"policy_lr", &cfg->policy_lr, 1, kNonNegative}, {"value_lr", &cfg->value_lr, 1, kNonNegative}, {"beta1", &cfg->beta1, 1, kBelowOne},
+                             {"beta2", &cfg->beta2, 1, kBelowOne}, {"adam_eps", &cfg->adam_eps, 1, kPositive}, {"kl_target", &cfg->kl_target, 1, kPositive},
+                             {"kl_cutoff_factor", &cfg->kl_cutoff_factor, 1, kNonNegative}, {"kl_cutoff_coef", &cfg->kl_cutoff_coef, 1, kNonNegative}};
+  return check_abi("ppo_cfg.", cfg->abi_version, RG_PPO_ABI_VERSION, err) && check_ints("ppo_cfg.", ints, err) && check_reals("ppo_cfg.", reals, err);
+}
+
+int hip_fail(rg_bptt_handle *h, const char *what, hipError_t e) { return hip_fail(h, RG_BPTT_ERR_HIP, what, e); }
+int no_device(rg_bptt_handle *h) { return no_device(h, RG_BPTT_ERR_NO_DEVICE, "RG_BPTT"); }
+int launch_status(rg_bptt_handle *h, const char *what) { return launch_status(h, RG_BPTT_ERR_HIP, what); }
+int null_arg(rg_bptt_handle *h, const char *call, const char *name) { return null_arg(h, RG_BPTT_ERR_INVALID, call, name); }
+
+unsigned blocks_of(long long n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+
+long long *step_of(void *opt) { return reinterpret_cast<long long *>(opt); }
+double *penalty_of(void *opt) { return reinterpret_cast<double *>(static_cast<char *>(opt) + 8); }
+const double *penalty_of(const void *opt) { return reinterpret_cast<const double *>(static_cast<const char *>(opt) + 8); }
+
+// what the kernels of a call read: the handle's part, the call's pointers, the workspace's regions
+struct Call {
+  const rg_ppo_rollout *ro;
+  const int32_t *reset;
+  const float *h0;
+  const double *adv_stats, *norm, *penalty;
+};
+
+int run_describe(rg_bptt_handle *h, const Call &c, void *ws, hipStream_t s) {
+  BpttDev d = h->dv;
+  d.obs = c.ro->obs; d.action = c.ro->action; d.mean0 = c.ro->mean; d.logstd0 = c.ro->logstd; d.adv = c.ro->adv; d.mask = (const int *)c.ro->mask;
+  d.reset = (const int *)c.reset; d.h0 = c.h0; d.norm = c.norm; d.scal = c.adv_stats; d.penalty = c.penalty;
+  for (int l = 0; l < 3; l++) d.a[l] = ws_at<float>(ws, h->o_a[l]);
+  d.hin = ws_at<float>(ws, h->o_hin); d.r = ws_at<float>(ws, h->o_r); d.u = ws_at<float>(ws, h->o_u); d.cc = ws_at<float>(ws, h->o_c);
+  d.rh = ws_at<float>(ws, h->o_rh); d.hn = ws_at<float>(ws, h->o_hn); d.mean = ws_at<float>(ws, h->o_mean); d.dmean = ws_at<float>(ws, h->o_dmean);
+  d.dru = ws_at<float>(ws, h->o_dru); d.dcs = ws_at<float>(ws, h->o_dcs);
+  for (int l = 0; l < 2; l++) d.dd[l] = ws_at<float>(ws, h->o_dd[l]);
+  d.wt = ws_at<float>(ws, h->o_wt);
+  d.kls = ws_at<double>(ws, h->o_kls); d.klr = ws_at<double>(ws, h->o_klr); d.part = ws_at<double>(ws, h->o_part); d.gpart = ws_at<double>(ws, h->o_gpart);
+  // the blocks of the W phase, in the buffer's order
+  const int nd = d.n_dense;
+  int k = 0, tile = 0;
+  auto add = [&](const float *in0, int n0, const float *in1, int n1, const float *delta, int out, int w_off, int b_off) {
+    d.blk[k] = WBlock{in0, in1, delta, n0, n1, out, w_off, b_off, tile};
+    tile += (n0 + n1 + 1 + kRows - 1) / kRows;
+    k++;
+  };
+  for (int l = 0; l < nd; l++) add(d.a[l], d.dense_in[l], nullptr, 0, d.dd[l], d.dense_out[l], d.dense_w[l], d.dense_b[l]);
+  add(d.a[nd], d.n_x, d.hin, d.H, d.dru, 2 * d.H, d.w_ru, d.b_ru);
+  add(d.a[nd], d.n_x, d.rh, d.H, d.dcs, d.H, d.w_c, d.b_c);
+  add(d.hn, d.H, nullptr, 0, d.dmean, d.act_dim, d.head_w, d.head_b);
+  d.nblk = k;
+  h->tiles = tile;
+  hipLaunchKernelGGL(rg_bptt_describe_kernel, dim3(1), dim3(64), 0, s, d, ws_at<BpttDev>(ws, h->o_desc));
+  return launch_status(h, "rg_bptt_describe_kernel launch");
+}
+
+int run_forward(rg_bptt_handle *h, const float *pp, void *ws, hipStream_t s) {
+  hipLaunchKernelGGL(rg_bptt_forward_kernel, dim3(((unsigned)h->B + kTile - 1) / kTile), dim3(kThreads), 0, s, ws_at<const BpttDev>(ws, h->o_desc), pp);
+  return launch_status(h, "rg_bptt_forward_kernel launch");
+}
+
+// F, then KL_b per robot into kl_out
+int run_robot_kl(rg_bptt_handle *h, const float *pp, void *ws, double *kl_out, hipStream_t s) {
+  int rc = run_forward(h, pp, ws, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_bptt_sample_kl_kernel, dim3(blocks_of(h->N)), dim3(kThreads), 0, s, ws_at<const BpttDev>(ws, h->o_desc), pp);
+  rc = launch_status(h, "rg_bptt_sample_kl_kernel launch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_bptt_robot_kl_kernel, dim3(blocks_of(h->B)), dim3(kThreads), 0, s, h->T, h->B, ws_at<const double>(ws, h->o_kls), kl_out);
+  return launch_status(h, "rg_bptt_robot_kl_kernel launch");
+}
+
+int run_policy_grad(rg_bptt_handle *h, const float *pp, const void *opt, void *ws, float *grad, double *loss_out, double *loss_out2, hipStream_t s) {
+  const BpttDev &d = h->dv;
+  const BpttDev *desc = ws_at<const BpttDev>(ws, h->o_desc);
+  hipLaunchKernelGGL(rg_bptt_transpose_kernel, dim3(blocks_of(d.count)), dim3(kThreads), 0, s, h->tr, d.count, pp, ws_at<float>(ws, h->o_wt));
+  int rc = launch_status(h, "rg_bptt_transpose_kernel launch");
+  if (rc) return rc;
+  rc = run_robot_kl(h, pp, ws, ws_at<double>(ws, h->o_klr), s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_bptt_head_kernel, dim3((unsigned)d.P), dim3(kThreads), 0, s, desc, pp);
+  rc = launch_status(h, "rg_bptt_head_kernel launch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_bptt_delta_kernel, dim3(((unsigned)h->B + kTile - 1) / kTile), dim3(kThreads), 0, s, desc);
+  rc = launch_status(h, "rg_bptt_delta_kernel launch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_bptt_weight_kernel, dim3((unsigned)h->tiles, (unsigned)d.G), dim3(kThreads), 0, s, desc);
+  rc = launch_status(h, "rg_bptt_weight_kernel launch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_bptt_grad_finish_kernel, dim3(blocks_of(d.logstd_off)), dim3(kThreads), 0, s, d.logstd_off, d.count, d.G,
+                     ws_at<const double>(ws, h->o_gpart), grad);
+  rc = launch_status(h, "rg_bptt_grad_finish_kernel launch");
+  if (rc) return rc;
+  const LossCfg lc{h->T, h->B, d.P, d.act_dim, d.logstd_off, 0, d.thr, d.coef};
+  hipLaunchKernelGGL(rg_bptt_loss_finish_kernel, dim3(1), dim3(kThreads), 0, s, lc, ws_at<const double>(ws, h->o_part), ws_at<const double>(ws, h->o_klr),
+                     penalty_of(opt), grad, loss_out, loss_out2);
+  return launch_status(h, "rg_bptt_loss_finish_kernel launch");
+}
+
+int run_adam(rg_bptt_handle *h, float *params, const float *grad, void *opt, hipStream_t s) {
+  const int count = h->dv.count;
+  float *m = reinterpret_cast<float *>(static_cast<char *>(opt) + RG_BPTT_OPT_HEADER_BYTES);
+  const AdamCfg c{count, 0, h->cfg.policy_lr, h->cfg.beta1, h->cfg.beta2, h->cfg.adam_eps};
+  hipLaunchKernelGGL(rg_bptt_adam_kernel, dim3(blocks_of(count)), dim3(kThreads), 0, s, c, params, grad, m, m + count, (const long long *)step_of(opt));
+  int rc = launch_status(h, "rg_bptt_adam_kernel launch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(rg_bptt_adam_count_kernel, dim3(1), dim3(64), 0, s, step_of(opt));
+  return launch_status(h, "rg_bptt_adam_count_kernel launch");
+}
+
+int run_penalty(rg_bptt_handle *h, const double *kl, void *opt, double *stats, double *nan_out, hipStream_t s) {
+  hipLaunchKernelGGL(rg_bptt_penalty_kernel, dim3(1), dim3(kThreads), 0, s, h->B, h->cfg.kl_target, kl, penalty_of(opt), stats, nan_out);
+  return launch_status(h, "rg_bptt_penalty_kernel launch");
+}
+
+int check_rollout(rg_bptt_handle *h, const char *call, const rg_ppo_rollout *ro, bool grad) {
+  RG_NEED(call, ro, "rollout");
+  RG_NEED(call, ro->obs, "rollout.obs");
+  if (grad) RG_NEED(call, ro->action, "rollout.action");
+  RG_NEED(call, ro->mean, "rollout.mean");
+  RG_NEED(call, ro->logstd, "rollout.logstd");
+  if (grad) RG_NEED(call, ro->adv, "rollout.adv");
+  RG_NEED(call, ro->mask, "rollout.mask");
+  return RG_BPTT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t rg_bptt_abi_version(void) { return RG_BPTT_ABI_VERSION; }
+int32_t rg_bptt_tile(void) { return RG_RNN_TILE; }
+const char *rg_bptt_last_error(const rg_bptt_handle *h) { return h ? h->err.c_str() : g_create_err.c_str(); }
+int64_t rg_bptt_workspace_bytes(const rg_bptt_handle *h) { return h ? (int64_t)h->ws_bytes : -1; }
+int64_t rg_bptt_opt_state_bytes(const rg_bptt_handle *h) { return h ? (int64_t)h->opt_bytes : -1; }
+int32_t rg_bptt_groups(const rg_bptt_handle *h) { return h ? h->dv.G : -1; }
+
+int rg_bptt_create(const rg_rnn_config *rnn_cfg, const rg_ppo_config *ppo_cfg, int32_t T, int32_t B, int32_t device, rg_bptt_handle **out) {
+  if (!rnn_cfg || !ppo_cfg || !out) { g_create_err = "create: null rnn_cfg, ppo_cfg or out"; return RG_BPTT_ERR_INVALID; }
+  *out = nullptr;
+  char msg[128];
+  std::string err;
+  if (!validate_rnn(rnn_cfg, err) || !validate_ppo(ppo_cfg, err)) { g_create_err = err; return RG_BPTT_ERR_INVALID; }
+  if (T < 1 || T > RG_RNN_MAX_T) {
+    snprintf(msg, sizeof(msg), "T: %d outside [1, %d]", T, RG_RNN_MAX_T);
+    g_create_err = msg;
+    return RG_BPTT_ERR_INVALID;
+  }
+  if (B < 1 || B > RG_RNN_MAX_BATCH) {
+    snprintf(msg, sizeof(msg), "B: %d outside [1, %d]", B, RG_RNN_MAX_BATCH);
+    g_create_err = msg;
+    return RG_BPTT_ERR_INVALID;
+  }
+  if ((long long)T * B > RG_PPO_MAX_SAMPLES) {
+    snprintf(msg, sizeof(msg), "T * B: %lld above %d", (long long)T * B, RG_PPO_MAX_SAMPLES);
+    g_create_err = msg;
+    return RG_BPTT_ERR_INVALID;
+  }
+  rg_bptt_handle *h = new rg_bptt_handle();
+  h->rcfg = *rnn_cfg;
+  h->cfg = *ppo_cfg;
+  h->T = T; h->B = B; h->N = T * B; h->device = device;
+  BpttDev &d = h->dv;
+  const int H = rnn_cfg->gru_units, nd = rnn_cfg->n_policy_layers, A = rnn_cfg->act_dim;
+  d.T = T; d.B = B; d.N = h->N; d.obs_dim = rnn_cfg->obs_dim; d.act_dim = A; d.H = H; d.n_dense = nd;
+  int off = 0, prev = rnn_cfg->obs_dim;   // the layout rule of rg_rnn.h
+  for (int l = 0; l < nd; l++) {
+    const int width = rnn_cfg->policy_layers[l];
+    d.dense_in[l] = prev; d.dense_out[l] = width;
+    d.dense_w[l] = off; off += prev * width;
+    d.dense_b[l] = off; off += width;
+    prev = width;
+  }
+  d.n_x = prev;
+  d.w_ru = off; off += (prev + H) * 2 * H;
+  d.b_ru = off; off += 2 * H;
+  d.w_c = off; off += (prev + H) * H;
+  d.b_c = off; off += H;
+  d.head_w = off; off += H * A;
+  d.head_b = off; off += A;
+  d.logstd_off = off;
+  d.count = off + A;
+  d.nchunks = (h->N + kChunk - 1) / kChunk;
+  const int gmax = d.nchunks < kMaxGroups ? d.nchunks : kMaxGroups;
+  d.per = (d.nchunks + gmax - 1) / gmax;
+  d.G = (d.nchunks + d.per - 1) / d.per;
+  d.P = (int)((h->N + kThreads - 1) / kThreads);
+  if (d.P > kMaxParts) d.P = kMaxParts;
+  d.obs_clip = rnn_cfg->obs_clip;
+  d.c = ppo_cfg->conv_logpdf == RG_PPO_LOGPDF_EXACT ? 1.0 : 0.5;
+  d.thr = ppo_cfg->kl_target * ppo_cfg->kl_cutoff_factor;
+  d.coef = ppo_cfg->kl_cutoff_coef;
+  // the transposed copies: the second dense layer, W_ru, W_c, the head
+  NetDesc &tr = h->tr;
+  int k = 0;
+  auto add = [&](int in, int out_, int w) { tr.in[k] = in; tr.out[k] = out_; tr.w[k] = w; tr.b[k] = 0; k++; };
+  if (nd == 2) add(d.dense_in[1], d.dense_out[1], d.dense_w[1]);
+  add(prev + H, 2 * H, d.w_ru);
+  add(prev + H, H, d.w_c);
+  add(H, A, d.head_w);
+  tr.n = k;
+  const size_t N = (size_t)h->N, f = sizeof(float);
+  size_t o = 0;
+  h->o_desc = o; o += round8(sizeof(BpttDev));
+  h->o_part = o; o += sizeof(double) * (size_t)d.P * kPart;
+  h->o_klr = o; o += sizeof(double) * (size_t)B;
+  h->o_kls = o; o += sizeof(double) * N;
+  h->o_grad = o; o += round8(f * (size_t)d.count);
+  h->o_wt = o; o += round8(f * (size_t)d.count);
+  h->o_gpart = o; o += sizeof(double) * (size_t)d.G * (size_t)d.count;
+  h->o_a[0] = o; o += round8(f * N * (size_t)d.obs_dim);
+  for (int l = 0; l < 2; l++) { h->o_a[l + 1] = o; if (l < nd) o += round8(f * N * (size_t)d.dense_out[l]); }
+  size_t *cell[] = {&h->o_hin, &h->o_r, &h->o_u, &h->o_c, &h->o_rh, &h->o_hn, &h->o_dcs};
+  for (size_t *p : cell) { *p = o; o += round8(f * N * (size_t)H); }
+  h->o_dru = o; o += round8(f * N * 2 * (size_t)H);
+  h->o_mean = o; o += round8(f * N * (size_t)A);
+  h->o_dmean = o; o += round8(f * N * (size_t)A);
+  for (int l = 0; l < 2; l++) { h->o_dd[l] = o; if (l < nd) o += round8(f * N * (size_t)d.dense_out[l]); }
+  h->ws_bytes = o;
+  h->opt_bytes = RG_BPTT_OPT_HEADER_BYTES + f * 2 * (size_t)d.count;
+  if (device == RG_BPTT_DEVICE_NONE) {   // a host-only handle: the configuration, for argument checks on any machine
+    *out = h;
+    return RG_BPTT_OK;
+  }
+  if (const int rc = enter_device(device, nullptr, RG_BPTT_ERR_NO_DEVICE, RG_BPTT_ERR_INVALID, RG_BPTT_ERR_HIP, g_create_err)) { delete h; return rc; }
+  *out = h;
+  return RG_BPTT_OK;
+}
+
+void rg_bptt_destroy(rg_bptt_handle *h) { delete h; }
+
+int rg_bptt_policy_grad(rg_bptt_handle *h, const rg_ppo_rollout *ro, const int32_t *reset, const float *h0, const double *adv_stats,
+                        const double *norm_state, const float *policy_params, const void *opt_state, void *workspace, float *grad_out,
+                        double *loss_out, void *stream) {
+  if (!h) { g_create_err = "policy_grad: null handle"; return RG_BPTT_ERR_INVALID; }
+  int rc = check_rollout(h, "policy_grad", ro, true);
+  if (rc) return rc;
+  RG_NEED("policy_grad", reset, "reset");
+  RG_NEED("policy_grad", h0, "h0");
+  RG_NEED("policy_grad", adv_stats, "adv_stats");
+  RG_NEED("policy_grad", norm_state, "norm_state");
+  RG_NEED("policy_grad", policy_params, "policy_params");
+  RG_NEED("policy_grad", opt_state, "opt_state");
+  RG_NEED("policy_grad", workspace, "workspace");
+  RG_NEED("policy_grad", grad_out, "grad_out");
+  RG_NEED("policy_grad", loss_out, "loss_out");
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  hipStream_t s = (hipStream_t)stream;
+  rc = run_describe(h, Call{ro, reset, h0, adv_stats, norm_state, penalty_of(opt_state)}, workspace, s);
+  if (rc) return rc;
+  return run_policy_grad(h, policy_params, opt_state, workspace, grad_out, loss_out, nullptr, s);
+}
+
+int rg_bptt_kl(rg_bptt_handle *h, const rg_ppo_rollout *ro, const int32_t *reset, const float *h0, const double *norm_state,
+               const float *policy_params, void *workspace, double *kl_out, void *stream) {
+  if (!h) { g_create_err = "kl: null handle"; return RG_BPTT_ERR_INVALID; }
+  int rc = check_rollout(h, "kl", ro, false);
+  if (rc) return rc;
+  RG_NEED("kl", reset, "reset");
+  RG_NEED("kl", h0, "h0");
+  RG_NEED("kl", norm_state, "norm_state");
+  RG_NEED("kl", policy_params, "policy_params");
+  RG_NEED("kl", workspace, "workspace");
+  RG_NEED("kl", kl_out, "kl_out");
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  hipStream_t s = (hipStream_t)stream;
+  rc = run_describe(h, Call{ro, reset, h0, nullptr, norm_state, nullptr}, workspace, s);
+  if (rc) return rc;
+  return run_robot_kl(h, policy_params, workspace, kl_out, s);
+}
+
+int rg_bptt_adam(rg_bptt_handle *h, float *params, const float *grad, void *opt_state, void *stream) {
+  if (!h) { g_create_err = "adam: null handle"; return RG_BPTT_ERR_INVALID; }
+  RG_NEED("adam", params, "params");
+  RG_NEED("adam", grad, "grad");
+  RG_NEED("adam", opt_state, "opt_state");
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  return run_adam(h, params, grad, opt_state, (hipStream_t)stream);
+}
+
+int rg_bptt_penalty(rg_bptt_handle *h, const double *kl, void *opt_state, double *stats, void *stream) {
+  if (!h) { g_create_err = "penalty: null handle"; return RG_BPTT_ERR_INVALID; }
+  RG_NEED("penalty", kl, "kl");
+  RG_NEED("penalty", opt_state, "opt_state");
+  RG_NEED("penalty", stats, "stats");
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  return run_penalty(h, kl, opt_state, stats, nullptr, (hipStream_t)stream);
+}
+
+int rg_bptt_update_policy(rg_bptt_handle *h, const rg_ppo_rollout *ro, const int32_t *reset, const float *h0, const double *adv_stats,
+                          const double *norm_state, float *policy_params, void *opt_state, void *workspace, double *stats, void *stream) {
+  if (!h) { g_create_err = "update_policy: null handle"; return RG_BPTT_ERR_INVALID; }
+  int rc = check_rollout(h, "update_policy", ro, true);
+  if (rc) return rc;
+  RG_NEED("update_policy", reset, "reset");
+  RG_NEED("update_policy", h0, "h0");
+  RG_NEED("update_policy", adv_stats, "adv_stats");
+  RG_NEED("update_policy", norm_state, "norm_state");
+  RG_NEED("update_policy", policy_params, "policy_params");
+  RG_NEED("update_policy", opt_state, "opt_state");
+  RG_NEED("update_policy", workspace, "workspace");
+  RG_NEED("update_policy", stats, "stats");
+  if (h->device < 0) return no_device(h);
+  DeviceScope dev(h->device);
+  if (dev.err != hipSuccess) return hip_fail(h, "hipSetDevice failed", dev.err);
+  hipStream_t s = (hipStream_t)stream;
+  float *grad = ws_at<float>(workspace, h->o_grad);
+  rc = run_describe(h, Call{ro, reset, h0, adv_stats, norm_state, penalty_of(opt_state)}, workspace, s);
+  for (int e = 0; e < h->cfg.epochs_policy && !rc; e++) {
+    rc = run_policy_grad(h, policy_params, opt_state, workspace, grad, e == 0 ? stats + 0 : stats + 1, e == 0 ? stats + 1 : nullptr, s);
+    if (!rc) rc = run_adam(h, policy_params, grad, opt_state, s);
+  }
+  if (rc) return rc;
+  double *klr = ws_at<double>(workspace, h->o_klr);
+  rc = run_robot_kl(h, policy_params, workspace, klr, s);
+  if (rc) return rc;
+  return run_penalty(h, klr, opt_state, stats + 2, h->cfg.epochs_policy == 0 ? stats : nullptr, s);
+}
+
+}  // extern "C"

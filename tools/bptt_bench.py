@@ -1,0 +1,146 @@
+"""Times the recurrent agent's update, in one process and run, at T = 32 and batch 64, 4096 and 32768 with the default networks
+and 10 + 10 epochs: DeviceRecurrentPPO.update (include/rg_bptt.h and the value sweep of rg_ppo.h) and RecurrentPPO.update (torch
+autograd through the ticks) on the same collected rollout, alternating, each from the same parameters.  hipEvents around the
+whole update with one synchronisation, after a warm-up of each.  Beside them the kernel times of one policy gradient by
+phase -- F (forward and store), H (the head), B (the delta pass, with the transposes), W (the weight gradients, with the
+finishing sum) -- from torch's profiler over one rg_bptt_policy_grad, and the workspace's size.  For the record, not a gate:
+the yardstick is the torch update of the same run and no ratio is promised.
+
+    python tools/bptt_bench.py [--robot ghost] [--batches 64,4096,32768] [--reps 3] [--out profiles/bptt_update.json]
+"""
+import argparse
+import hashlib
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bench  # noqa: E402
+from robot_gym_amd.agents.ppo import (DeviceRecurrentPPO, RecurrentGaussianPolicy, RecurrentPPO, RecurrentRolloutBuffer,  # noqa: E402
+                                      collect_recurrent)
+from robot_gym_amd.core.config import MPCConfig  # noqa: E402
+from robot_gym_amd.gym.batched_go_env import BatchedGoEnv  # noqa: E402
+
+T = 32
+EPOCHS = 10
+SOURCES = ("robot_gym_amd/csrc/rg_bptt.hip", "robot_gym_amd/csrc/rg_ppo.hip", "robot_gym_amd/csrc/rg_agent_dev.inc", "robot_gym_amd/csrc/rg_host.h",
+           "include/rg_bptt.h", "include/rg_ppo.h", "include/rg_rnn.h")
+PHASES = {"F": ("rg_bptt_forward_kernel",), "H": ("rg_bptt_sample_kl_kernel", "rg_bptt_robot_kl_kernel", "rg_bptt_head_kernel", "rg_bptt_loss_finish_kernel"),
+          "B": ("rg_bptt_transpose_kernel", "rg_bptt_delta_kernel"), "W": ("rg_bptt_weight_kernel", "rg_bptt_grad_finish_kernel")}
+
+
+def bptt_hash():
+    h = hashlib.sha256()
+    for rel in SOURCES:
+        h.update(open(os.path.join(ROOT, rel), "rb").read())
+    return h.hexdigest()[:16]
+
+
+def one_update_ms(fn):
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    fn()
+    stop.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(stop)
+
+
+def phase_times(upd, ro):
+    """{phase: us} of the kernels of one rg_bptt_policy_grad, or {"error": text} where the profiler gives no kernel times."""
+    from torch.profiler import ProfilerActivity, profile
+    try:
+        upd.prepare(ro)
+        upd.policy_grad(ro)
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            upd.policy_grad(ro)
+            torch.cuda.synchronize()
+        times = {}
+        for ev in prof.events():
+            for phase, names in PHASES.items():
+                if any(n in ev.name for n in names):
+                    times[phase] = times.get(phase, 0.0) + float(getattr(ev, "device_time", None) or getattr(ev, "cuda_time", 0.0))
+        if set(times) != set(PHASES):
+            return dict(error=f"the profiler reported kernels of {sorted(times)} only")
+        return {k: round(v, 1) for k, v in times.items()}
+    except Exception as e:      # a measurement that could not be taken is recorded as such, not dropped
+        return dict(error=f"{type(e).__name__}: {e}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--robot", default="ghost")
+    ap.add_argument("--batches", default="64,4096,32768")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    cfg = MPCConfig.for_robot(args.robot, vx_offset=0.0, vy_offset=0.0, wz_offset=0.0)
+    commit, dirty = bench.git_head()
+    rows = []
+    for B in [int(x) for x in args.batches.split(",")]:
+        env = BatchedGoEnv(B, cfg, seed=B, device=dev, auto_reset=True, max_time=0.45)
+        env.reset()
+        policy = RecurrentGaussianPolicy(B, seed=B, device=dev)
+        ro = RecurrentRolloutBuffer(T, B, device=dev)
+        collect_recurrent(env, policy, ro)
+        start = (policy.policy_params.detach().clone(), policy.value_params.detach().clone())
+        device = DeviceRecurrentPPO(policy, T, epochs_policy=EPOCHS, epochs_value=EPOCHS)
+        opt = (device.opt_state.clone(), device.value_opt_state.clone())
+        host = RecurrentPPO(policy, epochs_policy=EPOCHS, epochs_value=EPOCHS)
+
+        def restore():
+            with torch.no_grad():
+                policy.policy_params.copy_(start[0]), policy.value_params.copy_(start[1])
+            device.opt_state.copy_(opt[0]), device.value_opt_state.copy_(opt[1])
+            torch.cuda.synchronize()
+
+        stats = {}
+        times = dict(device=[], torch=[])
+        for rep in range(args.reps + 1):                    # the first round of each is the warm-up
+            for name, fn in (("device", lambda: device.update(ro)), ("torch", lambda: host.update(ro))):
+                restore()
+                ms = one_update_ms(fn)
+                if rep:
+                    times[name].append(ms)
+        restore()
+        device.update(ro)
+        stats["device"] = device.stats_dict()
+        restore()
+        stats["torch"] = host.update(ro)
+        restore()
+        phases = phase_times(device, ro)
+        d_ms, t_ms = statistics.median(times["device"]), statistics.median(times["torch"])
+        rows.append(dict(batch=B, T=T, epochs_policy=EPOCHS, epochs_value=EPOCHS, device_update_ms=round(d_ms, 3), torch_update_ms=round(t_ms, 3),
+                         device_over_torch=round(d_ms / t_ms, 4), device_update_ms_all=[round(x, 3) for x in times["device"]],
+                         torch_update_ms_all=[round(x, 3) for x in times["torch"]], policy_grad_phase_us=phases,
+                         workspace_bytes=device._handle.workspace_bytes, value_workspace_bytes=device._value.workspace_bytes,
+                         groups=device._handle.groups, device_stats=stats["device"], torch_stats=stats["torch"]))
+        print(json.dumps(rows[-1]), flush=True)
+        device.close()
+        policy.close()
+        env.close()
+        del device, host, ro, policy, env
+        torch.cuda.empty_cache()
+    result = dict(what="the recurrent agent's update, one process and run, ms per update (median of `reps` after a warm-up of each, alternating, each "
+                       "from the same parameters and optimiser state): DeviceRecurrentPPO.update and RecurrentPPO.update on the same collected rollout, "
+                       "T = 32, default networks, 10 + 10 epochs; policy_grad_phase_us: the kernel times of one rg_bptt_policy_grad by phase (F forward "
+                       "and store, H head, B delta pass and transposes, W weight gradients and finishing sum).  `commit` is the commit the measured "
+                       "tree was based on; bptt_source_sha256 is the hash of " + ", ".join(os.path.basename(s) for s in SOURCES) + " as measured",
+                  robot=args.robot, commit=commit, dirty=dirty, source_hash=bench.source_hash(), bptt_source_sha256=bptt_hash(),
+                  device=torch.cuda.get_device_name(0), reps=args.reps, rows=rows)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
