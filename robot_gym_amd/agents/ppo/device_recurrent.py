@@ -8,11 +8,13 @@ import torch
 
 from robot_gym_amd.core import bptt_abi, ppo_abi
 
+from .device_update import _DeviceUpdate
+
 _SLOTS = ("obs", "action", "mean", "logstd", "adv", "ret", "mask")
 _GRAD_SLOTS = ("obs", "action", "mean", "logstd", "adv", "mask")
 
 
-class DeviceRecurrentPPO:
+class DeviceRecurrentPPO(_DeviceUpdate):
     """update(rollout) enqueues rg_ppo_prepare, rg_bptt_update_policy and epochs_value x (rg_ppo_value_grad, rg_ppo_adam) for a
     RecurrentRolloutBuffer of T ticks of policy.batch robots and returns the device tensor `stats` (float64 [6],
     ppo_abi.STAT_NAMES); stats_dict() reads it.  The KL and the penalty read the policy alone, so taking them before the value
@@ -32,35 +34,14 @@ class DeviceRecurrentPPO:
     have it.  A host-only policy (device="cpu") gives host-only handles: arguments are checked, every entry then raises
     NO_DEVICE."""
 
-    def __init__(self, policy, T=None, policy_lr=1e-4, value_lr=3e-4, epochs_policy=50, epochs_value=50, kl_target=1e-2, kl_cutoff_factor=2,
-                 kl_cutoff_coef=1000, kl_init_penalty=1, conv_logpdf="exact", beta1=0.9, beta2=0.999, adam_eps=1e-8):
-        self.policy = policy
-        self.T, self.batch = None, int(policy.batch)
-        self._settings = dict(policy_lr=policy_lr, value_lr=value_lr, epochs_policy=epochs_policy, epochs_value=epochs_value, kl_target=kl_target,
-                              kl_cutoff_factor=kl_cutoff_factor, kl_cutoff_coef=kl_cutoff_coef, conv_logpdf=conv_logpdf, beta1=beta1, beta2=beta2,
-                              adam_eps=adam_eps)
-        self.fields = ppo_abi.ppo_fields(**self._settings)
+    def _alloc(self):
         self._handle = self._value = self.workspace = self.value_workspace = self.value_opt_state = None
-        self.device = dev = policy.device
-        self.epochs_policy, self.epochs_value = int(epochs_policy), int(epochs_value)
-        self.kl_target = float(kl_target)
-        self.kl_init_penalty = float(kl_init_penalty)
-        lay = policy.layout
-        self.policy_count, self.value_count = lay["policy_count"], lay["value_count"]
         opt_bytes = bptt_abi.OPT_HEADER_BYTES + 4 * 2 * self.policy_count                # rg_bptt.h, opt_state
-        self.opt_state = torch.zeros(opt_bytes // 8, dtype=torch.float64, device=dev)
+        self.opt_state = torch.zeros(opt_bytes // 8, dtype=torch.float64, device=self.device)
         self.step = self.opt_state[:1].view(torch.int64)
         self.penalty = self.opt_state[1:2]
         self.moments = self.opt_state[bptt_abi.OPT_HEADER_BYTES // 8:].view(torch.float32)
-        self.penalty.fill_(self.kl_init_penalty)
-        self.stats = torch.zeros(ppo_abi.STATS, dtype=torch.float64, device=dev)
-        self._policy_stats = torch.zeros(bptt_abi.STATS, dtype=torch.float64, device=dev)
-        self._grad = {ppo_abi.POLICY: torch.zeros(self.policy_count, dtype=torch.float32, device=dev),
-                      ppo_abi.VALUE: torch.zeros(self.value_count, dtype=torch.float32, device=dev)}
-        self._loss = torch.zeros(2, dtype=torch.float64, device=dev)
-        self._kl = torch.zeros(self.batch, dtype=torch.float64, device=dev)
-        if T is not None:
-            self._bind(T)
+        self._policy_stats = torch.zeros(bptt_abi.STATS, dtype=torch.float64, device=self.device)
 
     def _bind(self, T):
         """The two handles, their workspaces and the value side's opt_state for rollouts of T ticks."""
@@ -97,38 +78,14 @@ class DeviceRecurrentPPO:
 
     # ---- argument checks ------------------------------------------------------------------------------------------------
 
-    def _check(self, call, name, t, shape, dtype):
-        if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
-            kind = {torch.float32: "float32", torch.int32: "int32", torch.float64: "float64"}[dtype]
-            raise ValueError(f"{call}: {name} must be a contiguous {kind} {list(shape)} tensor on {self.device}")
-        return t.data_ptr()
-
     def _rollout(self, call, rollout, slots, recurrent=True):
         """(rg_ppo_rollout over the named slots, reset pointer, h0 pointer) of a RecurrentRolloutBuffer, each tensor checked before
         the library sees its pointer: contiguous, of the shape and dtype the headers give, on this device."""
-        if self.T is None:
-            if int(rollout.T) < 1:
-                raise ValueError(f"{call}: rollout.T is {rollout.T}, it must be at least 1")
-            self._bind(rollout.T)
-        p, T, B = self.policy, self.T, self.batch
-        if int(rollout.T) != T:
-            raise ValueError(f"{call}: rollout.T is {rollout.T}, this update was made for T = {T}")
-        if int(rollout.batch) != B:
-            raise ValueError(f"{call}: rollout.batch is {rollout.batch}, the policy's batch is {B}")
-        f32, i32 = torch.float32, torch.int32
-        shapes = dict(obs=((T, p.obs_dim, B), f32), action=((T, B, p.act_dim), f32), mean=((T, B, p.act_dim), f32), logstd=((p.act_dim,), f32),
-                      adv=((T, B), f32), ret=((T, B), f32), mask=((T, B), i32))
-        ptrs = {name: self._check(call, "rollout." + name, getattr(rollout, name, None), *shapes[name]) for name in slots}
-        ro = ppo_abi.make_crollout(**ptrs)
+        ro = super()._rollout(call, rollout, slots)
         if not recurrent:
             return ro
-        return (ro, self._check(call, "rollout.reset", getattr(rollout, "reset", None), (T, B), i32),
-                self._check(call, "rollout.h0", getattr(rollout, "h0", None), (B, p.gru_units), f32))
-
-    def _params(self, call):
-        p = self.policy
-        return (self._check(call, "policy.policy_params", p.policy_params, (self.policy_count,), torch.float32),
-                self._check(call, "policy.value_params", p.value_params, (self.value_count,), torch.float32))
+        return (ro, self._check(call, "rollout.reset", getattr(rollout, "reset", None), (self.T, self.batch), torch.int32),
+                self._check(call, "rollout.h0", getattr(rollout, "h0", None), (self.batch, self.policy.gru_units), torch.float32))
 
     def _norm(self, call):
         return self._check(call, "policy.norm_state", self.policy.norm_state, tuple(self.policy.norm_state.shape), torch.float64)
@@ -159,11 +116,6 @@ class DeviceRecurrentPPO:
         self.stats[4:6].copy_(self._policy_stats[2:4])
         return self.stats
 
-    def stats_dict(self):
-        """The dict RecurrentPPO.update returns, read from the device (this synchronises); a loss of a network with 0 epochs is
-        None."""
-        return {name: (None if x != x else x) for name, x in zip(ppo_abi.STAT_NAMES, self.stats.tolist())}
-
     def prepare(self, rollout):
         """rg_ppo_prepare: the advantage's n, mean and std for policy_grad."""
         self._value.prepare(self._rollout("prepare", rollout, ("adv", "mask"), recurrent=False), self.value_workspace.data_ptr())
@@ -190,23 +142,10 @@ class DeviceRecurrentPPO:
         self._value.value_grad(ro, self._norm("value_grad"), vp, self.value_workspace.data_ptr(), grad.data_ptr(), self._loss[1:2].data_ptr())
         return grad, self._loss[1]
 
-    def _out(self, call, out, which):
-        n = self.policy_count if which == ppo_abi.POLICY else self.value_count
-        if out is None:
-            return self._grad[which]
-        self._check(call, "out", out, (n,), torch.float32)
-        return out
-
     def adam(self, which, grad):
         """One Adam step on the policy's buffer `which` ("policy" / "value" or ppo_abi.POLICY / VALUE) with `grad`: rg_bptt_adam or
         rg_ppo_adam."""
-        which = {"policy": ppo_abi.POLICY, "value": ppo_abi.VALUE}.get(which, which)
-        if which not in (ppo_abi.POLICY, ppo_abi.VALUE):
-            raise ValueError("adam: which must be 'policy' or 'value'")
-        grad = self._out("adam", grad, which)
-        if self._handle is None:
-            raise ValueError("adam: no rollout has been seen yet; pass T to DeviceRecurrentPPO or call an entry that takes the rollout first")
-        pp, vp = self._params("adam")
+        which, grad, (pp, vp) = self._adam_args(which, grad)
         if which == ppo_abi.POLICY:
             self._handle.adam(pp, grad.data_ptr(), self.opt_state.data_ptr())
         else:
@@ -216,10 +155,7 @@ class DeviceRecurrentPPO:
         """KL(behaviour || current) per robot, float64 [B] on the device."""
         ro, reset, h0 = self._rollout("kl", rollout, ("obs", "mean", "logstd", "mask"))
         pp, _ = self._params("kl")
-        if out is None:
-            out = self._kl
-        else:
-            self._check("kl", "out", out, (self.batch,), torch.float64)
+        out = self._kl_out(out)
         self._handle.kl(ro, reset, h0, self._norm("kl"), pp, self.workspace.data_ptr(), out.data_ptr())
         return out
 

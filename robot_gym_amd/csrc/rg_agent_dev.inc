@@ -203,7 +203,12 @@ __device__ __forceinline__ float slab_sum(const float *__restrict__ slabs, const
   return (float)s;
 }
 
-// Not here: the Adam arithmetic, which rg_ppo_adam_kernel and rg_ddpg_adam_kernel write out in the same words.  As a shared
-// function it moved a load in rg_ppo_adam_kernel and raised its VGPRs from 33 to 34 (profiles/agents_isa_identity.txt).
+// Not here: the Adam arithmetic, which rg_ppo_adam_kernel, rg_ddpg_adam_kernel and the recurrent update's Adam kernel write
+// out in the same words.  As a shared function it moved a load in rg_ppo_adam_kernel and raised its VGPRs from 33 to 34
+// (profiles/agents_isa_identity.txt).
+// Not here either: the Gaussian head of rg_ppo.h, written out in rg_ppo.hip's sweep and in the recurrent update's head.  As
+// one templated function with lambdas for the mean's load and the delta's store it took rg_ppo_policy_forward_kernel from
+// 94 to 114 VGPRs and from 5 to 4 waves per SIMD, and rg_ppo_policy_backward_kernel from 156 to 157 VGPRs, to save 40 lines.
+// The GRU tick that the recurrent policy's acting kernels and its update share is rg_gru_dev.inc, included after this file.
 
 }  // namespace

@@ -1,8 +1,9 @@
 // rg_bptt.hip -- the recurrent PPO policy update of include/rg_bptt.h: back-propagation through time through the GRU cell of
 // rg_rnn.h, with the head, Adam and the penalty rule of rg_ppo.h.  Its own translation unit of librg_mpc.so.  The normaliser's
 // arithmetic, the workgroup sums and the transpose body are those of rg_agent_dev.inc and the host helpers those of rg_host.h;
-// rg_mpc.hip includes neither this file nor them, so the source hash behind profiles/ is unaffected.  The tick's arithmetic is
-// restated from rg_rnn.hip (whose device functions are its own): the GPU tests hold the two to the same bits.
+// rg_mpc.hip includes neither this file nor them, so the source hash behind profiles/ is unaffected.  The tick lives in
+// rg_gru_dev.inc, which the acting kernels run too: the forward pass here is that code with a sink that keeps everything, so
+// its means are the rollout's to the bit.
 //
 // One gradient is four kinds of launch (rg_bptt.h):
 //   F  rg_bptt_forward_kernel: kTile robots per 256-thread workgroup through all T ticks, one output neuron per thread with
@@ -38,15 +39,11 @@
 #pragma clang fp contract(off)
 
 #include "rg_agent_dev.inc"
+#include "rg_gru_dev.inc"
 
 namespace {
 
-constexpr int kTile = RG_RNN_TILE;
-constexpr int kMaxW = RG_RNN_MAX_WIDTH;
-constexpr int kMaxH = RG_RNN_MAX_UNITS;
-constexpr int kMaxAct = RG_RNN_MAX_ACT;
 constexpr int kThreads = kAgentThreads;
-constexpr int kCols = RG_POLICY_NORM_COLS;
 constexpr int kChunk = RG_BPTT_CHUNK;
 constexpr int kRows = RG_BPTT_ROWS;
 constexpr int kMaxGroups = RG_BPTT_MAX_GROUPS;
@@ -54,7 +51,6 @@ constexpr int kMaxParts = 256;       // workgroups of the head kernel, at most
 constexpr int kPart = 1 + kMaxAct;   // per workgroup of the head kernel: the loss sum, then the logstd gradient
 constexpr int kBlocks = RG_RNN_MAX_DENSE + 3;
 
-static_assert(kTile == 8, "a neuron reads the activations of an input as two float4");
 static_assert(2 * kMaxH <= kThreads && kMaxW <= kThreads, "one output neuron, one column of a block per thread");
 static_assert(kTile * kMaxAct <= kThreads && kMaxAct <= kMaxW, "the mean's thread map; the head's output fits an x buffer");
 static_assert(kChunk * kRows == kThreads && kRows % 4 == 0, "a thread stages one input of a chunk; rows are read as float4");
@@ -85,102 +81,26 @@ __global__ void rg_bptt_describe_kernel(const BpttDev src, BpttDev *__restrict__
   if (blockIdx.x == 0 && threadIdx.x == 0) *dst = src;
 }
 
-__device__ __forceinline__ const BpttDev *descriptor_to_lds(const BpttDev *__restrict__ dg, BpttDev *dsh) {
-  for (int idx = threadIdx.x; idx < (int)(sizeof(BpttDev) / sizeof(int)); idx += kThreads)
-    reinterpret_cast<int *>(dsh)[idx] = reinterpret_cast<const int *>(dg)[idx];
-  __syncthreads();
-  return dsh;
-}
-
-// acc[r] = fma(W[i * stride], x[i][r], acc[r]) for i = 0 .. nin-1 in order
-__device__ __forceinline__ void chain8(const float *__restrict__ W, const int stride, const float *x, const int nin, float (&acc)[kTile]) {
-#pragma unroll 8
-  for (int i = 0; i < nin; i++) {
-    const float w = W[(size_t)i * stride];
-    const float4 xa = *reinterpret_cast<const float4 *>(x + i * kTile);
-    const float4 xb = *reinterpret_cast<const float4 *>(x + i * kTile + 4);
-    acc[0] = __builtin_fmaf(w, xa.x, acc[0]); acc[1] = __builtin_fmaf(w, xa.y, acc[1]);
-    acc[2] = __builtin_fmaf(w, xa.z, acc[2]); acc[3] = __builtin_fmaf(w, xa.w, acc[3]);
-    acc[4] = __builtin_fmaf(w, xb.x, acc[4]); acc[5] = __builtin_fmaf(w, xb.y, acc[5]);
-    acc[6] = __builtin_fmaf(w, xb.z, acc[6]); acc[7] = __builtin_fmaf(w, xb.w, acc[7]);
-  }
-}
-
-__device__ __forceinline__ float sigmoidf(const float a) { return 1.0f / (1.0f + expf(-a)); }
-
 // ---- F: the forward pass, every intermediate kept --------------------------------------------------------------------------
 
-// stage s of the tick for output neuron j (rg_rnn.hip, policy_stage), t0 = t * B: what it forms also goes to the workspace
-__device__ __forceinline__ void forward_stage(const BpttDev *d, const float *__restrict__ pp, const int s, const int j, const int b0, const size_t t0,
-                                              float (*xs)[kMaxW * kTile], float *hs, float *rh, float *us) {
-  const int n_dense = d->n_dense, H = d->H, n_x = d->n_x, B = d->B;
-  float acc[kTile];
-#pragma unroll
-  for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
-  if (s < n_dense) {
-    const int nin = d->dense_in[s], nout = d->dense_out[s];
-    if (j < nout) {
-      chain8(pp + d->dense_w[s] + j, nout, xs[s & 1], nin, acc);
-      const float bias = pp[d->dense_b[s] + j];
-      float *y = xs[(s & 1) ^ 1] + j * kTile;
-      float *out = d->a[s + 1];
-#pragma unroll
-      for (int r = 0; r < kTile; r++) {
-        const float v = acc[r] + bias;
-        const float a = v > 0.0f ? v : 0.0f;
-        y[r] = a;
-        if (b0 + r < B) out[(t0 + b0 + r) * nout + j] = a;
-      }
-    }
-  } else if (s == n_dense) {
-    if (j < 2 * H) {
-      const float *__restrict__ W = pp + d->w_ru + j;
-      chain8(W, 2 * H, xs[n_dense & 1], n_x, acc);
-      chain8(W + (size_t)n_x * 2 * H, 2 * H, hs, H, acc);
-      const float bias = pp[d->b_ru + j];
-      if (j < H) {
-#pragma unroll
-        for (int r = 0; r < kTile; r++) {
-          const float g = sigmoidf(acc[r] + bias);
-          const float p = g * hs[j * kTile + r];
-          rh[j * kTile + r] = p;
-          if (b0 + r < B) { d->r[(t0 + b0 + r) * H + j] = g; d->rh[(t0 + b0 + r) * H + j] = p; }
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < kTile; r++) {
-          const float g = sigmoidf(acc[r] + bias);
-          us[(j - H) * kTile + r] = g;
-          if (b0 + r < B) d->u[(t0 + b0 + r) * H + (j - H)] = g;
-        }
-      }
-    }
-  } else if (s == n_dense + 1) {
-    if (j < H) {
-      const float *__restrict__ W = pp + d->w_c + j;
-      chain8(W, H, xs[n_dense & 1], n_x, acc);
-      chain8(W + (size_t)n_x * H, H, rh, H, acc);
-      const float bias = pp[d->b_c + j];
-#pragma unroll
-      for (int r = 0; r < kTile; r++) {
-        const float c = tanhf(acc[r] + bias);
-        const float u = us[j * kTile + r], h = hs[j * kTile + r];
-        const float hn = __builtin_fmaf(u, h, __builtin_fmaf(-u, c, c));
-        hs[j * kTile + r] = hn;   // only this thread reads or writes h[j] in this stage
-        if (b0 + r < B) { d->cc[(t0 + b0 + r) * H + j] = c; d->hn[(t0 + b0 + r) * H + j] = hn; }
-      }
-    }
-  } else if (s == n_dense + 2) {
-    const int act_dim = d->act_dim;
-    if (j < act_dim) {
-      chain8(pp + d->head_w + j, act_dim, hs, H, acc);
-      const float bias = pp[d->head_b + j];
-      float *y = xs[(n_dense & 1) ^ 1] + j * kTile;
-#pragma unroll
-      for (int r = 0; r < kTile; r++) y[r] = tanhf(acc[r] + bias);
-    }
+// what the update keeps of a tick: everything, in the workspace's regions at sample t0 + b0 + r, t0 = t * B
+struct KeepSink {
+  const BpttDev *d;
+  int b0;
+  size_t t0;
+  __device__ __forceinline__ void dense(const int s, const int nout, const int j, const int r, const float a) const {
+    if (b0 + r < d->B) d->a[s + 1][(t0 + b0 + r) * nout + j] = a;
   }
-}
+  __device__ __forceinline__ void reset_gate(const int H, const int j, const int r, const float g, const float p) const {
+    if (b0 + r < d->B) { d->r[(t0 + b0 + r) * H + j] = g; d->rh[(t0 + b0 + r) * H + j] = p; }
+  }
+  __device__ __forceinline__ void update_gate(const int H, const int j, const int r, const float u) const {
+    if (b0 + r < d->B) d->u[(t0 + b0 + r) * H + j] = u;
+  }
+  __device__ __forceinline__ void cell(const int H, const int j, const int r, const float c, const float hn) const {
+    if (b0 + r < d->B) { d->cc[(t0 + b0 + r) * H + j] = c; d->hn[(t0 + b0 + r) * H + j] = hn; }
+  }
+};
 
 __global__ void __launch_bounds__(kThreads) rg_bptt_forward_kernel(const BpttDev *__restrict__ dg, const float *__restrict__ pp) {
   __shared__ BpttDev dsh;
@@ -203,14 +123,11 @@ __global__ void __launch_bounds__(kThreads) rg_bptt_forward_kernel(const BpttDev
     const size_t t0 = (size_t)t * B;
     const float *__restrict__ obs_t = d->obs + t0 * obs_dim;
     const int *__restrict__ reset_t = d->reset + t0;
-    // the observation through the normaliser: float64, rounded to float32 once (rg_policy.h, transform)
     for (int idx = tid; idx < obs_dim * kTile; idx += kThreads) {
       const int r = idx / obs_dim, i = idx - r * obs_dim, b = b0 + r;
       float xn = 0.0f;
       if (b < B) {
-        double v = (double)obs_t[(size_t)i * B + b] - norm[kCols + i];
-        v = v / norm_scale(norm[i], norm[2 * kCols + i]);
-        xn = (float)clip_sym(v, d->obs_clip);
+        xn = normalised(obs_t, norm, i, b, B, d->obs_clip);
         d->a[0][(t0 + b) * obs_dim + i] = xn;
       }
       xs[0][i * kTile + r] = xn;
@@ -224,7 +141,7 @@ __global__ void __launch_bounds__(kThreads) rg_bptt_forward_kernel(const BpttDev
     }
     for (int s = 0; s < n_pol; s++) {
       __syncthreads();
-      forward_stage(d, pp, s, tid, b0, t0, xs, hs, rh, us);
+      gru_stage(d, pp, s, tid, xs, hs, rh, us, KeepSink{d, b0, t0});
     }
     __syncthreads();
     if (tid < kTile * act_dim) {
@@ -615,29 +532,6 @@ struct rg_bptt_handle {
 
 namespace {
 
-bool validate_rnn(const rg_rnn_config *cfg, std::string &err) {
-  const char *prefix = "rnn_cfg.";
-  if (!check_abi(prefix, cfg->abi_version, RG_RNN_ABI_VERSION, err)) return false;
-  if (!check_reserved(prefix, "reserved0", cfg->reserved0, err)) return false;
-  const IntField ints[] = {{"obs_dim", cfg->obs_dim, 1, RG_RNN_MAX_OBS}, {"act_dim", cfg->act_dim, 1, RG_RNN_MAX_ACT},
-                           {"n_policy_layers", cfg->n_policy_layers, 0, RG_RNN_MAX_DENSE}, {"gru_units", cfg->gru_units, 1, RG_RNN_MAX_UNITS},
-                           {"n_value_layers", cfg->n_value_layers, 0, RG_RNN_MAX_VALUE_LAYERS}};
-  const RealField reals[] = {{"obs_clip", &cfg->obs_clip, 1, kNonNegative}};
-  return check_ints(prefix, ints, err) &&
-         check_widths(prefix, "policy_layers", cfg->policy_layers, cfg->n_policy_layers, RG_RNN_MAX_DENSE, RG_RNN_MAX_WIDTH, err) &&
-         check_widths(prefix, "value_layers", cfg->value_layers, cfg->n_value_layers, RG_RNN_MAX_VALUE_LAYERS, RG_RNN_MAX_WIDTH, err) &&
-         check_reals(prefix, reals, err);
-}
-
-bool validate_ppo(const rg_ppo_config *cfg, std::string &err) {
-  const IntField ints[] = {{"epochs_policy", cfg->epochs_policy, 0, RG_PPO_MAX_EPOCHS}, {"epochs_value", cfg->epochs_value, 0, RG_PPO_MAX_EPOCHS},
-                           {"conv_logpdf", cfg->conv_logpdf, RG_PPO_LOGPDF_EXACT, RG_PPO_LOGPDF_REFERENCE}};
-  const RealField reals[] = {{"policy_lr", &cfg->policy_lr, 1, kNonNegative}, {"value_lr", &cfg->value_lr, 1, kNonNegative}, {"beta1", &cfg->beta1, 1, kBelowOne},
-                             {"beta2", &cfg->beta2, 1, kBelowOne}, {"adam_eps", &cfg->adam_eps, 1, kPositive}, {"kl_target", &cfg->kl_target, 1, kPositive},
-                             {"kl_cutoff_factor", &cfg->kl_cutoff_factor, 1, kNonNegative}, {"kl_cutoff_coef", &cfg->kl_cutoff_coef, 1, kNonNegative}};
-  return check_abi("ppo_cfg.", cfg->abi_version, RG_PPO_ABI_VERSION, err) && check_ints("ppo_cfg.", ints, err) && check_reals("ppo_cfg.", reals, err);
-}
-
 int hip_fail(rg_bptt_handle *h, const char *what, hipError_t e) { return hip_fail(h, RG_BPTT_ERR_HIP, what, e); }
 int no_device(rg_bptt_handle *h) { return no_device(h, RG_BPTT_ERR_NO_DEVICE, "RG_BPTT"); }
 int launch_status(rg_bptt_handle *h, const char *what) { return launch_status(h, RG_BPTT_ERR_HIP, what); }
@@ -772,15 +666,9 @@ int rg_bptt_create(const rg_rnn_config *rnn_cfg, const rg_ppo_config *ppo_cfg, i
   *out = nullptr;
   char msg[128];
   std::string err;
-  if (!validate_rnn(rnn_cfg, err) || !validate_ppo(ppo_cfg, err)) { g_create_err = err; return RG_BPTT_ERR_INVALID; }
-  if (T < 1 || T > RG_RNN_MAX_T) {
-    snprintf(msg, sizeof(msg), "T: %d outside [1, %d]", T, RG_RNN_MAX_T);
-    g_create_err = msg;
-    return RG_BPTT_ERR_INVALID;
-  }
-  if (B < 1 || B > RG_RNN_MAX_BATCH) {
-    snprintf(msg, sizeof(msg), "B: %d outside [1, %d]", B, RG_RNN_MAX_BATCH);
-    g_create_err = msg;
+  const IntField sizes[] = {{"T", T, 1, RG_RNN_MAX_T}, {"B", B, 1, RG_RNN_MAX_BATCH}};
+  if (!check_rnn_config("rnn_cfg.", rnn_cfg, err) || !check_ppo_config(ppo_cfg, err) || !check_ints("", sizes, err)) {
+    g_create_err = err;
     return RG_BPTT_ERR_INVALID;
   }
   if ((long long)T * B > RG_PPO_MAX_SAMPLES) {
@@ -793,25 +681,12 @@ int rg_bptt_create(const rg_rnn_config *rnn_cfg, const rg_ppo_config *ppo_cfg, i
   h->cfg = *ppo_cfg;
   h->T = T; h->B = B; h->N = T * B; h->device = device;
   BpttDev &d = h->dv;
-  const int H = rnn_cfg->gru_units, nd = rnn_cfg->n_policy_layers, A = rnn_cfg->act_dim;
-  d.T = T; d.B = B; d.N = h->N; d.obs_dim = rnn_cfg->obs_dim; d.act_dim = A; d.H = H; d.n_dense = nd;
-  int off = 0, prev = rnn_cfg->obs_dim;   // the layout rule of rg_rnn.h
-  for (int l = 0; l < nd; l++) {
-    const int width = rnn_cfg->policy_layers[l];
-    d.dense_in[l] = prev; d.dense_out[l] = width;
-    d.dense_w[l] = off; off += prev * width;
-    d.dense_b[l] = off; off += width;
-    prev = width;
-  }
-  d.n_x = prev;
-  d.w_ru = off; off += (prev + H) * 2 * H;
-  d.b_ru = off; off += 2 * H;
-  d.w_c = off; off += (prev + H) * H;
-  d.b_c = off; off += H;
-  d.head_w = off; off += H * A;
-  d.head_b = off; off += A;
-  d.logstd_off = off;
-  d.count = off + A;
+  rg_rnn_layout L;
+  fill_layout(rnn_cfg, L);
+  const int H = L.gru_units, nd = L.n_dense, n_x = L.n_x, A = rnn_cfg->act_dim;
+  d.T = T; d.B = B; d.N = h->N; d.obs_dim = rnn_cfg->obs_dim; d.act_dim = A;
+  layout_to_dev(L, d);
+  d.count = L.policy_count;
   d.nchunks = (h->N + kChunk - 1) / kChunk;
   const int gmax = d.nchunks < kMaxGroups ? d.nchunks : kMaxGroups;
   d.per = (d.nchunks + gmax - 1) / gmax;
@@ -827,8 +702,8 @@ int rg_bptt_create(const rg_rnn_config *rnn_cfg, const rg_ppo_config *ppo_cfg, i
   int k = 0;
   auto add = [&](int in, int out_, int w) { tr.in[k] = in; tr.out[k] = out_; tr.w[k] = w; tr.b[k] = 0; k++; };
   if (nd == 2) add(d.dense_in[1], d.dense_out[1], d.dense_w[1]);
-  add(prev + H, 2 * H, d.w_ru);
-  add(prev + H, H, d.w_c);
+  add(n_x + H, 2 * H, d.w_ru);
+  add(n_x + H, H, d.w_c);
   add(H, A, d.head_w);
   tr.n = k;
   const size_t N = (size_t)h->N, f = sizeof(float);

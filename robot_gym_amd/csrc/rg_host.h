@@ -1,7 +1,8 @@
 // rg_host.h -- the host helpers that every translation unit of the library but the controller's shares: the device scope and
-// the device preamble of a create, the workspace arithmetic, the layer-layout rule, the checks of a configuration's fields
+// the device preamble of a create, the workspace arithmetic, the layout rules, the checks of a configuration's fields (and
+// of a whole rg_policy_config, rg_rnn_config or rg_ppo_config, where the header that declares it has been included first)
 // and the error helpers.  Every message is formed here once; the callers give the prefix ("config.", "policy_cfg.",
-// "ppo_cfg.") and their API's status codes.
+// "rnn_cfg.", "" for an argument) and their API's status codes.
 // rg_mpc.hip does not include it, so the source hash behind profiles/ does not move.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -151,6 +152,67 @@ inline bool check_policy_config(const char *prefix, const rg_policy_config *cfg,
          check_widths(prefix, "policy_layers", cfg->policy_layers, cfg->n_policy_layers, RG_POLICY_MAX_LAYERS, RG_POLICY_MAX_WIDTH, err) &&
          check_widths(prefix, "value_layers", cfg->value_layers, cfg->n_value_layers, RG_POLICY_MAX_LAYERS, RG_POLICY_MAX_WIDTH, err) &&
          check_reals(prefix, reals, err);
+}
+#endif
+
+#ifdef RG_RNN_ABI_VERSION
+// what the acting side and the update check alike of an rg_rnn_config (where rg_rnn.h has been included): every field
+inline bool check_rnn_config(const char *prefix, const rg_rnn_config *cfg, std::string &err) {
+  if (!check_abi(prefix, cfg->abi_version, RG_RNN_ABI_VERSION, err)) return false;
+  if (!check_reserved(prefix, "reserved0", cfg->reserved0, err)) return false;
+  const IntField ints[] = {{"obs_dim", cfg->obs_dim, 1, RG_RNN_MAX_OBS}, {"act_dim", cfg->act_dim, 1, RG_RNN_MAX_ACT},
+                           {"n_policy_layers", cfg->n_policy_layers, 0, RG_RNN_MAX_DENSE}, {"gru_units", cfg->gru_units, 1, RG_RNN_MAX_UNITS},
+                           {"n_value_layers", cfg->n_value_layers, 0, RG_RNN_MAX_VALUE_LAYERS}};
+  const RealField reals[] = {{"obs_clip", &cfg->obs_clip, 1, kNonNegative}};
+  return check_ints(prefix, ints, err) &&
+         check_widths(prefix, "policy_layers", cfg->policy_layers, cfg->n_policy_layers, RG_RNN_MAX_DENSE, RG_RNN_MAX_WIDTH, err) &&
+         check_widths(prefix, "value_layers", cfg->value_layers, cfg->n_value_layers, RG_RNN_MAX_VALUE_LAYERS, RG_RNN_MAX_WIDTH, err) &&
+         check_reals(prefix, reals, err);
+}
+
+// the parameter layout rule of rg_rnn.h
+inline void fill_layout(const rg_rnn_config *cfg, rg_rnn_layout &L) {
+  L = rg_rnn_layout{};
+  const int H = cfg->gru_units, nd = cfg->n_policy_layers;
+  int off = 0, prev = cfg->obs_dim;
+  for (int l = 0; l < nd; l++) {
+    const int width = cfg->policy_layers[l];
+    L.dense_in[l] = prev; L.dense_out[l] = width;
+    L.dense_w[l] = off; off += prev * width;
+    L.dense_b[l] = off; off += width;
+    prev = width;
+  }
+  L.n_dense = nd; L.n_x = prev; L.gru_units = H;
+  L.w_ru = off; off += (prev + H) * 2 * H;
+  L.b_ru = off; off += 2 * H;
+  L.w_c = off; off += (prev + H) * H;
+  L.b_c = off; off += H;
+  L.head_w = off; off += H * cfg->act_dim;
+  L.head_b = off; off += cfg->act_dim;
+  L.logstd_offset = off;
+  L.policy_count = off + cfg->act_dim;
+  L.n_value = cfg->n_value_layers + 1;
+  L.value_count = layer_layout(cfg->obs_dim, cfg->value_layers, cfg->n_value_layers, 1, L.value_in, L.value_out, L.value_w, L.value_b);
+}
+
+// the policy buffer's layout into the fields a kernel's descriptor D names as the tick's device code reads them
+template <typename D>
+void layout_to_dev(const rg_rnn_layout &L, D &d) {
+  d.H = L.gru_units; d.n_dense = L.n_dense; d.n_x = L.n_x;
+  for (int l = 0; l < 2; l++) { d.dense_in[l] = L.dense_in[l]; d.dense_out[l] = L.dense_out[l]; d.dense_w[l] = L.dense_w[l]; d.dense_b[l] = L.dense_b[l]; }
+  d.w_ru = L.w_ru; d.b_ru = L.b_ru; d.w_c = L.w_c; d.b_c = L.b_c; d.head_w = L.head_w; d.head_b = L.head_b; d.logstd_off = L.logstd_offset;
+}
+#endif
+
+#ifdef RG_PPO_ABI_VERSION
+// an rg_ppo_config (where rg_ppo.h has been included): every update that takes one checks it alike
+inline bool check_ppo_config(const rg_ppo_config *cfg, std::string &err) {
+  const IntField ints[] = {{"epochs_policy", cfg->epochs_policy, 0, RG_PPO_MAX_EPOCHS}, {"epochs_value", cfg->epochs_value, 0, RG_PPO_MAX_EPOCHS},
+                           {"conv_logpdf", cfg->conv_logpdf, RG_PPO_LOGPDF_EXACT, RG_PPO_LOGPDF_REFERENCE}};
+  const RealField reals[] = {{"policy_lr", &cfg->policy_lr, 1, kNonNegative}, {"value_lr", &cfg->value_lr, 1, kNonNegative}, {"beta1", &cfg->beta1, 1, kBelowOne},
+                             {"beta2", &cfg->beta2, 1, kBelowOne}, {"adam_eps", &cfg->adam_eps, 1, kPositive}, {"kl_target", &cfg->kl_target, 1, kPositive},
+                             {"kl_cutoff_factor", &cfg->kl_cutoff_factor, 1, kNonNegative}, {"kl_cutoff_coef", &cfg->kl_cutoff_coef, 1, kNonNegative}};
+  return check_abi("ppo_cfg.", cfg->abi_version, RG_PPO_ABI_VERSION, err) && check_ints("ppo_cfg.", ints, err) && check_reals("ppo_cfg.", reals, err);
 }
 #endif
 

@@ -396,15 +396,6 @@ struct rg_ppo_handle {
 
 namespace {
 
-bool validate_ppo(const rg_ppo_config *cfg, std::string &err) {
-  const IntField ints[] = {{"epochs_policy", cfg->epochs_policy, 0, RG_PPO_MAX_EPOCHS}, {"epochs_value", cfg->epochs_value, 0, RG_PPO_MAX_EPOCHS},
-                           {"conv_logpdf", cfg->conv_logpdf, RG_PPO_LOGPDF_EXACT, RG_PPO_LOGPDF_REFERENCE}};
-  const RealField reals[] = {{"policy_lr", &cfg->policy_lr, 1, kNonNegative}, {"value_lr", &cfg->value_lr, 1, kNonNegative}, {"beta1", &cfg->beta1, 1, kBelowOne},
-                             {"beta2", &cfg->beta2, 1, kBelowOne}, {"adam_eps", &cfg->adam_eps, 1, kPositive}, {"kl_target", &cfg->kl_target, 1, kPositive},
-                             {"kl_cutoff_factor", &cfg->kl_cutoff_factor, 1, kNonNegative}, {"kl_cutoff_coef", &cfg->kl_cutoff_coef, 1, kNonNegative}};
-  return check_abi("ppo_cfg.", cfg->abi_version, RG_PPO_ABI_VERSION, err) && check_ints("ppo_cfg.", ints, err) && check_reals("ppo_cfg.", reals, err);
-}
-
 int hip_fail(rg_ppo_handle *h, const char *what, hipError_t e) { return hip_fail(h, RG_PPO_ERR_HIP, what, e); }
 int no_device(rg_ppo_handle *h) { return no_device(h, RG_PPO_ERR_NO_DEVICE, "RG_PPO"); }
 int launch_status(rg_ppo_handle *h, const char *what) { return launch_status(h, RG_PPO_ERR_HIP, what); }
@@ -529,7 +520,7 @@ int rg_ppo_create(const rg_policy_config *policy_cfg, const rg_ppo_config *ppo_c
   *out = nullptr;
   char msg[128];
   std::string err;
-  if (!check_policy_config("policy_cfg.", policy_cfg, err) || !validate_ppo(ppo_cfg, err)) { g_create_err = err; return RG_PPO_ERR_INVALID; }
+  if (!check_policy_config("policy_cfg.", policy_cfg, err) || !check_ppo_config(ppo_cfg, err)) { g_create_err = err; return RG_PPO_ERR_INVALID; }
   if (T < 1 || T > RG_POLICY_MAX_T) {
     snprintf(msg, sizeof(msg), "T: %d outside [1, %d]", T, RG_POLICY_MAX_T);
     g_create_err = msg;

@@ -1,23 +1,14 @@
 // rg_rnn.hip -- the recurrent Gaussian policy of include/rg_rnn.h: one tick (rg_rnn_act) and T ticks with the state kept on
 // the chip (rg_rnn_unroll).  Its own translation unit of librg_mpc.so.  The noise stream, the normaliser's arithmetic and the
-// layer descriptor are those of rg_agent_dev.inc and the host helpers those of rg_host.h; rg_mpc.hip includes neither
-// this file nor them, so the source hash behind profiles/ is unaffected.
+// layer descriptor are those of rg_agent_dev.inc, the tick (its tiling, its stages, the fmaf chain) that of rg_gru_dev.inc and
+// the host helpers those of rg_host.h; rg_mpc.hip includes neither this file nor them, so the source hash behind profiles/ is
+// unaffected.
 //
-// A tile of kTile robots per workgroup.  One output neuron per thread with kTile accumulators in registers; the activations
-// of a layer lie in LDS as x[i][robot] (a thread reads the kTile values of input i as two 16-byte broadcasts); the weight
-// W[i][j] is read once per (workgroup, neuron), coalesced along j, and used kTile times.  The sum over i runs in order with
-// explicit fmaf: over the x inputs, then over the h (or r*h) inputs.
-//
-// The policy's tick is policy_stage(s) for s = 0 .. n_dense + 2, a barrier in front of each:
-//   s < n_dense       dense relu layer s, ping-pong between the two x buffers
-//   s = n_dense       the 2H gates: threads 0 .. H-1 leave r*h, threads H .. 2H-1 leave u
-//   s = n_dense + 1   the H candidates; thread j forms h'[j] from its own h[j] and u[j], writes it over h[j] and to memory
-//   s = n_dense + 2   the head from h', into the x buffer the cell did not read
 // rg_rnn_act_kernel: 512 threads, threads 0..255 (waves 0..3) the policy's stages, threads 256..511 (waves 4..7) the value
 // network's layers (rg_policy_act_kernel's neuron, so the value is that kernel's to the bit); every branch on the network is
 // uniform over a wave and both halves meet at the same barriers.  A workgroup reads its robots' rows of hidden_in before
 // the first barrier and writes hidden_out after it: hidden_out may be hidden_in.
-// rg_rnn_unroll_kernel: 256 threads, the same policy_stage calls T times; h stays in LDS between ticks.
+// rg_rnn_unroll_kernel: 256 threads, the same gru_stage calls T times; h stays in LDS between ticks.
 // LDS, floats: act (4 * RG_RNN_MAX_WIDTH + 3 * RG_RNN_MAX_UNITS + RG_RNN_MAX_ACT) * RG_RNN_TILE = 45184 bytes;
 //              unroll (2 * RG_RNN_MAX_WIDTH + 3 * RG_RNN_MAX_UNITS) * RG_RNN_TILE = 28672 bytes, and its copy of the descriptor
 //              (at most 256 bytes).
@@ -35,21 +26,16 @@
 #pragma clang fp contract(off)
 
 #include "rg_agent_dev.inc"
+#include "rg_gru_dev.inc"
 
 namespace {
 
-constexpr int kTile = RG_RNN_TILE;
-constexpr int kMaxW = RG_RNN_MAX_WIDTH;
-constexpr int kMaxH = RG_RNN_MAX_UNITS;
-constexpr int kMaxAct = RG_RNN_MAX_ACT;
 constexpr int kHalf = 256;
 constexpr int kActThreads = 2 * kHalf;
-constexpr int kCols = RG_POLICY_NORM_COLS;
 
-static_assert(kTile == 8, "a neuron reads the activations of an input as two float4");
+static_assert(kHalf == kAgentThreads, "the workgroup that copies the descriptor");
 static_assert(2 * kMaxH <= kHalf && kMaxW <= kHalf, "one output neuron per thread of the policy's half");
 static_assert(kTile * kMaxAct <= 64 && kMaxAct <= kMaxW, "sampling thread map; the head's output fits an x buffer");
-static_assert(RG_RNN_MAX_OBS <= RG_POLICY_MAX_OBS && RG_RNN_MAX_OBS <= kMaxW, "norm_state columns");
 static_assert(RG_RNN_MODE_SAMPLE == RG_POLICY_MODE_SAMPLE && RG_RNN_MODE_MEAN == RG_POLICY_MODE_MEAN, "modes");
 
 struct RnnDev {
@@ -61,94 +47,23 @@ struct RnnDev {
   NetDesc val;
 };
 
-// acc[r] = fma(W[i][j], x[i][r], acc[r]) for i = 0 .. nin-1 in order; W points at W[0][j], stride = the layer's `out`
-__device__ __forceinline__ void chain8(const float *__restrict__ W, const int stride, const float *x, const int nin, float (&acc)[kTile]) {
-#pragma unroll 8
-  for (int i = 0; i < nin; i++) {
-    const float w = W[(size_t)i * stride];
-    const float4 xa = *reinterpret_cast<const float4 *>(x + i * kTile);
-    const float4 xb = *reinterpret_cast<const float4 *>(x + i * kTile + 4);
-    acc[0] = __builtin_fmaf(w, xa.x, acc[0]); acc[1] = __builtin_fmaf(w, xa.y, acc[1]);
-    acc[2] = __builtin_fmaf(w, xa.z, acc[2]); acc[3] = __builtin_fmaf(w, xa.w, acc[3]);
-    acc[4] = __builtin_fmaf(w, xb.x, acc[4]); acc[5] = __builtin_fmaf(w, xb.y, acc[5]);
-    acc[6] = __builtin_fmaf(w, xb.z, acc[6]); acc[7] = __builtin_fmaf(w, xb.w, acc[7]);
-  }
-}
-
-__device__ __forceinline__ float sigmoidf(const float a) { return 1.0f / (1.0f + expf(-a)); }
-
-// observation component i of robot b through the normaliser: float64, rounded to float32 (rg_policy.h, transform)
-__device__ __forceinline__ float normalised(const float *__restrict__ obs, const double *__restrict__ norm, const int i, const int b, const int B,
-                                            const double clip) {
-  double v = (double)obs[(size_t)i * B + b] - norm[kCols + i];
-  v = v / norm_scale(norm[i], norm[2 * kCols + i]);
-  return (float)clip_sym(v, clip);
-}
-
-// stage s of the policy's tick for output neuron j (0 .. 255).  xs: the two x buffers, x0 in xs[0]; hs, rh, us [H][kTile].
-// hout_a, hout_b: where h' goes in memory ([B][H] each), either may be null.
-__device__ __forceinline__ void policy_stage(const RnnDev *d, const float *__restrict__ pp, const int s, const int j, const int b0,
-                                             float (*xs)[kMaxW * kTile], float *hs, float *rh, float *us, float *hout_a, float *hout_b) {
-  const int n_dense = d->n_dense, H = d->H, n_x = d->n_x;
-  float acc[kTile];
-#pragma unroll
-  for (int r = 0; r < kTile; r++) acc[r] = 0.0f;
-  if (s < n_dense) {
-    const int nin = d->dense_in[s], nout = d->dense_out[s];
-    if (j < nout) {
-      chain8(pp + d->dense_w[s] + j, nout, xs[s & 1], nin, acc);
-      const float bias = pp[d->dense_b[s] + j];
-      float *y = xs[(s & 1) ^ 1] + j * kTile;
-#pragma unroll
-      for (int r = 0; r < kTile; r++) {
-        const float v = acc[r] + bias;
-        y[r] = v > 0.0f ? v : 0.0f;
-      }
-    }
-  } else if (s == n_dense) {
-    if (j < 2 * H) {
-      const float *__restrict__ W = pp + d->w_ru + j;
-      chain8(W, 2 * H, xs[n_dense & 1], n_x, acc);
-      chain8(W + (size_t)n_x * 2 * H, 2 * H, hs, H, acc);
-      const float bias = pp[d->b_ru + j];
-      if (j < H) {
-#pragma unroll
-        for (int r = 0; r < kTile; r++) rh[j * kTile + r] = sigmoidf(acc[r] + bias) * hs[j * kTile + r];
-      } else {
-#pragma unroll
-        for (int r = 0; r < kTile; r++) us[(j - H) * kTile + r] = sigmoidf(acc[r] + bias);
-      }
-    }
-  } else if (s == n_dense + 1) {
-    if (j < H) {
-      const float *__restrict__ W = pp + d->w_c + j;
-      chain8(W, H, xs[n_dense & 1], n_x, acc);
-      chain8(W + (size_t)n_x * H, H, rh, H, acc);
-      const float bias = pp[d->b_c + j];
-#pragma unroll
-      for (int r = 0; r < kTile; r++) {
-        const float c = tanhf(acc[r] + bias);
-        const float u = us[j * kTile + r], h = hs[j * kTile + r];
-        const float hn = __builtin_fmaf(u, h, __builtin_fmaf(-u, c, c));
-        hs[j * kTile + r] = hn;   // only this thread reads or writes h[j] in this stage
-        const int b = b0 + r;
-        if (b < d->B) {
-          if (hout_a) hout_a[(size_t)b * H + j] = hn;
-          if (hout_b) hout_b[(size_t)b * H + j] = hn;
-        }
-      }
-    }
-  } else if (s == n_dense + 2) {
-    const int act_dim = d->act_dim;
-    if (j < act_dim) {
-      chain8(pp + d->head_w + j, act_dim, hs, H, acc);
-      const float bias = pp[d->head_b + j];
-      float *y = xs[(n_dense & 1) ^ 1] + j * kTile;
-#pragma unroll
-      for (int r = 0; r < kTile; r++) y[r] = tanhf(acc[r] + bias);
+// what the acting kernels keep of a tick: h' of the tile's robots from b0 on, in memory at hout_a and hout_b ([B][H] each,
+// either may be null)
+struct HiddenSink {
+  const RnnDev *d;
+  int b0;
+  float *hout_a, *hout_b;
+  __device__ __forceinline__ void dense(int, int, int, int, float) const {}
+  __device__ __forceinline__ void reset_gate(int, int, int, float, float) const {}
+  __device__ __forceinline__ void update_gate(int, int, int, float) const {}
+  __device__ __forceinline__ void cell(const int H, const int j, const int r, float, const float hn) const {
+    const int b = b0 + r;
+    if (b < d->B) {
+      if (hout_a) hout_a[(size_t)b * H + j] = hn;
+      if (hout_b) hout_b[(size_t)b * H + j] = hn;
     }
   }
-}
+};
 
 __global__ void __launch_bounds__(kActThreads) rg_rnn_act_kernel(const RnnDev *__restrict__ d, const float *__restrict__ obs,
                                                                  const double *__restrict__ norm, const float *__restrict__ pp,
@@ -184,7 +99,7 @@ __global__ void __launch_bounds__(kActThreads) rg_rnn_act_kernel(const RnnDev *_
   for (int s = 0; s < n_max; s++) {
     __syncthreads();
     if (net == 0) {
-      if (s < n_pol) policy_stage(d, pp, s, j, b0, xp, hs, rh, us, hidden_out, nullptr);
+      if (s < n_pol) gru_stage(d, pp, s, j, xp, hs, rh, us, HiddenSink{d, b0, hidden_out, nullptr});
     } else if (s < n_val) {
       const int nin = d->val.in[s], nout = d->val.out[s];
       if (j < nout) {
@@ -246,10 +161,7 @@ __global__ void __launch_bounds__(kHalf) rg_rnn_unroll_kernel(const RnnDev *__re
                                                               float *__restrict__ hidden_seq, float *hidden_last) {
   // the descriptor from LDS: as scalar registers its fields, live through the loop over t, do not fit beside the pointers
   __shared__ RnnDev dsh;
-  for (int idx = threadIdx.x; idx < (int)(sizeof(RnnDev) / sizeof(int)); idx += kHalf)
-    reinterpret_cast<int *>(&dsh)[idx] = reinterpret_cast<const int *>(dg)[idx];
-  __syncthreads();
-  const RnnDev *d = &dsh;
+  const RnnDev *d = descriptor_to_lds(dg, &dsh);
   __shared__ __attribute__((aligned(16))) float xs[2][kMaxW * kTile];
   __shared__ __attribute__((aligned(16))) float hs[kMaxH * kTile];
   __shared__ __attribute__((aligned(16))) float rh[kMaxH * kTile];
@@ -278,7 +190,7 @@ __global__ void __launch_bounds__(kHalf) rg_rnn_unroll_kernel(const RnnDev *__re
     float *hlast = t == T - 1 ? hidden_last : nullptr;
     for (int s = 0; s < n_pol; s++) {
       __syncthreads();
-      policy_stage(d, pp, s, tid, b0, xs, hs, rh, us, hseq_t, hlast);
+      gru_stage(d, pp, s, tid, xs, hs, rh, us, HiddenSink{d, b0, hseq_t, hlast});
     }
     __syncthreads();
     if (tid < kTile * act_dim) {
@@ -304,44 +216,6 @@ struct rg_rnn_handle {
 
 namespace {
 
-bool validate(const rg_rnn_config *cfg, std::string &err) {
-  const char *prefix = "config.";
-  if (!check_abi(prefix, cfg->abi_version, RG_RNN_ABI_VERSION, err)) return false;
-  if (!check_reserved(prefix, "reserved0", cfg->reserved0, err)) return false;
-  const IntField ints[] = {{"obs_dim", cfg->obs_dim, 1, RG_RNN_MAX_OBS}, {"act_dim", cfg->act_dim, 1, RG_RNN_MAX_ACT},
-                           {"n_policy_layers", cfg->n_policy_layers, 0, RG_RNN_MAX_DENSE}, {"gru_units", cfg->gru_units, 1, RG_RNN_MAX_UNITS},
-                           {"n_value_layers", cfg->n_value_layers, 0, RG_RNN_MAX_VALUE_LAYERS}};
-  const RealField reals[] = {{"obs_clip", &cfg->obs_clip, 1, kNonNegative}};
-  return check_ints(prefix, ints, err) &&
-         check_widths(prefix, "policy_layers", cfg->policy_layers, cfg->n_policy_layers, RG_RNN_MAX_DENSE, RG_RNN_MAX_WIDTH, err) &&
-         check_widths(prefix, "value_layers", cfg->value_layers, cfg->n_value_layers, RG_RNN_MAX_VALUE_LAYERS, RG_RNN_MAX_WIDTH, err) &&
-         check_reals(prefix, reals, err);
-}
-
-void fill_layout(const rg_rnn_config *cfg, rg_rnn_layout &L) {
-  std::memset(&L, 0, sizeof(L));
-  const int H = cfg->gru_units, nd = cfg->n_policy_layers;
-  int off = 0, prev = cfg->obs_dim;
-  for (int l = 0; l < nd; l++) {
-    const int width = cfg->policy_layers[l];
-    L.dense_in[l] = prev; L.dense_out[l] = width;
-    L.dense_w[l] = off; off += prev * width;
-    L.dense_b[l] = off; off += width;
-    prev = width;
-  }
-  L.n_dense = nd; L.n_x = prev; L.gru_units = H;
-  L.w_ru = off; off += (prev + H) * 2 * H;
-  L.b_ru = off; off += 2 * H;
-  L.w_c = off; off += (prev + H) * H;
-  L.b_c = off; off += H;
-  L.head_w = off; off += H * cfg->act_dim;
-  L.head_b = off; off += cfg->act_dim;
-  L.logstd_offset = off;
-  L.policy_count = off + cfg->act_dim;
-  L.n_value = cfg->n_value_layers + 1;
-  L.value_count = layer_layout(cfg->obs_dim, cfg->value_layers, cfg->n_value_layers, 1, L.value_in, L.value_out, L.value_w, L.value_b);
-}
-
 int hip_fail(rg_rnn_handle *h, const char *what, hipError_t e) { return hip_fail(h, RG_RNN_ERR_HIP, what, e); }
 int no_device(rg_rnn_handle *h) { return no_device(h, RG_RNN_ERR_NO_DEVICE, "RG_RNN"); }
 int launch_status(rg_rnn_handle *h, const char *what) { return launch_status(h, RG_RNN_ERR_HIP, what); }
@@ -360,7 +234,7 @@ const char *rg_rnn_last_error(const rg_rnn_handle *h) { return h ? h->err.c_str(
 int rg_rnn_param_layout(const rg_rnn_config *cfg, rg_rnn_layout *out) {
   if (!cfg || !out) { g_create_err = "param_layout: null config or out"; return RG_RNN_ERR_INVALID; }
   std::string err;
-  if (!validate(cfg, err)) { g_create_err = err; return RG_RNN_ERR_INVALID; }
+  if (!check_rnn_config("config.", cfg, err)) { g_create_err = err; return RG_RNN_ERR_INVALID; }
   fill_layout(cfg, *out);
   return RG_RNN_OK;
 }
@@ -369,7 +243,7 @@ int rg_rnn_create(const rg_rnn_config *cfg, int32_t batch, int32_t device, rg_rn
   if (!cfg || !out) { g_create_err = "create: null config or out"; return RG_RNN_ERR_INVALID; }
   *out = nullptr;
   std::string err;
-  if (!check_batch(batch, RG_RNN_MAX_BATCH, err) || !validate(cfg, err)) { g_create_err = err; return RG_RNN_ERR_INVALID; }
+  if (!check_batch(batch, RG_RNN_MAX_BATCH, err) || !check_rnn_config("config.", cfg, err)) { g_create_err = err; return RG_RNN_ERR_INVALID; }
   rg_rnn_handle *h = new rg_rnn_handle();
   h->cfg = *cfg;
   h->B = batch;
@@ -377,9 +251,8 @@ int rg_rnn_create(const rg_rnn_config *cfg, int32_t batch, int32_t device, rg_rn
   fill_layout(cfg, h->lay);
   const rg_rnn_layout &L = h->lay;
   RnnDev &d = h->dv;
-  d.B = batch; d.obs_dim = cfg->obs_dim; d.act_dim = cfg->act_dim; d.H = L.gru_units; d.n_dense = L.n_dense; d.n_x = L.n_x;
-  for (int l = 0; l < 2; l++) { d.dense_in[l] = L.dense_in[l]; d.dense_out[l] = L.dense_out[l]; d.dense_w[l] = L.dense_w[l]; d.dense_b[l] = L.dense_b[l]; }
-  d.w_ru = L.w_ru; d.b_ru = L.b_ru; d.w_c = L.w_c; d.b_c = L.b_c; d.head_w = L.head_w; d.head_b = L.head_b; d.logstd_off = L.logstd_offset;
+  d.B = batch; d.obs_dim = cfg->obs_dim; d.act_dim = cfg->act_dim;
+  layout_to_dev(L, d);
   d.obs_clip = cfg->obs_clip; d.seed = cfg->seed;
   d.val.n = L.n_value;
   for (int l = 0; l < 4; l++) { d.val.in[l] = L.value_in[l]; d.val.out[l] = L.value_out[l]; d.val.w[l] = L.value_w[l]; d.val.b[l] = L.value_b[l]; }

@@ -450,9 +450,10 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
     assert "asm" not in code and "atomic" not in own.lower()
     assert code.index("#pragma clang fp contract(off)") < code.index("__global__")
     assert code.index("#pragma clang fp contract(off)") < code.index("__device__")
-    assert code.index("#pragma clang fp contract(off)") < code.index('#include "rg_agent_dev.inc"')
+    assert code.index("#pragma clang fp contract(off)") < code.index('#include "rg_agent_dev.inc"') < code.index('#include "rg_gru_dev.inc"')
     assert re.findall(r'#include "([^"]+)"', code) == ["../../include/rg_policy.h", "../../include/rg_ppo.h", "../../include/rg_rnn.h",
-                                                      "../../include/rg_bptt.h", "rg_host.h", "rg_agent_dev.inc"]
+                                                      "../../include/rg_bptt.h", "rg_host.h", "rg_agent_dev.inc", "rg_gru_dev.inc"]
+    assert not re.search(r"\b(chain8|sigmoidf)\s*\([^;{]*\)\s*\{", code)         # the tick's device code is rg_gru_dev.inc's alone
     assert len(re.findall(r"__global__", code)) == len(KERNELS)
     import bench
     assert not any("rg_bptt" in rel for rel in bench.compiled_sources())         # the MPC hash behind profiles/ does not follow it

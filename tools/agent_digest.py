@@ -1,9 +1,12 @@
 """One sha256 per output buffer of the agents' update entries at fixed seeds: two builds of librg_mpc.so (RG_MPC_LIB, as
 mpc_abi.LIB_PATH takes it) that print the same lines compute the same bytes.  PPO: policy_grad, value_grad, adam on both
-networks, kl; DDPG: critic_grad, actor_grad, adam on both networks, soft_update on both.  The configurations are the smallest
-of the GPU tests that reach every path of the code the agents' files share: below one tile, one sample past a tile with
-256-wide layers, more tiles than workgroups with a ragged tail.  Every configuration runs in a child process of its own under
-a time limit (`--limit` seconds); after a failure nothing more is started.
+networks, kl; DDPG: critic_grad, actor_grad, adam on both networks, soft_update on both; the recurrent policy: act and
+unroll; its update: policy_grad, kl, adam and the whole policy update.  The configurations are the smallest of the GPU tests
+that reach every path of the code the agents' files share: below one tile, one sample past a tile with 256-wide layers, more
+tiles than workgroups with a ragged tail; for the GRU tick one robot, one robot past a tile of 8, two dense layers (the
+ping-pong buffers and the extra barrier), the header limits and a sample count that is no multiple of the chunk of 16.  Every
+configuration runs in a child process of its own under a time limit (`--limit` seconds); after a failure nothing more is
+started.
 
     RG_MPC_LIB=/path/to/librg_mpc.so python tools/agent_digest.py
 """
@@ -18,6 +21,9 @@ sys.path.insert(0, ROOT)
 
 PPO_CASES = [("lopsided", 3, 5), ("limits", 1, 17), ("default", 5, 1037)]
 DDPG_CASES = [("lopsided", 3, 4, 6, 5), ("limits", 3, 7, 10, 17)]
+RNN_CASES = [("lopsided", 1), ("lopsided", 9), ("two dense", 9), ("limits", 37)]     # (configuration of tests/bptt_cases.py, batch), T = RNN_T
+RNN_T = 3
+BPTT_CASES = [("lopsided", 3, 5), ("two dense", 2, 9), ("limits", 5, 37), ("default", 8, 1037)]
 
 
 def digest(label, tensor):
@@ -63,6 +69,58 @@ def ddpg(*cs):
     a.close()
 
 
+def rnn(name, B):
+    import numpy as np
+    import torch
+    from robot_gym_amd.agents.ppo import RecurrentRolloutBuffer
+    from tests import bptt_cases as BC
+    from tests import test_bptt_gpu as G
+    dev, T, tag = torch.device("cuda", 0), RNN_T, f"rnn {name} T={RNN_T} B={B}"
+    cfg, lay, pp, vp, state, centre, spread = BC.net(name)
+    d, A, H = cfg["obs_dim"], cfg["act_dim"], cfg["gru_units"]
+    rng = np.random.default_rng(B)
+    pol = G._policy(dev, dict(B=B, cfg=cfg, lay=lay, pp=pp, vp=vp, state=state))
+    ro = RecurrentRolloutBuffer(T, B, d, A, H, device=dev)
+    ro.obs.copy_(torch.as_tensor((centre[None, :, None] + spread[None, :, None] * rng.normal(size=(T, d, B)) * 2.5).astype(np.float32)))
+    ro.reset.copy_(torch.as_tensor(BC.resets(T, B, rng)))
+    ro.h0.copy_(torch.as_tensor(rng.uniform(-0.9, 0.9, size=(B, H)).astype(np.float32)))
+    full = lambda *shape: torch.full(shape, 7.0, device=dev)
+    # one sampling tick from h0 under the first tick's resets
+    pol.hidden.copy_(ro.h0), pol.pending_reset.copy_(ro.reset[0])
+    pol.act_state.copy_(torch.as_tensor(np.stack((1000 + 3 * np.arange(B, dtype=np.int64), (np.arange(B, dtype=np.int64) * 7) % 5))))
+    out = pol.act(ro.obs[0], sample=True, out=dict(action=full(B, A), mean=full(B, A), value=full(B), logprob=full(B)))
+    for k in ("action", "mean", "value", "logprob"):
+        digest(f"{tag} act.{k}", out[k])
+    digest(f"{tag} act.hidden_out", pol.hidden), digest(f"{tag} act.act_state", pol.act_state)
+    out = pol.unroll(ro, out=dict(mean=full(T, B, A), hidden_seq=full(T, B, H), hidden_last=full(B, H)))
+    for k in ("mean", "hidden_seq", "hidden_last"):
+        digest(f"{tag} unroll.{k}", out[k])
+    pol.close()
+
+
+def bptt(name, T, B):
+    import torch
+    from robot_gym_amd.agents.ppo import DeviceRecurrentPPO
+    from tests import bptt_cases as BC
+    from tests import test_bptt_gpu as G
+    dev, tag = torch.device("cuda", 0), f"bptt {name} T={T} B={B}"
+    c = BC.case(name, T, B)
+    pol, ro = G._policy(dev, c), G._rollout(dev, c)
+    upd = DeviceRecurrentPPO(pol, T, **c["ppo_kw"])
+    upd.prepare(ro)
+    grad, loss = upd.policy_grad(ro)
+    digest(f"{tag} policy_grad.grad", grad), digest(f"{tag} policy_grad.loss", loss)
+    digest(f"{tag} kl", upd.kl(ro))
+    upd.adam("policy", grad)
+    digest(f"{tag} adam.params", pol.policy_params), digest(f"{tag} adam.opt_state", upd.opt_state)
+    upd.close()
+    upd = DeviceRecurrentPPO(pol, T, epochs_policy=3, epochs_value=0, **c["ppo_kw"])       # update() is then prepare and rg_bptt_update_policy
+    stats = upd.update(ro)
+    digest(f"{tag} update_policy.params", pol.policy_params), digest(f"{tag} update_policy.opt_state", upd.opt_state)
+    digest(f"{tag} update_policy.stats", stats)
+    upd.close(), pol.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--limit", type=int, default=120, help="seconds a configuration's child process may take")
@@ -70,9 +128,9 @@ def main():
     args = ap.parse_args()
     if args.child is not None:
         agent, name, *shape = args.child.split(",")
-        (ppo if agent == "ppo" else ddpg)(name, *[int(v) for v in shape])
+        dict(ppo=ppo, ddpg=ddpg, rnn=rnn, bptt=bptt)[agent](name, *[int(v) for v in shape])
         return 0
-    for cs in [("ppo",) + c for c in PPO_CASES] + [("ddpg",) + c for c in DDPG_CASES]:
+    for cs in [("ppo",) + c for c in PPO_CASES] + [("ddpg",) + c for c in DDPG_CASES] + [("rnn",) + c for c in RNN_CASES] + [("bptt",) + c for c in BPTT_CASES]:
         child = ",".join(str(v) for v in cs)
         res = subprocess.run(["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child", child])
         if res.returncode != 0:                    # a fault, an abort or the time limit: nothing more is started on the GPU
