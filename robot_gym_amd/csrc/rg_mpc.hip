@@ -261,6 +261,8 @@ static int build_devcfg(const rg_mpc_config *c, DevCfg *d, std::string &err) {
   d->alpha = c->conv_alpha_doubled ? 2.0 * c->alpha : c->alpha;   // P = 2 (B'WB + alpha I) is the default form with twice the regulariser
   d->conv_feet_rotation = c->conv_feet_rotation; d->conv_com_height = c->conv_com_height; d->conv_first_latch = c->conv_first_latch; d->conv_window_divide = c->conv_window_divide;
   d->mu = c->mu[0]; d->g = c->gravity;
+  // (the bits the device's own arithmetic gave: it contracts 1 + 2 mu mu into one fma, which the host compiler does not, and divides IEEE)
+  d->proj_kA = 1.0 / fma(2.0 * d->mu, d->mu, 1.0); d->proj_kB = 1.0 / fma(d->mu, d->mu, 1.0);
   for (int i = 0; i < 4; i++) d->mu4[i] = c->mu[i];   // (per leg -- per cone row under conv_friction_rows: read by the MU4 kernel instantiations only)
   d->mu_rows = (c->conv_friction_rows && mu_differ) ? 1 : 0;
   d->fz_min = c->mass * c->gravity * c->fz_min_scale; d->fz_max = c->mass * c->gravity * c->fz_max_scale;

@@ -90,6 +90,8 @@ struct DevCfg {
   const double *body;        // [B][RG_BODY_N] per-robot body rows (rg_mpc_set_body); null: every robot has body_cfg
   double body_cfg[RG_BODY_N]; // the config's body model as one row
   int body_rec;              // 1: the front kernel fills the record's body block (REC_BODY) -- the step runs the MU4 instantiations
+  double proj_kA, proj_kB;   // 1 / (1 + 2 mu^2), 1 / (1 + mu^2) of `mu`: the friction-pyramid projection's constants, divided once on the host (the
+                             // wrench-space ADMM body divided after every sweep; the MU4 instantiations still do, per lane)
 };
 
 struct DevState {

@@ -411,9 +411,12 @@ __device__ __forceinline__ void qp_exact_robot(const DevCfg *__restrict__ c, con
     for (int e = tid; e < LY::LAMC; e += NT) lamc[e] = 0.0;
     __syncthreads();
     cmask = (int)rec[REC_CONTACT];
-    force_space_tables<NC, H, NT, false, MU4>(c, rec, cmask, tid, Bw, TBw, GU, GV, nullptr, nullptr, c1, c2);
+    if constexpr (LY::RANK5) {   // the reflector with B_w, the projected Gram blocks with the linear term's tables: two stages in all
+      force_space_reflector(c, rec, cmask, tid, lds + LY::hv);
+      force_space_tables<NC, H, NT, false, MU4, false>(c, rec, cmask, tid, Bw, TBw, GU, GV, nullptr, nullptr, c1, c2);
+      force_space_rank5<NT, MU4>(c, rec, tid, Bw, TBw, GU, GV, lds + LY::hv);
+    } else force_space_tables<NC, H, NT, false, MU4>(c, rec, cmask, tid, Bw, TBw, GU, GV, nullptr, nullptr, c1, c2);
     __syncthreads();
-    if constexpr (LY::RANK5) force_space_rank5<NT, MU4>(c, rec, cmask, tid, Bw, TBw, GU, GV, lds + LY::hv);
     // ---- my T x T tile of P = 2 (N (x) G_U + S (x) G_V) + alpha I (identity in the padding), and q of the row I own ----
     int lrv = tid >> LG, lcv = tid & (LC - 1);
     asm volatile("" : "+v"(lrv), "+v"(lcv));

@@ -307,7 +307,8 @@ template <> struct FusedShape<20> { static constexpr int LG = 4, T1 = 4; };   //
 // G_U = U' W U, G_V = V' W V (m3 x m3; their periodic extensions when the tile is built by build_tile_kron6) and the two
 // per-variable coefficient tables of the linear term: q_(a,i) = 2 sum_{k >= a} [ c1(k,i) + (k - a + 1/2) c2(k,i) ].
 // cmask: contact mask whose set bits are the NC stance legs, in order.  Ends with a workgroup barrier.
-template <int NC, int H, int NT, bool KRON6, bool MU4 = false>
+// GRAM = false: G_U / G_V are left to the caller (two legs on the rank-5 form: force_space_rank5 writes the projected blocks).
+template <int NC, int H, int NT, bool KRON6, bool MU4 = false, bool GRAM = true>
 __device__ __forceinline__ void force_space_tables(const DevCfg *__restrict__ c, const double *rec, const int cmask, const int tid, double *Bw, double *TBw,
                                                    double *GU, double *GV, double *EU, double *EV, double *c1, double *c2) {
   constexpr int m3 = 3 * NC, N = m3 * H;
@@ -326,6 +327,7 @@ __device__ __forceinline__ void force_space_tables(const DevCfg *__restrict__ c,
     TBw[tid] = rec[REC_INVCP] * b0; TBw[m3 + tid] = b1; TBw[2 * m3 + tid] = rec[REC_TANP] * b0 + b2;
   }
   __syncthreads();
+  if constexpr (GRAM)
   for (int e = tid; e < m3 * m3; e += NT) {
     int i = e / m3, j = e % m3;
     double gu = c->w[6] * Bw[i] * Bw[j] + c->w[7] * Bw[m3 + i] * Bw[m3 + j] + c->w[8] * Bw[2 * m3 + i] * Bw[2 * m3 + j];
@@ -362,30 +364,24 @@ __device__ __forceinline__ void force_space_tables(const DevCfg *__restrict__ c,
 // 1 / (1 + |n_5|) (v'v >= 2: no cancellation) the reflector that maps e_6 to -+n, and Q5 its first five columns,
 //     P^-1 = (I (x) Q5) (alpha I + 2 N (x) Q5' G_U Q5 + 2 S (x) Q5' G_V Q5)^-1 (I (x) Q5') + I (x) n n' / alpha:
 // only a 5 NB x 5 NB matrix is swept (sym6_sweep<.., 5>) and sym5_back_transform puts the sixth direction back.
-// Runs after force_space_tables<2, ..>: overwrites GU / GV with the projected Gram blocks, built from B_w Q5, T B_w Q5 and
-// [I I] Q5 -- so that the dropped sixth row and column are zero by construction, not by cancellation -- and padded to 6 x 6
-// with zeros (sym6_build_kron6 keeps its addresses).  hv (RG_RANK5_HV = 18 doubles, 17 used): v[0..5], beta, 2 - 1 / alpha (what
-// the sweep's result has in the sixth direction of a diagonal block) in hv[0..7], then beta (B_w v), beta (T B_w v),
-// beta ([I I] v), three entries each, in hv[8..16].
+// Two halves around force_space_tables<2, .., GRAM = false>, and no stage of their own (each stage is a barrier and an LDS round
+// trip of a job that nobody overlaps):
+//   force_space_reflector, BEFORE it: the reflector depends on the two stance feet only, so it is built in the stage that builds
+//     B_w / T B_w and published by that stage's barrier.  hv (RG_RANK5_HV doubles, 8 used): v[0..5], beta, 2 - 1 / alpha (what the
+//     sweep's result has in the sixth direction of a diagonal block).
+//   force_space_rank5, AFTER it, next to the linear term's tables: writes GU / GV, the projected Gram blocks, built from B_w Q5,
+//     T B_w Q5 and [I I] Q5 -- so that the dropped sixth row and column are zero by construction, not by cancellation -- and padded
+//     to 6 x 6 with zeros (sym6_build_kron6 keeps its addresses).  Every lane that owns an entry takes the nine projections
+//     beta (B_w v), beta (T B_w v), beta ([I I] v) itself (36 FMAs on broadcast reads; they used to be a stage of nine lanes).
+//     The caller's barrier follows.
 // Coincident feet (or a difference that is not finite) take e = x: any unit e is right there, the null space only grows.
-// Ends with a workgroup barrier.
 constexpr int RG_RANK5_HV = 18;   // doubles of hv (even: what follows it in a layout stays 16-byte aligned)
-static_assert(8 + 9 <= RG_RANK5_HV && RG_RANK5_HV % 2 == 0, "hv holds v, beta, 2 - 1 / alpha and nine projections");
-template <int NT, bool MU4 = false>
-__device__ __forceinline__ void force_space_rank5(const DevCfg *__restrict__ c, const double *rec, const int cmask, const int tid, const double *Bw_, const double *TBw_,
-                                                  double *GU_, double *GV_, double *hv_) {
-  constexpr int m3 = 6;
-  // KEEP the odd forms below; tests/test_kernel_resources.py fails without them.  Whatever is loop-invariant in this helper is
-  // hoisted out of the re-solve kernel's work loop (rg_qp_resolve_kernel) and held in VGPRs across its robots: with M_SQRT1_2,
-  // INFINITY and the LDS addresses as literals that kernel needed 8 VGPRs more (231 -> 239), with a byte compare of i % 3 one
-  // more (LAB_NOTES).  So: every LDS address is one opaque register (a zero the compiler cannot see through) plus a constant;
-  // the only floating-point constants are inline ones (0.5, 1.0, 2.0), which occupy no register -- 1 / sqrt 2 comes out of
-  // v_rsq_f64 and two Newton steps, finiteness is tested as d2 - d2 == 0; i % 3 is made an opaque 32-bit value.
+static_assert(8 <= RG_RANK5_HV && RG_RANK5_HV % 2 == 0, "hv holds v, beta and 2 - 1 / alpha");
+__device__ __forceinline__ void force_space_reflector(const DevCfg *__restrict__ c, const double *rec, const int cmask, const int tid, double *hv_) {
+  // (the odd forms: see force_space_rank5)
   int opaque0 = 0;
   asm volatile("" : "+v"(opaque0));
   double *hv = hv_ + opaque0;
-  const double *Bw = hv + (Bw_ - hv_), *TBw = hv + (TBw_ - hv_);
-  double *GU = hv + (GU_ - hv_), *GV = hv + (GV_ - hv_);
   if (tid < 8) {
     const double *r1 = &rec[REC_FEETW + 3 * nth_leg(cmask, 0)], *r2 = &rec[REC_FEETW + 3 * nth_leg(cmask, 1)];
     double e0 = r1[0] - r2[0], e1 = r1[1] - r2[1], e2 = r1[2] - r2[2];
@@ -404,33 +400,44 @@ __device__ __forceinline__ void force_space_rank5(const DevCfg *__restrict__ c, 
     if (tid == 7) o = 2.0 - 1.0 / c->alpha;
     hv[tid] = o;
   }
-  __syncthreads();
-  if (tid < 9) {
-    const int r = tid % 3;
-    double s;
-    if (tid < 6) {
-      const double *src = (tid < 3 ? Bw : TBw) + r * m3;
-      s = src[0] * hv[0];
-#pragma unroll
-      for (int i = 1; i < m3; i++) s = fma(src[i], hv[i], s);
-    } else s = hv[r] + hv[3 + r];
-    hv[8 + tid] = hv[6] * s;
-  }
-  __syncthreads();
+}
+template <int NT, bool MU4 = false>
+__device__ __forceinline__ void force_space_rank5(const DevCfg *__restrict__ c, const double *rec, const int tid, const double *Bw_, const double *TBw_,
+                                                  double *GU_, double *GV_, double *hv_) {
+  constexpr int m3 = 6;
+  // KEEP the odd forms below; tests/test_kernel_resources.py fails without them.  Whatever is loop-invariant in this helper is
+  // hoisted out of the re-solve kernel's work loop (rg_qp_resolve_kernel) and held in VGPRs across its robots: with M_SQRT1_2,
+  // INFINITY and the LDS addresses as literals that kernel needed 8 VGPRs more (231 -> 239), with a byte compare of i % 3 one
+  // more (LAB_NOTES).  So: every LDS address is one opaque register (a zero the compiler cannot see through) plus a constant;
+  // the only floating-point constants are inline ones (0.5, 1.0, 2.0), which occupy no register -- 1 / sqrt 2 comes out of
+  // v_rsq_f64 and two Newton steps, finiteness is tested as d2 - d2 == 0; i % 3 is made an opaque 32-bit value.
+  int opaque0 = 0;
+  asm volatile("" : "+v"(opaque0));
+  double *hv = hv_ + opaque0;
+  const double *Bw = hv + (Bw_ - hv_), *TBw = hv + (TBw_ - hv_);
+  double *GU = hv + (GU_ - hv_), *GV = hv + (GV_ - hv_);
   for (int e = tid; e < m3 * m3; e += NT) {
     const int i = e / m3, j = e % m3;
     double gu = 0.0, gv = 0.0;
     if (i < 5 && j < 5) {
       const double vi = hv[i], vj = hv[j];
+      double pb[3], pt[3], pe[3];   // beta (B_w v), beta (T B_w v), beta ([I I] v)
+#pragma unroll
+      for (int r = 0; r < 3; r++) {
+        double sb = Bw[r * m3] * hv[0], st = TBw[r * m3] * hv[0];
+#pragma unroll
+        for (int k = 1; k < m3; k++) { sb = fma(Bw[r * m3 + k], hv[k], sb); st = fma(TBw[r * m3 + k], hv[k], st); }
+        pb[r] = hv[6] * sb; pt[r] = hv[6] * st; pe[r] = hv[6] * (hv[r] + hv[3 + r]);
+      }
       const double im2 = body_val<MU4>(c, rec, BODY_INV_MASS) * body_val<MU4>(c, rec, BODY_INV_MASS);
       const double *cw = c->w;
       int ia = i % 3, ja = j % 3;
       asm volatile("" : "+v"(ia), "+v"(ja));   // (32-bit compares against inline constants: a byte compare takes its constant from a register)
 #pragma unroll
       for (int r = 0; r < 3; r++) {
-        const double bi = fma(-hv[8 + r], vi, Bw[r * m3 + i]), bj = fma(-hv[8 + r], vj, Bw[r * m3 + j]);
-        const double ti = fma(-hv[11 + r], vi, TBw[r * m3 + i]), tj = fma(-hv[11 + r], vj, TBw[r * m3 + j]);
-        const double ei = fma(-hv[14 + r], vi, ia == r ? 1.0 : 0.0), ej = fma(-hv[14 + r], vj, ja == r ? 1.0 : 0.0);
+        const double bi = fma(-pb[r], vi, Bw[r * m3 + i]), bj = fma(-pb[r], vj, Bw[r * m3 + j]);
+        const double ti = fma(-pt[r], vi, TBw[r * m3 + i]), tj = fma(-pt[r], vj, TBw[r * m3 + j]);
+        const double ei = fma(-pe[r], vi, ia == r ? 1.0 : 0.0), ej = fma(-pe[r], vj, ja == r ? 1.0 : 0.0);
         gu = fma(cw[6 + r] * bi, bj, fma(cw[9 + r] * im2 * ei, ej, gu));
         gv = fma(cw[r] * ti, tj, fma(cw[3 + r] * im2 * ei, ej, gv));
       }
@@ -439,5 +446,4 @@ __device__ __forceinline__ void force_space_rank5(const DevCfg *__restrict__ c, 
     GU[e] = gu * dt * dt;
     GV[e] = gv * dt * dt * dt * dt;
   }
-  __syncthreads();
 }

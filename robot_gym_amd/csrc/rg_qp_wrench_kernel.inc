@@ -103,6 +103,60 @@ __device__ __forceinline__ bool wrench_admm_vote(const DevCfg *__restrict__ c, c
   return false;
 }
 
+// The vote as qp_wrench_robot takes it on the one-wave grid with uniform friction: the same rules, stores, result and extrapolation
+// as wrench_admm_vote, in another order.  The distance estimates and the primal residual -- three reciprocals behind exec-masked
+// branches, and |x - z| -- can only turn a vote that nobody's movement has decided already, so they are evaluated behind a first
+// ballot on the movement alone: a robot that still iterates, nine votes of ten, never gets there.  xr: the unprojected forces x
+// of this iteration (the primal residual is |xr - zb|).  A function of its own: the schedule bodies' kernels, at the register
+// limit with pinned scratch frames, compile differently when wrench_admm_vote's text changes.
+__device__ __forceinline__ bool wrench_admm_vote_late(const DevCfg *__restrict__ c, const int tid, const bool active, double (&zb)[3], double (&yb)[3], double *zck, double *yst,
+                                                      double *yck, double *dyq, double *sum3, const double (&xr)[3], const double atol, const double etol, const double ptol,
+                                                      const int it, int &hist) {
+  constexpr int NT = 64;
+  double mmax = 0.0, d11 = 0.0, d00 = 0.0, d10 = 0.0, mpk[3];   // mpk: the window before's |movement|, for the estimates
+  const double gst = sum3[12];
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    const double dz = zb[d] - zck[d * NT + tid], dzp = yst[d * NT + tid];
+    const double dy = yb[d] - yck[d * NT + tid], dyp = dyq[d * NT + tid];
+    const double m = fabs(dz), mp = fabs(dzp);
+    mpk[d] = mp;
+    yst[d * NT + tid] = dz; dyq[d * NT + tid] = dy;
+    zck[d * NT + tid] = zb[d]; yck[d * NT + tid] = yb[d];
+    mmax = fmax(mmax, m);
+    if (gst > 0.0 && mp > 4.0 * atol) mmax = INFINITY;   // jumped robots pass only with two consecutive quiet windows
+    d11 = fma(dz, dz, fma(dy, dy, d11));
+    if (hist >= 1) { d00 = fma(dzp, dzp, fma(dyp, dyp, d00)); d10 = fma(dz, dzp, fma(dy, dyp, d10)); }
+  }
+  if (__ballot((active && mmax > atol) || (gst > 0.0 && hist <= 0)) == 0ull) {   // nobody's movement keeps the robot going: the estimates and |x - z| decide
+    const double rfac = gst > 0.0 ? fmax(gst, sum3[13]) : 0.0;   // the extra distance estimates apply to robots that have jumped in this stage
+    double emax = 0.0, pr = 0.0;
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+      const double m = fabs(yst[d * NT + tid]), mp = mpk[d];   // (yst: this window's movement, stored above)
+      emax = fmax(emax, fmax((mp > m && mp < 1.0e300) ? m * m * fast_rcp(mp - m) : 0.0, m * rfac));   // first window, or not shrinking: no per-entry estimate
+      pr = fmax(pr, fabs(xr[d] - zb[d]));
+    }
+    if (__ballot(active && (emax > etol || pr > ptol)) == 0ull) return true;
+  }
+  if (hist >= 1 && c->accel_from > 0 && it + 1 >= c->accel_from) {   // dominant-mode rate / extrapolation of (z, y)
+    sum3_collect<NT>(d11, d00, d10, sum3);
+    const double g = extrapolation_gain(c->accel_k, d11, d00, d10);
+    const bool jump = __builtin_amdgcn_readfirstlane(g > 0.0);   // same g in every lane: keep the branch (and hist) scalar
+    if (tid == 0) { sum3[13] = jump ? 0.0 : remaining_distance_factor(c->accel_k, d11, d00, d10); if (jump) sum3[12] = fmax(gst, g); }
+    if (jump) {
+#pragma unroll
+      for (int d = 0; d < 3; d++) {
+        zb[d] = fma(g, yst[d * NT + tid], zb[d]); yb[d] = fma(g, dyq[d * NT + tid], yb[d]);
+        zck[d * NT + tid] = zb[d]; yck[d * NT + tid] = yb[d];
+      }
+      hist = -1;
+    }
+  }
+  hist++;
+  return false;
+}
+
 // LDS of qp_wrench_robot (doubles).  What lives through the stages comes first; the rest is set-up data and per-stage state, and
 // on the one-wave grid -- where the matrix is swept with every 6 x 6 block held once (rg_qp_sym6.inc) -- the staging area of the
 // move into the 8 x 8 tiles covers all of it (nothing there is live at that moment: the iterate of a robot that goes into its
@@ -347,7 +401,9 @@ __device__ __forceinline__ void qp_wrench_robot(const DevCfg *__restrict__ c, co
     const int ubase0 = L.ubase0, ubase1 = L.ubase1;   // u6 rows 0..2 and 3..5 in this lane's order
     // friction coefficient of this block lane's leg and the projection's constants (one scalar set unless MU4)
     const double mu = leg_mu<MU4>(c, rec, MU4 ? nth_leg(cmask, bj) : 0);
-    const double kA = 1.0 / (1.0 + 2.0 * mu * mu), kB = 1.0 / (1.0 + mu * mu);
+    double kA, kB;
+    if constexpr (MU4) { kA = 1.0 / (1.0 + 2.0 * mu * mu); kB = 1.0 / (1.0 + mu * mu); }
+    else { kA = c->proj_kA; kB = c->proj_kB; }   // uniform friction: divided once, when the configuration was uploaded
     // (the constant terms qh[rA], qh[rB], qh[io] are re-read from LDS inside the loop: three more LDS reads per
     // iteration cost less than the scratch reloads six more live VGPRs caused)
     double yb[3] = {0.0, 0.0, 0.0};
@@ -404,7 +460,8 @@ __device__ __forceinline__ void qp_wrench_robot(const DevCfg *__restrict__ c, co
       const double tw = tile_matvec<T, LG>(tile, vv, lr, lc);   // (a I + K')^-1 w
       if (own_real) uv[io] = fma(-(vv[iov_pad] + qh[io]), inv_aa, tw);
       __syncthreads();
-      double pres = 0.0;
+      constexpr bool LATE = NT == 64 && !MU4;   // wrench_admm_vote_late: the vote looks at the estimates and at |x - z| only when the movement leaves it open
+      double pres = 0.0, xr[3] = {0.0, 0.0, 0.0};
       const bool vote_now = atol > 0.0 && it + 1 == next_chk;   // uniform: the primal residual is only needed on vote iterations
       if (blk_real) {
         const double u6[6] = {uv[ubase0], uv[ubase0 + 1], uv[ubase0 + 2], uv[ubase1], uv[ubase1 + 1], uv[ubase1 + 2]};
@@ -419,13 +476,17 @@ __device__ __forceinline__ void qp_wrench_robot(const DevCfg *__restrict__ c, co
         const double w2 = relax * x[2] + (1.0 - relax) * zb[2] + yb[2];
         double px, py, pz;
         proj_pyramid(w0, w1, w2, mu, lo, hi, kA, kB, px, py, pz);
-        if (vote_now) pres = fmax(fmax(fabs(x[0] - px), fabs(x[1] - py)), fabs(x[2] - pz));   // primal residual |x - z|
+        if constexpr (LATE) { xr[0] = x[0]; xr[1] = x[1]; xr[2] = x[2]; }
+        else if (vote_now) pres = fmax(fmax(fabs(x[0] - px), fabs(x[1] - py)), fabs(x[2] - pz));   // primal residual |x - z|
         yb[0] = w0 - px; yb[1] = w1 - py; yb[2] = w2 - pz;
         zb[0] = px; zb[1] = py; zb[2] = pz;
       }
       if (vote_now) {
         next_chk += chk;
-        if (wrench_admm_vote<NT>(c, tid, blk_real, zb, yb, zck, yst, yck, dyq, sum3, pres, atol, etol, ptol, it, hist)) { it++; converged = true; break; }
+        bool done;
+        if constexpr (LATE) done = wrench_admm_vote_late(c, tid, blk_real, zb, yb, zck, yst, yck, dyq, sum3, xr, atol, etol, ptol, it, hist);
+        else done = wrench_admm_vote<NT>(c, tid, blk_real, zb, yb, zck, yst, yck, dyq, sum3, pres, atol, etol, ptol, it, hist);
+        if (done) { it++; converged = true; break; }
       }
     }
     if (!converged && atol > 0.0 && it < c->admm_iters) {   // second stage
