@@ -1,0 +1,107 @@
+/*
+ * rg_scan.h -- C-ABI of the terrain height scan of librg_mpc.so: an elevation sensor for the robots of the batched
+ * single-rigid-body simulator (rg_srb.h).  A fixed nx x ny grid of points in the robot's YAW frame (x forward), the height
+ * of the body above the ground under each point, written straight into rows of a component-major float32 observation.
+ *
+ * It is a height SAMPLE, not a ray: nothing occludes, there is no sensor noise or dropout, and roll and pitch do not tilt
+ * the grid.  The ground is the simulator's own ground function (rg_srb.h, "Terrain"): the work per point is fixed.
+ *
+ * Conventions (those of rg_episode.h)
+ *   - return 0 on success, a negative rg_scan_status otherwise; nothing throws across the ABI; rg_scan_last_error() gives
+ *     the text of the last failure on a handle (or of create(), with a NULL handle).
+ *   - the CALLER owns every buffer (device memory), the terrain's key and heights included.  The handle holds the
+ *     configuration and the terrain's descriptor.
+ *   - all work is enqueued on the hipStream_t passed in (NULL = default stream); NO call synchronises or stages anything.
+ *   - one handle per (device, stream); calls on one handle are not thread-safe.  Every call leaves the calling thread's
+ *     current HIP device as it found it.
+ *
+ * Arithmetic, per robot b and point k = a * ny + c_ (grid node (a, c_), 0 <= a < nx, 0 <= c_ < ny).  IEEE float64,
+ * floating-point contraction off, every expression evaluated left to right as written; (px, py, pz) are rows 0..2 and
+ * (qx, qy, qz, qw) rows 3..6 of the simulator's state:
+ *      c0 = 1 - 2*(qy*qy + qz*qz);  s0 = 2*(qx*qy + qz*qw);  n = sqrt(c0*c0 + s0*s0)
+ *      (c, s) = n > 0 ? (c0/n, s0/n) : (1, 0)                                   a NaN n gives (1, 0)
+ *      fx = x_first + a*dx;  fy = y_first + c_*dy                                a, c_ converted to double
+ *      X = px + (c*fx - s*fy);  Y = py + (s*fx + c*fy)
+ *      h = ground(b, X, Y)                                                       rg_srb.h; on the plane the literal 0.0
+ *      d = (pz - z_offset) - h;   clip > 0:  d = fmin(fmax(d, -clip), clip)      a NaN becomes -clip
+ *      out[k][b] = (float)(d * scale)
+ *   There is no trigonometric call: the heading is the normalised first column of the body's rotation, and sqrt and the
+ *   divisions are correctly rounded, so tests/scan_model.py restates this in numpy bit for bit.  A fallen robot is scanned
+ *   like any other; its state is frozen, so its scan is too.
+ *
+ * Launch: one kernel, one lane per robot (consecutive lanes, consecutive robots: the row stores and the state-row loads
+ * coalesce).  A lane loads its robot's seven pose values once and walks a slice of the points; how the points are split
+ * over the grid's second dimension is a function of the configuration and the batch alone, and no output depends on it.
+ */
+#ifndef RG_SCAN_H
+#define RG_SCAN_H
+
+#include <stdint.h>
+#include "rg_srb.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define RG_SCAN_ABI_VERSION 1
+#define RG_SCAN_MAX_POINTS 256
+#define RG_SCAN_MAX_BATCH (1 << 24)
+#define RG_SCAN_DEVICE_NONE (-1) /* create(): a host-only handle, see rg_scan_create */
+
+typedef enum {
+  RG_SCAN_OK = 0,
+  RG_SCAN_ERR_INVALID = -1,   /* bad argument / configuration (the text names the field) */
+  RG_SCAN_ERR_HIP = -2,       /* HIP runtime error (text in last_error) */
+  RG_SCAN_ERR_NO_DEVICE = -3, /* no usable GPU */
+  RG_SCAN_ERR_ALLOC = -4
+} rg_scan_status;
+
+/* The defaults are those of robot_gym_amd/core/scan_abi.py. */
+typedef struct {
+  int32_t abi_version;   /* RG_SCAN_ABI_VERSION */
+  int32_t nx;            /* 8     points along x (forward); >= 1 */
+  int32_t ny;            /* 6     points along y (left); >= 1; nx * ny <= RG_SCAN_MAX_POINTS */
+  int32_t reserved0;     /* must be 0 */
+  double x_first;        /* -0.2  x of the first row of points, m, yaw frame; finite */
+  double dx;             /* 0.1   spacing along x, m; finite */
+  double y_first;        /* -0.25 */
+  double dy;             /* 0.1 */
+  double z_offset;       /* nominal body height, m (Python: the MPCConfig's body_height); finite */
+  double clip;           /* 1.0   the distance is clipped to [-clip, clip]; >= 0, 0 = no clipping */
+  double scale;          /* 1.0   output scale; finite */
+  int32_t reserved1;     /* must be 0 */
+  int32_t reserved2;     /* must be 0 */
+} rg_scan_config;
+
+typedef struct rg_scan_handle rg_scan_handle;
+
+/* Validates cfg (abi_version, reserved words, nx, ny, nx * ny, finite reals, clip >= 0) and batch
+ * (1 .. RG_SCAN_MAX_BATCH) BEFORE it looks for a device.  The new handle scans the plane.  device = RG_SCAN_DEVICE_NONE
+ * makes a host-only handle: every later call checks its arguments (RG_SCAN_ERR_INVALID, naming the argument) and, where
+ * they are valid, returns RG_SCAN_ERR_NO_DEVICE. */
+int rg_scan_create(const rg_scan_config *cfg, int32_t batch, int32_t device, rg_scan_handle **out);
+void rg_scan_destroy(rg_scan_handle *h);
+const char *rg_scan_last_error(const rg_scan_handle *h);   /* h may be NULL: the last create() failure of this thread */
+int32_t rg_scan_abi_version(void);
+int32_t rg_scan_config_size(void);
+
+/* The ground the handle scans: the terrain the simulator was given (rg_srb_set_terrain), validated by
+ * rg_srb_terrain_check, whose text is passed on, before anything changes.  NULL or kind 0: the plane.  key and heights
+ * stay the caller's and must stay alive while the terrain is set; key has one entry per robot of this handle's batch. */
+int rg_scan_set_terrain(rg_scan_handle *h, const rg_srb_terrain *t);
+
+/* The scan described at the top of this file.  Device pointers:
+ *   sim_state  float64 [RG_SRB_STATE_ROWS][B]   the simulator's state
+ *   mask       int32 [B], or NULL               which robots (NULL: all)
+ *   out        float32 [nx * ny][B]             component-major with row stride B: it may point at a row of a taller
+ *                                               observation buffer
+ *   prev       as out, or NULL; must not overlap out
+ * For a robot b with mask[b] != 0 and every point k: where prev is given, prev[k][b] first takes the value out[k][b] held
+ * before the call; then out[k][b] is written.  A robot outside the mask is touched in neither buffer. */
+int rg_scan_observe(rg_scan_handle *h, const double *sim_state, const int32_t *mask, float *out, float *prev, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RG_SCAN_H */

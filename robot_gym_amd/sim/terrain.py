@@ -32,6 +32,13 @@ class RandomTerrain:
             if tuple(k.shape) != (batch,):
                 raise ValueError(f"RandomTerrain: keys must be [{batch}], got {list(k.shape)}")
             self.keys = k.to(device).contiguous()
+        return self.descriptor()
+
+    def descriptor(self):
+        """The srb_abi.CTerrain of the bound terrain: it names the `keys` tensor bind() made, so whoever takes it (the simulator,
+        a HeightScan) reads the same worlds."""
+        if self.keys is None:
+            raise RuntimeError("RandomTerrain: not bound yet (a simulator's set_terrain binds it)")
         return srb_abi.make_cterrain(srb_abi.TERRAIN_RANDOM, cell=self.cell, amplitude=self.amplitude, seed=self.seed, key=self.keys.data_ptr())
 
 
@@ -52,6 +59,12 @@ class GridTerrain:
 
     def bind(self, batch, device):
         self.heights = self._heights_host.to(device).contiguous()
+        return self.descriptor()
+
+    def descriptor(self):
+        """The srb_abi.CTerrain of the bound terrain: it names the `heights` tensor bind() made."""
+        if self.heights is None:
+            raise RuntimeError("GridTerrain: not bound yet (a simulator's set_terrain binds it)")
         rows, cols = self.heights.shape
         return srb_abi.make_cterrain(srb_abi.TERRAIN_GRID, cell=self.cell, heights=self.heights.data_ptr(), rows=rows, cols=cols,
                                      x0=self.origin[0], y0=self.origin[1])
