@@ -1,6 +1,6 @@
 // rg_agent_dev.inc -- the device code that rg_policy.hip, rg_ppo.hip and rg_ddpg.hip share: the noise stream, the observation
 // transform's arithmetic, the workgroup sums, a layer's forward and backward pass over a tile of 16 samples, and the
-// per-element bodies of the transpose and slab-finish kernels.  The GPU tests demand that the three agree to the bit
+// per-element bodies of the transpose, slab-finish and Adam kernels.  The GPU tests demand that the three agree to the bit
 // (the update's forward mean is rg_policy_act's, DDPG's noise is the policy's stream), so each of these exists once.
 // Included after the including file's `#pragma clang fp contract(off)`: a product and a sum stay two roundings, and every
 // fused multiply-add below is an explicit __builtin_fmaf.  Device functions and plain structs only, no kernel: what is not
@@ -203,12 +203,34 @@ __device__ __forceinline__ float slab_sum(const float *__restrict__ slabs, const
   return (float)s;
 }
 
-// Not here: the Adam arithmetic, which rg_ppo_adam_kernel, rg_ddpg_adam_kernel and the recurrent update's Adam kernel write
-// out in the same words.  As a shared function it moved a load in rg_ppo_adam_kernel and raised its VGPRs from 33 to 34
-// (profiles/agents_isa_identity.txt).
-// Not here either: the Gaussian head of rg_ppo.h, written out in rg_ppo.hip's sweep and in the recurrent update's head.  As
-// one templated function with lambdas for the mean's load and the delta's store it took rg_ppo_policy_forward_kernel from
-// 94 to 114 VGPRs and from 5 to 4 waves per SIMD, and rg_ppo_policy_backward_kernel from 156 to 157 VGPRs, to save 40 lines.
-// The GRU tick that the recurrent policy's acting kernels and its update share is rg_gru_dev.inc, included after this file.
+// Adam, as the three updates' Adam kernels run it (torch.optim.Adam's order): the bias corrections of the step after `step`
+// updates, the same for every element, then element e with gradient gg (DDPG's clips it first): moments in float32, the
+// parameter's move in float64.  Cfg is the kernel's own argument struct: its lr, b1, b2 and eps are read where they are used.
+// The corrections are formed before a kernel loads its gradient, as each kernel's own text had it: with the load as an
+// argument in front of the two pow, rg_ppo_adam_kernel took 34 VGPRs for 33.
+struct AdamBias { double bc1, bc2s; };
+
+template <typename Cfg>
+__device__ __forceinline__ AdamBias adam_bias(const Cfg &c, const long long step) {
+  const double t = (double)(step + 1);
+  return AdamBias{1.0 - pow(c.b1, t), sqrt(1.0 - pow(c.b2, t))};
+}
+
+template <typename Cfg>
+__device__ __forceinline__ void adam_element(const Cfg &c, const AdamBias &bias, const float gg, float *p, float *m, float *v, const int e) {
+  const float b1 = (float)c.b1, b2 = (float)c.b2, o1 = (float)(1.0 - c.b1), o2 = (float)(1.0 - c.b2);
+  const float t1 = b1 * m[e], t2 = o1 * gg;
+  const float mn = t1 + t2;
+  const float t3 = b2 * v[e], t4 = gg * gg;
+  const float t5 = o2 * t4;
+  const float vn = t3 + t5;
+  m[e] = mn;
+  v[e] = vn;
+  const double denom = sqrt((double)vn) / bias.bc2s + c.eps;
+  p[e] = (float)((double)p[e] - (c.lr / bias.bc1) * (double)mn / denom);
+}
+
+// The Gaussian head of rg_ppo.h, which the two PPO updates share, is rg_ppo_dev.inc, and the GRU tick that the recurrent
+// policy's acting kernels and its update share is rg_gru_dev.inc; both are included after this file.
 
 }  // namespace

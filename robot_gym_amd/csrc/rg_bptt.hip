@@ -1,7 +1,9 @@
 // rg_bptt.hip -- the recurrent PPO policy update of include/rg_bptt.h: back-propagation through time through the GRU cell of
 // rg_rnn.h, with the head, Adam and the penalty rule of rg_ppo.h.  Its own translation unit of librg_mpc.so.  The normaliser's
-// arithmetic, the workgroup sums and the transpose body are those of rg_agent_dev.inc and the host helpers those of rg_host.h;
-// rg_mpc.hip includes neither this file nor them, so the source hash behind profiles/ is unaffected.  The tick lives in
+// arithmetic, the workgroup sums, the transpose body and Adam's arithmetic are those of rg_agent_dev.inc; the Gaussian head of
+// a sample, the robot-KL element, the loss finish and the penalty rule are those of rg_ppo_dev.inc, the text rg_ppo.hip runs
+// (StoredHead is this file's view of a sample); the host helpers are those of rg_host.h.  rg_mpc.hip includes neither this
+// file nor them, so the source hash behind profiles/ is unaffected.  The tick lives in
 // rg_gru_dev.inc, which the acting kernels run too: the forward pass here is that code with a sink that keeps everything, so
 // its means are the rollout's to the bit.
 //
@@ -40,6 +42,7 @@
 
 #include "rg_agent_dev.inc"
 #include "rg_gru_dev.inc"
+#include "rg_ppo_dev.inc"
 
 namespace {
 
@@ -48,13 +51,13 @@ constexpr int kChunk = RG_BPTT_CHUNK;
 constexpr int kRows = RG_BPTT_ROWS;
 constexpr int kMaxGroups = RG_BPTT_MAX_GROUPS;
 constexpr int kMaxParts = 256;       // workgroups of the head kernel, at most
-constexpr int kPart = 1 + kMaxAct;   // per workgroup of the head kernel: the loss sum, then the logstd gradient
+constexpr int kPart = kHeadPart;     // per workgroup of the head kernel: the loss sum, then the logstd gradient
 constexpr int kBlocks = RG_RNN_MAX_DENSE + 3;
 
 static_assert(2 * kMaxH <= kThreads && kMaxW <= kThreads, "one output neuron, one column of a block per thread");
 static_assert(kTile * kMaxAct <= kThreads && kMaxAct <= kMaxW, "the mean's thread map; the head's output fits an x buffer");
 static_assert(kChunk * kRows == kThreads && kRows % 4 == 0, "a thread stages one input of a chunk; rows are read as float4");
-static_assert(kMaxParts <= kThreads && kMaxAct == RG_POLICY_MAX_ACT, "strided sums; the head's arrays");
+static_assert(kMaxParts <= kThreads && kMaxAct == kHeadAct, "strided sums; the head's arrays");
 static_assert(RG_RNN_MAX_DENSE == 2, "the delta pass has two dense delta buffers and the transpose four blocks");
 
 struct WBlock {                // one block of policy_params for the W phase
@@ -154,61 +157,26 @@ __global__ void __launch_bounds__(kThreads) rg_bptt_forward_kernel(const BpttDev
 
 // ---- H: the head, float64 --------------------------------------------------------------------------------------------------
 
-// sample n of rg_ppo.h's policy loss.  kBackward false: kls[n]; true: delta_mean[n], and the sample's terms of the loss and of
-// the logstd gradient are added to loss and gls.
+// gaussian_head's view of sample n: the new mean from the workspace, where the forward pass left it, the delta beside it
+struct StoredHead {
+  const BpttDev *d;
+  __device__ __forceinline__ const BpttDev &cfg() const { return *d; }
+  __device__ __forceinline__ int mask(const int n) const { return d->mask[n]; }
+  __device__ __forceinline__ float logstd0(const int k) const { return d->logstd0[k]; }
+  __device__ __forceinline__ float mean(const int n, const int k) const { return d->mean[(size_t)n * d->act_dim + k]; }
+  __device__ __forceinline__ float mean0(const int n, const int k) const { return d->mean0[(size_t)n * d->act_dim + k]; }
+  __device__ __forceinline__ float action(const int n, const int k) const { return d->action[(size_t)n * d->act_dim + k]; }
+  __device__ __forceinline__ float adv(const int n) const { return d->adv[n]; }
+  __device__ __forceinline__ const double *scal() const { return d->scal; }
+  __device__ __forceinline__ double robot_kl(const int b) const { return d->klr[b]; }
+  __device__ __forceinline__ double penalty() const { return *d->penalty; }
+  __device__ __forceinline__ void keep_kl(const int n, const double v) const { d->kls[n] = v; }
+  __device__ __forceinline__ void keep_delta(const int n, const int k, const float v) const { d->dmean[(size_t)n * d->act_dim + k] = v; }
+};
+
 template <bool kBackward>
 __device__ __forceinline__ void head_sample(const BpttDev *__restrict__ d, const float *__restrict__ P, const int n, double &loss, double (&gls)[kMaxAct]) {
-  const int act_dim = d->act_dim;
-  const bool valid = d->mask[n] != 0;
-  const double inv = 1.0 / ((double)d->T * (double)d->B);
-  double kl = 0.0, lp = 0.0, lp0 = 0.0;
-  double z[kMaxAct], D[kMaxAct], q[kMaxAct], sg[kMaxAct], mu[kMaxAct];
-#pragma unroll
-  for (int k = 0; k < kMaxAct; k++) {
-    z[k] = D[k] = q[k] = mu[k] = 0.0;
-    sg[k] = 1.0;
-    if (k < act_dim) {
-      const double ls = (double)P[d->logstd_off + k], ls0 = (double)d->logstd0[k];
-      const double s1 = exp(ls), s0 = exp(ls0);
-      const double m1 = (double)d->mean[(size_t)n * act_dim + k], m0 = (double)d->mean0[(size_t)n * act_dim + k];
-      const double dk = m1 - m0;
-      const double qk = (s0 * s0 + dk * dk) / (s1 * s1);
-      kl = kl + ((qk - 1.0) + 2.0 * (ls - ls0));
-      if (kBackward) {
-        const double a = (double)d->action[(size_t)n * act_dim + k];
-        const double zk = (a - m1) / s1, z0 = (a - m0) / s0;
-        lp = lp + (-d->c * ls - 0.5 * (zk * zk));
-        lp0 = lp0 + (-d->c * ls0 - 0.5 * (z0 * z0));
-        z[k] = zk;
-      }
-      D[k] = dk; q[k] = qk; sg[k] = s1; mu[k] = m1;
-    }
-  }
-  kl = 0.5 * kl;
-  if (!kBackward) {
-    d->kls[n] = valid ? kl : 0.0;
-  } else {
-    double ratio = 0.0, advn = 0.0, gb = 0.0;
-    if (valid) {
-      ratio = exp(lp - lp0);
-      advn = ((double)d->adv[n] - d->scal[1]) / d->scal[2];
-      const double klb = d->klr[n % d->B];
-      gb = *d->penalty + (klb > d->thr ? 2.0 * d->coef * (klb - d->thr) : 0.0);
-      loss = loss + ratio * advn;
-    }
-#pragma unroll
-    for (int k = 0; k < kMaxAct; k++) {
-      if (k < act_dim) {
-        float dlt = 0.0f;
-        if (valid) {
-          const double dmu = (-advn * ratio * z[k] / sg[k] + gb * D[k] / (sg[k] * sg[k])) * inv;
-          dlt = (float)(dmu * (1.0 - mu[k] * mu[k]));
-          gls[k] = gls[k] + (-advn * ratio * (z[k] * z[k] - d->c) + gb * (1.0 - q[k])) * inv;
-        }
-        d->dmean[(size_t)n * act_dim + k] = dlt;
-      }
-    }
-  }
+  gaussian_head<kBackward>(StoredHead{d}, P, n, true, 1.0 / ((double)d->T * (double)d->B), loss, gls);
 }
 
 __global__ void __launch_bounds__(kThreads) rg_bptt_sample_kl_kernel(const BpttDev *__restrict__ d, const float *__restrict__ P) {
@@ -220,11 +188,7 @@ __global__ void __launch_bounds__(kThreads) rg_bptt_sample_kl_kernel(const BpttD
 
 // KL_b = (sum_t kls[t][b]) / T, t in order
 __global__ void __launch_bounds__(kThreads) rg_bptt_robot_kl_kernel(const int T, const int B, const double *__restrict__ kls, double *__restrict__ out) {
-  const int b = blockIdx.x * kThreads + (int)threadIdx.x;
-  if (b >= B) return;
-  double s = 0.0;
-  for (int t = 0; t < T; t++) s = s + kls[(size_t)t * B + b];
-  out[b] = s / (double)T;
+  robot_kl_element(T, B, kls, out, blockIdx.x * kThreads + (int)threadIdx.x);
 }
 
 __global__ void __launch_bounds__(kThreads) rg_bptt_head_kernel(const BpttDev *__restrict__ d, const float *__restrict__ P) {
@@ -242,36 +206,11 @@ __global__ void __launch_bounds__(kThreads) rg_bptt_head_kernel(const BpttDev *_
   }
 }
 
-struct LossCfg {
-  int T, B, P, act_dim, logstd_off, pad0;
-  double thr, coef;
-};
-
 __global__ void __launch_bounds__(kThreads) rg_bptt_loss_finish_kernel(const LossCfg c, const double *__restrict__ part, const double *__restrict__ klr,
                                                                        const double *__restrict__ penalty, float *__restrict__ grad,
                                                                        double *__restrict__ loss_out, double *__restrict__ loss_out2) {
   __shared__ double sh[4];
-  const double s1 = strided_sum(part, c.P, kPart, sh);
-  const double inv = 1.0 / ((double)c.T * (double)c.B);
-  const double pen = *penalty;
-  double s2 = 0.0;
-  for (int b = threadIdx.x; b < c.B; b += kThreads) {
-    const double k = klr[b], over = k - c.thr;
-    s2 = s2 + (pen * k + (k > c.thr ? c.coef * (over * over) : 0.0));
-  }
-  s2 = block_sum(s2, sh);
-  const double loss = -(s1 * inv) + s2 / (double)c.B;
-#pragma unroll
-  for (int k = 0; k < kMaxAct; k++) {
-    if (k < c.act_dim) {   // uniform
-      const double gk = strided_sum(part + 1 + k, c.P, kPart, sh);
-      if (threadIdx.x == 0) grad[c.logstd_off + k] = (float)gk;
-    }
-  }
-  if (threadIdx.x == 0) {
-    *loss_out = loss;
-    if (loss_out2) *loss_out2 = loss;
-  }
+  loss_finish(c, c.parts, true, part, klr, penalty, grad, loss_out, loss_out2, sh);
 }
 
 // ---- B: the delta pass -----------------------------------------------------------------------------------------------------
@@ -467,30 +406,14 @@ __global__ void __launch_bounds__(kThreads) rg_bptt_grad_finish_kernel(const int
   grad[e] = (float)s;
 }
 
-// ---- Adam and the penalty (rg_ppo.hip's arithmetic) --------------------------------------------------------------------------
-
-struct AdamCfg {
-  int count, pad0;
-  double lr, b1, b2, eps;
-};
+// ---- Adam and the penalty ----------------------------------------------------------------------------------------------------
 
 __global__ void __launch_bounds__(kThreads) rg_bptt_adam_kernel(const AdamCfg c, float *__restrict__ p, const float *__restrict__ grad,
                                                                 float *__restrict__ m, float *__restrict__ v, const long long *__restrict__ step) {
   const int e = blockIdx.x * kThreads + (int)threadIdx.x;
   if (e >= c.count) return;
-  const double t = (double)(*step + 1);
-  const double bc1 = 1.0 - pow(c.b1, t), bc2s = sqrt(1.0 - pow(c.b2, t));
-  const float b1 = (float)c.b1, b2 = (float)c.b2, o1 = (float)(1.0 - c.b1), o2 = (float)(1.0 - c.b2);
-  const float gg = grad[e];
-  const float t1 = b1 * m[e], t2 = o1 * gg;
-  const float mn = t1 + t2;
-  const float t3 = b2 * v[e], t4 = gg * gg;
-  const float t5 = o2 * t4;
-  const float vn = t3 + t5;
-  m[e] = mn;
-  v[e] = vn;
-  const double denom = sqrt((double)vn) / bc2s + c.eps;
-  p[e] = (float)((double)p[e] - (c.lr / bc1) * (double)mn / denom);
+  const AdamBias bias = adam_bias(c, *step);
+  adam_element(c, bias, grad[e], p, m, v, e);
 }
 
 __global__ void rg_bptt_adam_count_kernel(long long *__restrict__ step) {
@@ -503,13 +426,10 @@ __global__ void __launch_bounds__(kThreads) rg_bptt_penalty_kernel(const int B, 
   __shared__ double sh[4];
   const double s = strided_sum(klr, B, 1, sh);
   if (threadIdx.x == 0) {
-    const double change = s / (double)B;
-    double pen = *penalty;
-    if (change > 1.3 * target) pen = pen * 1.5;
-    else if (change < 0.7 * target) pen = pen / 1.5;
-    *penalty = pen;
-    stats[0] = change;
-    stats[1] = pen;
+    const PenaltyMove mv = move_penalty(s, B, target, penalty);
+    *penalty = mv.penalty;
+    stats[0] = mv.change;
+    stats[1] = mv.penalty;
     if (nan_out) nan_out[0] = nan_out[1] = nan("");
   }
 }
@@ -617,7 +537,7 @@ int run_policy_grad(rg_bptt_handle *h, const float *pp, const void *opt, void *w
                      ws_at<const double>(ws, h->o_gpart), grad);
   rc = launch_status(h, "rg_bptt_grad_finish_kernel launch");
   if (rc) return rc;
-  const LossCfg lc{h->T, h->B, d.P, d.act_dim, d.logstd_off, 0, d.thr, d.coef};
+  const LossCfg lc{h->T, h->B, d.P, d.act_dim, d.logstd_off, 1, d.thr, d.coef};
   hipLaunchKernelGGL(rg_bptt_loss_finish_kernel, dim3(1), dim3(kThreads), 0, s, lc, ws_at<const double>(ws, h->o_part), ws_at<const double>(ws, h->o_klr),
                      penalty_of(opt), grad, loss_out, loss_out2);
   return launch_status(h, "rg_bptt_loss_finish_kernel launch");
@@ -664,16 +584,10 @@ int32_t rg_bptt_groups(const rg_bptt_handle *h) { return h ? h->dv.G : -1; }
 int rg_bptt_create(const rg_rnn_config *rnn_cfg, const rg_ppo_config *ppo_cfg, int32_t T, int32_t B, int32_t device, rg_bptt_handle **out) {
   if (!rnn_cfg || !ppo_cfg || !out) { g_create_err = "create: null rnn_cfg, ppo_cfg or out"; return RG_BPTT_ERR_INVALID; }
   *out = nullptr;
-  char msg[128];
   std::string err;
   const IntField sizes[] = {{"T", T, 1, RG_RNN_MAX_T}, {"B", B, 1, RG_RNN_MAX_BATCH}};
-  if (!check_rnn_config("rnn_cfg.", rnn_cfg, err) || !check_ppo_config(ppo_cfg, err) || !check_ints("", sizes, err)) {
+  if (!check_rnn_config("rnn_cfg.", rnn_cfg, err) || !check_ppo_config(ppo_cfg, err) || !check_ints("", sizes, err) || !check_samples(T, B, err)) {
     g_create_err = err;
-    return RG_BPTT_ERR_INVALID;
-  }
-  if ((long long)T * B > RG_PPO_MAX_SAMPLES) {
-    snprintf(msg, sizeof(msg), "T * B: %lld above %d", (long long)T * B, RG_PPO_MAX_SAMPLES);
-    g_create_err = msg;
     return RG_BPTT_ERR_INVALID;
   }
   rg_bptt_handle *h = new rg_bptt_handle();

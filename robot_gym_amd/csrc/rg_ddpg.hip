@@ -1,6 +1,6 @@
 // rg_ddpg.hip -- the DDPG agent of include/rg_ddpg.h.  Its own translation unit of librg_mpc.so.  The noise stream, a layer's
-// forward and backward pass over a tile, the workgroup sums and the bodies of the transpose and slab-finish kernels
-// are those of rg_agent_dev.inc, which the PPO agent's files include too, and the host helpers those of rg_host.h;
+// forward and backward pass over a tile, the workgroup sums, the bodies of the transpose and slab-finish kernels and Adam's
+// arithmetic behind the clip are those of rg_agent_dev.inc, which the PPO agent's files include too, and the host helpers those of rg_host.h;
 // rg_mpc.hip includes neither, so the source hash behind profiles/ is unaffected.
 //
 // Sweeps (rg_ddpg_critic_sweep_kernel, rg_ddpg_actor_sweep_kernel): G workgroups of 256 threads, workgroup g walks the tiles
@@ -477,18 +477,8 @@ __global__ void __launch_bounds__(kThreads) rg_ddpg_adam_kernel(const AdamCfg c,
     gg = (float)((double)gg * (c.clipnorm / norm));
     grad[e] = gg;
   }
-  const double t = (double)(*step + 1);
-  const double bc1 = 1.0 - pow(c.b1, t), bc2s = sqrt(1.0 - pow(c.b2, t));
-  const float b1 = (float)c.b1, b2 = (float)c.b2, o1 = (float)(1.0 - c.b1), o2 = (float)(1.0 - c.b2);
-  const float t1 = b1 * m[e], t2 = o1 * gg;
-  const float mn = t1 + t2;
-  const float t3 = b2 * v[e], t4 = gg * gg;
-  const float t5 = o2 * t4;
-  const float vn = t3 + t5;
-  m[e] = mn;
-  v[e] = vn;
-  const double denom = sqrt((double)vn) / bc2s + c.eps;
-  p[e] = (float)((double)p[e] - (c.lr / bc1) * (double)mn / denom);
+  const AdamBias bias = adam_bias(c, *step);
+  adam_element(c, bias, gg, p, m, v, e);
 }
 
 __global__ void rg_ddpg_adam_count_kernel(long long *__restrict__ step, const long long *__restrict__ gate) {

@@ -214,6 +214,15 @@ inline bool check_ppo_config(const rg_ppo_config *cfg, std::string &err) {
                              {"kl_cutoff_factor", &cfg->kl_cutoff_factor, 1, kNonNegative}, {"kl_cutoff_coef", &cfg->kl_cutoff_coef, 1, kNonNegative}};
   return check_abi("ppo_cfg.", cfg->abi_version, RG_PPO_ABI_VERSION, err) && check_ints("ppo_cfg.", ints, err) && check_reals("ppo_cfg.", reals, err);
 }
+
+// the samples of a rollout, T and B each within their own range: every update's create checks the product alike
+inline bool check_samples(int T, int B, std::string &err) {
+  if ((long long)T * B <= RG_PPO_MAX_SAMPLES) return true;
+  char msg[128];
+  snprintf(msg, sizeof(msg), "T * B: %lld above %d", (long long)T * B, RG_PPO_MAX_SAMPLES);
+  err = msg;
+  return false;
+}
 #endif
 
 // ---- errors: h->err and the status of the caller's API ----------------------------------------------------------------------

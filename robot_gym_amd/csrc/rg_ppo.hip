@@ -1,8 +1,9 @@
 // rg_ppo.hip -- the PPO update of include/rg_ppo.h.  Its own translation unit of librg_mpc.so.  A layer's forward and backward
 // pass over a tile, the normaliser's arithmetic, the workgroup sums and the bodies of the transpose and slab-finish
-// kernels are those of rg_agent_dev.inc, which the acting side includes too (so the forward pass gives rg_policy_act's mean
-// to the bit from one text), and the host helpers those of rg_host.h; rg_mpc.hip includes neither, so the source hash
-// behind profiles/ is unaffected.
+// kernels and Adam's arithmetic are those of rg_agent_dev.inc, which the acting side includes too (so the forward pass gives
+// rg_policy_act's mean to the bit from one text); the Gaussian head of a sample, the robot-KL element, the loss finish and
+// the penalty rule are those of rg_ppo_dev.inc, which the recurrent update includes too; the host helpers are those of
+// rg_host.h.  rg_mpc.hip includes none of them, so the source hash behind profiles/ is unaffected.
 //
 // Sweeps (rg_ppo_policy_forward_kernel, rg_ppo_policy_backward_kernel, rg_ppo_value_backward_kernel): G workgroups of 256
 // threads, workgroup g walks the tiles g, g + G, ... of kTile samples.  LDS (dynamic): the tile's activations of every layer
@@ -10,7 +11,8 @@
 // (obs_dim + sum(out) + 2 max(out)) * kTile floats: 45 KB at the defaults, 86 KB at the limits (64 -> 3 x 256 -> 4).
 //   forward   thread j owns output neuron j: kTile accumulators, acc = fma(W[i][j], x[i][s], acc) for i in order; W read once
 //             per (tile, neuron) coalesced along j, x as float4 broadcasts.
-//   head      thread s < kTile owns sample s: float64 over the float32 mean (rg_ppo.h), delta rounded to float32.
+//   head      thread s < kTile owns sample s: float64 over the float32 mean (rg_ppo.h), delta rounded to float32;
+//             gaussian_head of rg_ppo_dev.inc through TileHead, this file's view of a tile's sample.
 //   backward  per layer, last to first: thread j folds sum_s x[i][s] delta[j][s] (an fma chain over s) into
 //             slab[g][W[i][j]] for every i, coalesced along j -- the slab is the workgroup's own and each of its elements belongs
 //             to one thread (which clears it first), so the running sum over the workgroup's tiles is plain loads and stores; thread i forms
@@ -29,15 +31,16 @@
 #pragma clang fp contract(off)
 
 #include "rg_agent_dev.inc"
+#include "rg_ppo_dev.inc"
 
 namespace {
 
 constexpr int kTile = RG_PPO_TILE;
 constexpr int kThreads = kAgentThreads;
 constexpr int kMaxGroups = RG_PPO_MAX_GROUPS;
-constexpr int kMaxAct = RG_POLICY_MAX_ACT;
+constexpr int kMaxAct = kHeadAct;
 constexpr int kCols = RG_POLICY_NORM_COLS;
-constexpr int kPart = 1 + kMaxAct;   // per (workgroup, lane): the loss sum, then the logstd gradient
+constexpr int kPart = kHeadPart;     // per (workgroup, lane): the loss sum, then the logstd gradient
 constexpr int kPrep = 3;             // per workgroup of prepare: n, sum(adv), sum((adv - m)^2)
 // dynamic LDS of a sweep at the widest configuration: (obs + three hidden layers + head + two delta buffers) * kTile floats
 constexpr int kMaxLds = (RG_POLICY_MAX_OBS + RG_POLICY_MAX_LAYERS * RG_POLICY_MAX_WIDTH + RG_POLICY_MAX_ACT + 2 * RG_POLICY_MAX_WIDTH) * kTile * 4;
@@ -136,6 +139,27 @@ __global__ void rg_ppo_describe_kernel(const SweepCfg pol, const SweepCfg val, c
 
 // ---- the sweeps -------------------------------------------------------------------------------------------------------
 
+// gaussian_head's view of a sample of a tile: the new mean from the head's activations in LDS, out[k * kTile] (this thread's
+// column), the delta into its column of the first delta buffer, the rest from the descriptor
+struct TileHead {
+  const Desc *dp;
+  const SweepCfg &c;
+  const float *out;
+  float *d0;
+  __device__ __forceinline__ const SweepCfg &cfg() const { return c; }
+  __device__ __forceinline__ int mask(const int n) const { return dp->ro.mask[n]; }
+  __device__ __forceinline__ float logstd0(const int k) const { return dp->ro.logstd[k]; }
+  __device__ __forceinline__ float mean(const int, const int k) const { return out[k * kTile]; }
+  __device__ __forceinline__ float mean0(const int n, const int k) const { return dp->ro.mean[(size_t)n * c.act_dim + k]; }
+  __device__ __forceinline__ float action(const int n, const int k) const { return dp->ro.action[(size_t)n * c.act_dim + k]; }
+  __device__ __forceinline__ float adv(const int n) const { return dp->ro.adv[n]; }
+  __device__ __forceinline__ const double *scal() const { return dp->scal; }
+  __device__ __forceinline__ double robot_kl(const int b) const { return dp->klr[b]; }
+  __device__ __forceinline__ double penalty() const { return *dp->penalty; }
+  __device__ __forceinline__ void keep_kl(const int n, const double v) const { dp->kls[n] = v; }
+  __device__ __forceinline__ void keep_delta(const int, const int k, const float v) const { d0[k * kTile] = v; }
+};
+
 template <bool kPolicy, bool kBackward>
 __device__ __forceinline__ void sweep(const Desc *__restrict__ dp, const float *__restrict__ P) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -144,9 +168,6 @@ __device__ __forceinline__ void sweep(const Desc *__restrict__ dp, const float *
   const RoDev &ro = dp->ro;
   const double *__restrict__ norm = dp->norm;
   const float *__restrict__ Wt = dp->wt;
-  const double *__restrict__ scal = dp->scal;
-  const double *__restrict__ klr = dp->klr;
-  double *__restrict__ kls = dp->kls;
   const NetDesc &nd = c.nd;
   float *d0 = lds + c.asum * kTile, *d1 = d0 + c.dmax * kTile;
   float *slab = dp->slabs + (size_t)g * c.count;
@@ -187,56 +208,11 @@ __device__ __forceinline__ void sweep(const Desc *__restrict__ dp, const float *
       const int n = tile * kTile + tid;
       const float *out = lds + c.asum * kTile - (kPolicy ? c.act_dim : 1) * kTile + tid;   // the head's activations, [k * kTile]
       const bool live = n < c.N;
-      const bool valid = live && ro.mask[n] != 0;
       if (kPolicy) {
-        const int b = live ? n % c.B : 0;
-        double kl = 0.0, lp = 0.0, lp0 = 0.0;
-        double z[kMaxAct], D[kMaxAct], q[kMaxAct], sg[kMaxAct], mu[kMaxAct];
-#pragma unroll
-        for (int k = 0; k < kMaxAct; k++) {
-          z[k] = D[k] = q[k] = mu[k] = 0.0;
-          sg[k] = 1.0;
-          if (k < c.act_dim && live) {
-            const double ls = (double)P[c.logstd_off + k], ls0 = (double)ro.logstd[k];
-            const double s1 = exp(ls), s0 = exp(ls0);
-            const double m1 = (double)out[k * kTile], m0 = (double)ro.mean[(size_t)n * c.act_dim + k];
-            const double a = (double)ro.action[(size_t)n * c.act_dim + k];
-            const double dk = m1 - m0, zk = (a - m1) / s1, z0 = (a - m0) / s0;
-            const double qk = (s0 * s0 + dk * dk) / (s1 * s1);
-            kl = kl + ((qk - 1.0) + 2.0 * (ls - ls0));
-            lp = lp + (-c.c * ls - 0.5 * (zk * zk));
-            lp0 = lp0 + (-c.c * ls0 - 0.5 * (z0 * z0));
-            z[k] = zk; D[k] = dk; q[k] = qk; sg[k] = s1; mu[k] = m1;
-          }
-        }
-        kl = 0.5 * kl;
-        if (!kBackward) {
-          if (live) kls[n] = valid ? kl : 0.0;
-        } else {
-          double ratio = 0.0, advn = 0.0, gb = 0.0;
-          if (valid) {
-            ratio = exp(lp - lp0);
-            advn = ((double)ro.adv[n] - scal[1]) / scal[2];
-            const double klb = klr[b];
-            gb = *dp->penalty + (klb > c.thr ? 2.0 * c.coef * (klb - c.thr) : 0.0);
-            loss = loss + ratio * advn;
-          }
-#pragma unroll
-          for (int k = 0; k < kMaxAct; k++) {
-            if (k < c.act_dim) {
-              float dlt = 0.0f;
-              if (valid) {
-                const double dmu = (-advn * ratio * z[k] / sg[k] + gb * D[k] / (sg[k] * sg[k])) * inv;
-                dlt = (float)(dmu * (1.0 - mu[k] * mu[k]));
-                gls[k] = gls[k] + (-advn * ratio * (z[k] * z[k] - c.c) + gb * (1.0 - q[k])) * inv;
-              }
-              d0[k * kTile + tid] = dlt;
-            }
-          }
-        }
+        gaussian_head<kBackward>(TileHead{dp, c, out, d0 + tid}, P, n, live, inv, loss, gls);
       } else {
         float dlt = 0.0f;
-        if (valid) {
+        if (live && ro.mask[n] != 0) {
           const double e = (double)ro.ret[n] - (double)out[0];
           loss = loss + 0.5 * (e * e);
           dlt = (float)(-e * inv);
@@ -279,11 +255,7 @@ __global__ void __launch_bounds__(kThreads) rg_ppo_value_backward_kernel(const D
 
 // KL_b = (sum_t kls[t][b]) / T, t in order
 __global__ void __launch_bounds__(kThreads) rg_ppo_robot_kl_kernel(const int T, const int B, const double *__restrict__ kls, double *__restrict__ out) {
-  const int b = blockIdx.x * kThreads + (int)threadIdx.x;
-  if (b >= B) return;
-  double s = 0.0;
-  for (int t = 0; t < T; t++) s = s + kls[(size_t)t * B + b];
-  out[b] = s / (double)T;
+  robot_kl_element(T, B, kls, out, blockIdx.x * kThreads + (int)threadIdx.x);
 }
 
 // grad[e] = (float) sum_g slab[g][e], g in order, for the first n elements (the networks; logstd is the loss kernel's)
@@ -294,65 +266,21 @@ __global__ void __launch_bounds__(kThreads) rg_ppo_grad_finish_kernel(const int 
   grad[e] = slab_sum(slabs, count, G, e);
 }
 
-struct LossCfg {
-  int policy, T, B, G, act_dim, logstd_off;
-  double thr, coef;
-};
-
 __global__ void __launch_bounds__(kThreads) rg_ppo_loss_finish_kernel(const LossCfg c, const double *__restrict__ part, const double *__restrict__ klr,
                                                                       const double *__restrict__ penalty, float *__restrict__ grad,
                                                                       double *__restrict__ loss_out, double *__restrict__ loss_out2) {
   __shared__ double sh[4];
-  const double s1 = strided_sum(part, c.G * kTile, kPart, sh);
-  const double inv = 1.0 / ((double)c.T * (double)c.B);
-  double loss = s1 * inv;
-  if (c.policy) {
-    const double pen = *penalty;
-    double s2 = 0.0;
-    for (int b = threadIdx.x; b < c.B; b += kThreads) {
-      const double k = klr[b], over = k - c.thr;
-      s2 = s2 + (pen * k + (k > c.thr ? c.coef * (over * over) : 0.0));
-    }
-    s2 = block_sum(s2, sh);
-    loss = -(s1 * inv) + s2 / (double)c.B;
-#pragma unroll
-    for (int k = 0; k < kMaxAct; k++) {
-      if (k < c.act_dim) {   // uniform
-        const double gk = strided_sum(part + 1 + k, c.G * kTile, kPart, sh);
-        if (threadIdx.x == 0) grad[c.logstd_off + k] = (float)gk;
-      }
-    }
-  }
-  if (threadIdx.x == 0) {
-    *loss_out = loss;
-    if (loss_out2) *loss_out2 = loss;
-  }
+  loss_finish(c, c.parts, c.policy != 0, part, klr, penalty, grad, loss_out, loss_out2, sh);
 }
 
 // ---- Adam -----------------------------------------------------------------------------------------------------------
-
-struct AdamCfg {
-  int count;
-  double lr, b1, b2, eps;
-};
 
 __global__ void __launch_bounds__(kThreads) rg_ppo_adam_kernel(const AdamCfg c, float *__restrict__ p, const float *__restrict__ grad,
                                                                float *__restrict__ m, float *__restrict__ v, const long long *__restrict__ step) {
   const int e = blockIdx.x * kThreads + (int)threadIdx.x;
   if (e >= c.count) return;
-  const double t = (double)(*step + 1);
-  const double bc1 = 1.0 - pow(c.b1, t), bc2s = sqrt(1.0 - pow(c.b2, t));
-  const float b1 = (float)c.b1, b2 = (float)c.b2, o1 = (float)(1.0 - c.b1), o2 = (float)(1.0 - c.b2);
-  const float gg = grad[e];
-  const float t1 = b1 * m[e], t2 = o1 * gg;
-  const float mn = t1 + t2;
-  const float t3 = b2 * v[e], t4 = gg * gg;
-  const float t5 = o2 * t4;
-  const float vn = t3 + t5;
-  m[e] = mn;
-  v[e] = vn;
-  const double denom = sqrt((double)vn) / bc2s + c.eps;
-  p[e] = (float)((double)p[e] - (c.lr / bc1) * (double)mn / denom);
+  const AdamBias bias = adam_bias(c, *step);
+  adam_element(c, bias, grad[e], p, m, v, e);
 }
 
 __global__ void rg_ppo_adam_count_kernel(long long *__restrict__ step) {
@@ -367,13 +295,10 @@ __global__ void __launch_bounds__(kThreads) rg_ppo_penalty_kernel(const int B, c
   __shared__ double sh[4];
   const double s = strided_sum(klr, B, 1, sh);
   if (threadIdx.x == 0) {
-    const double change = s / (double)B;
-    double pen = *penalty;
-    if (change > 1.3 * target) pen = pen * 1.5;
-    else if (change < 0.7 * target) pen = pen / 1.5;
-    *penalty = pen;
-    stats[4] = change;
-    stats[5] = pen;
+    const PenaltyMove mv = move_penalty(s, B, target, penalty);
+    *penalty = mv.penalty;
+    stats[4] = mv.change;
+    stats[5] = mv.penalty;
     if (epochs_policy == 0) stats[0] = stats[1] = nan("");
     if (epochs_value == 0) stats[2] = stats[3] = nan("");
   }
@@ -403,6 +328,7 @@ int null_arg(rg_ppo_handle *h, const char *call, const char *name) { return null
 
 RoDev ro_dev(const rg_ppo_rollout *ro) { return RoDev{ro->obs, ro->action, ro->mean, ro->logstd, ro->adv, ro->ret, (const int *)ro->mask}; }
 
+double *penalty_of(void *opt_state) { return reinterpret_cast<double *>(static_cast<char *>(opt_state) + 16); }
 const double *penalty_of(const void *opt_state) { return reinterpret_cast<const double *>(static_cast<const char *>(opt_state) + 16); }
 
 unsigned blocks_of(int n) { return (unsigned)((n + kThreads - 1) / kThreads); }
@@ -443,7 +369,7 @@ int run_finish(rg_ppo_handle *h, bool policy, const double *penalty, void *ws, f
   hipLaunchKernelGGL(rg_ppo_grad_finish_kernel, dim3(blocks_of(n)), dim3(kThreads), 0, s, n, c.count, h->G, ws_at<float>(ws, h->o_slab), grad);
   int rc = launch_status(h, "rg_ppo_grad_finish_kernel launch");
   if (rc) return rc;
-  const LossCfg lc{policy ? 1 : 0, h->T, h->B, h->G, c.act_dim, c.logstd_off, c.thr, c.coef};
+  const LossCfg lc{h->T, h->B, h->G * kTile, c.act_dim, c.logstd_off, policy ? 1 : 0, c.thr, c.coef};
   hipLaunchKernelGGL(rg_ppo_loss_finish_kernel, dim3(1), dim3(kThreads), 0, s, lc, ws_at<double>(ws, h->o_part), ws_at<double>(ws, h->o_klr), penalty,
                      grad, loss_out, loss_out2);
   return launch_status(h, "rg_ppo_loss_finish_kernel launch");
@@ -482,7 +408,7 @@ int run_adam(rg_ppo_handle *h, int which, float *params, const float *grad, void
   float *mom = reinterpret_cast<float *>(static_cast<char *>(opt) + RG_PPO_OPT_HEADER_BYTES);
   float *m = which == RG_PPO_POLICY ? mom : mom + 2 * (size_t)pc;
   long long *step = reinterpret_cast<long long *>(opt) + which;
-  const AdamCfg c{count, which == RG_PPO_POLICY ? h->cfg.policy_lr : h->cfg.value_lr, h->cfg.beta1, h->cfg.beta2, h->cfg.adam_eps};
+  const AdamCfg c{count, 0, which == RG_PPO_POLICY ? h->cfg.policy_lr : h->cfg.value_lr, h->cfg.beta1, h->cfg.beta2, h->cfg.adam_eps};
   hipLaunchKernelGGL(rg_ppo_adam_kernel, dim3(blocks_of(count)), dim3(kThreads), 0, s, c, params, grad, m, m + count, (const long long *)step);
   int rc = launch_status(h, "rg_ppo_adam_kernel launch");
   if (rc) return rc;
@@ -518,22 +444,10 @@ int64_t rg_ppo_scalars_offset(const rg_ppo_handle *h) { return h ? (int64_t)h->o
 int rg_ppo_create(const rg_policy_config *policy_cfg, const rg_ppo_config *ppo_cfg, int32_t T, int32_t B, int32_t device, rg_ppo_handle **out) {
   if (!policy_cfg || !ppo_cfg || !out) { g_create_err = "create: null policy_cfg, ppo_cfg or out"; return RG_PPO_ERR_INVALID; }
   *out = nullptr;
-  char msg[128];
   std::string err;
-  if (!check_policy_config("policy_cfg.", policy_cfg, err) || !check_ppo_config(ppo_cfg, err)) { g_create_err = err; return RG_PPO_ERR_INVALID; }
-  if (T < 1 || T > RG_POLICY_MAX_T) {
-    snprintf(msg, sizeof(msg), "T: %d outside [1, %d]", T, RG_POLICY_MAX_T);
-    g_create_err = msg;
-    return RG_PPO_ERR_INVALID;
-  }
-  if (B < 1 || B > RG_POLICY_MAX_BATCH) {
-    snprintf(msg, sizeof(msg), "B: %d outside [1, %d]", B, RG_POLICY_MAX_BATCH);
-    g_create_err = msg;
-    return RG_PPO_ERR_INVALID;
-  }
-  if ((long long)T * B > RG_PPO_MAX_SAMPLES) {
-    snprintf(msg, sizeof(msg), "T * B: %lld above %d", (long long)T * B, RG_PPO_MAX_SAMPLES);
-    g_create_err = msg;
+  const IntField sizes[] = {{"T", T, 1, RG_POLICY_MAX_T}, {"B", B, 1, RG_POLICY_MAX_BATCH}};
+  if (!check_policy_config("policy_cfg.", policy_cfg, err) || !check_ppo_config(ppo_cfg, err) || !check_ints("", sizes, err) || !check_samples(T, B, err)) {
+    g_create_err = err;
     return RG_PPO_ERR_INVALID;
   }
   rg_ppo_handle *h = new rg_ppo_handle();
@@ -708,7 +622,7 @@ int rg_ppo_update(rg_ppo_handle *h, const rg_ppo_rollout *ro, const double *norm
   rc = run_robot_kl(h, ro, norm_state, policy_params, workspace, klr, s);
   if (rc) return rc;
   hipLaunchKernelGGL(rg_ppo_penalty_kernel, dim3(1), dim3(kThreads), 0, s, h->B, h->cfg.kl_target, h->cfg.epochs_policy, h->cfg.epochs_value,
-                     (const double *)klr, reinterpret_cast<double *>(static_cast<char *>(opt_state) + 16), stats);
+                     (const double *)klr, penalty_of(opt_state), stats);
   return launch_status(h, "rg_ppo_penalty_kernel launch");
 }
 

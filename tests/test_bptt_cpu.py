@@ -451,9 +451,20 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
     assert code.index("#pragma clang fp contract(off)") < code.index("__global__")
     assert code.index("#pragma clang fp contract(off)") < code.index("__device__")
     assert code.index("#pragma clang fp contract(off)") < code.index('#include "rg_agent_dev.inc"') < code.index('#include "rg_gru_dev.inc"')
+    assert code.index('#include "rg_gru_dev.inc"') < code.index('#include "rg_ppo_dev.inc"')
     assert re.findall(r'#include "([^"]+)"', code) == ["../../include/rg_policy.h", "../../include/rg_ppo.h", "../../include/rg_rnn.h",
-                                                      "../../include/rg_bptt.h", "rg_host.h", "rg_agent_dev.inc", "rg_gru_dev.inc"]
+                                                      "../../include/rg_bptt.h", "rg_host.h", "rg_agent_dev.inc", "rg_gru_dev.inc", "rg_ppo_dev.inc"]
     assert not re.search(r"\b(chain8|sigmoidf)\s*\([^;{]*\)\s*\{", code)         # the tick's device code is rg_gru_dev.inc's alone
+    shared = [open(os.path.join(SRC, name)).read() for name in ("rg_agent_dev.inc", "rg_gru_dev.inc", "rg_ppo_dev.inc")]
+    for text in shared:
+        assert "asm" not in re.sub(r"//.*", "", text) and "atomic" not in text.lower()
+        assert "__global__" not in text and '#include "' not in text
+    # the head's and Adam's arithmetic is the shared files' alone: no update writes an exp or a pow of its own
+    for name in ("rg_ppo.hip", "rg_bptt.hip", "rg_ddpg.hip"):
+        text = re.sub(r"//.*", "", open(os.path.join(SRC, name)).read())
+        assert "pow(" not in text, name
+        assert name == "rg_ddpg.hip" or "exp(" not in text, name
+    assert "pow(" in re.sub(r"//.*", "", shared[0]) and "exp(" in re.sub(r"//.*", "", shared[2])
     assert len(re.findall(r"__global__", code)) == len(KERNELS)
     import bench
     assert not any("rg_bptt" in rel for rel in bench.compiled_sources())         # the MPC hash behind profiles/ does not follow it

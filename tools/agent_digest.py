@@ -1,6 +1,6 @@
 """One sha256 per output buffer of the agents' update entries at fixed seeds: two builds of librg_mpc.so (RG_MPC_LIB, as
 mpc_abi.LIB_PATH takes it) that print the same lines compute the same bytes.  PPO: policy_grad, value_grad, adam on both
-networks, kl; DDPG: critic_grad, actor_grad, adam on both networks, soft_update on both; the recurrent policy: act and
+networks, kl and the whole update (two policy and two value epochs, the penalty move); DDPG: critic_grad, actor_grad, adam on both networks, soft_update on both; the recurrent policy: act and
 unroll; its update: policy_grad, kl, adam and the whole policy update.  The configurations are the smallest of the GPU tests
 that reach every path of the code the agents' files share: below one tile, one sample past a tile with 256-wide layers, more
 tiles than workgroups with a ragged tail; for the GRU tick one robot, one robot past a tile of 8, two dense layers (the
@@ -46,6 +46,11 @@ def ppo(name, T, B):
         digest(f"{tag} adam.{which}_params", params)
     digest(f"{tag} adam.opt_state", upd.opt_state)
     digest(f"{tag} kl", upd.kl(ro))
+    upd.close()
+    upd = DevicePPO(pol, T, epochs_policy=2, epochs_value=2, **G.PPO_KW)      # the whole update: both losses' second outputs, the penalty move
+    stats = upd.update(ro)
+    digest(f"{tag} update.policy_params", pol.policy_params), digest(f"{tag} update.value_params", pol.value_params)
+    digest(f"{tag} update.opt_state", upd.opt_state), digest(f"{tag} update.stats", stats)
     upd.close(), pol.close()
 
 

@@ -46,7 +46,7 @@ def policy_hash():
 
 
 def ppo_hash():
-    return _hash(("robot_gym_amd/csrc/rg_ppo.hip",) + SHARED + ("include/rg_ppo.h",))
+    return _hash(("robot_gym_amd/csrc/rg_ppo.hip", "robot_gym_amd/csrc/rg_ppo_dev.inc") + SHARED + ("include/rg_ppo.h",))
 
 
 def _once(fn, restore):
