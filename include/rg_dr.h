@@ -1,0 +1,161 @@
+/*
+ * rg_dr.h -- C-ABI of the domain randomisation of librg_mpc.so: per episode a TRUE body (mass and inertia scales) and a
+ * world (the key of the random terrain) for each robot of the batched single-rigid-body simulator (rg_srb.h), and random
+ * pushes (the `ext` wrench of rg_srb_step / rg_srb_step_contact) on every tick -- drawn on the device for the robots a
+ * DEVICE mask names, with no host in the loop.
+ *
+ * Not covered: observation or action noise, latency, friction (the model has no slip), per-axis inertia scales, offsets
+ * of the centre of mass.  Every magnitude is the caller's: the defaults are the identity (scales 1, no new worlds, no push).
+ *
+ * Conventions (those of rg_episode.h)
+ *   - return 0 on success, a negative rg_dr_status otherwise; nothing throws across the ABI; rg_dr_last_error() gives the
+ *     text of the last failure on a handle (or of create(), with a NULL handle).
+ *   - the CALLER owns every buffer (device memory).  The handle holds the configuration and `base`, a device table
+ *     [19][B] (mass, I[9], I^-1[9]) of the body the scales multiply (rg_dr_capture_body).
+ *   - all work is enqueued on the hipStream_t passed in (NULL = default stream); NO call synchronises or stages anything
+ *     except rg_dr_capture_body, a set-up call, which waits for its own copy.
+ *   - one handle per (device, stream); calls on one handle are not thread-safe.  Every call leaves the calling thread's
+ *     current HIP device as it found it.
+ *   - every value is computed in IEEE float64 with floating-point contraction off, every expression left to right as
+ *     written.  There is no trigonometric call, no pow and no exp: every operation is an integer operation or a correctly
+ *     rounded + - * /, so tests/dr_model.py restates every output in numpy bit for bit.
+ *
+ * The stream is the counter-based hash of rg_episode.h, stateless:
+ *      mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31   (uint64)
+ *      hash(key, draw, purpose, index):  h = seed;  for w in (key, draw, purpose, index):  h = mix((h ^ w) + 0x9E3779B97F4A7C15)
+ *      u(key, draw, purpose, index) = (hash >> 11) * 2^-53                                    in [0, 1)
+ *   purpose: 0 mass, 1 inertia, 2 world, 3 push start, 4 push component, 5 push gate (RG_DR_PURPOSE_*).
+ *
+ * State (owned by the caller): double dr_state[RG_DR_ROWS][B], component-major, integers stored as exactly representable
+ * doubles (read as rg_episode.h reads its own: through int64 to uint64), rows
+ *      0  key            THE CALLER INITIALISES IT, usually to the robot's index, and nothing here writes it.  The stream is
+ *                        keyed by this row, never by the robot's position in the batch.
+ *      1  draws          number of draws (rg_dr_reset) this robot has had
+ *      2  mass_scale     current value; the caller fills 1 before the first draw
+ *      3  inertia_scale  current value; the caller fills 1 before the first draw
+ *      4  world          the world key rg_dr_reset wrote last (the caller's initial key before that)
+ *      5..7              reserved, zero
+ *   Save, restore and clone are plain copies of columns, followed by rg_dr_apply for the robots written.
+ *
+ * rg_srb_set_body.  The scales multiply `base`, the copy rg_dr_capture_body took of the simulator's host
+ * mirror of the true body.  rg_srb_set_body uploads its WHOLE host mirror and so undoes the scale of EVERY robot: after any
+ * rg_srb_set_body call rg_dr_capture_body again and then rg_dr_apply with a NULL mask (Python: DomainRandomizer.set_body does
+ * all three).  rg_dr_apply without the capture would scale the old base.
+ *
+ * Launches: one kernel per entry (reset, apply, push), one lane per robot, consecutive lanes for consecutive robots (every
+ * load and store is row * B + b and coalesces), 256-thread workgroups, no LDS, no cross-lane operation.  A robot outside
+ * the mask costs a load and an exit.
+ */
+#ifndef RG_DR_H
+#define RG_DR_H
+
+#include <stdint.h>
+#include "rg_srb.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define RG_DR_ABI_VERSION 1
+#define RG_DR_ROWS 8
+#define RG_DR_ROW_KEY 0
+#define RG_DR_ROW_DRAWS 1
+#define RG_DR_ROW_MASS_SCALE 2
+#define RG_DR_ROW_INERTIA_SCALE 3
+#define RG_DR_ROW_WORLD 4
+#define RG_DR_BODY_ROWS 19 /* mass, I[9], I^-1[9] */
+#define RG_DR_PURPOSE_MASS 0
+#define RG_DR_PURPOSE_INERTIA 1
+#define RG_DR_PURPOSE_WORLD 2
+#define RG_DR_PURPOSE_PUSH_START 3
+#define RG_DR_PURPOSE_PUSH_COMPONENT 4
+#define RG_DR_PURPOSE_PUSH_GATE 5
+#define RG_DR_MAX_BATCH (1 << 24)
+#define RG_DR_DEVICE_NONE (-1) /* create(): a host-only handle, see rg_dr_create */
+
+typedef enum {
+  RG_DR_OK = 0,
+  RG_DR_ERR_INVALID = -1,   /* bad argument / configuration (the text names the field) */
+  RG_DR_ERR_HIP = -2,       /* HIP runtime error (text in last_error) */
+  RG_DR_ERR_NO_DEVICE = -3, /* no usable GPU */
+  RG_DR_ERR_ALLOC = -4
+} rg_dr_status;
+
+/* The defaults (robot_gym_amd/core/dr_abi.py) are the identity. */
+typedef struct {
+  int32_t abi_version;      /* RG_DR_ABI_VERSION */
+  int32_t worlds;           /* 0      1: rg_dr_reset draws a new terrain key; 0 or 1 */
+  uint64_t seed;            /* 0      of the stream */
+  double mass_lo;           /* 1.0    range of the mass scale: 0 < lo <= hi, finite */
+  double mass_hi;           /* 1.0 */
+  double inertia_lo;        /* 1.0    range of the inertia scale: 0 < lo <= hi, finite */
+  double inertia_hi;        /* 1.0 */
+  int32_t push_interval;    /* 0      ticks per push window, >= 0; 0: no pushes */
+  int32_t push_ticks;       /* 0      active ticks per window: 1 .. push_interval; 0 when the interval is 0 */
+  double push_probability;  /* 0.0    chance that a window pushes, in [0, 1] */
+  double push_force_xy;     /* 0.0    half-widths of the ranges of the six components, N and N m; >= 0, finite */
+  double push_force_z;      /* 0.0 */
+  double push_torque_xy;    /* 0.0 */
+  double push_torque_z;     /* 0.0 */
+  int32_t substeps;         /* 10     the simulator's sub-steps per tick (rg_srb_config.substeps): 1 .. RG_SRB_MAX_SUBSTEPS */
+  int32_t reserved0;        /* must be 0 */
+} rg_dr_config;
+
+typedef struct rg_dr_handle rg_dr_handle;
+
+/* Validates cfg (abi_version, reserved0, the constraints above) and batch (1 .. RG_DR_MAX_BATCH) BEFORE it looks for a
+ * device.  device = RG_DR_DEVICE_NONE makes a host-only handle: every later call checks its arguments (RG_DR_ERR_INVALID,
+ * naming the argument) and, where they are valid, returns RG_DR_ERR_NO_DEVICE. */
+int rg_dr_create(const rg_dr_config *cfg, int32_t batch, int32_t device, rg_dr_handle **out);
+void rg_dr_destroy(rg_dr_handle *h);
+const char *rg_dr_last_error(const rg_dr_handle *h);   /* h may be NULL: the last create() failure of this thread */
+int32_t rg_dr_abi_version(void);
+int32_t rg_dr_config_size(void);
+int32_t rg_dr_state_rows(void);
+
+/* base = the simulator handle's host mirror of the true body ([19][B]: mass, I, I^-1, what rg_srb_create and
+ * rg_srb_set_body left), copied to the device; WAITS for its copy.  srb must have this handle's batch and device.  Call it
+ * once after create and again after every rg_srb_set_body (see the top of this file), with no work in flight that reads
+ * base (rg_srb_set_body has waited for its stream); reset and apply refuse to run before the first capture. */
+int rg_dr_capture_body(rg_dr_handle *h, rg_srb_handle *srb);
+
+/* A draw for each robot b with mask[b] != 0; a robot outside the mask is written in no buffer.  With key = row 0 and
+ * d = row 1 (draws):
+ *      sm = mass_lo + (mass_hi - mass_lo) * u(key, d, 0, 0);   si = inertia_lo + (inertia_hi - inertia_lo) * u(key, d, 1, 0)
+ *      body table of srb:  mass = base_mass * sm;  I[i] = base_I[i] * si,  Iinv[i] = base_Iinv[i] / si   (i = 0..8: a positive
+ *      scalar keeps the inertia symmetric positive definite, and nothing is inverted on the device)
+ *      worlds == 1:  w = hash(key, d, 2, 0) >> 33 (31 bits);  terrain_key[b] = w;  row 4 = w
+ *      rows 2, 3 = sm, si;  row 1 = d + 1
+ * Device pointers: mask int32 [B]; dr_state float64 [RG_DR_ROWS][B]; terrain_key int64 [B], the key row of the RANDOM
+ * terrain the simulator was given: required when worlds == 1, and must be NULL otherwise. */
+int rg_dr_reset(rg_dr_handle *h, rg_srb_handle *srb, const int32_t *mask, double *dr_state, int64_t *terrain_key, void *stream);
+
+/* The body lines of rg_dr_reset from the scales ALREADY in rows 2 and 3 of dr_state, for each robot b with mask[b] != 0
+ * (mask NULL: every robot).  It draws nothing and writes no row of dr_state and no world.  For clone, restore and set_body.
+ * Rows 2 and 3 are data the caller may have written: where either is not finite and positive, that robot's body stays as
+ * it was. */
+int rg_dr_apply(rg_dr_handle *h, rg_srb_handle *srb, const int32_t *mask, const double *dr_state, void *stream);
+
+/* The push of this tick for EVERY robot: all six rows of ext float64 [6][B] (world force, world torque about the CoM, as
+ * rg_srb_step takes them) are written.  sim_state is the simulator's state float64 [RG_SRB_STATE_ROWS][B], of which row 41
+ * (steps) is read; key and d are rows 0 and 1 of dr_state, which is not written.
+ *      k = (uint64) fmin(fmax(steps, 0), 2^52) / substeps        integer division: the tick since the robot's reset; a NaN
+ *                                                                steps is 0
+ *      win = k / push_interval;  r = k % push_interval;  n = push_interval - push_ticks + 1
+ *      start = min((uint64)((double) n * u(key, d, 3, win)), n - 1)
+ *      active = start <= r < start + push_ticks  and  u(key, d, 5, win) < push_probability
+ *      ext[a][b] = active ? amp_a * (2.0 * u(key, d, 4, 8 * win + a) - 1.0) : 0.0
+ *      amp = push_force_xy, push_force_xy, push_force_z, push_torque_xy, push_torque_xy, push_torque_z  (a = 0..5)
+ * The wrench is constant over a window's push.  A fallen robot's column is written like any other; the simulator ignores
+ * it.  With push_interval == 0 there is nothing to do: RG_DR_ERR_INVALID (pass the simulator ext = NULL). */
+int rg_dr_push(rg_dr_handle *h, const double *sim_state, const double *dr_state, double *ext, void *stream);
+
+/* out float64 [RG_DR_BODY_ROWS][B] (device) = the simulator's body table as it is now, a device-to-device copy on the
+ * stream: for tests and for privileged critics. */
+int rg_dr_get_body(rg_dr_handle *h, rg_srb_handle *srb, double *out, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RG_DR_H */

@@ -20,6 +20,9 @@ frozen (reward 0, done 1, its last observation) until reset(idx) -- host work --
     env = BatchedGoEnv(B, cfg, terrain=RandomTerrain(), height_scan=HeightScan())   # robot_gym_amd/sim/height_scan.py
     env.obs                                       # [B, 16 + 48]: the path columns as they are without the scan, then the
                                                   # height of the body above the ground under 48 points around the robot
+
+    env = BatchedGoEnv(B, cfg, terrain=RandomTerrain(), auto_reset=True,             # robot_gym_amd/sim/randomizer.py: per episode a
+                       randomizer=DomainRandomizer(mass_scale=(0.8, 1.2), new_world_each_episode=True))   # true body and a world, drawn on the device
 """
 import numpy as np
 import torch
@@ -39,10 +42,12 @@ class BatchedGoEnv:
     reset_on_device reset).  episode_settings: planner settings of episode_abi.DEFAULTS other than the seed; they govern BOTH
     resets: reset() plans on the host with them (goto_path.plan_path / build_path), reset_on_device() on the device.
     height_scan: a HeightScan (robot_gym_amd/sim/height_scan.py) or None; with one, N = height_scan.num_points rows follow the path
-    rows of obs and final_obs (one more launch per step, two under auto_reset); without one, N = 0 and nothing changes."""
+    rows of obs and final_obs (one more launch per step, two under auto_reset); without one, N = 0 and nothing changes.
+    randomizer: a DomainRandomizer (robot_gym_amd/sim/randomizer.py) or None; with one, each reset (host or device) draws the
+    robot's true body and, if asked, its world, and each step pushes (one more launch per reset, one per step with pushes on)."""
 
     def __init__(self, batch, cfg: MPCConfig = None, targets=None, obstacles=None, seed=0, device=None, sim_settings=None, auto_reset=False,
-                 episode_settings=None, terrain=None, contact="schedule", height_scan=None, **task):
+                 episode_settings=None, terrain=None, contact="schedule", height_scan=None, randomizer=None, **task):
         # The default robot is ghost WITH ITS COMMAND OFFSETS ZEROED: vy_offset / wz_offset trim a drift of the reference's
         # PyBullet robot that the reduced model does not have, and with them a straight command walks a curve off the path.
         # A cfg passed in is taken as it is, offsets included.
@@ -92,6 +97,11 @@ class BatchedGoEnv:
             height_scan.bind(self.sim)
             self._scan_obs, self._scan_final = self._obs_cm[2 * self.num_cam_pts:], self._final_obs_cm[2 * self.num_cam_pts:]
         self.reset_mask = torch.zeros(B, dtype=torch.int32, device=dev)
+        # randomizer: a DomainRandomizer (robot_gym_amd/sim/randomizer.py) or None.  With one, every reset draws the robot's true
+        # body (and world) before the simulator stands it up, and every step pushes; without one nothing changes.
+        self.randomizer = randomizer
+        if randomizer is not None:
+            randomizer.bind(self.sim)
         # the constructor's targets as a per-robot device table, uploaded once
         self._target_table = None
         if self._fixed_targets is not None:
@@ -193,6 +203,11 @@ class BatchedGoEnv:
         else:
             self.episode_state[torch.as_tensor(running, device=self.device)[:, None], torch.as_tensor(idx, device=self.device)[None, :]] = 0.0
         self._handle.set_path(self._paths, self.task_state.data_ptr(), None if whole else idx, **rows)
+        if self.randomizer is not None:
+            # before the simulator's reset: its own settle then stands the robot in the world drawn here
+            drawn = torch.zeros(B, dtype=torch.int32, device=self.device)
+            drawn[torch.as_tensor(idx, device=self.device)] = 1
+            self.randomizer.on_reset(drawn)
         self.sim.reset(None if whole else idx, xy=np.array([p.start_xy for p in built]), yaw=np.array([p.start_angle for p in built]))
         self.ctl.reset(None if whole else idx)
         self._handle.observe(self.task_state.data_ptr(), self.sim.state.data_ptr(), self._paths, self._obs_cm.data_ptr())
@@ -210,7 +225,7 @@ class BatchedGoEnv:
         ts, ss = self.task_state.data_ptr(), self.sim.state.data_ptr()
         self._handle.pre_step(ts, ss, self._paths, action.data_ptr(), self.cmd.data_ptr())
         self.ctl.get_action(0.0, self.sim.obs)
-        self.sim.step(self.ctl)
+        self.sim.step(self.ctl, None if self.randomizer is None else self.randomizer.pushes())
         self._handle.post_step(ts, ss, self._paths, self._obs_cm.data_ptr(), self.reward.data_ptr(), self.done.data_ptr())
         if self.height_scan is not None:
             self.height_scan.observe(self.sim.state, out=self._scan_obs)   # of a robot that just finished: its terminal scan
@@ -243,6 +258,8 @@ class BatchedGoEnv:
         self._episode.reset(mask.data_ptr(), None if targets is None else targets.data_ptr(), self.episode_state.data_ptr(), self.task_state.data_ptr(),
                             self.sim.state.data_ptr(), self.sim._obs_ptrs, self._paths, self._obs_cm.data_ptr(), self._final_obs_cm.data_ptr(),
                             self.reset_mask.data_ptr())
+        if self.randomizer is not None:
+            self.randomizer.on_reset(self.reset_mask)   # a robot whose plan failed is not in reset_mask and draws nothing
         if self.sim.terrain is not None:
             # the episode reset stands the robot on the plane; the task observation it wrote reads x, y and heading only, which
             # settle leaves as they are
@@ -269,11 +286,15 @@ class BatchedGoEnv:
                          (self._target_table, 1)):
             if ten is not None:
                 ten.index_copy_(dim, t, ten.index_select(dim, s))
+        if self.randomizer is not None:
+            self.randomizer.copy_columns(s, t)   # the draws the source will make, and its body; the world went with sim_clone
         sh, th = s.cpu().numpy(), t.cpu().numpy()
         for a, b in zip(sh, th):
             self.paths[b], self.targets[b] = self.paths[a], self.targets[a]
 
     def close(self):
+        if self.randomizer is not None:
+            self.randomizer.close()
         if self.height_scan is not None:
             self.height_scan.close()
         self._episode.close()

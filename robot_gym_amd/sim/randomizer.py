@@ -1,0 +1,146 @@
+"""Domain randomisation on the device for the robots of BatchedSRBSim (include/rg_dr.h): per episode a TRUE body -- the
+simulator's mass and inertia scaled, while the planner keeps the body it believes in -- and a world (the key of a
+RandomTerrain), and random pushes, the `ext` wrench of BatchedSRBSim.step, on every tick.  A stateless counter-based stream
+keyed by a per-robot key: reproducible, clonable (copy_columns), with no host work in the loop.  All arithmetic happens in
+librg_mpc.so.
+
+    dr = DomainRandomizer(mass_scale=(0.8, 1.2), inertia_scale=(0.8, 1.2), new_world_each_episode=True,
+                          push_interval=100, push_ticks=10, push_probability=0.5, push_force_xy=30.0)
+    env = BatchedGoEnv(B, cfg, terrain=RandomTerrain(), auto_reset=True, randomizer=dr)     # binds it, draws at every reset, pushes
+
+    sim = BatchedSRBSim(B, cfg); dr.bind(sim)                  # the bare simulator
+    dr.on_reset(mask); sim.reset(...)                          # mask: int32 [B] device tensor
+    rollout(ctl, sim, ticks=T, ext=lambda k: dr.pushes())
+
+The defaults are the identity: scales (1, 1), the world kept, no push.  Every magnitude is the caller's choice.  Not covered:
+observation or action noise, latency, friction (the model has no slip), per-axis inertia, offsets of the centre of mass.
+
+BatchedSRBSim.set_body uploads the body of EVERY robot and so undoes every scale: with a randomiser bound, change the base body
+through DomainRandomizer.set_body, which forwards, captures the new base and scales it again.
+"""
+import torch
+
+from robot_gym_amd.core import dr_abi
+from robot_gym_amd.sim.terrain import RandomTerrain
+
+PUSH_FIELDS = ("push_interval", "push_ticks", "push_probability", "push_force_xy", "push_force_z", "push_torque_xy", "push_torque_z")
+
+
+def _range(v, name):
+    try:
+        lo, hi = (float(x) for x in v)
+    except (TypeError, ValueError):
+        raise ValueError(f"DomainRandomizer: {name} must be a pair (lo, hi), got {v!r}") from None
+    return lo, hi
+
+
+class DomainRandomizer:
+    """The fields of rg_dr_config as keywords: mass_scale=(lo, hi), inertia_scale=(lo, hi), new_world_each_episode, seed and
+    the push fields under their own names.  The library checks them at bind(); nothing touches the device before it.
+    After bind(): state float64 [8, B] (rows: rg_dr.h; row 0 the robot's key in the stream, arange(B)), ext float64 [6, B]
+    (None without pushes)."""
+
+    def __init__(self, mass_scale=(1.0, 1.0), inertia_scale=(1.0, 1.0), new_world_each_episode=False, seed=0, push_interval=0, push_ticks=0,
+                 push_probability=0.0, push_force_xy=0.0, push_force_z=0.0, push_torque_xy=0.0, push_torque_z=0.0):
+        (mlo, mhi), (ilo, ihi) = _range(mass_scale, "mass_scale"), _range(inertia_scale, "inertia_scale")
+        self.settings = dict(worlds=int(bool(new_world_each_episode)), seed=int(seed), mass_lo=mlo, mass_hi=mhi, inertia_lo=ilo, inertia_hi=ihi,
+                             push_interval=int(push_interval), push_ticks=int(push_ticks), push_probability=float(push_probability),
+                             push_force_xy=float(push_force_xy), push_force_z=float(push_force_z), push_torque_xy=float(push_torque_xy),
+                             push_torque_z=float(push_torque_z))
+        self.new_world_each_episode = bool(new_world_each_episode)
+        self.pushing = self.settings["push_interval"] != 0
+        self.batch = self.device = self.sim = self.state = self.ext = self._handle = self._keys = None
+
+    def bind(self, sim):
+        """Creates the handle for the simulator's batch, device and sub-steps, the state and ext tensors, and captures the
+        simulator's body as the base the scales multiply.  Returns self."""
+        if self._handle is not None:
+            raise RuntimeError("DomainRandomizer: already bound (one randomiser per simulator)")
+        keys = getattr(sim.terrain, "keys", None)
+        if self.new_world_each_episode and not (isinstance(sim.terrain, RandomTerrain) and torch.is_tensor(keys)):
+            raise ValueError("DomainRandomizer: new_world_each_episode needs a simulator with a bound RandomTerrain (its keys are the worlds)")
+        B, dev = sim.batch, sim.device
+        self._handle = dr_abi.DrHandle(B, dev, substeps=sim.substeps, **self.settings)
+        self.batch, self.device, self.sim = B, dev, sim
+        self._keys = keys if self.new_world_each_episode else None
+        self.state = torch.zeros(dr_abi.ROWS, B, dtype=torch.float64, device=dev)
+        self.state[dr_abi.ROW_KEY] = torch.arange(B, dtype=torch.float64, device=dev)
+        self.state[dr_abi.ROW_MASS_SCALE] = 1.0
+        self.state[dr_abi.ROW_INERTIA_SCALE] = 1.0
+        if torch.is_tensor(keys):
+            self.state[dr_abi.ROW_WORLD] = keys.to(torch.float64)
+        self.ext = torch.zeros(6, B, dtype=torch.float64, device=dev) if self.pushing else None
+        self._handle.capture_body(sim._handle)
+        return self
+
+    def _bound(self, what):
+        if self._handle is None:
+            raise RuntimeError(f"DomainRandomizer: bind(sim) before {what}")
+
+    def _mask(self, mask, what):
+        B = self.batch
+        if not torch.is_tensor(mask) or mask.dtype != torch.int32 or tuple(mask.shape) != (B,) or not mask.is_contiguous() or mask.device != self.device:
+            raise ValueError(f"{what}: mask must be a contiguous int32 [{B}] tensor on {self.device}")
+        return mask.data_ptr()
+
+    @property
+    def scales(self):
+        """float64 [2, B] view of the state: the mass scale and the inertia scale each robot has now."""
+        self._bound("scales")
+        return self.state[dr_abi.ROW_MASS_SCALE:dr_abi.ROW_INERTIA_SCALE + 1]
+
+    def on_reset(self, mask):
+        """A draw -- body scales and, with new_world_each_episode, a world -- for the robots b with mask[b] != 0 (int32 [B]
+        device tensor), BEFORE the simulator resets them, so that its settle stands them in the new world.  Enqueued on the
+        current stream; nothing waits."""
+        self._bound("on_reset")
+        self._handle.reset(self.sim._handle, self._mask(mask, "on_reset"), self.state.data_ptr(), None if self._keys is None else self._keys.data_ptr())
+
+    def pushes(self):
+        """The ext tensor [6, B] with this tick's push of every robot, for BatchedSRBSim.step(ctl, ext), after enqueuing the
+        kernel that writes it from the robots' step counts; None when pushes are off."""
+        self._bound("pushes")
+        if not self.pushing:
+            return None
+        self._handle.push(self.sim.state.data_ptr(), self.state.data_ptr(), self.ext.data_ptr())
+        return self.ext
+
+    def apply(self, mask=None):
+        """The scales in `scales` onto the bodies of the robots of mask (None: all) again: base * scale.  After a restore or a
+        copy of state columns."""
+        self._bound("apply")
+        self._handle.apply(self.sim._handle, None if mask is None else self._mask(mask, "apply"), self.state.data_ptr())
+
+    def set_body(self, mass=None, inertia=None, idx=None):
+        """BatchedSRBSim.set_body for a simulator with a randomiser: forwards, captures the new body as the base and scales
+        every robot again.  Waits, like the simulator's."""
+        self._bound("set_body")
+        self.sim.set_body(mass=mass, inertia=inertia, idx=idx)
+        self._handle.capture_body(self.sim._handle)
+        self.apply()
+
+    def body(self):
+        """float64 [19, B]: the simulator's true body as it is now (mass, I row-major, I^-1 row-major), a copy on the device."""
+        self._bound("body")
+        out = torch.empty(dr_abi.BODY_ROWS, self.batch, dtype=torch.float64, device=self.device)
+        self._handle.get_body(self.sim._handle, out.data_ptr())
+        return out
+
+    def copy_columns(self, src, dst):
+        """The state columns of robot src[k] into robot dst[k] (key, draws, scales and world: the clone draws what its source
+        draws), then the body of every dst robot from its new scales.  The terrain key itself goes with
+        BatchedSRBSim.copy_columns."""
+        self._bound("copy_columns")
+        s, t = self.sim._index(src), self.sim._index(dst)
+        if s.numel() != t.numel():
+            raise ValueError("copy_columns: src and dst differ in length")
+        self.state.index_copy_(1, t, self.state.index_select(1, s))
+        mask = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
+        mask[t] = 1
+        self.apply(mask)
+
+    def close(self):
+        if self._handle is not None:
+            self._handle.close()
+            self._handle = None
+        self.state = self.ext = self.sim = self._keys = None

@@ -188,7 +188,8 @@ def rollout(ctl, sim, commands=None, ticks=1, record_every=0, ext=None, on_tick=
     """The closed loop ctl.get_action(0.0, sim.obs) -> sim.step(ctl) for `ticks` control ticks on the current stream, with no
     synchronisation inside.  commands: [B,2] (vx, wz) or [B,3] (vx, vy, wz) for update_controller_params, a callable of the
     tick returning such values (or None: keep), or None (the controller keeps the command it has).  ext: None, a [6,B]
-    float64 tensor, or a callable of the tick returning one or None.  on_tick: a callable of the tick, called after each tick (a
+    float64 tensor, or a callable of the tick returning one or None (random pushes from a DomainRandomizer bound to this
+    simulator: ext=lambda k: dr.pushes()).  on_tick: a callable of the tick, called after each tick (a
     test reads the solver statistics of every tick with it; what it does is the caller's, a wait included).  Returns (final state [43,B], trajectory): the
     trajectory is None, or with record_every = n > 0 the states after ticks n, 2n, ... as one [T,43,B] device tensor."""
     if commands is not None and not callable(commands):
