@@ -4,8 +4,9 @@
  * pushes (the `ext` wrench of rg_srb_step / rg_srb_step_contact) on every tick -- drawn on the device for the robots a
  * DEVICE mask names, with no host in the loop.
  *
- * Not covered: observation or action noise, latency, friction (the model has no slip), per-axis inertia scales, offsets
- * of the centre of mass.  Every magnitude is the caller's: the defaults are the identity (scales 1, no new worlds, no push).
+ * Not covered: friction (the model has no slip), per-axis inertia scales, offsets of the centre of mass.  Observation and
+ * action noise, dropout and latency are the sensor model's (rg_sensor.h).  Every magnitude is the caller's: the defaults are
+ * the identity (scales 1, no new worlds, no push).
  *
  * Conventions (those of rg_episode.h)
  *   - return 0 on success, a negative rg_dr_status otherwise; nothing throws across the ABI; rg_dr_last_error() gives the

@@ -3,8 +3,9 @@
  * single-rigid-body simulator (rg_srb.h).  A fixed nx x ny grid of points in the robot's YAW frame (x forward), the height
  * of the body above the ground under each point, written straight into rows of a component-major float32 observation.
  *
- * It is a height SAMPLE, not a ray: nothing occludes, there is no sensor noise or dropout, and roll and pitch do not tilt
- * the grid.  The ground is the simulator's own ground function (rg_srb.h, "Terrain"): the work per point is fixed.
+ * It is a height SAMPLE, not a ray: nothing occludes, and roll and pitch do not tilt the grid.  It is exact: noise, bias,
+ * dropout and latency are the sensor model's (rg_sensor.h), applied to the rows this scan writes.  The ground is the
+ * simulator's own ground function (rg_srb.h, "Terrain"): the work per point is fixed.
  *
  * Conventions (those of rg_episode.h)
  *   - return 0 on success, a negative rg_scan_status otherwise; nothing throws across the ABI; rg_scan_last_error() gives

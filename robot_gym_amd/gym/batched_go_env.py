@@ -23,6 +23,10 @@ frozen (reward 0, done 1, its last observation) until reset(idx) -- host work --
 
     env = BatchedGoEnv(B, cfg, terrain=RandomTerrain(), auto_reset=True,             # robot_gym_amd/sim/randomizer.py: per episode a
                        randomizer=DomainRandomizer(mass_scale=(0.8, 1.2), new_world_each_episode=True))   # true body and a world, drawn on the device
+
+    env = BatchedGoEnv(B, cfg, auto_reset=True, sensor_model=SensorModel(path=dict(noise_sigma=0.005), obs_delay=(0, 2), act_delay=(0, 1)))
+    env.obs, env.final_obs                        # robot_gym_amd/sim/sensor_model.py: what the sensors DELIVER (noise, bias, dropout,
+    env.true_obs, env.true_final_obs              # latency); the buffers the task and scan kernels write stay clean
 """
 import numpy as np
 import torch
@@ -44,10 +48,13 @@ class BatchedGoEnv:
     height_scan: a HeightScan (robot_gym_amd/sim/height_scan.py) or None; with one, N = height_scan.num_points rows follow the path
     rows of obs and final_obs (one more launch per step, two under auto_reset); without one, N = 0 and nothing changes.
     randomizer: a DomainRandomizer (robot_gym_amd/sim/randomizer.py) or None; with one, each reset (host or device) draws the
-    robot's true body and, if asked, its world, and each step pushes (one more launch per reset, one per step with pushes on)."""
+    robot's true body and, if asked, its world, and each step pushes (one more launch per reset, one per step with pushes on).
+    sensor_model: a SensorModel (robot_gym_amd/sim/sensor_model.py) or None; with one, obs and final_obs are what the sensors deliver
+    (true_obs and true_final_obs stay what the task and scan wrote) and the action passes through the actuator model before
+    pre_step (two more launches per step, three under auto_reset); without one nothing changes."""
 
     def __init__(self, batch, cfg: MPCConfig = None, targets=None, obstacles=None, seed=0, device=None, sim_settings=None, auto_reset=False,
-                 episode_settings=None, terrain=None, contact="schedule", height_scan=None, randomizer=None, **task):
+                 episode_settings=None, terrain=None, contact="schedule", height_scan=None, randomizer=None, sensor_model=None, **task):
         # The default robot is ghost WITH ITS COMMAND OFFSETS ZEROED: vy_offset / wz_offset trim a drift of the reference's
         # PyBullet robot that the reduced model does not have, and with them a straight command walks a curve off the path.
         # A cfg passed in is taken as it is, offsets included.
@@ -102,6 +109,12 @@ class BatchedGoEnv:
         self.randomizer = randomizer
         if randomizer is not None:
             randomizer.bind(self.sim)
+        # sensor_model: a SensorModel or None.  The task and scan kernels keep writing _obs_cm and _final_obs_cm, which must stay
+        # clean (the path observation latches its previous value); the model writes buffers of its own, which obs and final_obs show.
+        self.sensor_model = sensor_model
+        if sensor_model is not None:
+            rows = 2 * self.num_cam_pts
+            sensor_model.bind(B, dev, rows + self._scan_rows, 2, path_rows=(0, rows), scan_rows=(rows, rows + self._scan_rows))
         # the constructor's targets as a per-robot device table, uploaded once
         self._target_table = None
         if self._fixed_targets is not None:
@@ -111,13 +124,24 @@ class BatchedGoEnv:
 
     @property
     def obs(self):
-        """[B, 2 * num_cam_pts + N] view of the observation buffer."""
+        """[B, 2 * num_cam_pts + N] view of the observation buffer: with a sensor model, of what it delivers."""
+        return self._obs_cm.t() if self.sensor_model is None else self.sensor_model.obs_out.t()
+
+    @property
+    def true_obs(self):
+        """[B, 2 * num_cam_pts + N] view of the observation the task and scan kernels wrote; obs itself without a sensor model."""
         return self._obs_cm.t()
 
     @property
-    def final_obs(self):
-        """[B, 2 * num_cam_pts + N] view: the observation each robot had before its last reset on the device (the terminal one)."""
+    def true_final_obs(self):
+        """[B, 2 * num_cam_pts + N] view: final_obs as the task and scan kernels wrote it."""
         return self._final_obs_cm.t()
+
+    @property
+    def final_obs(self):
+        """[B, 2 * num_cam_pts + N] view: the observation each robot had before its last reset on the device (the terminal one);
+        with a sensor model, the one it delivered."""
+        return self._final_obs_cm.t() if self.sensor_model is None else self.sensor_model.final_obs.t()
 
     @property
     def episode_count(self):
@@ -213,6 +237,10 @@ class BatchedGoEnv:
         self._handle.observe(self.task_state.data_ptr(), self.sim.state.data_ptr(), self._paths, self._obs_cm.data_ptr())
         if self.height_scan is not None:
             self.height_scan.observe(self.sim.state, out=self._scan_obs)
+        if self.sensor_model is not None:
+            fresh = torch.zeros(B, dtype=torch.int32, device=self.device)
+            fresh[torch.as_tensor(idx, device=self.device)] = 1
+            self.sensor_model.on_reset(fresh, self._obs_cm)
         return self.obs
 
     def step(self, action):
@@ -222,6 +250,8 @@ class BatchedGoEnv:
             raise ValueError(f"step: action must be a [{self.batch},2] tensor on {self.device}")
         if action.dtype != torch.float32 or not action.is_contiguous():
             action = action.to(torch.float32).contiguous()   # the kernel reads the rows as they are: a float32 action costs no torch op
+        if self.sensor_model is not None:
+            action = self.sensor_model.act(action)   # noise and latency; pre_step clips what arrives to the action box
         ts, ss = self.task_state.data_ptr(), self.sim.state.data_ptr()
         self._handle.pre_step(ts, ss, self._paths, action.data_ptr(), self.cmd.data_ptr())
         self.ctl.get_action(0.0, self.sim.obs)
@@ -229,6 +259,8 @@ class BatchedGoEnv:
         self._handle.post_step(ts, ss, self._paths, self._obs_cm.data_ptr(), self.reward.data_ptr(), self.done.data_ptr())
         if self.height_scan is not None:
             self.height_scan.observe(self.sim.state, out=self._scan_obs)   # of a robot that just finished: its terminal scan
+        if self.sensor_model is not None:
+            self.sensor_model.observe(self._obs_cm)   # of a robot that just finished: its delivered terminal observation
         if self.auto_reset:
             self._episode.accumulate(self.episode_state.data_ptr(), self.reward.data_ptr(), self.done.data_ptr())
             self.reset_on_device(self.done)
@@ -268,6 +300,10 @@ class BatchedGoEnv:
             # one launch for the robots that were reset: the terminal scan moves into final_obs, the first scan of the new episode
             # takes its place
             self.height_scan.observe(self.sim.state, out=self._scan_obs, mask=self.reset_mask, prev=self._scan_final)
+        if self.sensor_model is not None:
+            # after the clean buffer holds the first observation of the new episode: the delivered terminal one moves into the
+            # model's final_obs, new delays are drawn and the rings start over.  A robot whose plan failed draws nothing.
+            self.sensor_model.on_reset(self.reset_mask, self._obs_cm, prev=self.sensor_model.final_obs)
         if not self._mirrors_stale:
             self.paths = [None] * B
             self.targets[:] = np.nan
@@ -288,11 +324,15 @@ class BatchedGoEnv:
                 ten.index_copy_(dim, t, ten.index_select(dim, s))
         if self.randomizer is not None:
             self.randomizer.copy_columns(s, t)   # the draws the source will make, and its body; the world went with sim_clone
+        if self.sensor_model is not None:
+            self.sensor_model.copy_columns(s, t)   # rings, delays, ticks and the stream's key: the clone sees what its source sees
         sh, th = s.cpu().numpy(), t.cpu().numpy()
         for a, b in zip(sh, th):
             self.paths[b], self.targets[b] = self.paths[a], self.targets[a]
 
     def close(self):
+        if self.sensor_model is not None:
+            self.sensor_model.close()
         if self.randomizer is not None:
             self.randomizer.close()
         if self.height_scan is not None:

@@ -2,8 +2,9 @@
 
 A fixed nx x ny grid of points in the robot's yaw frame (x forward, y left); under each point the height of the body above
 the ground, less the nominal body height, clipped and scaled: float32 [nx * ny, B], component-major like every observation
-the policy kernels read.  It is a height sample, not a ray -- nothing occludes -- with no sensor noise or dropout, and roll
-and pitch do not tilt the grid.  The ground is the simulator's own; all arithmetic happens in librg_mpc.so.
+the policy kernels read.  It is a height sample, not a ray -- nothing occludes -- and roll and pitch do not tilt the grid.  It
+is exact: noise, dropout and latency are SensorModel's (robot_gym_amd/sim/sensor_model.py).  The ground is the simulator's own;
+all arithmetic happens in librg_mpc.so.
 
     sim = BatchedSRBSim(B, cfg, terrain=RandomTerrain())
     scan = HeightScan()                  # 8 x 6 points, 0.1 m apart, from 0.2 m behind the body to 0.5 m ahead

@@ -13,7 +13,8 @@ librg_mpc.so.
     rollout(ctl, sim, ticks=T, ext=lambda k: dr.pushes())
 
 The defaults are the identity: scales (1, 1), the world kept, no push.  Every magnitude is the caller's choice.  Not covered:
-observation or action noise, latency, friction (the model has no slip), per-axis inertia, offsets of the centre of mass.
+friction (the model has no slip), per-axis inertia, offsets of the centre of mass.  Observation and action noise, dropout and
+latency are SensorModel's (robot_gym_amd/sim/sensor_model.py).
 
 BatchedSRBSim.set_body uploads the body of EVERY robot and so undoes every scale: with a randomiser bound, change the base body
 through DomainRandomizer.set_body, which forwards, captures the new base and scales it again.
