@@ -6,8 +6,8 @@
  * write, which must STAY clean (the go-to task latches its previous path observation), so the model writes buffers of its own.
  *
  * Stated limits
- *   - the controller's own state estimate (the simulator's obs tensors) stays exact: its rpy and quat are both read by the
- *     controller's front kernel, and consistent noise on the two needs trigonometry and a design of its own;
+ *   - this model leaves the controller's own state estimate (the simulator's obs tensors) alone: its rpy and quat are both read
+ *     by the controller's front kernel, and consistent errors on the two are the design of rg_est.h, the estimator model;
  *   - dropout is per row and per tick: there is no frame-level dropout (all rows of a sensor lost together);
  *   - the noise is white (no correlation over ticks or rows) and has bounded support (see `n` below);
  *   - a robot's delays are drawn at its reset and constant over the episode.

@@ -27,6 +27,11 @@ frozen (reward 0, done 1, its last observation) until reset(idx) -- host work --
     env = BatchedGoEnv(B, cfg, auto_reset=True, sensor_model=SensorModel(path=dict(noise_sigma=0.005), obs_delay=(0, 2), act_delay=(0, 1)))
     env.obs, env.final_obs                        # robot_gym_amd/sim/sensor_model.py: what the sensors DELIVER (noise, bias, dropout,
     env.true_obs, env.true_final_obs              # latency); the buffers the task and scan kernels write stay clean
+
+    env = BatchedGoEnv(B, cfg, auto_reset=True, state_estimator=StateEstimator(imu=dict(bias_half_width=(0.03, 0.03, 0.0)),
+                                                                               contact=dict(rise_ticks=2, miss_probability=0.02)))
+    env.est_obs                                   # robot_gym_amd/sim/state_estimator.py: what the CONTROLLER is given (IMU, gyro, velocity,
+                                                  # encoder and foot-switch errors); env.sim.obs stays the truth
 """
 import numpy as np
 import torch
@@ -51,10 +56,14 @@ class BatchedGoEnv:
     robot's true body and, if asked, its world, and each step pushes (one more launch per reset, one per step with pushes on).
     sensor_model: a SensorModel (robot_gym_amd/sim/sensor_model.py) or None; with one, obs and final_obs are what the sensors deliver
     (true_obs and true_final_obs stay what the task and scan wrote) and the action passes through the actuator model before
-    pre_step (two more launches per step, three under auto_reset); without one nothing changes."""
+    pre_step (two more launches per step, three under auto_reset); without one nothing changes.
+    state_estimator: a StateEstimator (robot_gym_amd/sim/state_estimator.py) or None; with one, the controller is given est_obs, the
+    estimator's view of sim.obs, instead of sim.obs (one more launch per step, one per reset); the simulator, the task, the scan
+    and the sensor model keep reading the true state; without one nothing changes."""
 
     def __init__(self, batch, cfg: MPCConfig = None, targets=None, obstacles=None, seed=0, device=None, sim_settings=None, auto_reset=False,
-                 episode_settings=None, terrain=None, contact="schedule", height_scan=None, randomizer=None, sensor_model=None, **task):
+                 episode_settings=None, terrain=None, contact="schedule", height_scan=None, randomizer=None, sensor_model=None, state_estimator=None,
+                 **task):
         # The default robot is ghost WITH ITS COMMAND OFFSETS ZEROED: vy_offset / wz_offset trim a drift of the reference's
         # PyBullet robot that the reduced model does not have, and with them a straight command walks a curve off the path.
         # A cfg passed in is taken as it is, offsets included.
@@ -115,6 +124,11 @@ class BatchedGoEnv:
         if sensor_model is not None:
             rows = 2 * self.num_cam_pts
             sensor_model.bind(B, dev, rows + self._scan_rows, 2, path_rows=(0, rows), scan_rows=(rows, rows + self._scan_rows))
+        # state_estimator: a StateEstimator or None.  It stands between sim.obs and the controller only; the simulator reads its own
+        # buffers back, so they stay clean and the estimate goes to tensors of the estimator's.
+        self.state_estimator = state_estimator
+        if state_estimator is not None:
+            state_estimator.bind(self.sim)
         # the constructor's targets as a per-robot device table, uploaded once
         self._target_table = None
         if self._fixed_targets is not None:
@@ -126,6 +140,12 @@ class BatchedGoEnv:
     def obs(self):
         """[B, 2 * num_cam_pts + N] view of the observation buffer: with a sensor model, of what it delivers."""
         return self._obs_cm.t() if self.sensor_model is None else self.sensor_model.obs_out.t()
+
+    @property
+    def est_obs(self):
+        """The dict of component-major tensors the controller was given on the last step: the state estimator's; sim.obs itself
+        without one."""
+        return self.sim.obs if self.state_estimator is None else self.state_estimator.obs
 
     @property
     def true_obs(self):
@@ -234,6 +254,8 @@ class BatchedGoEnv:
             self.randomizer.on_reset(drawn)
         self.sim.reset(None if whole else idx, xy=np.array([p.start_xy for p in built]), yaw=np.array([p.start_angle for p in built]))
         self.ctl.reset(None if whole else idx)
+        if self.state_estimator is not None:
+            self.state_estimator.on_reset(None if whole else idx)
         self._handle.observe(self.task_state.data_ptr(), self.sim.state.data_ptr(), self._paths, self._obs_cm.data_ptr())
         if self.height_scan is not None:
             self.height_scan.observe(self.sim.state, out=self._scan_obs)
@@ -254,7 +276,7 @@ class BatchedGoEnv:
             action = self.sensor_model.act(action)   # noise and latency; pre_step clips what arrives to the action box
         ts, ss = self.task_state.data_ptr(), self.sim.state.data_ptr()
         self._handle.pre_step(ts, ss, self._paths, action.data_ptr(), self.cmd.data_ptr())
-        self.ctl.get_action(0.0, self.sim.obs)
+        self.ctl.get_action(0.0, self.sim.obs if self.state_estimator is None else self.state_estimator.estimate())
         self.sim.step(self.ctl, None if self.randomizer is None else self.randomizer.pushes())
         self._handle.post_step(ts, ss, self._paths, self._obs_cm.data_ptr(), self.reward.data_ptr(), self.done.data_ptr())
         if self.height_scan is not None:
@@ -292,6 +314,8 @@ class BatchedGoEnv:
                             self.reset_mask.data_ptr())
         if self.randomizer is not None:
             self.randomizer.on_reset(self.reset_mask)   # a robot whose plan failed is not in reset_mask and draws nothing
+        if self.state_estimator is not None:
+            self.state_estimator.on_reset(self.reset_mask)   # after the simulator's reset; a robot whose plan failed keeps its episode
         if self.sim.terrain is not None:
             # the episode reset stands the robot on the plane; the task observation it wrote reads x, y and heading only, which
             # settle leaves as they are
@@ -326,11 +350,15 @@ class BatchedGoEnv:
             self.randomizer.copy_columns(s, t)   # the draws the source will make, and its body; the world went with sim_clone
         if self.sensor_model is not None:
             self.sensor_model.copy_columns(s, t)   # rings, delays, ticks and the stream's key: the clone sees what its source sees
+        if self.state_estimator is not None:
+            self.state_estimator.copy_columns(s, t)   # draws, ticks, contact runs and the stream's key: the clone's controller is given what its source's is
         sh, th = s.cpu().numpy(), t.cpu().numpy()
         for a, b in zip(sh, th):
             self.paths[b], self.targets[b] = self.paths[a], self.targets[a]
 
     def close(self):
+        if self.state_estimator is not None:
+            self.state_estimator.close()
         if self.sensor_model is not None:
             self.sensor_model.close()
         if self.randomizer is not None:

@@ -13,8 +13,8 @@ and a per-episode latency.  A stateless counter-based stream keyed by a per-robo
     seen = sm.observe(clean)            # [D, B], once per tick
     applied = sm.act(action)            # [B, A], once per tick
 
-The defaults are the identity, and the identity copies bits.  Limits (rg_sensor.h): the controller's own state estimate stays
-exact; dropout is per row, not per frame; the noise is white and bounded (a sum of four uniforms, |n| < 3.4642 sigma, not a
+The defaults are the identity, and the identity copies bits.  Limits (rg_sensor.h): the controller's own state estimate is not
+this model's (StateEstimator, state_estimator.py, is); dropout is per row, not per frame; the noise is white and bounded (a sum of four uniforms, |n| < 3.4642 sigma, not a
 Gaussian: that is what keeps tests/sensor_model.py bit-exact); a robot's delays are constant over an episode.
 """
 import torch

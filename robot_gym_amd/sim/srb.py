@@ -184,13 +184,15 @@ class BatchedSRBSim:
         self._handle.close()
 
 
-def rollout(ctl, sim, commands=None, ticks=1, record_every=0, ext=None, on_tick=None):
+def rollout(ctl, sim, commands=None, ticks=1, record_every=0, ext=None, on_tick=None, estimator=None):
     """The closed loop ctl.get_action(0.0, sim.obs) -> sim.step(ctl) for `ticks` control ticks on the current stream, with no
     synchronisation inside.  commands: [B,2] (vx, wz) or [B,3] (vx, vy, wz) for update_controller_params, a callable of the
     tick returning such values (or None: keep), or None (the controller keeps the command it has).  ext: None, a [6,B]
     float64 tensor, or a callable of the tick returning one or None (random pushes from a DomainRandomizer bound to this
     simulator: ext=lambda k: dr.pushes()).  on_tick: a callable of the tick, called after each tick (a
-    test reads the solver statistics of every tick with it; what it does is the caller's, a wait included).  Returns (final state [43,B], trajectory): the
+    test reads the solver statistics of every tick with it; what it does is the caller's, a wait included).  estimator: a
+    StateEstimator (robot_gym_amd/sim/state_estimator.py) bound to this simulator, or None: with one the controller is given
+    estimator.estimate() instead of sim.obs (reset it with estimator.on_reset() after sim.reset()).  Returns (final state [43,B], trajectory): the
     trajectory is None, or with record_every = n > 0 the states after ticks n, 2n, ... as one [T,43,B] device tensor."""
     if commands is not None and not callable(commands):
         ctl.update_controller_params(commands)
@@ -200,7 +202,7 @@ def rollout(ctl, sim, commands=None, ticks=1, record_every=0, ext=None, on_tick=
             c = commands(k)
             if c is not None:
                 ctl.update_controller_params(c)
-        ctl.get_action(0.0, sim.obs)
+        ctl.get_action(0.0, sim.obs if estimator is None else estimator.estimate())
         sim.step(ctl, ext(k) if callable(ext) else ext)
         if record_every and (k + 1) % record_every == 0:
             traj.append(sim.state.clone())
@@ -209,10 +211,13 @@ def rollout(ctl, sim, commands=None, ticks=1, record_every=0, ext=None, on_tick=
     return sim.state.clone(), (torch.stack(traj) if traj else None)
 
 
-def clone(ctl, sim, src, dst):
+def clone(ctl, sim, src, dst, estimator=None):
     """Branch rollouts: controller state (ctl.copy_state), simulation state and observation of robot src[k] into robot
     dst[k].  For bit-identical continuations keep dst = src modulo 16 (rg_mpc.h, direct routing).  rg_mpc_copy_state takes host
-    index lists, so src / dst given as device tensors are read back for it once."""
+    index lists, so src / dst given as device tensors are read back for it once.  estimator: the StateEstimator bound to this
+    simulator, or None; its columns go with the robot."""
     host = lambda i: i.cpu().numpy() if torch.is_tensor(i) else i
     ctl.copy_state(host(src), host(dst))
     sim.copy_columns(src, dst)
+    if estimator is not None:
+        estimator.copy_columns(src, dst)

@@ -1,0 +1,140 @@
+"""State estimator error model on the device (include/rg_est.h): what the CONTROLLER plans on is the simulator's exact
+observation with an IMU tilt offset and noise, gyro and velocity bias and noise, encoder offset, noise and resolution, and foot
+switches that report late, miss a contact or report a ghost one.  A stateless counter-based stream keyed by a per-robot key:
+reproducible, clonable (copy_columns), with no host work in the loop.  All arithmetic happens in librg_mpc.so.
+
+    est = StateEstimator(imu=dict(bias_half_width=(0.03, 0.03, 0.0), noise_sigma=(0.002, 0.002, 0.002)),
+                         gyro=dict(noise_sigma=(0.02, 0.02, 0.02)), velocity=dict(bias_half_width=(0.05, 0.05, 0.0)),
+                         encoders=dict(bias_half_width=0.01, quantum=2 * math.pi / 4096),
+                         contact=dict(miss_probability=0.02, ghost_probability=0.005, rise_ticks=2))
+    env = BatchedGoEnv(B, cfg, auto_reset=True, state_estimator=est)
+    env.est_obs                         # what the controller was given; env.sim.obs stays the truth
+
+    est = StateEstimator(...).bind(sim)                       # on its own, next to a BatchedSRBSim
+    est.on_reset(mask_or_idx)                                 # after the simulator's reset of those robots
+    rollout(ctl, sim, ticks=100, estimator=est)               # ctl.get_action(0.0, est.estimate()) -> sim.step(ctl)
+
+The defaults are the identity, and the identity copies bits.  rpy and quat are perturbed TOGETHER (one rotation by
+construction), and foot_pos and jac are the controller's own kinematics at the estimated joint angles, so a kin_mode 0 and a
+kin_mode 1 controller plan on the same legs.  Limits (rg_est.h): no latency; the noise is white and bounded (a sum of four
+uniforms, |n| < 3.4642 sigma); a bias is constant over an episode; no error on t_robot; the controller's own velocity filter is
+downstream and unchanged.
+"""
+import torch
+
+from robot_gym_amd.core import est_abi, srb_abi
+
+GROUPS = {
+    "imu": dict(bias_half_width="imu_bias_half_width", noise_sigma="imu_noise_sigma"),
+    "gyro": dict(bias_half_width="gyro_bias_half_width", noise_sigma="gyro_noise_sigma"),
+    "velocity": dict(bias_half_width="velocity_bias_half_width", noise_sigma="velocity_noise_sigma"),
+    "encoders": dict(bias_half_width="encoder_bias_half_width", noise_sigma="encoder_noise_sigma", quantum="encoder_quantum"),
+    "contact": dict(miss_probability="contact_miss_probability", ghost_probability="contact_ghost_probability", rise_ticks="contact_rise_ticks"),
+}
+
+
+class StateEstimator:
+    """imu, gyro, velocity: dict(bias_half_width=(3 values), noise_sigma=(3 values)) -- roll, pitch, yaw in the body frame in
+    radians; the rows of rpy_rate in rad/s; the rows of v_world in m/s.  encoders: dict(bias_half_width, noise_sigma, quantum),
+    scalars in radians shared by the twelve joints (each draws its own).  contact: dict(miss_probability, ghost_probability,
+    rise_ticks).  Unknown keys and malformed values are refused here, by name; ranges are the library's at bind().
+    After bind(): state float64 [8, B] (rows: rg_est.h; row 0 the robot's key in the stream, arange(B)) and obs, the dict
+    estimate() returns: the simulator's keys, the modelled ones as tensors of this model's own."""
+
+    def __init__(self, imu=None, gyro=None, velocity=None, encoders=None, contact=None, seed=0):
+        settings = dict(seed=int(seed))
+        for group, given in (("imu", imu), ("gyro", gyro), ("velocity", velocity), ("encoders", encoders), ("contact", contact)):
+            if given is None:
+                continue
+            names = GROUPS[group]
+            try:
+                items = dict(given).items()
+            except (TypeError, ValueError):
+                raise ValueError(f"StateEstimator: {group} must be a dict of {sorted(names)}, got {given!r}") from None
+            for key, v in items:
+                if key not in names:
+                    raise TypeError(f"StateEstimator: unknown {group} setting {key!r} (known: {sorted(names)})")
+                field = names[key]
+                try:
+                    if field in est_abi.TRIPLES:
+                        v = tuple(float(x) for x in v)
+                        if len(v) != 3:
+                            raise ValueError
+                    elif field == "contact_rise_ticks":
+                        if int(v) != v:
+                            raise ValueError
+                        v = int(v)
+                    else:
+                        v = float(v)
+                except (TypeError, ValueError):
+                    want = "three numbers" if field in est_abi.TRIPLES else "a whole number of ticks" if field == "contact_rise_ticks" else "a number"
+                    raise ValueError(f"StateEstimator: {group}[{key!r}] must be {want}, got {v!r}") from None
+                settings[field] = v
+        self.settings = settings
+        self.batch = self.device = self.sim = self.state = self.obs = self._own = self._handle = self._true_ptrs = self._est_ptrs = None
+
+    def bind(self, sim):
+        """Creates the handle for the simulator's batch, device and leg chains, the state and the estimated tensors.  Returns self."""
+        if self._handle is not None:
+            raise RuntimeError("StateEstimator: already bound (one estimator per simulator)")
+        B, dev = sim.batch, sim.device
+        self._handle = est_abi.EstHandle(B, sim.cfg, dev, sim_settings=dict(dt_sim=sim.dt_sim, substeps=sim.substeps), **self.settings)
+        self.batch, self.device, self.sim = B, dev, sim
+        self.state = torch.zeros(est_abi.ROWS, B, dtype=torch.float64, device=dev)
+        self.state[est_abi.ROW_KEY] = torch.arange(B, dtype=torch.float64, device=dev)
+        self._own = {name: torch.zeros_like(sim.obs[name]) for name in srb_abi.OBS_FIELDS}
+        self._true_ptrs, self._est_ptrs = sim._obs_ptrs, srb_abi.CObsPtrs()
+        for name in srb_abi.OBS_FIELDS:
+            setattr(self._est_ptrs, name, self._own[name].data_ptr())
+        self.obs = dict(self._own)
+        return self
+
+    def _bound(self, what):
+        if self._handle is None:
+            raise RuntimeError(f"StateEstimator: bind(sim) before {what}")
+
+    def on_reset(self, mask_or_idx=None):
+        """A new episode for robots: an int32 [B] mask on this device (mask[b] != 0; no host work), or a list / array / int64
+        tensor of robot indices, or None for every robot.  AFTER the simulator's reset of those robots.  Enqueued on the current
+        stream."""
+        self._bound("on_reset")
+        B, m = self.batch, mask_or_idx
+        if torch.is_tensor(m) and m.dtype == torch.int32:
+            if tuple(m.shape) != (B,) or not m.is_contiguous() or m.device != self.device:
+                raise ValueError(f"on_reset: a mask must be a contiguous int32 [{B}] tensor on {self.device}")
+        elif m is None:
+            m = torch.ones(B, dtype=torch.int32, device=self.device)
+        else:
+            idx = self.sim._index(m)
+            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= B):
+                raise ValueError(f"on_reset: robot indices outside [0, {B})")
+            m = torch.zeros(B, dtype=torch.int32, device=self.device)
+            m[idx] = 1
+        self._handle.reset(m.data_ptr(), self.state.data_ptr())
+
+    def estimate(self):
+        """This tick's estimate of every robot from sim.obs, after enqueuing the kernel that writes it: the dict the controller
+        takes.  Every key of sim.obs this model does not write (the command an env adds, for one) is the simulator's own tensor,
+        looked up now."""
+        self._bound("estimate")
+        self._handle.estimate(self.state.data_ptr(), self._true_ptrs, self._est_ptrs)
+        for name, t in self.sim.obs.items():
+            if name not in self._own:
+                self.obs[name] = t
+        return self.obs
+
+    def copy_columns(self, src, dst):
+        """The state and estimate columns of robot src[k] into robot dst[k] (index tensors or lists): the clone is given what
+        its source is given, the key included."""
+        self._bound("copy_columns")
+        s, t = self.sim._index(src), self.sim._index(dst)
+        if s.numel() != t.numel():
+            raise ValueError("copy_columns: src and dst differ in length")
+        for ten in [self.state] + list(self._own.values()):
+            ten.index_copy_(ten.dim() - 1, t, ten.index_select(ten.dim() - 1, s))
+
+    def close(self):
+        if self._handle is not None:
+            self._handle.close()
+            self._handle = None
+        self.state = self.obs = self._own = self._true_ptrs = self._est_ptrs = None
