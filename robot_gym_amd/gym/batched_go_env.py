@@ -51,7 +51,8 @@ class BatchedGoEnv:
     reset_on_device reset).  episode_settings: planner settings of episode_abi.DEFAULTS other than the seed; they govern BOTH
     resets: reset() plans on the host with them (goto_path.plan_path / build_path), reset_on_device() on the device.
     height_scan: a HeightScan (robot_gym_amd/sim/height_scan.py) or None; with one, N = height_scan.num_points rows follow the path
-    rows of obs and final_obs (one more launch per step, two under auto_reset); without one, N = 0 and nothing changes.
+    rows of obs and final_obs (one more launch per step, two under auto_reset, and one elementwise op for the mask of the robots
+    that were not done before the tick: a done robot is frozen and keeps its scan rows too); without one, N = 0 and nothing changes.
     randomizer: a DomainRandomizer (robot_gym_amd/sim/randomizer.py) or None; with one, each reset (host or device) draws the
     robot's true body and, if asked, its world, and each step pushes (one more launch per reset, one per step with pushes on).
     sensor_model: a SensorModel (robot_gym_amd/sim/sensor_model.py) or None; with one, obs and final_obs are what the sensors deliver
@@ -112,6 +113,9 @@ class BatchedGoEnv:
         if height_scan is not None:
             height_scan.bind(self.sim)
             self._scan_obs, self._scan_final = self._obs_cm[2 * self.num_cam_pts:], self._final_obs_cm[2 * self.num_cam_pts:]
+            # the robots whose scan a step takes: those not done BEFORE the tick.  A done robot is frozen (rg_goto.h, 5.): the task
+            # latches its path rows, but the simulator goes on integrating it, so its scan rows are kept by leaving it out here
+            self._live = torch.ones(B, dtype=torch.int32, device=dev)
         self.reset_mask = torch.zeros(B, dtype=torch.int32, device=dev)
         # randomizer: a DomainRandomizer (robot_gym_amd/sim/randomizer.py) or None.  With one, every reset draws the robot's true
         # body (and world) before the simulator stands it up, and every step pushes; without one nothing changes.
@@ -258,7 +262,8 @@ class BatchedGoEnv:
             self.state_estimator.on_reset(None if whole else idx)
         self._handle.observe(self.task_state.data_ptr(), self.sim.state.data_ptr(), self._paths, self._obs_cm.data_ptr())
         if self.height_scan is not None:
-            self.height_scan.observe(self.sim.state, out=self._scan_obs)
+            # set_path cleared the done flag of the robots it was given; a done robot outside idx keeps its last scan
+            self.height_scan.observe(self.sim.state, out=self._scan_obs, mask=torch.eq(self.task_state[goto_abi.ROW_DONE], 0.0, out=self._live))
         if self.sensor_model is not None:
             fresh = torch.zeros(B, dtype=torch.int32, device=self.device)
             fresh[torch.as_tensor(idx, device=self.device)] = 1
@@ -275,12 +280,14 @@ class BatchedGoEnv:
         if self.sensor_model is not None:
             action = self.sensor_model.act(action)   # noise and latency; pre_step clips what arrives to the action box
         ts, ss = self.task_state.data_ptr(), self.sim.state.data_ptr()
+        if self.height_scan is not None:
+            torch.eq(self.task_state[goto_abi.ROW_DONE], 0.0, out=self._live)   # before post_step sets the flag of a robot that finishes now
         self._handle.pre_step(ts, ss, self._paths, action.data_ptr(), self.cmd.data_ptr())
         self.ctl.get_action(0.0, self.sim.obs if self.state_estimator is None else self.state_estimator.estimate())
         self.sim.step(self.ctl, None if self.randomizer is None else self.randomizer.pushes())
         self._handle.post_step(ts, ss, self._paths, self._obs_cm.data_ptr(), self.reward.data_ptr(), self.done.data_ptr())
         if self.height_scan is not None:
-            self.height_scan.observe(self.sim.state, out=self._scan_obs)   # of a robot that just finished: its terminal scan
+            self.height_scan.observe(self.sim.state, out=self._scan_obs, mask=self._live)   # of a robot that just finished: its terminal scan
         if self.sensor_model is not None:
             self.sensor_model.observe(self._obs_cm)   # of a robot that just finished: its delivered terminal observation
         if self.auto_reset:

@@ -316,3 +316,67 @@ def test_closed_loop_levels_the_estimated_body_as_the_cpu_loop_does(robot):
         slope, se = EF.CPU_SLOPES[robot][axis]
         assert got[axis][0] < 0
         assert abs(got[axis][0] - slope) <= 3.0 * se, (robot, axis, got[axis], (slope, se))
+
+
+# ---- state rows the caller may write ---------------------------------------------------------------------------------------
+
+GUARD, SENTINEL = 64, -7.25
+TICK_VALUES = (np.nan, -3.0, 0.5, 2.0 ** 52 - 1.0, 2.0 ** 52, 1e30, np.inf)
+RUN_VALUES = (np.nan, -5.0, 1e30, float(EM.RUN_MAX - 1), float(EM.RUN_MAX))
+
+
+def test_tick_and_run_rows_the_caller_wrote_are_read_as_the_header_says():
+    """rg_est.h: the tick row is read as (uint64) fmin(fmax(v, 0), 2^52) and a run row as (uint64) fmin(fmax(v, 0), RG_EST_RUN_MAX), a
+    NaN as 0.  The kernel indexes nothing by these rows, so this checks arithmetic; the state lies between sentinel bands all the
+    same.  Even robots hold contact for three ticks (a run saturates), lift off, and touch down for three (the run passes the
+    debounce); odd robots lift off first."""
+    B = 65
+    rng = np.random.default_rng(65)
+    chain, cfg = M.Chain(MPCConfig.for_robot("ghost")), EM.settings(**EF.FULL)
+    keys = rng.permutation(B) + 2 ** 33
+    st = EM.new_state(B, keys)
+    rig = _Rig("ghost", B, EF.FULL, keys)
+    big = torch.full((st.size + 2 * GUARD,), SENTINEL, dtype=torch.float64, device=DEV)
+    guarded = big[GUARD:GUARD + st.size].view(st.shape)
+    guarded.copy_(rig.state)
+    rig.state = guarded                                                        # every call takes the pointer anew
+    EM.reset(np.ones(B), st)
+    rig.reset(np.ones(B))
+    worst = {}
+
+    def tick(k, contact):
+        true = EM.random_obs(rng, B, chain)
+        true["contact"][:] = contact
+        want = EM.estimate(cfg, chain, st, true)
+        _compare(rig.estimate(true), want, worst, k)
+        assert rig.state.cpu().numpy().tobytes() == st.tobytes(), k
+        return want
+
+    for k in range(3):
+        tick(k, rng.integers(0, 2, (4, B)))
+    b = np.arange(B)
+    st[EM.ROW_TICKS] = np.array(TICK_VALUES)[b % 7]
+    for leg in range(4):
+        st[EM.ROW_RUN + leg] = np.array(RUN_VALUES)[(b + leg) % 5]
+    rig.state.copy_(torch.as_tensor(st))
+    pattern = np.array([1, 1, 1, 0, 1, 1, 1])
+    seen = []
+    for k in range(7):
+        contact = np.where(b % 2 == 0, pattern[k], pattern[(k + 3) % 7])[None, :].repeat(4, 0)
+        seen.append(tick(3 + k, contact)["contact"])
+        run = st[EM.ROW_RUN:EM.ROW_RUN + 4]
+        if k == 0:      # what the header prescribes for the written values, stated without the model's bounded()
+            first = np.array([1.0, 1.0, float(EM.RUN_MAX), float(EM.RUN_MAX), float(EM.RUN_MAX)])
+            want = np.stack([np.where(b % 2 == 0, first[(b + leg) % 5], 0.0) for leg in range(4)])
+            assert (run == want).all()
+        if k == 2:      # a run that was one below the bound has saturated and stays
+            assert (run[:, b % 2 == 0] <= EM.RUN_MAX).all() and (run[0, (b % 2 == 0) & (b % 5 == 3)] == EM.RUN_MAX).all()
+    assert (st[EM.ROW_RUN:EM.ROW_RUN + 4][:, b % 2 == 0] == 3.0).all()           # lifted off on the fourth tick, three ticks down since
+    first = {0: 0.0, 1: 0.0, 2: 0.0, 3: 2.0 ** 52 - 1.0, 4: 2.0 ** 52, 5: 2.0 ** 52, 6: 2.0 ** 52}
+    assert (st[EM.ROW_TICKS] == np.array([min(first[k] + 7.0, 2.0 ** 52 + 1.0) for k in range(7)])[b % 7]).all()
+    seen = np.stack(seen)
+    assert not seen[4:6][:, :, b % 2 == 0].any() and seen[6][:, b % 2 == 0].any()          # inside the debounce of 2, then past it
+    print("est written rows", {n: round(v, 3) for n, v in worst.items()})
+    a = big.cpu().numpy()
+    assert np.all(a[:GUARD] == SENTINEL) and np.all(a[-GUARD:] == SENTINEL)
+    rig.close()

@@ -346,3 +346,80 @@ def test_collect_runs_on_delivered_observations():
     assert (env.sensor_model.state[SM.ROW_ACT_TICKS] <= 8).all() and (env.obs != env.true_obs).any()
     env.close()
     policy.close()
+
+
+# ---- state rows the caller may write ---------------------------------------------------------------------------------------
+
+GUARD, SENTINEL = 64, -7.25
+TICK_VALUES = (np.nan, -3.0, 0.5, 2.0 ** 52 - 1.0, 2.0 ** 52, 1e30, np.inf)
+DELAY_VALUES = (np.nan, -1.0, 2.7, 99.0, np.inf)
+
+
+def _guarded(host):
+    """A device copy of `host` between two bands of SENTINEL: (the whole buffer, the view)."""
+    big = torch.full((host.size + 2 * GUARD,), SENTINEL, dtype=torch.as_tensor(host).dtype, device=DEV)
+    view = big[GUARD:GUARD + host.size].view(host.shape)
+    view.copy_(torch.as_tensor(host))
+    return big, view
+
+
+def _bands_intact(big):
+    a = big.cpu().numpy()
+    assert np.all(a[:GUARD] == SENTINEL) and np.all(a[-GUARD:] == SENTINEL)
+
+
+def test_tick_and_delay_rows_the_caller_wrote_are_read_as_the_header_says():
+    """rg_sensor.h: a tick row v is read as (uint64) fmin(fmax(v, 0), 2^52), a delay row as (uint64) fmin(fmax(v, 0), delay_max), a
+    NaN as 0.  Every ring index is taken modulo the ring length, so this checks arithmetic, not memory safety; the rings lie between
+    sentinel bands all the same."""
+    B = 65
+    raw = dict(obs_dim=19, act_dim=2, seed=3, groups=[(1, 18, ALL_ON)], obs_delay_min=0, obs_delay_max=3, act_delay_min=0, act_delay_max=3,
+               act_noise_sigma=[0.1, 0.2], act_fill=[0.25, -0.5])
+    cfg = SM.settings(**raw)
+    D, A, Lo = cfg["obs_dim"], cfg["act_dim"], cfg["obs_delay_max"] + 1
+    rng = np.random.default_rng(65)
+    buf = SM.new_buffers(cfg, B, keys=rng.permutation(B) + 2 ** 33)
+    bands, dev = {}, {}
+    for n, v in buf.items():
+        bands[n], dev[n] = _guarded(v)
+    h = _handle(raw, B)
+    out = torch.zeros(B, A, dtype=torch.float32, device=DEV)
+
+    def tick(t):
+        clean, act_in = _clean(rng, D, B, t), rng.uniform(-1.0, 1.0, (B, A)).astype(np.float32)
+        SM.observe(cfg, buf, clean)
+        want = SM.act(cfg, buf, act_in)
+        dclean, din = torch.as_tensor(clean, device=DEV), torch.as_tensor(act_in, device=DEV)
+        h.observe(dev["state"].data_ptr(), dclean.data_ptr(), dev["obs_ring"].data_ptr(), dev["obs_out"].data_ptr())
+        h.act(dev["state"].data_ptr(), din.data_ptr(), dev["act_ring"].data_ptr(), out.data_ptr())
+        torch.cuda.synchronize()
+        assert torch.equal(_bits(out), _bits(torch.as_tensor(want))), t
+        _same(dev, buf, f"tick {t}")
+
+    clean0 = _clean(rng, D, B, 0)
+    SM.reset(cfg, np.ones(B, dtype=np.int32), buf, clean0)
+    mask, dclean = torch.ones(B, dtype=torch.int32, device=DEV), torch.as_tensor(clean0, device=DEV)
+    h.reset(mask.data_ptr(), dev["state"].data_ptr(), dclean.data_ptr(), dev["obs_ring"].data_ptr(), dev["obs_out"].data_ptr(), None, dev["act_ring"].data_ptr())
+    torch.cuda.synchronize()
+    _same(dev, buf, "reset")
+    assert set(buf["state"][SM.ROW_OBS_DELAY].tolist()) == set(buf["state"][SM.ROW_ACT_DELAY].tolist()) == {0.0, 1.0, 2.0, 3.0}
+    for t in range(1, 4):
+        tick(t)
+    b = np.arange(B)                                                            # 7 and 5 are coprime: every pair of a tick and a delay value
+    st = buf["state"]
+    st[SM.ROW_OBS_TICKS], st[SM.ROW_ACT_TICKS] = np.array(TICK_VALUES)[b % 7], np.array(TICK_VALUES)[(b + 3) % 7]
+    st[SM.ROW_OBS_DELAY], st[SM.ROW_ACT_DELAY] = np.array(DELAY_VALUES)[b % 5], np.array(DELAY_VALUES)[(b + 2) % 5]
+    dev["state"].copy_(torch.as_tensor(st))
+    written = st.copy()
+    for t in range(4, 4 + 2 * Lo + 1):
+        tick(t)
+    # what the header prescribes, stated without the model's bounded(): the rows after 2 Lo + 1 ticks
+    first = {0: 0.0, 1: 0.0, 2: 0.0, 3: 2.0 ** 52 - 1.0, 4: 2.0 ** 52, 5: 2.0 ** 52, 6: 2.0 ** 52}      # by index into TICK_VALUES
+    want_ticks = np.array([min(first[k] + 2 * Lo + 1, 2.0 ** 52 + 1.0) for k in range(7)])                 # past 2^52 the row stays at 2^52 + 1
+    assert (st[SM.ROW_OBS_TICKS] == want_ticks[b % 7]).all() and (st[SM.ROW_ACT_TICKS] == want_ticks[(b + 3) % 7]).all()
+    for row in (SM.ROW_OBS_DELAY, SM.ROW_ACT_DELAY):                                                       # observe and act write no delay row
+        assert st[row].tobytes() == written[row].tobytes()
+    assert (SM.bounded(np.array(DELAY_VALUES), 3) == np.array([0, 0, 2, 3, 3], dtype=np.uint64)).all()
+    for big in bands.values():
+        _bands_intact(big)
+    h.close()
