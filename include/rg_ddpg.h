@@ -61,7 +61,7 @@
  *   done != 0 (keras-rl's reset_states), then head = (head + 1) mod C, count = min(count + 1, C).  A head outside [0, C) (a ring
  *   state the caller spoilt) is first clamped to the nearest slot, 0 or C - 1, so that no write leaves the ring.
  * rg_ddpg_sample: idx int32 [M][2] = (age, robot), with replacement:
- *   h(draw) = seed; for w in (updates, m, draw): h = mix((h ^ w) + 0x9E3779B97F4A7C15);  age = 1 + h(0) mod (count - 1),
+ *   h(draw) = the hash of rg_stream.h over the words (updates, m, draw);  age = 1 + h(0) mod (count - 1),
  *   robot = h(1) mod B (unsigned).
  * rg_ddpg_critic_grad, per sample (age, robot) of idx: a' = target_actor(s1); Q' = target_critic([a', s1]);
  *   y = r + (gamma * nd) * Q' (float64); Q = critic([action, s0]); loss = (sum 0.5 (y - Q)^2) / M (keras-rl's huber_loss with

@@ -21,11 +21,9 @@
  *     written.  There is no trigonometric call, no pow and no exp: every operation is an integer operation or a correctly
  *     rounded + - * /, so tests/dr_model.py restates every output in numpy bit for bit.
  *
- * The stream is the counter-based hash of rg_episode.h, stateless:
- *      mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31   (uint64)
- *      hash(key, draw, purpose, index):  h = seed;  for w in (key, draw, purpose, index):  h = mix((h ^ w) + 0x9E3779B97F4A7C15)
- *      u(key, draw, purpose, index) = (hash >> 11) * 2^-53                                    in [0, 1)
- *   purpose: 0 mass, 1 inertia, 2 world, 3 push start, 4 push component, 5 push gate (RG_DR_PURPOSE_*).
+ * The stream is rg_stream.h's: hash and u over the words (key, draw, purpose, index).
+ *   purpose: 0 mass, 1 inertia, 2 world, 3 push start, 4 push component, 5 push gate (RG_DR_PURPOSE_*), block 0 of that
+ *   header's registry.
  *
  * State (owned by the caller): double dr_state[RG_DR_ROWS][B], component-major, integers stored as exactly representable
  * doubles (read as rg_episode.h reads its own: through int64 to uint64), rows

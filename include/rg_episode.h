@@ -35,10 +35,7 @@
  *
  * rg_episode_reset, per robot b with mask[b] != 0 (a robot whose mask is 0 costs its wave a load or two and an exit)
  *   a. Target.  targets[0][b], targets[1][b] if both are not NaN (an infinite entry is taken and fails the plan); otherwise,
- *      or with targets == NULL, a draw.  The stream is a counter-based hash, stateless: with
- *          mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31   (uint64)
- *          h = seed;  for w in (key, episode, attempt, axis):  h = mix((h ^ w) + 0x9E3779B97F4A7C15)
- *          u = (h >> 11) * 2^-53
+ *      or with targets == NULL, a draw: u of rg_stream.h over the words (key, episode, attempt, axis), stateless.
  *      key and episode are the robot's rows 9 and 0 as uint64, attempt counts from 0, axis is 0 (x) or 1 (y).  Then
  *      v = -2.5 + 5 u, c = rint(100 v), 0 < c < 100 -> 100, -100 < c < 0 -> -100, coordinate = (c + 0.0) / 100.0 (the sum
  *      turns -0.0 into 0.0).  (0, 0) is drawn again with attempt + 1 (at most 64 times).  This restates go_env.py:163-175 /

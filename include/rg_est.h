@@ -28,17 +28,8 @@
  *   - every value is computed in IEEE float64 with floating-point contraction off, every expression left to right as written;
  *     float32 only where a conversion is written.
  *
- * The stream is the counter-based hash of rg_episode.h, stateless:
- *      mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31   (uint64)
- *      hash(key, draw, purpose, index):  h = seed;  for w in (key, draw, purpose, index):  h = mix((h ^ w) + 0x9E3779B97F4A7C15)
- *      u(key, draw, purpose, index) = (hash >> 11) * 2^-53                                    in [0, 1)
- *      ix(k, row, j) = (k << 12) | (row << 2) | j     (uint64; k the robot's tick counter, row < 256, j in 0..3)
- *      n(key, draw, purpose, k, row) = (((u0 + u1) + (u2 + u3)) - 2.0) * 1.7320508075688772,   uj = u(key, draw, purpose, ix(k, row, j))
- *   n is an Irwin-Hall sum of four uniforms, centred and scaled to variance 1, NOT a Gaussian: |n| < 3.4642.
- *   purpose: 32 bias, 33 noise, 34 contact miss, 35 contact ghost (RG_EST_PURPOSE_*): disjoint from the purposes 0..5 of the
- *   domain randomisation and 16..21 of the sensor model, so a seed and a key shared with them do not correlate the streams.  (The
- *   target stream of rg_episode.h has no purpose word: its third word is the attempt, a different chain position by meaning; give
- *   the estimator a seed of its own where that matters.)
+ * The stream is rg_stream.h's: hash, u, ix and n (bounded, not a Gaussian) over the words (key, draw, purpose, index).
+ *   purpose: 32 bias, 33 noise, 34 contact miss, 35 contact ghost (RG_EST_PURPOSE_*), block 2 of that header's registry.
  *   `row` is the row of the value in the simulator's observation order: rpy 0..2, rpy_rate 3..5, v_world 6..8, quat 9..12,
  *   q 13..24, foot_pos 25..36, jac 37..72, contact 73..76.  One bias purpose and one noise purpose serve every sensor, because
  *   the row tells them apart.

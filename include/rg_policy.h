@@ -36,8 +36,7 @@
  *   formed as partial sums per workgroup (a fixed tree) and one finishing pass in a fixed order: the result is a function of
  *   the inputs and B alone.  No atomics.
  *
- * Noise.  Counter-based and stateless, on the mix of rg_episode.h:
- *     h(draw) = seed;  for w in (key, counter, axis, draw):  h = mix((h ^ w) + 0x9E3779B97F4A7C15)
+ * Noise.  Counter-based and stateless: h(draw) = the hash of rg_stream.h over the words (key, counter, axis, draw),
  *     u1 = ((h(0) >> 11) + 1) * 2^-53  (never 0),  u2 = (h(1) >> 11) * 2^-53
  *     eps = sqrt(-2 ln u1) * cos(6.283185307179586 * u2)   in float64, rounded to float32
  * axis is the action component.  tests/policy_model.py is the stream in numpy (ln and cos are the device's: an eps can

@@ -9,7 +9,7 @@
  *   - this model leaves the controller's own state estimate (the simulator's obs tensors) alone: its rpy and quat are both read
  *     by the controller's front kernel, and consistent errors on the two are the design of rg_est.h, the estimator model;
  *   - dropout is per row and per tick: there is no frame-level dropout (all rows of a sensor lost together);
- *   - the noise is white (no correlation over ticks or rows) and has bounded support (see `n` below);
+ *   - the noise is white (no correlation over ticks or rows) and has bounded support (`n` of rg_stream.h);
  *   - a robot's delays are drawn at its reset and constant over the episode.
  * Every magnitude is the caller's: the defaults are the identity (no group, delays 0, no action noise), and the identity
  * copies bits (-0.0f, NaN payloads and denormals survive).
@@ -26,21 +26,11 @@
  *     conversions float32 <-> float64 are used: there is no log, cos, sqrt or exp, so tests/sensor_model.py restates every
  *     output in numpy bit for bit.
  *
- * The stream is the counter-based hash of rg_episode.h, stateless:
- *      mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31   (uint64)
- *      hash(key, draw, purpose, index):  h = seed;  for w in (key, draw, purpose, index):  h = mix((h ^ w) + 0x9E3779B97F4A7C15)
- *      u(key, draw, purpose, index) = (hash >> 11) * 2^-53                                    in [0, 1)
+ * The stream is rg_stream.h's: hash, u, ix and n (see there why n is bounded and not a Gaussian) over the words (key, draw,
+ * purpose, index).
  *   purpose: 16 observation delay, 17 action delay, 18 bias, 19 observation noise, 20 dropout, 21 action noise
- *   (RG_SENSOR_PURPOSE_*): disjoint from the purposes 0..5 of the domain randomisation, so a seed and a key shared with it do
- *   not correlate the two.
- *   index of a per-tick draw:  ix(k, row, j) = (k << 12) | (row << 2) | j     (uint64; k the robot's tick counter, row < 256,
- *   j in 0..3)
- *   A unit-variance noise draw takes four hashes:
- *      n(key, draw, purpose, k, row) = (((u0 + u1) + (u2 + u3)) - 2.0) * 1.7320508075688772,   uj = u(key, draw, purpose, ix(k, row, j))
- *   This is an Irwin-Hall sum of four uniforms, centred and scaled to variance 1 (4 / 12 * 3), NOT a Gaussian: |n| < 3.4642
- *   (2 * sqrt 3), and its fourth moment is 2.7, not 3.  A Gaussian needs log and cos (or an inverse error function), whose
- *   device and host implementations differ in the last bits; four additions are correctly rounded everywhere, and that is
- *   what keeps the model bit-exact.
+ *   (RG_SENSOR_PURPOSE_*), block 1 of that header's registry.
+ *   The row of ix(k, row, j) is the observation row (< 256) or the action component.
  *
  * State (owned by the caller): double sensor_state[RG_SENSOR_ROWS][B], component-major, integers stored as exactly
  * representable doubles, rows

@@ -64,8 +64,8 @@
  *   The ground is a height h(x, y; robot) over a square lattice of vertices, float64 with contraction off.
  *   RANDOM: the reference's `random` heightfield made stateless and unbounded.  Vertex (i, j) sits at (i cell, j cell) and
  *     its height is amplitude * u(seed, key_robot, i >> 1, j >> 1) (arithmetic shifts: heights are constant over 2 x 2 vertex
- *     groups, as in the reference), u = (h >> 11) * 2^-53 of the chain of rg_episode.h over the words (key, I, J):
- *     h = seed; for w in (key, I, J): h = mix((h ^ w) + 0x9E3779B97F4A7C15), I and J as two's-complement 64-bit words.
+ *     groups, as in the reference), u of rg_stream.h over the words (key, I, J), I and J as two's-complement 64-bit
+ *     words.
  *     key: a caller-owned int64 [B] device row the caller initialises (robots with equal keys walk the same world); NULL
  *     means key 0 for every robot.  The reference's defaults: cell 0.05, amplitude 0.06.
  *   GRID: caller-owned float64 heights[rows][cols] on the device, heights[i][j] at (x0 + i cell, y0 + j cell), indices

@@ -18,27 +18,17 @@ struct NetDesc {
 
 // ---- the noise stream -------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
+#include "rg_stream_dev.inc"   // the chain over the four words (key, counter, axis, draw)
 
 __device__ __forceinline__ unsigned long long noise_hash(unsigned long long seed, unsigned long long key, unsigned long long counter,
                                                          unsigned long long axis, unsigned long long draw) {
-  unsigned long long h = seed;
-  h = mix64((h ^ key) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ counter) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ axis) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ draw) + 0x9E3779B97F4A7C15ull);
-  return h;
+  return mix_word(mix_word(mix_word(mix_word(seed, key), counter), axis), draw);
 }
 
 // the standard normal of (seed, key, counter, axis): rg_policy.h, Noise
 __device__ __forceinline__ float noise_eps(unsigned long long seed, unsigned long long key, unsigned long long counter, unsigned long long axis) {
   const double u1 = (double)((noise_hash(seed, key, counter, axis, 0) >> 11) + 1ull) * 0x1.0p-53;
-  const double u2 = (double)(noise_hash(seed, key, counter, axis, 1) >> 11) * 0x1.0p-53;
+  const double u2 = unit53(noise_hash(seed, key, counter, axis, 1));
   return (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
 }
 

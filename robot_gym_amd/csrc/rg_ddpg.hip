@@ -60,14 +60,10 @@ struct Geo {
   double gamma;
 };
 
-// the sample stream: rg_ddpg.h, rg_ddpg_sample
+// the sample stream: rg_ddpg.h, rg_ddpg_sample (the chain of rg_stream_dev.inc, which rg_agent_dev.inc includes)
 __device__ __forceinline__ unsigned long long sample_hash(unsigned long long seed, unsigned long long updates, unsigned long long m,
                                                           unsigned long long draw) {
-  unsigned long long h = seed;
-  h = mix64((h ^ updates) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ m) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ draw) + 0x9E3779B97F4A7C15ull);
-  return h;
+  return mix_word(mix_word(mix_word(seed, updates), m), draw);
 }
 
 __device__ __forceinline__ bool short_ring(const long long *__restrict__ state) { return state[1] < 2; }

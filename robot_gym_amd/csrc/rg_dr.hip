@@ -6,8 +6,7 @@
 // Layout: lane = robot, float64 and 64-bit integers, no LDS, no cross-lane operation, 256-thread workgroups.  Consecutive
 // lanes are consecutive robots and every load and store is row * B + b, so all of them coalesce.  A lane past the batch
 // leaves at once; a robot outside the mask leaves after the mask load, so a wave with nobody to draw for costs a load and
-// an exit.  The stream is the chain of rg_episode.h (rg_srb_ground.inc has the same rounds for the ground; they are
-// restated here because that file is the ground function's and needs the ground's types).
+// an exit.  The stream is rg_stream_dev.inc's, the one the ground function reads the world key with.
 //
 // Parity: tests/dr_model.py restates every output in numpy (uint64 and float64), bit for bit.  Floating-point contraction
 // is off for the whole file.
@@ -45,7 +44,6 @@ struct rg_dr_handle {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr double kStepsBound = 4503599627370496.0;   // 2^52: steps are clamped to it before they become an integer
 
 struct DrCfg {
   int B, worlds, interval, ticks, substeps;
@@ -54,17 +52,11 @@ struct DrCfg {
   double amp[6];
 };
 
-// the chain of rg_episode.h over the four words (key, draw, purpose, index)
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-__device__ __forceinline__ unsigned long long mix_word(unsigned long long h, unsigned long long w) { return mix64((h ^ w) + 0x9E3779B97F4A7C15ull); }
-__device__ __forceinline__ double unit53(unsigned long long h) { return (double)(h >> 11) * 0x1.0p-53; }
-// a state row's integer, as rg_episode.hip reads its own
-__device__ __forceinline__ unsigned long long word_of(double v) { return (unsigned long long)(long long)v; }
+#include "rg_stream_dev.inc"   // the chain over the four words (key, draw, purpose, index)
+
+static_assert(purposes_in_block(0, RG_DR_PURPOSE_MASS, RG_DR_PURPOSE_INERTIA, RG_DR_PURPOSE_WORLD, RG_DR_PURPOSE_PUSH_START, RG_DR_PURPOSE_PUSH_COMPONENT,
+                                RG_DR_PURPOSE_PUSH_GATE),
+              "the randomiser's purposes are block 0 of rg_stream.h's registry, 0..15");
 
 // body of robot b = base scaled: mass by sm, I by si, I^-1 by 1 / si
 __device__ __forceinline__ void write_body(const double *__restrict__ base, double *__restrict__ body, size_t sB, int b, double sm, double si) {
@@ -113,7 +105,7 @@ __global__ void __launch_bounds__(kBlock) rg_dr_push_kernel(DrCfg c, const doubl
   if (b >= c.B) return;
   const size_t sB = (size_t)c.B;
   const double steps = sim_state[RG_SRB_ROW_STEPS * sB + b];
-  const unsigned long long k = (unsigned long long)fmin(fmax(steps, 0.0), kStepsBound) / (unsigned long long)c.substeps;   // a NaN is 0
+  const unsigned long long k = bounded(steps, kTickBound) / (unsigned long long)c.substeps;   // steps are clamped like a tick row
   const unsigned long long interval = (unsigned long long)c.interval, ticks = (unsigned long long)c.ticks;
   const unsigned long long win = k / interval, r = k % interval;
   const unsigned long long hd = mix_word(mix_word(c.seed, word_of(st[RG_DR_ROW_KEY * sB + b])), word_of(st[RG_DR_ROW_DRAWS * sB + b]));

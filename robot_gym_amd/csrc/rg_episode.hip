@@ -55,22 +55,12 @@ struct EpDev {
   double ox[kMaxObs], oy[kMaxObs];   // the obstacles; without any, the planner's dummy one
 };
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
+#include "rg_stream_dev.inc"
 
 // one coordinate of the target stream (rg_episode.h, a.)
 __device__ __forceinline__ double draw_coord(unsigned long long seed, unsigned long long key, unsigned long long episode,
                                              unsigned long long attempt, unsigned long long axis) {
-  unsigned long long h = seed;
-  h = mix64((h ^ key) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ episode) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ attempt) + 0x9E3779B97F4A7C15ull);
-  h = mix64((h ^ axis) + 0x9E3779B97F4A7C15ull);
-  const double u = (double)(h >> 11) * 0x1.0p-53;
+  const double u = unit53(mix_word(mix_word(mix_word(mix_word(seed, key), episode), attempt), axis));
   const double v = -2.5 + 5.0 * u;
   double c = rint(100.0 * v);
   if (c > 0.0 && c < 100.0) c = 100.0;
@@ -117,11 +107,11 @@ __global__ void __launch_bounds__(kWave) rg_episode_plan_kernel(const EpCfg c, c
   if (lane < c.nobs) { obx[lane] = a.dv->ox[lane]; oby[lane] = a.dv->oy[lane]; }
   __syncthreads();
   // a. target
-  const unsigned long long key = (unsigned long long)(long long)a.ep[RG_EPISODE_ROW_KEY * sB + b];
+  const unsigned long long key = word_of(a.ep[RG_EPISODE_ROW_KEY * sB + b]);
   const double episode = a.ep[RG_EPISODE_ROW_EPISODE * sB + b];
   double gx = a.targets ? a.targets[b] : __builtin_nan(""), gy = a.targets ? a.targets[sB + b] : __builtin_nan("");
   if (gx != gx || gy != gy) {
-    const unsigned long long e = (unsigned long long)(long long)episode;
+    const unsigned long long e = word_of(episode);
     #pragma unroll 1
     for (unsigned long long attempt = 0; attempt < 64; attempt++) {
       gx = draw_coord(c.seed, key, e, attempt, 0);

@@ -14,7 +14,7 @@
 // (unrolled loops); the tests on them are uniform over the grid, so a skipped term costs no divergence.  The leg chains are read
 // from device memory (the DevCfg the create uploaded), where indexing by the leg is an address, not a register file.
 //
-// The stream is the chain of rg_episode.h, restated here as every unit that draws restates it.
+// The stream is rg_stream_dev.inc's.
 // Parity: tests/est_model.py restates every output in numpy; bit for bit but for the rows that go through sqrt, atan2, asin and
 // the kinematics' sincos (quat, rpy, foot_pos, jac).  Floating-point contraction is off for the whole file.
 #include <hip/hip_runtime.h>
@@ -46,9 +46,7 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kRobots = 64;                          // robots of a workgroup of estimate: one wave per leg
-constexpr double kTickBound = 4503599627370496.0;    // 2^52: a tick row is clamped to it before it becomes an integer
 constexpr double kRunMax = (double)RG_EST_RUN_MAX;
-constexpr double kRoot3 = 1.7320508075688772;
 
 struct EstCfg {
   int B, rise;
@@ -57,30 +55,15 @@ struct EstCfg {
   double enc_bias, enc_sigma, enc_quantum, miss, ghost;
 };
 
-// the chain of rg_episode.h over the four words (key, draw, purpose, index)
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-__device__ __forceinline__ unsigned long long mix_word(unsigned long long h, unsigned long long w) { return mix64((h ^ w) + 0x9E3779B97F4A7C15ull); }
-__device__ __forceinline__ double unit53(unsigned long long h) { return (double)(h >> 11) * 0x1.0p-53; }
-// a state row's integer, as rg_episode.hip reads its own
-__device__ __forceinline__ unsigned long long word_of(double v) { return (unsigned long long)(long long)v; }
-// a tick or run row, which the caller may have written: clamped, a NaN is 0
-__device__ __forceinline__ unsigned long long bounded(double v, double hi) { return (unsigned long long)fmin(fmax(v, 0.0), hi); }
+#include "rg_stream_dev.inc"   // the chain over the four words (key, draw, purpose, index)
 
-// n of rg_est.h: hp = the chain up to and with the purpose, ix = ix(k, row, 0)
-__device__ __forceinline__ double unit_noise(unsigned long long hp, unsigned long long ix) {
-  const double u0 = unit53(mix_word(hp, ix)), u1 = unit53(mix_word(hp, ix | 1ull)), u2 = unit53(mix_word(hp, ix | 2ull)), u3 = unit53(mix_word(hp, ix | 3ull));
-  return (((u0 + u1) + (u2 + u3)) - 2.0) * kRoot3;
-}
+static_assert(purposes_in_block(2, RG_EST_PURPOSE_BIAS, RG_EST_PURPOSE_NOISE, RG_EST_PURPOSE_MISS, RG_EST_PURPOSE_GHOST),
+              "the estimator model's purposes are block 2 of rg_stream.h's registry, 32..47");
 
 // x + bias(w, row) + noise(s, k, row), each term skipped where its amplitude is 0; hb, hn = the chain with the purpose
 __device__ __forceinline__ double perturb(double x, double w, double s, unsigned long long hb, unsigned long long hn, unsigned long long k, int row) {
   if (w != 0.0) x = x + w * (2.0 * unit53(mix_word(hb, (unsigned long long)row)) - 1.0);
-  if (s != 0.0) x = x + s * unit_noise(hn, (k << 12) | ((unsigned long long)row << 2));
+  if (s != 0.0) x = x + s * unit_noise(hn, index_word(k, row));
   return x;
 }
 
@@ -159,7 +142,7 @@ __global__ void __launch_bounds__(kBlock) rg_est_estimate_kernel(EstCfg c, const
       e.contact[at] = raw;
     } else {
       const bool seen = on && run > (unsigned long long)c.rise;
-      const unsigned long long ix = (k << 12) | ((unsigned long long)(RG_EST_OBS_ROW_CONTACT + leg) << 2);
+      const unsigned long long ix = index_word(k, RG_EST_OBS_ROW_CONTACT + leg);
       int out = seen ? 1 : 0;
       if (seen && c.miss != 0.0 && unit53(mix_word(mix_word(hd, RG_EST_PURPOSE_MISS), ix)) < c.miss) out = 0;
       if (!on && c.ghost != 0.0 && unit53(mix_word(mix_word(hd, RG_EST_PURPOSE_GHOST), ix)) < c.ghost) out = 1;

@@ -12,7 +12,7 @@
 // No LDS, no atomics, no cross-lane operation.  The groups and the per-component settings are read from the kernel argument
 // with constant indices only (unrolled loops and selects), so nothing is indexed dynamically and nothing goes to scratch.
 //
-// The stream is the chain of rg_episode.h, restated here as every unit that draws restates it.
+// The stream is rg_stream_dev.inc's.
 // Parity: tests/sensor_model.py restates every output in numpy (uint64 and float64), bit for bit.  Floating-point
 // contraction is off for the whole file.
 #include <hip/hip_runtime.h>
@@ -36,8 +36,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kRobots = 32;                  // robots of a workgroup of reset and observe
 constexpr int kSlices = kBlock / kRobots;    // lanes of a robot: row slices
-constexpr double kTickBound = 4503599627370496.0;   // 2^52: a tick row is clamped to it before it becomes an integer
-constexpr double kRoot3 = 1.7320508075688772;
 
 struct SensorCfg {
   int B, D, A, Lo, La;
@@ -48,25 +46,11 @@ struct SensorCfg {
   double act_sigma[RG_SENSOR_MAX_ACT], act_fill[RG_SENSOR_MAX_ACT];
 };
 
-// the chain of rg_episode.h over the four words (key, draw, purpose, index)
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-__device__ __forceinline__ unsigned long long mix_word(unsigned long long h, unsigned long long w) { return mix64((h ^ w) + 0x9E3779B97F4A7C15ull); }
-__device__ __forceinline__ double unit53(unsigned long long h) { return (double)(h >> 11) * 0x1.0p-53; }
-// a state row's integer, as rg_episode.hip reads its own
-__device__ __forceinline__ unsigned long long word_of(double v) { return (unsigned long long)(long long)v; }
-// a tick or delay row, which the caller may have written: clamped, a NaN is 0
-__device__ __forceinline__ unsigned long long bounded(double v, double hi) { return (unsigned long long)fmin(fmax(v, 0.0), hi); }
+#include "rg_stream_dev.inc"   // the chain over the four words (key, draw, purpose, index)
 
-// n of rg_sensor.h: hp = the chain up to and with the purpose, ix = ix(k, row, 0)
-__device__ __forceinline__ double unit_noise(unsigned long long hp, unsigned long long ix) {
-  const double u0 = unit53(mix_word(hp, ix)), u1 = unit53(mix_word(hp, ix | 1ull)), u2 = unit53(mix_word(hp, ix | 2ull)), u3 = unit53(mix_word(hp, ix | 3ull));
-  return (((u0 + u1) + (u2 + u3)) - 2.0) * kRoot3;
-}
+static_assert(purposes_in_block(1, RG_SENSOR_PURPOSE_OBS_DELAY, RG_SENSOR_PURPOSE_ACT_DELAY, RG_SENSOR_PURPOSE_BIAS, RG_SENSOR_PURPOSE_NOISE,
+                                RG_SENSOR_PURPOSE_DROPOUT, RG_SENSOR_PURPOSE_ACT_NOISE),
+              "the sensor model's purposes are block 1 of rg_stream.h's registry, 16..31");
 
 // the delay of an episode in lo .. hi
 __device__ __forceinline__ unsigned long long draw_delay(unsigned long long hd, unsigned long long purpose, int lo, int hi) {
@@ -82,7 +66,7 @@ __device__ __forceinline__ float measure(const SensorCfg &c, unsigned long long 
   for (int g = 0; g < RG_SENSOR_MAX_GROUPS; g++)
     if (r >= c.begin[g] && r < c.end[g]) { sigma = c.sigma[g]; bias = c.bias[g]; prob = c.prob[g]; dropv = c.dropv[g]; quantum = c.quantum[g]; }
   if (sigma == 0.0 && bias == 0.0 && prob == 0.0 && quantum == 0.0) return clean;   // bits
-  const unsigned long long ix = (k << 12) | ((unsigned long long)r << 2);
+  const unsigned long long ix = index_word(k, r);
   double x = (double)clean;
   if (bias != 0.0) x = x + bias * (2.0 * unit53(mix_word(mix_word(hd, RG_SENSOR_PURPOSE_BIAS), (unsigned long long)r)) - 1.0);
   if (sigma != 0.0) x = x + sigma * unit_noise(mix_word(hd, RG_SENSOR_PURPOSE_NOISE), ix);
@@ -168,7 +152,7 @@ __global__ void __launch_bounds__(kBlock) rg_sensor_act_kernel(SensorCfg c, doub
     if (a < c.A) {
       float v = act_in[(size_t)b * c.A + a];
       const double sigma = c.act_sigma[a];
-      if (sigma != 0.0) v = (float)((double)v + sigma * unit_noise(hp, (k << 12) | ((unsigned long long)a << 2)));
+      if (sigma != 0.0) v = (float)((double)v + sigma * unit_noise(hp, index_word(k, a)));
       const size_t at = (size_t)a * sB + b;
       ring[wr + at] = v;
       act_out[(size_t)b * c.A + a] = rd == wr ? v : ring[rd + at];

@@ -4,15 +4,7 @@
 
 constexpr double kCoordBound = 1099511627776.0;   // 2^40: lattice coordinates are clamped to it before they become integers
 
-// the chain of rg_episode.h
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-__device__ __forceinline__ unsigned long long mix_word(unsigned long long h, unsigned long long w) { return mix64((h ^ w) + 0x9E3779B97F4A7C15ull); }
-__device__ __forceinline__ double unit53(unsigned long long h) { return (double)(h >> 11) * 0x1.0p-53; }
+#include "rg_stream_dev.inc"   // the chain over the three words (key, I, J)
 
 // h(x, y; robot b) of rg_srb.h.  g.kind is RANDOM or GRID (wave-uniform).
 struct Ground {

@@ -22,6 +22,7 @@ through DomainRandomizer.set_body, which forwards, captures the new base and sca
 import torch
 
 from robot_gym_amd.core import dr_abi
+from robot_gym_amd.sim.stream_state import copy_robot_columns, stream_state
 from robot_gym_amd.sim.terrain import RandomTerrain
 
 PUSH_FIELDS = ("push_interval", "push_ticks", "push_probability", "push_force_xy", "push_force_z", "push_torque_xy", "push_torque_z")
@@ -64,8 +65,7 @@ class DomainRandomizer:
         self._handle = dr_abi.DrHandle(B, dev, substeps=sim.substeps, **self.settings)
         self.batch, self.device, self.sim = B, dev, sim
         self._keys = keys if self.new_world_each_episode else None
-        self.state = torch.zeros(dr_abi.ROWS, B, dtype=torch.float64, device=dev)
-        self.state[dr_abi.ROW_KEY] = torch.arange(B, dtype=torch.float64, device=dev)
+        self.state = stream_state(dr_abi.ROWS, B, dev)
         self.state[dr_abi.ROW_MASS_SCALE] = 1.0
         self.state[dr_abi.ROW_INERTIA_SCALE] = 1.0
         if torch.is_tensor(keys):
@@ -132,10 +132,7 @@ class DomainRandomizer:
         draws), then the body of every dst robot from its new scales.  The terrain key itself goes with
         BatchedSRBSim.copy_columns."""
         self._bound("copy_columns")
-        s, t = self.sim._index(src), self.sim._index(dst)
-        if s.numel() != t.numel():
-            raise ValueError("copy_columns: src and dst differ in length")
-        self.state.index_copy_(1, t, self.state.index_select(1, s))
+        t = copy_robot_columns([(self.state, 1)], src, dst, index=self.sim._index)
         mask = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
         mask[t] = 1
         self.apply(mask)

@@ -20,6 +20,7 @@ Gaussian: that is what keeps tests/sensor_model.py bit-exact); a robot's delays 
 import torch
 
 from robot_gym_amd.core import sensor_abi
+from robot_gym_amd.sim.stream_state import copy_robot_columns, stream_state
 
 
 def _pair(v, name):
@@ -73,8 +74,7 @@ class SensorModel:
         self.batch, self.device, self.obs_dim, self.act_dim = B, self._handle.device, D, A
         dev = self.device
         self.bound_groups = groups
-        self.state = torch.zeros(sensor_abi.ROWS, B, dtype=torch.float64, device=dev)
-        self.state[sensor_abi.ROW_KEY] = torch.arange(B, dtype=torch.float64, device=dev)
+        self.state = stream_state(sensor_abi.ROWS, B, dev)
         self.obs_ring = torch.zeros(self.settings["obs_delay_max"] + 1, D, B, dtype=torch.float32, device=dev)
         self.act_ring = torch.zeros(self.settings["act_delay_max"] + 1, A, B, dtype=torch.float32, device=dev)
         self.obs_out = torch.zeros(D, B, dtype=torch.float32, device=dev)
@@ -128,12 +128,8 @@ class SensorModel:
         """The state, ring and delivered columns of robot src[k] into robot dst[k] (index tensors or lists): the clone sees and
         applies what its source does, the key included."""
         self._bound("copy_columns")
-        s = torch.as_tensor(src, dtype=torch.int64, device=self.device).reshape(-1)
-        t = torch.as_tensor(dst, dtype=torch.int64, device=self.device).reshape(-1)
-        if s.numel() != t.numel():
-            raise ValueError("copy_columns: src and dst differ in length")
-        for ten, dim in ((self.state, 1), (self.obs_ring, 2), (self.act_ring, 2), (self.obs_out, 1), (self.final_obs, 1), (self.act_out, 0)):
-            ten.index_copy_(dim, t, ten.index_select(dim, s))
+        copy_robot_columns(((self.state, 1), (self.obs_ring, 2), (self.act_ring, 2), (self.obs_out, 1), (self.final_obs, 1), (self.act_out, 0)), src, dst,
+                           index=lambda idx: torch.as_tensor(idx, dtype=torch.int64, device=self.device).reshape(-1))
 
     def close(self):
         if self._handle is not None:

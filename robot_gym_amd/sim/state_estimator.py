@@ -23,6 +23,7 @@ downstream and unchanged.
 import torch
 
 from robot_gym_amd.core import est_abi, srb_abi
+from robot_gym_amd.sim.stream_state import copy_robot_columns, stream_state
 
 GROUPS = {
     "imu": dict(bias_half_width="imu_bias_half_width", noise_sigma="imu_noise_sigma"),
@@ -80,8 +81,7 @@ class StateEstimator:
         B, dev = sim.batch, sim.device
         self._handle = est_abi.EstHandle(B, sim.cfg, dev, sim_settings=dict(dt_sim=sim.dt_sim, substeps=sim.substeps), **self.settings)
         self.batch, self.device, self.sim = B, dev, sim
-        self.state = torch.zeros(est_abi.ROWS, B, dtype=torch.float64, device=dev)
-        self.state[est_abi.ROW_KEY] = torch.arange(B, dtype=torch.float64, device=dev)
+        self.state = stream_state(est_abi.ROWS, B, dev)
         self._own = {name: torch.zeros_like(sim.obs[name]) for name in srb_abi.OBS_FIELDS}
         self._true_ptrs, self._est_ptrs = sim._obs_ptrs, srb_abi.CObsPtrs()
         for name in srb_abi.OBS_FIELDS:
@@ -127,11 +127,7 @@ class StateEstimator:
         """The state and estimate columns of robot src[k] into robot dst[k] (index tensors or lists): the clone is given what
         its source is given, the key included."""
         self._bound("copy_columns")
-        s, t = self.sim._index(src), self.sim._index(dst)
-        if s.numel() != t.numel():
-            raise ValueError("copy_columns: src and dst differ in length")
-        for ten in [self.state] + list(self._own.values()):
-            ten.index_copy_(ten.dim() - 1, t, ten.index_select(ten.dim() - 1, s))
+        copy_robot_columns([(ten, ten.dim() - 1) for ten in [self.state] + list(self._own.values())], src, dst, index=self.sim._index)
 
     def close(self):
         if self._handle is not None:

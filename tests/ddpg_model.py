@@ -10,7 +10,7 @@ import numpy as np
 
 from tests import policy_model as PM
 from tests import ppo_update_model as UM
-from tests.episode_model import GOLDEN, M64, mix64
+from tests.stream_model import chain as sample_hash     # over (updates, m, draw)
 
 adam_step = UM.adam_step
 tensors = UM.tensors
@@ -86,13 +86,6 @@ def ou_step(x, eps, theta=0.5, mu=0.4, sigma=0.3, dt=1e-2):
     """One Ornstein-Uhlenbeck step in float64 over float32 x and eps, rounded to float32 (rg_ddpg.h, rg_ddpg_act)."""
     x, eps = np.asarray(x, dtype=np.float32).astype(np.float64), np.asarray(eps, dtype=np.float32).astype(np.float64)
     return ((x + (theta * (mu - x)) * dt) + (sigma * math.sqrt(dt)) * eps).astype(np.float32)
-
-
-def sample_hash(seed, updates, m, draw):
-    h = seed & M64
-    for w in (updates, m, draw):
-        h = mix64(((h ^ (w & M64)) + GOLDEN) & M64)
-    return h
 
 
 def sample(seed, updates, M, count, B):

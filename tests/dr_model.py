@@ -1,38 +1,17 @@
-"""Numpy model of the domain randomisation (include/rg_dr.h): the stream in uint64, every real in float64 with each
+"""Numpy model of the domain randomisation (include/rg_dr.h): the stream of tests/stream_model.py, every real in float64 with each
 expression evaluated left to right as the header writes it, so that the device's outputs are compared bit for bit.  The
 state is the header's [8, B] table; the body table is [19, B] (mass, I, I^-1)."""
 import numpy as np
 
-M64 = (1 << 64) - 1
-GOLDEN = 0x9E3779B97F4A7C15
+from tests.stream_model import GOLDEN, M64, mix64, uniform  # noqa: F401
+from tests.stream_model import chain as hash4
+
 ROWS, BODY_ROWS = 8, 19
 ROW_KEY, ROW_DRAWS, ROW_MASS_SCALE, ROW_INERTIA_SCALE, ROW_WORLD = range(5)
 MASS, INERTIA, WORLD, PUSH_START, PUSH_COMPONENT, PUSH_GATE = range(6)
 STEPS_ROW = 41
 DEFAULTS = dict(worlds=0, seed=0, mass_lo=1.0, mass_hi=1.0, inertia_lo=1.0, inertia_hi=1.0, push_interval=0, push_ticks=0, push_probability=0.0,
                 push_force_xy=0.0, push_force_z=0.0, push_torque_xy=0.0, push_torque_z=0.0, substeps=10)
-
-
-def mix64(z):
-    z &= M64
-    z ^= z >> 30
-    z = (z * 0xBF58476D1CE4E5B9) & M64
-    z ^= z >> 27
-    z = (z * 0x94D049BB133111EB) & M64
-    z ^= z >> 31
-    return z
-
-
-def hash4(seed, key, draw, purpose, index):
-    h = seed & M64
-    for w in (key, draw, purpose, index):
-        h = mix64(((h ^ (int(w) & M64)) + GOLDEN) & M64)
-    return h
-
-
-def uniform(seed, key, draw, purpose, index):
-    """The 53-bit uniform in [0, 1) of the four words."""
-    return float(hash4(seed, key, draw, purpose, index) >> 11) * 2.0 ** -53
 
 
 def word(v):

@@ -10,9 +10,8 @@ from concurrent.futures import ProcessPoolExecutor
 import numpy as np
 
 from robot_gym_amd.gym import goto_path
+from tests.stream_model import GOLDEN, M64, mix64, uniform  # noqa: F401  (uniform: of seed, robot key, episode, attempt, axis)
 
-M64 = (1 << 64) - 1
-GOLDEN = 0x9E3779B97F4A7C15
 # A stop test with |d - reso| < FLAG_REL * reso may go either way on the device (its hypot is not libm's) -- unless one of the
 # two components is exactly 0: hypot(x, +-0) is |x| exactly on both sides (C Annex F; the device's scales and takes one
 # sqrt), so that test cannot flip and is not flagged.  That case is common: a target with a negative coordinate is the
@@ -25,24 +24,6 @@ PLAN_OK, PLAN_TARGET, PLAN_WAYPOINTS, PLAN_SHORT, PLAN_LONG = range(5)
 (ROW_EPISODE, ROW_PLAN_STATUS, ROW_RETURN, ROW_LENGTH, ROW_LAST_RETURN, ROW_LAST_LENGTH, ROW_LAST_REASON, ROW_NPTS, ROW_NWAY, ROW_KEY,
  ROW_ENDED) = range(11)
 ROWS = 12
-
-
-def mix64(z):
-    z &= M64
-    z ^= z >> 30
-    z = (z * 0xBF58476D1CE4E5B9) & M64
-    z ^= z >> 27
-    z = (z * 0x94D049BB133111EB) & M64
-    z ^= z >> 31
-    return z
-
-
-def uniform(seed, key, episode, attempt, axis):
-    """The 53-bit uniform of (seed, robot key, episode, attempt, axis)."""
-    h = seed & M64
-    for w in (key, episode, attempt, axis):
-        h = mix64(((h ^ (w & M64)) + GOLDEN) & M64)
-    return (h >> 11) * 2.0 ** -53
 
 
 def coordinate(u):

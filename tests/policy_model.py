@@ -6,7 +6,8 @@ import math
 
 import numpy as np
 
-from tests.episode_model import GOLDEN, M64, mix64
+from tests.stream_model import M64  # noqa: F401
+from tests.stream_model import chain as noise_hash     # over (key, counter, axis, draw)
 
 NORM_COLS, NORM_REWARD, NORM_ROWS = 65, 64, 195
 LOG_2PI = 1.8378770664093453
@@ -14,13 +15,6 @@ TWO_PI = 6.283185307179586
 
 
 # ---- the noise stream -------------------------------------------------------------------------------------------------
-
-def noise_hash(seed, key, counter, axis, draw):
-    h = seed & M64
-    for w in (key, counter, axis, draw):
-        h = mix64(((h ^ (w & M64)) + GOLDEN) & M64)
-    return h
-
 
 def uniforms(seed, key, counter, axis):
     """(u1, u2): u1 in (0, 1], u2 in [0, 1)."""

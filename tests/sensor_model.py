@@ -1,106 +1,19 @@
 """Numpy model of the sensor and actuator model (include/rg_sensor.h), written from the header alone: the stream in uint64,
 every real in float64 with each expression evaluated left to right as the header writes it, float32 only where the header
-converts, so that the device's outputs are compared bit for bit.  Arrays are vectorised over rows and robots; the scalar
-functions (hash4, uniform) are the plain restatement the vector ones are checked against.
+converts, so that the device's outputs are compared bit for bit.  Arrays are vectorised over rows and robots.  The stream
+is tests/stream_model.py's; its names are kept here (hash4 and vhash are its chain and vchain) for the tests that use them.
 
 A configuration is a dict: DEFAULTS' fields; groups is a list of (begin, end, dict of GROUP_DEFAULTS' fields)."""
 import numpy as np
 
-M64 = (1 << 64) - 1
-GOLDEN = 0x9E3779B97F4A7C15
+from tests.stream_model import GOLDEN, M64, U, bounded, delay_draw, ix, mix64, noise, uniform, vmix, vnoise, vuniform, words  # noqa: F401
+from tests.stream_model import chain as hash4, vchain as vhash  # noqa: F401
+
 ROWS = 8
 ROW_KEY, ROW_DRAWS, ROW_OBS_TICKS, ROW_ACT_TICKS, ROW_OBS_DELAY, ROW_ACT_DELAY = range(6)
 OBS_DELAY, ACT_DELAY, BIAS, NOISE, DROPOUT, ACT_NOISE = range(16, 22)
-ROOT3 = 1.7320508075688772
 GROUP_DEFAULTS = dict(noise_sigma=0.0, bias_half_width=0.0, dropout_probability=0.0, dropout_value=0.0, quantum=0.0)
 DEFAULTS = dict(obs_dim=1, act_dim=1, seed=0, groups=(), obs_delay_min=0, obs_delay_max=0, act_delay_min=0, act_delay_max=0, act_noise_sigma=(), act_fill=())
-
-U = np.uint64
-
-
-# ---- the stream: scalars -------------------------------------------------------------------------------------------------
-
-def mix64(z):
-    z &= M64
-    z ^= z >> 30
-    z = (z * 0xBF58476D1CE4E5B9) & M64
-    z ^= z >> 27
-    z = (z * 0x94D049BB133111EB) & M64
-    z ^= z >> 31
-    return z
-
-
-def hash4(seed, key, draw, purpose, index):
-    h = seed & M64
-    for w in (key, draw, purpose, index):
-        h = mix64(((h ^ (int(w) & M64)) + GOLDEN) & M64)
-    return h
-
-
-def uniform(seed, key, draw, purpose, index):
-    """The 53-bit uniform in [0, 1) of the four words."""
-    return float(hash4(seed, key, draw, purpose, index) >> 11) * 2.0 ** -53
-
-
-def ix(k, row, j=0):
-    """The index word of a per-tick draw."""
-    return ((int(k) << 12) | (int(row) << 2) | int(j)) & M64
-
-
-def noise(seed, key, draw, purpose, k, row):
-    """n of the header: one unit-variance draw, a scalar."""
-    u0, u1, u2, u3 = (uniform(seed, key, draw, purpose, ix(k, row, j)) for j in range(4))
-    return (((u0 + u1) + (u2 + u3)) - 2.0) * ROOT3
-
-
-def delay_draw(seed, key, draw, purpose, lo, hi):
-    return lo + min(int(float(hi - lo + 1) * uniform(seed, key, draw, purpose, 0)), hi - lo)
-
-
-# ---- the stream: arrays --------------------------------------------------------------------------------------------------
-
-def _u64(a):
-    return np.asarray(a).astype(U) if not (isinstance(a, np.ndarray) and a.dtype == U) else a
-
-
-def vmix(z):
-    with np.errstate(over="ignore"):
-        z = z ^ (z >> U(30))
-        z = z * U(0xBF58476D1CE4E5B9)
-        z = z ^ (z >> U(27))
-        z = z * U(0x94D049BB133111EB)
-        return z ^ (z >> U(31))
-
-
-def vhash(seed, key, draw, purpose, index):
-    """hash4 on uint64 arrays that broadcast."""
-    h = U(seed & M64)
-    with np.errstate(over="ignore"):
-        for w in (key, draw, purpose, index):
-            h = vmix((h ^ _u64(w)) + U(GOLDEN))
-    return h
-
-
-def vuniform(seed, key, draw, purpose, index):
-    return (vhash(seed, key, draw, purpose, index) >> U(11)).astype(np.float64) * 2.0 ** -53
-
-
-def vnoise(seed, key, draw, purpose, k, row):
-    """n on arrays: key, draw, k uint64 (robots), row uint64; all broadcast."""
-    base = (_u64(k) << U(12)) | (_u64(row) << U(2))
-    u0, u1, u2, u3 = (vuniform(seed, key, draw, purpose, base | U(j)) for j in range(4))
-    return (((u0 + u1) + (u2 + u3)) - 2.0) * ROOT3
-
-
-def words(v):
-    """A state row's integers as the device reads key and draws: through int64 to uint64."""
-    return np.asarray(v, dtype=np.float64).astype(np.int64).astype(U)
-
-
-def bounded(v, hi):
-    """A tick or delay row: (uint64) fmin(fmax(v, 0), hi); a NaN is 0."""
-    v = np.asarray(v, dtype=np.float64)
-    return np.minimum(np.maximum(np.where(np.isnan(v), 0.0, v), 0.0), float(hi)).astype(U)
 
 
 # ---- configuration and buffers -------------------------------------------------------------------------------------------

@@ -2,49 +2,21 @@
 srb_model.SRBModel with the three rules a terrain changes (where a foot lands, the clearance of the fall test, settle after
 a reset).  It restates robot_gym_amd/csrc/rg_srb_terrain.hip operation for operation -- the same divisions, the fmax / fmin
 clamp (np.fmax / np.fmin: a NaN becomes the lower bound), floor, the 2 x 2 grouping by arithmetic shift, the hash words of
-tests/episode_model.py's mix64, and the two triangle formulas left to right -- so the ground is held to it BIT FOR BIT
+tests/stream_model.py's chain, and the two triangle formulas left to right -- so the ground is held to it BIT FOR BIT
 (tests/test_terrain_gpu.py) and the kernels to it within the simulator's existing tolerances.
 """
 import numpy as np
 
 from tests import srb_model as M
-from tests.episode_model import GOLDEN, M64, mix64
+from tests.stream_model import chain as hash_words, uniform as unit, vuniform     # over (key, I, J): ints of any sign
 
 BOUND = 2.0 ** 40
 MAX_DIM = 4096
 
 
-def hash_words(seed, key, I, J):
-    """h of the chain over (key, I, J), Python ints of any sign (taken as two's-complement 64-bit words)."""
-    h = int(seed) & M64
-    for w in (key, I, J):
-        h = mix64(((h ^ (int(w) & M64)) + GOLDEN) & M64)
-    return h
-
-
-def unit(seed, key, I, J):
-    return (hash_words(seed, key, I, J) >> 11) * 2.0 ** -53
-
-
-def _mix_vec(z):
-    z = z ^ (z >> np.uint64(30))
-    z = z * np.uint64(0xBF58476D1CE4E5B9)
-    z = z ^ (z >> np.uint64(27))
-    z = z * np.uint64(0x94D049BB133111EB)
-    return z ^ (z >> np.uint64(31))
-
-
-def _word(h, w):
-    with np.errstate(over="ignore"):
-        return _mix_vec((h ^ w) + np.uint64(GOLDEN))
-
-
 def unit_vec(seed, key, I, J):
     """unit() over int64 arrays (key, I, J broadcast together): uint64 arithmetic wraps as the device's does."""
-    key, I, J = (np.asarray(a, dtype=np.int64).astype(np.uint64) for a in (key, I, J))
-    with np.errstate(over="ignore"):
-        h = _word(_word(_word(np.uint64(int(seed) & M64), key), I), J)
-    return (h >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    return vuniform(seed, *(np.asarray(a, dtype=np.int64).astype(np.uint64) for a in (key, I, J)))
 
 
 def _lattice(s):

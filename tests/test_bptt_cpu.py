@@ -455,10 +455,11 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
     assert re.findall(r'#include "([^"]+)"', code) == ["../../include/rg_policy.h", "../../include/rg_ppo.h", "../../include/rg_rnn.h",
                                                       "../../include/rg_bptt.h", "rg_host.h", "rg_agent_dev.inc", "rg_gru_dev.inc", "rg_ppo_dev.inc"]
     assert not re.search(r"\b(chain8|sigmoidf)\s*\([^;{]*\)\s*\{", code)         # the tick's device code is rg_gru_dev.inc's alone
-    shared = [open(os.path.join(SRC, name)).read() for name in ("rg_agent_dev.inc", "rg_gru_dev.inc", "rg_ppo_dev.inc")]
+    shared = [open(os.path.join(SRC, name)).read() for name in ("rg_agent_dev.inc", "rg_gru_dev.inc", "rg_ppo_dev.inc", "rg_stream_dev.inc")]
     for text in shared:
         assert "asm" not in re.sub(r"//.*", "", text) and "atomic" not in text.lower()
-        assert "__global__" not in text and '#include "' not in text
+        assert "__global__" not in text
+    assert [re.findall(r'#include "([^"]+)"', text) for text in shared] == [["rg_stream_dev.inc"], [], [], []]     # the one stream, under the agents' noise
     # the head's and Adam's arithmetic is the shared files' alone: no update writes an exp or a pow of its own
     for name in ("rg_ppo.hip", "rg_bptt.hip", "rg_ddpg.hip"):
         text = re.sub(r"//.*", "", open(os.path.join(SRC, name)).read())

@@ -179,16 +179,8 @@ def test_the_stream_is_the_episode_stream_on_the_same_four_words():
 def test_known_answers_of_the_stream():
     # the first output of splitmix64 seeded with 0 (Vigna's reference implementation): one round of the chain on zero words
     assert DM.mix64(DM.GOLDEN) == 0xE220A8397B1DCDAF
-    # by hand for the all-zero words: four rounds, each h = mix((h ^ 0) + GOLDEN)
-    h = 0
-    for _ in range(4):
-        z = (h + 0x9E3779B97F4A7C15) & DM.M64
-        z ^= z >> 30
-        z = (z * 0xBF58476D1CE4E5B9) & DM.M64
-        z ^= z >> 27
-        z = (z * 0x94D049BB133111EB) & DM.M64
-        h = z ^ (z >> 31)
-    assert h == DM.hash4(0, 0, 0, 0, 0) == 0x2130748AAAC80268
+    # the all-zero words: four rounds, each h = mix((h ^ 0) + GOLDEN); restated by hand in tests/test_stream_cpu.py
+    assert DM.hash4(0, 0, 0, 0, 0) == 0x2130748AAAC80268
     assert DM.uniform(0, 0, 0, 0, 0) == float.fromhex("0x1.0983a45556400p-3") == (0x2130748AAAC80268 >> 11) / 2 ** 53
     # one key (5) of seed 12345: the world of its first draw, a push component, and its first scales
     assert DM.hash4(12345, 5, 0, DM.WORLD, 0) == 0x40153532777E0227 and 0x40153532777E0227 >> 33 == 537565849 < 2 ** 31
@@ -394,10 +386,14 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
     assert pragma < code.index('#include "rg_mpc_dev.h"') < code.index('#include "rg_srb_dev.inc"') < code.index('#include "rg_srb_handle.h"')
     assert pragma < code.index("__global__") and pragma < code.index("__device__")
     assert "asm" not in code and "atomic" not in src.lower() and "__shared__" not in src and "__shfl" not in src
+    stream = open(os.path.join(SRC, "rg_stream_dev.inc")).read()                 # the stream's device functions, included after the pragma
+    assert "__global__" not in stream and '#include "' not in stream and "asm" not in re.sub(r"//.*", "", stream) and "atomic" not in stream.lower()
     for call in ("sin(", "cos(", "pow(", "exp(", "sqrt(", "fma("):
-        assert call not in code, call
+        assert call not in code and call not in stream, call
     assert len(re.findall(r"__global__", code)) == len(KERNELS) and code.count("__launch_bounds__(kBlock)") == 3 and "kBlock = 256" in code
-    assert re.findall(r'#include "([^"]+)"', code) == ["../../include/rg_dr.h", "rg_host.h", "rg_mpc_dev.h", "rg_srb_dev.inc", "rg_srb_handle.h"]
+    assert re.findall(r'#include "([^"]+)"', code) == ["../../include/rg_dr.h", "rg_host.h", "rg_mpc_dev.h", "rg_srb_dev.inc", "rg_srb_handle.h",
+                                                      "rg_stream_dev.inc"]
+    assert pragma < code.index('#include "rg_stream_dev.inc"') < code.index("__device__")
     for other in sorted(os.listdir(SRC)):                                        # included from nowhere
         if other.endswith((".hip", ".inc", ".h")) and other != "rg_dr.hip":
             assert "rg_dr" not in open(os.path.join(SRC, other)).read(), other

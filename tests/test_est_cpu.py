@@ -580,7 +580,11 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
     assert pragma < code.index("__global__") and pragma < code.index("__device__") and pragma < code.index('#include "rg_mpc_dev.h"')
     assert "asm" not in code and "atomic" not in code.lower() and "__shared__" not in src and "__shfl" not in src
     assert len(re.findall(r"__global__", code)) == len(KERNELS) and code.count("__launch_bounds__(kBlock)") == 2 and "kBlock = 256" in code
-    assert re.findall(r'#include "([^"]+)"', code) == ["../../include/rg_est.h", "rg_host.h", "rg_mpc_dev.h", "rg_srb_dev.inc"]
+    assert re.findall(r'#include "([^"]+)"', code) == ["../../include/rg_est.h", "rg_host.h", "rg_mpc_dev.h", "rg_srb_dev.inc", "rg_stream_dev.inc"]
+    stream = open(os.path.join(SRC, "rg_stream_dev.inc")).read()                 # the stream's device functions, included after the pragma
+    assert pragma < code.index('#include "rg_stream_dev.inc"') < code.index("__device__")
+    assert "__global__" not in stream and '#include "' not in stream and "asm" not in re.sub(r"//.*", "", stream) and "atomic" not in stream.lower()
+    assert "__shared__" not in stream and "__shfl" not in stream
     # one barrier in the kernel that gives a robot several lanes, and it comes before the first store and the first return
     body = code[code.index("rg_est_estimate_kernel("):]
     body = body[:body.index("\n}\n")]

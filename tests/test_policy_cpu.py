@@ -512,7 +512,7 @@ def test_register_use_is_pinned(remarks):
 
 def test_source_is_its_own_translation_unit_in_both_library_targets():
     own = open(os.path.join(SRC, "rg_policy.hip")).read()
-    shared = [open(os.path.join(SRC, name)).read() for name in ("rg_host.h", "rg_agent_dev.inc")]   # the agents' common code
+    shared = [open(os.path.join(SRC, name)).read() for name in ("rg_host.h", "rg_agent_dev.inc", "rg_stream_dev.inc")]   # the agents' common code
     src = "\n".join([own] + shared)
     code = re.sub(r"//.*", "", src)
     assert "asm" not in code and "atomic" not in src.lower()
@@ -520,9 +520,10 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
     assert own_code.index("#pragma clang fp contract(off)") < own_code.index("__global__")
     assert own_code.index("#pragma clang fp contract(off)") < own_code.index('#include "rg_agent_dev.inc"')
     assert re.findall(r'#include "([^"]+)"', own_code) == ["../../include/rg_policy.h", "rg_host.h", "rg_agent_dev.inc"]
-    assert all("__global__" not in text and '#include "' not in text for text in shared)
+    assert all("__global__" not in text for text in shared)
+    assert [re.findall(r'#include "([^"]+)"', text) for text in shared] == [[], ["rg_stream_dev.inc"], []]     # the one stream, under the agents' noise
     import bench
-    assert not any("rg_agent_" in rel or "rg_host" in rel for rel in bench.compiled_sources())     # the MPC hash behind profiles/ does not follow them
+    assert not any("rg_agent_" in rel or "rg_stream_" in rel or "rg_host" in rel for rel in bench.compiled_sources())     # the MPC hash behind profiles/ does not follow them
     assert "rg_policy" not in open(os.path.join(SRC, "rg_mpc.hip")).read()   # the source hash behind profiles/ does not move
     makefile = open(os.path.join(SRC, "Makefile")).read()
     assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_policy\.hip", makefile)) == 2   # both library targets

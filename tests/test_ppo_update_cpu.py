@@ -406,7 +406,7 @@ def test_register_use_is_pinned(remarks):
 
 def test_source_is_its_own_translation_unit_in_both_library_targets():
     own = open(os.path.join(SRC, "rg_ppo.hip")).read()
-    shared = [open(os.path.join(SRC, name)).read() for name in ("rg_host.h", "rg_agent_dev.inc", "rg_ppo_dev.inc")]   # the agents' common code
+    shared = [open(os.path.join(SRC, name)).read() for name in ("rg_host.h", "rg_agent_dev.inc", "rg_ppo_dev.inc", "rg_stream_dev.inc")]   # the agents' common code
     src = "\n".join([own] + shared)
     code = re.sub(r"//.*", "", src)
     assert "asm" not in code and "atomic" not in src.lower()
@@ -416,7 +416,8 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
     assert own_code.index("#pragma clang fp contract(off)") < own_code.index('#include "rg_agent_dev.inc"')
     assert own_code.index('#include "rg_agent_dev.inc"') < own_code.index('#include "rg_ppo_dev.inc"')
     assert re.findall(r'#include "([^"]+)"', own_code) == ["../../include/rg_ppo.h", "rg_host.h", "rg_agent_dev.inc", "rg_ppo_dev.inc"]
-    assert all("__global__" not in text and '#include "' not in text for text in shared)
+    assert all("__global__" not in text for text in shared)
+    assert [re.findall(r'#include "([^"]+)"', text) for text in shared] == [[], ["rg_stream_dev.inc"], [], []]     # the one stream, under the agents' noise
     # the head's and Adam's arithmetic is the shared files' alone: no update writes an exp or a pow of its own
     for name in ("rg_ppo.hip", "rg_bptt.hip", "rg_ddpg.hip"):
         text = re.sub(r"//.*", "", open(os.path.join(SRC, name)).read())
@@ -424,7 +425,7 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
         assert name == "rg_ddpg.hip" or "exp(" not in text, name
     assert "pow(" in re.sub(r"//.*", "", shared[1]) and "exp(" in re.sub(r"//.*", "", shared[2])
     import bench
-    assert not any("rg_agent_" in rel or "rg_host" in rel for rel in bench.compiled_sources())     # the MPC hash behind profiles/ does not follow them
+    assert not any("rg_agent_" in rel or "rg_stream_" in rel or "rg_host" in rel for rel in bench.compiled_sources())     # the MPC hash behind profiles/ does not follow them
     for other in ("rg_mpc.hip", "rg_policy.hip"):
         assert "rg_ppo" not in open(os.path.join(SRC, other)).read()                # the source hashes behind profiles/ do not move
     assert "__builtin_fmaf" in code and "mfma" not in code.lower()

@@ -472,10 +472,13 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
     pragma = code.index("#pragma clang fp contract(off)")
     assert pragma < code.index("__global__") and pragma < code.index("__device__")
     assert "asm" not in code and "atomic" not in code.lower() and "__shared__" not in src and "__shfl" not in src
+    stream = open(os.path.join(SRC, "rg_stream_dev.inc")).read()                 # the stream's device functions, included after the pragma
+    assert "__global__" not in stream and '#include "' not in stream and "asm" not in re.sub(r"//.*", "", stream) and "atomic" not in stream.lower()
     for call in ("sin(", "cos(", "pow(", "exp(", "sqrt(", "log(", "fma("):
-        assert call not in code, call
+        assert call not in code and call not in stream, call
     assert len(re.findall(r"__global__", code)) == len(KERNELS) and code.count("__launch_bounds__(kBlock)") == 3 and "kBlock = 256" in code
-    assert re.findall(r'#include "([^"]+)"', code) == ["../../include/rg_sensor.h", "rg_host.h"]
+    assert re.findall(r'#include "([^"]+)"', code) == ["../../include/rg_sensor.h", "rg_host.h", "rg_stream_dev.inc"]
+    assert pragma < code.index('#include "rg_stream_dev.inc"') < code.index("__device__")
     # one barrier in each kernel that gives a robot several lanes, and it comes before the first store of the kernel
     for kernel in ("rg_sensor_reset_kernel", "rg_sensor_observe_kernel"):
         body = code[code.index(kernel + "("):]

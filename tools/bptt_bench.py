@@ -28,8 +28,8 @@ from robot_gym_amd.gym.batched_go_env import BatchedGoEnv  # noqa: E402
 
 T = 32
 EPOCHS = 10
-SOURCES = ("robot_gym_amd/csrc/rg_bptt.hip", "robot_gym_amd/csrc/rg_ppo.hip", "robot_gym_amd/csrc/rg_agent_dev.inc", "robot_gym_amd/csrc/rg_gru_dev.inc",
-           "robot_gym_amd/csrc/rg_ppo_dev.inc", "robot_gym_amd/csrc/rg_host.h", "include/rg_bptt.h", "include/rg_ppo.h", "include/rg_rnn.h")
+SOURCES = ("robot_gym_amd/csrc/rg_bptt.hip", "robot_gym_amd/csrc/rg_ppo.hip", "robot_gym_amd/csrc/rg_agent_dev.inc", "robot_gym_amd/csrc/rg_stream_dev.inc",
+           "robot_gym_amd/csrc/rg_gru_dev.inc", "robot_gym_amd/csrc/rg_ppo_dev.inc", "robot_gym_amd/csrc/rg_host.h", "include/rg_bptt.h", "include/rg_ppo.h", "include/rg_rnn.h")
 PHASES = {"F": ("rg_bptt_forward_kernel",), "H": ("rg_bptt_sample_kl_kernel", "rg_bptt_robot_kl_kernel", "rg_bptt_head_kernel", "rg_bptt_loss_finish_kernel"),
           "B": ("rg_bptt_transpose_kernel", "rg_bptt_delta_kernel"), "W": ("rg_bptt_weight_kernel", "rg_bptt_grad_finish_kernel")}
 

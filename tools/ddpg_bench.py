@@ -33,7 +33,8 @@ RING_BATCH, RING_TICKS = 64, 256
 
 def ddpg_hash():
     h = hashlib.sha256()
-    for rel in ("robot_gym_amd/csrc/rg_ddpg.hip", "robot_gym_amd/csrc/rg_agent_dev.inc", "robot_gym_amd/csrc/rg_host.h", "include/rg_ddpg.h"):
+    for rel in ("robot_gym_amd/csrc/rg_ddpg.hip", "robot_gym_amd/csrc/rg_agent_dev.inc", "robot_gym_amd/csrc/rg_stream_dev.inc", "robot_gym_amd/csrc/rg_host.h",
+                "include/rg_ddpg.h"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]
 

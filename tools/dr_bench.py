@@ -28,8 +28,8 @@ from robot_gym_amd.gym.batched_go_env import BatchedGoEnv  # noqa: E402
 from robot_gym_amd.sim import BatchedSRBSim, DomainRandomizer, RandomTerrain  # noqa: E402
 from tools.scan_bench import timed  # noqa: E402
 
-DR_SOURCES = ("robot_gym_amd/csrc/rg_dr.hip", "robot_gym_amd/csrc/rg_srb_handle.h", "robot_gym_amd/csrc/rg_srb_dev.inc", "robot_gym_amd/csrc/rg_host.h",
-              "include/rg_dr.h")
+DR_SOURCES = ("robot_gym_amd/csrc/rg_dr.hip", "robot_gym_amd/csrc/rg_stream_dev.inc", "robot_gym_amd/csrc/rg_srb_handle.h", "robot_gym_amd/csrc/rg_srb_dev.inc",
+              "robot_gym_amd/csrc/rg_host.h", "include/rg_dr.h")
 SETTINGS = dict(mass_scale=(0.8, 1.2), inertia_scale=(0.8, 1.2), new_world_each_episode=True, push_interval=100, push_ticks=10, push_probability=0.5,
                 push_force_xy=20.0, push_force_z=5.0, push_torque_xy=2.0, push_torque_z=1.0)
 # both launches of a step, but unit scales, the worlds kept and zero amplitudes: the robots move exactly as without a randomiser

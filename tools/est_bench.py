@@ -32,8 +32,8 @@ from robot_gym_amd.sim.height_scan import HeightScan  # noqa: E402
 from tools.scan_bench import timed  # noqa: E402
 from tools.sensor_bench import D, A, PATH_ROWS, SETTINGS as SENSOR_SETTINGS  # noqa: E402
 
-EST_SOURCES = ("robot_gym_amd/csrc/rg_est.hip", "robot_gym_amd/csrc/rg_srb_dev.inc", "robot_gym_amd/csrc/rg_mpc_dev.h", "robot_gym_amd/csrc/rg_host.h",
-               "include/rg_est.h")
+EST_SOURCES = ("robot_gym_amd/csrc/rg_est.hip", "robot_gym_amd/csrc/rg_stream_dev.inc", "robot_gym_amd/csrc/rg_srb_dev.inc", "robot_gym_amd/csrc/rg_mpc_dev.h",
+               "robot_gym_amd/csrc/rg_host.h", "include/rg_est.h")
 FULL = dict(imu=dict(bias_half_width=(0.03, 0.03, 0.05), noise_sigma=(0.002, 0.002, 0.001)),
             gyro=dict(bias_half_width=(0.01, 0.01, 0.01), noise_sigma=(0.05, 0.05, 0.05)),
             velocity=dict(bias_half_width=(0.05, 0.05, 0.03), noise_sigma=(0.02, 0.02, 0.01)),

@@ -42,7 +42,7 @@ CREEP = 0.01   # m/s
 def goto_hash():
     h = hashlib.sha256()
     for rel in ("robot_gym_amd/csrc/rg_goto.hip", "robot_gym_amd/csrc/rg_goto_dev.inc", "include/rg_goto.h", "robot_gym_amd/csrc/rg_episode.hip",
-                "include/rg_episode.h"):
+                "robot_gym_amd/csrc/rg_stream_dev.inc", "include/rg_episode.h"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]
 

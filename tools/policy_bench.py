@@ -39,7 +39,8 @@ LOG_2PI = math.log(2.0 * math.pi)
 
 def policy_hash():
     h = hashlib.sha256()
-    for rel in ("robot_gym_amd/csrc/rg_policy.hip", "robot_gym_amd/csrc/rg_agent_dev.inc", "robot_gym_amd/csrc/rg_host.h", "include/rg_policy.h"):
+    for rel in ("robot_gym_amd/csrc/rg_policy.hip", "robot_gym_amd/csrc/rg_agent_dev.inc", "robot_gym_amd/csrc/rg_stream_dev.inc", "robot_gym_amd/csrc/rg_host.h",
+                "include/rg_policy.h"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]
 

@@ -38,7 +38,7 @@ def _hash(paths):
     return h.hexdigest()[:16]
 
 
-SHARED = ("robot_gym_amd/csrc/rg_agent_dev.inc", "robot_gym_amd/csrc/rg_host.h")   # what the agents' files include
+SHARED = ("robot_gym_amd/csrc/rg_agent_dev.inc", "robot_gym_amd/csrc/rg_stream_dev.inc", "robot_gym_amd/csrc/rg_host.h")   # what the agents' files include
 
 
 def policy_hash():

@@ -34,8 +34,8 @@ LOG_2PI = math.log(2.0 * math.pi)
 
 def rnn_hash():
     h = hashlib.sha256()
-    for rel in ("robot_gym_amd/csrc/rg_rnn.hip", "robot_gym_amd/csrc/rg_agent_dev.inc", "robot_gym_amd/csrc/rg_gru_dev.inc", "robot_gym_amd/csrc/rg_host.h",
-                "include/rg_rnn.h"):
+    for rel in ("robot_gym_amd/csrc/rg_rnn.hip", "robot_gym_amd/csrc/rg_agent_dev.inc", "robot_gym_amd/csrc/rg_stream_dev.inc", "robot_gym_amd/csrc/rg_gru_dev.inc",
+                "robot_gym_amd/csrc/rg_host.h", "include/rg_rnn.h"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]
 
@@ -125,7 +125,7 @@ def main():
     result = dict(what="recurrent policy kernels, one process and run, us per call: rg_rnn_act, rg_policy_act on the default feed-forward networks, "
                        "the GRU tick as torch ops, rg_rnn_unroll at T = 32 and a no-grad torch loop over the same sequence, one collect_recurrent "
                        "tick and env.step alone (auto-reset, limits out of reach).  `commit` is the commit the measured tree was based on; "
-                       "rnn_source_sha256 is the hash of rg_rnn.hip, rg_agent_dev.inc, rg_gru_dev.inc and rg_host.h, which it includes, and rg_rnn.h as measured",
+                       "rnn_source_sha256 is the hash of rg_rnn.hip, rg_agent_dev.inc, rg_stream_dev.inc, rg_gru_dev.inc and rg_host.h, which it includes, and rg_rnn.h as measured",
                   robot=args.robot, commit=commit, dirty=dirty, source_hash=bench.source_hash(), rnn_source_sha256=rnn_hash(),
                   device=torch.cuda.get_device_name(0), seconds_per_measurement=args.seconds, rows=rows)
     if args.out:

@@ -27,7 +27,7 @@ from robot_gym_amd.gym.batched_go_env import BatchedGoEnv  # noqa: E402
 from robot_gym_amd.sim import BatchedSRBSim, GridTerrain, RandomTerrain  # noqa: E402
 from robot_gym_amd.sim.height_scan import HeightScan  # noqa: E402
 
-SCAN_SOURCES = ("robot_gym_amd/csrc/rg_scan.hip", "robot_gym_amd/csrc/rg_srb_ground.inc", "robot_gym_amd/csrc/rg_srb_handle.h",
+SCAN_SOURCES = ("robot_gym_amd/csrc/rg_scan.hip", "robot_gym_amd/csrc/rg_srb_ground.inc", "robot_gym_amd/csrc/rg_stream_dev.inc", "robot_gym_amd/csrc/rg_srb_handle.h",
                 "robot_gym_amd/csrc/rg_srb_dev.inc", "robot_gym_amd/csrc/rg_host.h", "include/rg_scan.h")
 
 

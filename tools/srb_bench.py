@@ -65,8 +65,8 @@ def srb_hash():
     import hashlib
     h = hashlib.sha256()
     for rel in ("robot_gym_amd/csrc/rg_srb.hip", "robot_gym_amd/csrc/rg_srb_dev.inc", "robot_gym_amd/csrc/rg_srb_handle.h", "robot_gym_amd/csrc/rg_host.h",
-                "robot_gym_amd/csrc/rg_srb_terrain.hip", "robot_gym_amd/csrc/rg_srb_ground.inc", "robot_gym_amd/csrc/rg_srb_contact.hip",
-                "include/rg_srb.h", "include/rg_srb_terrain.h", "include/rg_srb_contact.h"):
+                "robot_gym_amd/csrc/rg_srb_terrain.hip", "robot_gym_amd/csrc/rg_srb_ground.inc", "robot_gym_amd/csrc/rg_stream_dev.inc",
+                "robot_gym_amd/csrc/rg_srb_contact.hip", "include/rg_srb.h", "include/rg_srb_terrain.h", "include/rg_srb_contact.h"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]
 
