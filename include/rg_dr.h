@@ -4,7 +4,8 @@
  * pushes (the `ext` wrench of rg_srb_step / rg_srb_step_contact) on every tick -- drawn on the device for the robots a
  * DEVICE mask names, with no host in the loop.
  *
- * Not covered: friction (the model has no slip), per-axis inertia scales, offsets of the centre of mass.  Observation and
+ * Not covered: per-axis inertia scales, offsets of the centre of mass.  The ground's friction coefficient is drawn per episode
+ * by rg_srb_friction_draw (rg_srb_friction.h) from rows 0 and 1 of the state below, before rg_dr_reset counts the draw.  Observation and
  * action noise, dropout and latency are the sensor model's (rg_sensor.h).  Every magnitude is the caller's: the defaults are
  * the identity (scales 1, no new worlds, no push).
  *

@@ -6,11 +6,14 @@
  * forward with the controller's own first-step forces and kinematic feet, for B robots per call with no host in the
  * loop.  It is for closed-loop validation of the controller, branched (cloned) rollouts and RL on the reduced model.
  *
- * Stated limits: feet that neither slip nor bounce; massless legs; first-order (semi-implicit Euler) integration.  The
- * ground is the plane z = 0 or a heightfield (rg_srb_set_terrain, below): kinematic feet, no slip.  In rg_srb_step touch-down
+ * Stated limits: feet that do not bounce and, in rg_srb_step and rg_srb_step_contact, do not slip; massless legs; first-order
+ * (semi-implicit Euler) integration.  The ground is the plane z = 0 or a heightfield (rg_srb_set_terrain, below): kinematic
+ * feet.  In rg_srb_step touch-down
  * and lift-off follow the gait schedule (the controller's desired_state), not a measurement.  rg_srb_step_contact
  * (rg_srb_contact.h, which states its rule) measures ONE thing on either ground: the early touch-down of a swinging foot, which
- * stops at the ground and reports contact.  Still not measured by any entry: late contact, slip, a reach limit of the leg,
+ * stops at the ground and reports contact.  rg_srb_step_friction (rg_srb_friction.h, which states its rule and its limits)
+ * gives every robot a Coulomb friction coefficient: a stance foot that is asked for more tangential force than the ground
+ * holds passes on what the ground holds, and slides.  Still not measured by any entry: late contact, a reach limit of the leg,
  * collision of the body with the ground.  Late contact is left out on purpose: a commanded-stance foot that descends at a
  * finite speed and carries no force until it arrives made every robot of the CPU model fall, on the plane too (rg_srb_contact.h).
  *
@@ -203,5 +206,9 @@ int rg_srb_step(rg_srb_handle *h, double *state, const float *grf, const float *
 
 /* The tick with measured foot contact (rg_srb_step_contact) and the text of its rule: part of this ABI, declared in its own file. */
 #include "rg_srb_contact.h"
+
+/* The tick with Coulomb friction at the stance feet (rg_srb_step_friction), the draw of its coefficient and the text of its
+ * rule: part of this ABI, declared in its own file. */
+#include "rg_srb_friction.h"
 
 #endif /* RG_SRB_H */

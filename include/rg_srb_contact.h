@@ -25,7 +25,8 @@
  *   obs.contact = stance, as in rg_srb_step: now a measurement.  While leg_state equals desired_state and no swung target
  *   comes to or below the ground, every value is rg_srb_step's, bit for bit.
  *
- * Stated limits.  Measured: the early touch-down of a swinging foot.  Still not measured: late contact, slip, a reach limit
+ * Stated limits.  Measured: the early touch-down of a swinging foot.  Slip is rg_srb_step_friction's (rg_srb_friction.h), in
+ * either contact mode.  Still not measured: late contact, a reach limit
  * of the leg, collision of the body with the ground.  Late contact stays out on purpose: with a commanded-stance foot that
  * descends at a finite speed (1 m/s and 0.3 m/s were tried on the CPU model) and gets no force until it arrives, every
  * robot fell, on the plane too -- the LOSE_CONTACT branch of the controller swings such a leg along a swing curve evaluated

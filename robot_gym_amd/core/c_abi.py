@@ -1,5 +1,5 @@
 """What the ctypes shims over librg_mpc.so (mpc_abi, srb_abi, goto_abi, episode_abi, posctl_abi, policy_abi, ppo_abi, ddpg_abi,
-rnn_abi, scan_abi, dr_abi, sensor_abi, est_abi) share: the type aliases and the library's path, the error and handle base classes, the loader with its version, size
+rnn_abi, scan_abi, dr_abi, sensor_abi, est_abi, friction_abi) share: the type aliases and the library's path, the error and handle base classes, the loader with its version, size
 and constant checks, the device and stream of a handle, and the settings, config and host-array helpers.  Only the shims
 import it.  Everything that belongs to one unit -- structures, constants, defaults, entry methods -- stays in that unit's module.
 """

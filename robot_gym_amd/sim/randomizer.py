@@ -12,8 +12,10 @@ librg_mpc.so.
     dr.on_reset(mask); sim.reset(...)                          # mask: int32 [B] device tensor
     rollout(ctl, sim, ticks=T, ext=lambda k: dr.pushes())
 
-The defaults are the identity: scales (1, 1), the world kept, no push.  Every magnitude is the caller's choice.  Not covered:
-friction (the model has no slip), per-axis inertia, offsets of the centre of mass.  Observation and action noise, dropout and
+The defaults are the identity: scales (1, 1), the world kept, no push, the friction kept.  Every magnitude is the caller's
+choice.  friction=(lo, hi) draws the ground's friction coefficient per episode into the mu row of a simulator built with
+friction= (include/rg_srb_friction.h); the planner keeps the friction it believes in (MPCConfig.mu).  Not covered:
+per-axis inertia, offsets of the centre of mass.  Observation and action noise, dropout and
 latency are SensorModel's (robot_gym_amd/sim/sensor_model.py).
 
 BatchedSRBSim.set_body uploads the body of EVERY robot and so undoes every scale: with a randomiser bound, change the base body
@@ -21,7 +23,7 @@ through DomainRandomizer.set_body, which forwards, captures the new base and sca
 """
 import torch
 
-from robot_gym_amd.core import dr_abi
+from robot_gym_amd.core import dr_abi, friction_abi
 from robot_gym_amd.sim.stream_state import copy_robot_columns, stream_state
 from robot_gym_amd.sim.terrain import RandomTerrain
 
@@ -43,8 +45,11 @@ class DomainRandomizer:
     (None without pushes)."""
 
     def __init__(self, mass_scale=(1.0, 1.0), inertia_scale=(1.0, 1.0), new_world_each_episode=False, seed=0, push_interval=0, push_ticks=0,
-                 push_probability=0.0, push_force_xy=0.0, push_force_z=0.0, push_torque_xy=0.0, push_torque_z=0.0):
+                 push_probability=0.0, push_force_xy=0.0, push_force_z=0.0, push_torque_xy=0.0, push_torque_z=0.0, friction=None):
         (mlo, mhi), (ilo, ihi) = _range(mass_scale, "mass_scale"), _range(inertia_scale, "inertia_scale")
+        # friction: None (nothing is drawn, nothing launched) or (lo, hi), the range of the friction coefficient each episode
+        # draws (include/rg_srb_friction.h): 0 <= lo <= hi, finite; needs a simulator built with friction=
+        self.friction = None if friction is None else friction_abi.checked_range(*_range(friction, "friction"), what="DomainRandomizer: friction")
         self.settings = dict(worlds=int(bool(new_world_each_episode)), seed=int(seed), mass_lo=mlo, mass_hi=mhi, inertia_lo=ilo, inertia_hi=ihi,
                              push_interval=int(push_interval), push_ticks=int(push_ticks), push_probability=float(push_probability),
                              push_force_xy=float(push_force_xy), push_force_z=float(push_force_z), push_torque_xy=float(push_torque_xy),
@@ -61,6 +66,9 @@ class DomainRandomizer:
         keys = getattr(sim.terrain, "keys", None)
         if self.new_world_each_episode and not (isinstance(sim.terrain, RandomTerrain) and torch.is_tensor(keys)):
             raise ValueError("DomainRandomizer: new_world_each_episode needs a simulator with a bound RandomTerrain (its keys are the worlds)")
+        if self.friction is not None and getattr(sim, "mu", None) is None:
+            raise ValueError("DomainRandomizer: friction=(lo, hi) needs a simulator built with friction (BatchedSRBSim(..., friction=...)): "
+                             "its mu row is what the draw writes")
         B, dev = sim.batch, sim.device
         self._handle = dr_abi.DrHandle(B, dev, substeps=sim.substeps, **self.settings)
         self.batch, self.device, self.sim = B, dev, sim
@@ -91,11 +99,16 @@ class DomainRandomizer:
         return self.state[dr_abi.ROW_MASS_SCALE:dr_abi.ROW_INERTIA_SCALE + 1]
 
     def on_reset(self, mask):
-        """A draw -- body scales and, with new_world_each_episode, a world -- for the robots b with mask[b] != 0 (int32 [B]
+        """A draw -- body scales, with new_world_each_episode a world, with friction=(lo, hi) a friction coefficient -- for the robots b with mask[b] != 0 (int32 [B]
         device tensor), BEFORE the simulator resets them, so that its settle stands them in the new world.  Enqueued on the
         current stream; nothing waits."""
         self._bound("on_reset")
-        self._handle.reset(self.sim._handle, self._mask(mask, "on_reset"), self.state.data_ptr(), None if self._keys is None else self._keys.data_ptr())
+        mask_ptr = self._mask(mask, "on_reset")
+        if self.friction is not None:
+            # before rg_dr_reset, which counts the draw: both read the same draw count
+            friction_abi.friction_draw(self.sim._handle, mask, self.state[dr_abi.ROW_KEY], self.state[dr_abi.ROW_DRAWS], self.settings["seed"],
+                                       self.friction[0], self.friction[1], self.sim.mu)
+        self._handle.reset(self.sim._handle, mask_ptr, self.state.data_ptr(), None if self._keys is None else self._keys.data_ptr())
 
     def pushes(self):
         """The ext tensor [6, B] with this tick's push of every robot, for BatchedSRBSim.step(ctl, ext), after enqueuing the

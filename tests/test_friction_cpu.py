@@ -1,0 +1,563 @@
+"""Coulomb friction at the stance feet (include/rg_srb_friction.h) without a GPU: the ABI of rg_srb_step_friction and
+rg_srb_friction_draw (header, binding, library; refusals that name the argument; validation before any device probe), known
+answers of the rule on the model (tests/friction_model.py) worked by hand, its equality with the ticks without friction for a
+robot that grips, the draw, the resources of robot_gym_amd/csrc/rg_srb_friction.hip from one device-only compile, and the CPU
+reference closed loop on floors of three coefficients with the band of tests/friction_fixtures.py."""
+import ctypes as C
+import glob
+import math
+import os
+import re
+import subprocess
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from robot_gym_amd.core import dr_abi, friction_abi, srb_abi
+from robot_gym_amd.core.config import MPCConfig
+from tests import contact_fixtures as CF
+from tests import contact_model as CM
+from tests import friction_fixtures as FF
+from tests import friction_model as FM
+from tests import srb_fixtures as F
+from tests import srb_model as M
+from tests import stream_model as SM
+from tests import terrain_model as TM
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
+HIPCC = "/opt/rocm/bin/hipcc"
+CPU = torch.device("cpu")
+
+
+# ---- the ABI -----------------------------------------------------------------------------------------------------------
+
+def _header(name):
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
+
+
+def _arg_names(hdr, entry):
+    args = re.search(rf"int {entry}\(([^)]*)\)", hdr).group(1)
+    return [a.strip().split()[-1].lstrip("*") for a in args.split(",")]
+
+
+def test_header_binding_and_library_agree_on_both_entries():
+    lib = friction_abi.load_library()
+    hdr = _header("rg_srb_friction.h")
+    declared = sorted(set(re.findall(r"\b(rg_srb_[a-z0-9_]+)\s*\(", hdr)))
+    assert declared == sorted(friction_abi.EXPORTS) == ["rg_srb_friction_draw", "rg_srb_step_friction"]
+    assert _arg_names(hdr, "rg_srb_step_friction") == ["h", "state", "grf", "foot_target", "leg_state", "measured", "ext", "obs", "mu", "slip_gain",
+                                                       "slip_speed_max", "touch", "slip", "stream"]
+    assert _arg_names(hdr, "rg_srb_friction_draw") == ["h", "mask", "key", "draws", "seed", "lo", "hi", "mu", "stream"]
+    for name in friction_abi.EXPORTS:
+        assert hasattr(lib, name) and len(getattr(lib, name).argtypes) == len(_arg_names(hdr, name)), name
+        assert getattr(lib, name).restype is C.c_int32
+    # by value: measured an int32, the two settings and the range doubles, the seed a uint64
+    assert [lib.rg_srb_step_friction.argtypes[i] for i in (5, 9, 10)] == [C.c_int32, C.c_double, C.c_double]
+    assert [lib.rg_srb_friction_draw.argtypes[i] for i in (4, 5, 6)] == [C.c_uint64, C.c_double, C.c_double]
+    whole = open(os.path.join(ROOT, "include", "rg_srb.h")).read()
+    assert whole.index('#include "rg_srb_contact.h"') < whole.index('#include "rg_srb_friction.h"')
+    # nothing else of the ABI moved, and srb_abi declares what it declared
+    defs = {k: int(v) for k, v in re.findall(r"#define (RG_SRB_\w+) (\d+)", _header("rg_srb.h"))}
+    assert defs["RG_SRB_ABI_VERSION"] == 1 and defs["RG_SRB_STATE_ROWS"] == 43
+    assert not any("friction" in k for k in srb_abi.SIGNATURES)
+    assert (friction_abi.SLIP_GAIN, friction_abi.SLIP_SPEED_MAX) == (FM.SLIP_GAIN, FM.SLIP_SPEED_MAX) == (0.01, 1.0)
+
+
+def test_the_purpose_lies_in_block_three_and_is_disjoint_from_every_other():
+    hdr = _header("rg_srb_friction.h")
+    mine = {k: int(v) for k, v in re.findall(r"#define (RG_\w*PURPOSE_\w+) (\d+)", hdr)}
+    assert mine == {"RG_SRB_FRICTION_PURPOSE_MU": 48} and friction_abi.PURPOSE_MU == FM.PURPOSE_MU == 48
+    assert 48 // 16 == 3
+    others = {}
+    for path in glob.glob(os.path.join(ROOT, "include", "*.h")):
+        if os.path.basename(path) != "rg_srb_friction.h":
+            others.update({k: int(v) for k, v in re.findall(r"#define (RG_\w*PURPOSE_\w+) (\d+)", open(path).read())})
+    assert len(others) == 16 and 48 not in others.values() and all(v // 16 != 3 for v in others.values()), others
+    assert sorted(n for n in vars(dr_abi) if n.startswith("PURPOSE_")) == sorted(
+        f"PURPOSE_{n}" for n in ("MASS", "INERTIA", "WORLD", "PUSH_START", "PUSH_COMPONENT", "PUSH_GATE"))
+    registry = open(os.path.join(ROOT, "include", "rg_stream.h")).read()
+    assert re.search(r"block 3\s+48\.\.63\s+rg_srb_friction\.h\s+48 ", registry)
+    src = open(os.path.join(SRC, "rg_srb_friction.hip")).read()
+    assert "static_assert(purposes_in_block(3, RG_SRB_FRICTION_PURPOSE_MU)" in src
+
+
+ADDR = 4096      # a non-null address: with a null handle nothing is read through it
+
+
+def _step_args(**change):
+    obs = srb_abi.CObsPtrs(*([ADDR] * len(srb_abi.OBS_FIELDS)))
+    a = dict(state=ADDR, grf=ADDR, foot_target=ADDR, leg_state=ADDR, measured=1, ext=None, obs=C.byref(obs), mu=ADDR, slip_gain=0.01,
+             slip_speed_max=1.0, touch=None, slip=None)
+    a.update(change)
+    return [None] + [a[k] for k in ("state", "grf", "foot_target", "leg_state", "measured", "ext", "obs", "mu", "slip_gain", "slip_speed_max", "touch",
+                                    "slip")] + [None], obs
+
+
+def _draw_args(**change):
+    a = dict(mask=ADDR, key=ADDR, draws=ADDR, seed=7, lo=0.2, hi=0.9, mu=ADDR)
+    a.update(change)
+    return [None] + [a[k] for k in ("mask", "key", "draws", "seed", "lo", "hi", "mu")] + [None]
+
+
+def test_a_null_handle_is_refused_by_name_without_a_device():
+    lib = friction_abi.load_library()
+    args, _keep = _step_args()
+    assert lib.rg_srb_step_friction(*args) == -1
+    assert b"step_friction: null handle" in lib.rg_srb_last_error(None)
+    assert lib.rg_srb_friction_draw(*_draw_args()) == -1
+    assert b"friction_draw: null handle" in lib.rg_srb_last_error(None)
+
+
+STEP_REFUSALS = [(dict([(n, None)]), f"step_friction: null {n}") for n in ("state", "grf", "foot_target", "leg_state", "obs", "mu")]
+STEP_REFUSALS += [(dict(measured=2), "measured"), (dict(measured=-1), "measured"),
+                  (dict(slip_gain=-0.5), "slip_gain"), (dict(slip_gain=math.nan), "slip_gain"), (dict(slip_gain=math.inf), "slip_gain"),
+                  (dict(slip_speed_max=-1.0), "slip_speed_max"), (dict(slip_speed_max=math.nan), "slip_speed_max"),
+                  (dict(slip_speed_max=math.inf), "slip_speed_max")]
+DRAW_REFUSALS = [(dict([(n, None)]), f"friction_draw: null {n}") for n in ("mask", "key", "draws", "mu")]
+DRAW_REFUSALS += [(dict(lo=-0.1), "friction_draw: lo"), (dict(lo=math.nan), "friction_draw: lo"), (dict(lo=math.inf), "friction_draw: lo"),
+                  (dict(lo=0.9, hi=0.2), "friction_draw: hi"), (dict(hi=math.nan), "friction_draw: hi"), (dict(hi=math.inf), "friction_draw: hi")]
+
+
+@pytest.mark.parametrize("change,text", STEP_REFUSALS, ids=[t + str(i) for i, (_, t) in enumerate(STEP_REFUSALS)])
+def test_step_friction_refuses_each_null_or_bad_argument_by_name_without_a_device(change, text):
+    lib = friction_abi.load_library()
+    args, _keep = _step_args(**change)
+    assert lib.rg_srb_step_friction(*args) == -1
+    assert text.encode() in lib.rg_srb_last_error(None), lib.rg_srb_last_error(None)
+
+
+def test_step_friction_refuses_a_hole_in_obs():
+    lib = friction_abi.load_library()
+    args, obs = _step_args()
+    obs.jac = None
+    assert lib.rg_srb_step_friction(*args) == -1
+    assert b"step_friction: null pointer in obs" in lib.rg_srb_last_error(None)
+
+
+@pytest.mark.parametrize("change,text", DRAW_REFUSALS, ids=[t + str(i) for i, (_, t) in enumerate(DRAW_REFUSALS)])
+def test_friction_draw_refuses_each_null_or_bad_argument_by_name_without_a_device(change, text):
+    lib = friction_abi.load_library()
+    assert lib.rg_srb_friction_draw(*_draw_args(**change)) == -1
+    assert text.encode() in lib.rg_srb_last_error(None), lib.rg_srb_last_error(None)
+
+
+def _good(B=5):
+    return dict(state=torch.zeros(43, B, dtype=torch.float64), grf=torch.zeros(B, 12), foot_target=torch.zeros(B, 12),
+                leg_state=torch.zeros(B, 4, dtype=torch.int32), mu=torch.zeros(B, dtype=torch.float64), ext=torch.zeros(6, B, dtype=torch.float64),
+                touch=torch.zeros(4, B, dtype=torch.int32), slip=torch.zeros(4, B, dtype=torch.float64))
+
+
+def test_the_binding_accepts_what_the_library_takes():
+    a = _good()
+    assert friction_abi.step_friction_ptrs(5, CPU, **a) == tuple(a[k].data_ptr() for k in ("state", "grf", "foot_target", "leg_state", "mu", "ext", "touch", "slip"))
+    a["ext"] = a["touch"] = a["slip"] = None
+    assert friction_abi.step_friction_ptrs(5, CPU, **a)[5:] == (None, None, None)
+    d = dict(mask=torch.zeros(5, dtype=torch.int32), key=torch.zeros(5, dtype=torch.float64), draws=torch.zeros(5, dtype=torch.float64),
+             mu=torch.zeros(5, dtype=torch.float64))
+    assert friction_abi.friction_draw_ptrs(5, CPU, **d) == tuple(d[k].data_ptr() for k in ("mask", "key", "draws", "mu"))
+    rows = torch.zeros(8, 5, dtype=torch.float64)            # rows 0 and 1 of a randomiser's state are such rows
+    assert friction_abi.friction_draw_ptrs(5, CPU, d["mask"], rows[0], rows[1], d["mu"])[1:3] == (rows.data_ptr(), rows.data_ptr() + 40)
+
+
+BAD_ARGS = [(name, how) for name in ("state", "grf", "foot_target", "leg_state", "mu", "ext", "touch", "slip") for how in ("dtype", "batch", "strided", "device", "type")]
+BAD_ARGS += [(name, "none") for name in ("state", "grf", "foot_target", "leg_state", "mu")]
+
+
+@pytest.mark.parametrize("name,how", BAD_ARGS)
+def test_the_binding_refuses_a_bad_tensor_naming_the_argument(name, how, monkeypatch):
+    for probe in ("is_available", "current_device", "current_stream", "device_count"):
+        monkeypatch.setattr(torch.cuda, probe, lambda *a, **k: pytest.fail(f"torch.cuda.{probe} called before validation"))
+    a = _good()
+    t = a[name]
+    if how == "dtype":
+        a[name] = t.to(torch.float16)
+    elif how == "batch":
+        a[name] = _good(6)[name]
+    elif how == "strided":
+        a[name] = torch.zeros(*t.shape[:-1], 2 * t.shape[-1], dtype=t.dtype)[..., ::2]
+        assert a[name].shape == t.shape and not a[name].is_contiguous()
+    elif how == "device":
+        a[name] = t.to("meta")
+    elif how == "type":
+        a[name] = t.numpy()
+    elif how == "none":
+        a[name] = None
+    with pytest.raises(ValueError, match=rf"step_friction: {name}\b"):
+        friction_abi.step_friction_ptrs(5, CPU, **a)
+
+
+def test_the_binding_refuses_bad_settings_and_ranges():
+    for bad in (-1.0, math.nan, math.inf, "fast", None):
+        with pytest.raises(ValueError, match="slip_gain"):
+            friction_abi.checked_settings(bad, 1.0)
+        with pytest.raises(ValueError, match="slip_speed_max"):
+            friction_abi.checked_settings(0.01, bad)
+    assert friction_abi.checked_settings(0, 0) == (0.0, 0.0)
+    for lo, hi in ((-0.1, 0.5), (0.6, 0.5), (0.1, math.inf), (math.nan, 0.5), ("a", 1)):
+        with pytest.raises(ValueError, match="friction_draw"):
+            friction_abi.checked_range(lo, hi)
+    assert friction_abi.checked_range(0, 0.5) == (0.0, 0.5)
+
+
+def test_the_python_layer_refuses_a_bad_friction_before_it_looks_for_a_device(monkeypatch):
+    from robot_gym_amd.sim import BatchedSRBSim
+    from robot_gym_amd.sim.randomizer import DomainRandomizer
+    for probe in ("is_available", "current_device", "current_stream", "device_count"):
+        monkeypatch.setattr(torch.cuda, probe, lambda *a, **k: pytest.fail(f"torch.cuda.{probe} called before validation"))
+    for bad in ("slippery", [0.3, 0.4], np.zeros((4, 1)), torch.zeros(3), object(), True):
+        with pytest.raises(ValueError, match="friction"):
+            BatchedSRBSim(4, friction=bad)
+    with pytest.raises(ValueError, match="slip_gain"):
+        BatchedSRBSim(4, friction=0.3, slip_gain=-1.0)
+    with pytest.raises(ValueError, match="slip_speed_max"):
+        BatchedSRBSim(4, friction=0.3, slip_speed_max=math.nan)
+    for bad in (0.3, (0.5, 0.2), (-0.1, 0.2), (0.1, math.inf), (0.1, 0.2, 0.3), "ab"):
+        with pytest.raises(ValueError, match="friction"):
+            DomainRandomizer(friction=bad)
+    # a simulator without friction has no mu row for the draw to write
+    sim = types.SimpleNamespace(terrain=None, mu=None, batch=4, device=CPU, substeps=10)
+    dr = DomainRandomizer(friction=(0.2, 0.9))
+    with pytest.raises(ValueError, match="needs a simulator built with friction"):
+        dr.bind(sim)
+    assert dr._handle is None and DomainRandomizer().friction is None
+
+
+# ---- known answers, worked by hand ---------------------------------------------------------------------------------------
+
+DT = 0.001
+
+
+def _standing(B, ground=None, substeps=1, **kw):
+    """B ghost robots at p.z = 0.5 with identity rotation, all four feet planted.  With one sub-step R is the identity exactly,
+    so f = -grf and every figure below is one rounding of what the header says."""
+    cfg = MPCConfig.for_robot("ghost")
+    m = FM.FrictionSRBModel(B, cfg, ground or TM.Flat(), substeps=substeps, **kw)
+    m.reset(height=np.full(B, 0.5))
+    assert (m.state[M.ROW_QUAT + 3] == 1.0).all() and (m.state[M.ROW_STANCE:M.ROW_STANCE + 4] == 1).all() and m.dt == DT
+    return cfg, m
+
+
+def _push(B, fx, fy, fz):
+    """grf [B,12] float32: the ground pushes foot 0 with (fx, fy, fz), the other feet with nothing."""
+    g = np.zeros((B, 12), np.float32)
+    g[:, 0], g[:, 1], g[:, 2] = -fx, -fy, -fz
+    return g
+
+
+STANCE4 = lambda B: np.full((B, 4), CM.STANCE, np.int32)
+
+
+@pytest.mark.parametrize("measured", [0, 1])
+def test_inside_the_cone_nothing_moves_and_on_its_edge_neither(measured):
+    cfg, m = _standing(2, mu=0.5)
+    before = m.state.copy()
+    g = _push(2, 3.0, 4.0, 10.0)              # |t| = 5 = mu n: the edge sticks
+    g[1, :2] = (-1.5, -2.0)                   # well inside
+    m.step_friction(g, np.zeros((2, 12), np.float32), STANCE4(2), measured)
+    assert (m.slip == 0.0).all() and not np.signbit(m.slip).any()
+    assert m.state[M.ROW_FOOT:M.ROW_FOOT + 12].tobytes() == before[M.ROW_FOOT:M.ROW_FOOT + 12].tobytes()
+    # the whole commanded force acted
+    assert m.state[M.ROW_V, 0] == DT * 3.0 / cfg.mass and m.state[M.ROW_V + 1, 0] == DT * 4.0 / cfg.mass
+    assert m.state[M.ROW_V, 1] == DT * 1.5 / cfg.mass and m.state[M.ROW_V + 1, 1] == DT * 2.0 / cfg.mass
+    assert (m.state[M.ROW_V + 2] == DT * (10.0 + cfg.mass * -cfg.gravity) / cfg.mass).all()
+
+
+def test_outside_the_cone_the_force_is_mu_n_and_the_foot_moves_against_it():
+    cfg, m = _standing(1, mu=0.5)
+    before = m.state.copy()
+    m.step_friction(_push(1, 6.0, 8.0, 10.0), np.zeros((1, 12), np.float32), STANCE4(1), 1)       # |t| = 10, lim = 5, excess 5
+    d = DT * (0.01 * 5.0)
+    assert m.slip[0, 0] == d and abs(d - 5e-5) < 1e-18 and (m.slip[1:] == 0.0).all()
+    assert m.state[M.ROW_FOOT, 0] == before[M.ROW_FOOT, 0] - 0.6 * d and m.state[M.ROW_FOOT + 1, 0] == before[M.ROW_FOOT + 1, 0] - 0.8 * d
+    assert m.state[M.ROW_FOOT + 2, 0] == 0.0
+    assert m.state[M.ROW_FOOT + 3:M.ROW_FOOT + 12].tobytes() == before[M.ROW_FOOT + 3:M.ROW_FOOT + 12].tobytes()
+    # the applied force: (6, 8) * (5 / 10) = (3, 4), magnitude mu n
+    assert m.state[M.ROW_V, 0] == DT * 3.0 / cfg.mass and m.state[M.ROW_V + 1, 0] == DT * 4.0 / cfg.mass
+    assert math.hypot(3.0, 4.0) == 0.5 * 10.0
+
+
+def test_ten_sub_steps_slide_ten_times_as_far_to_first_order():
+    cfg, m = _standing(1, substeps=10, mu=0.5)
+    x0 = m.state[M.ROW_FOOT, 0]
+    m.step_friction(_push(1, 6.0, 8.0, 10.0), np.zeros((1, 12), np.float32), STANCE4(1), 1)
+    # the body turns by a few 1e-4 rad under the torque within the tick, and f = R fbody with it
+    assert abs(m.slip[0, 0] - 10 * 5e-5) < 1e-3 * 5e-4 and abs((x0 - m.state[M.ROW_FOOT, 0]) - 0.6 * 5e-4) < 1e-3 * 5e-4
+    assert m.state[M.ROW_STEPS, 0] == 10
+
+
+def test_the_speed_cap_binds():
+    cfg, m = _standing(2, mu=0.5, slip_gain=1.0, slip_speed_max=0.25)
+    before = m.state.copy()
+    g = _push(2, 6.0, 8.0, 10.0)             # gain * excess = 5 m/s: capped at 0.25
+    g[1, :2] = (-3.06, -4.08)                # |t| = 5.1: 0.1 m/s, under the cap
+    m.step_friction(g, np.zeros((2, 12), np.float32), STANCE4(2), 1)
+    assert m.slip[0, 0] == DT * 0.25
+    assert m.state[M.ROW_FOOT, 0] == before[M.ROW_FOOT, 0] - 0.6 * (DT * 0.25)
+    assert abs(m.slip[0, 1] - DT * 0.1) < 1e-9 and m.slip[0, 1] < DT * 0.25
+    # a cap of zero: the force is clipped and the foot stays
+    cfg, z = _standing(1, mu=0.5, slip_speed_max=0.0)
+    z.step_friction(_push(1, 6.0, 8.0, 10.0), np.zeros((1, 12), np.float32), STANCE4(1), 1)
+    assert z.slip[0, 0] == 0.0 and z.state[M.ROW_V, 0] == DT * 3.0 / cfg.mass
+
+
+def test_a_downward_pull_is_clamped_to_zero_force():
+    cfg, m = _standing(2, mu=np.array([0.5, np.inf]))
+    m.step_friction(_push(2, 0.0, 0.0, -20.0), np.zeros((2, 12), np.float32), STANCE4(2), 1)
+    free = DT * (0.0 + cfg.mass * -cfg.gravity) / cfg.mass
+    assert m.state[M.ROW_V + 2, 0] == free                                          # the ground does not pull: free fall
+    assert m.state[M.ROW_V + 2, 1] == DT * (-20.0 + cfg.mass * -cfg.gravity) / cfg.mass < free      # the robot that grips is pulled
+    assert (m.slip == 0.0).all()
+    # with a tangential force on top: lim = 0, so none of it acts and the foot slides
+    cfg, t = _standing(1, mu=0.5)
+    t.step_friction(_push(1, 3.0, 4.0, -20.0), np.zeros((1, 12), np.float32), STANCE4(1), 1)
+    assert t.state[M.ROW_V, 0] == 0.0 and t.state[M.ROW_V + 1, 0] == 0.0 and t.state[M.ROW_V + 2, 0] == free
+    assert t.slip[0, 0] == DT * (0.01 * 5.0)
+
+
+def test_mu_zero_applies_no_horizontal_force():
+    cfg, m = _standing(1, mu=0.0)
+    x0, y0 = m.state[M.ROW_FOOT, 0], m.state[M.ROW_FOOT + 1, 0]
+    m.step_friction(_push(1, 3.0, 4.0, 10.0), np.zeros((1, 12), np.float32), STANCE4(1), 1)
+    assert m.state[M.ROW_V, 0] == 0.0 and m.state[M.ROW_V + 1, 0] == 0.0
+    assert m.state[M.ROW_V + 2, 0] == DT * (10.0 + cfg.mass * -cfg.gravity) / cfg.mass
+    assert m.slip[0, 0] == DT * (0.01 * 5.0)
+    assert m.state[M.ROW_FOOT, 0] == x0 - 0.6 * m.slip[0, 0] and m.state[M.ROW_FOOT + 1, 0] == y0 - 0.8 * m.slip[0, 0]
+    assert (m.state[M.ROW_W:M.ROW_W + 3, 0] != 0.0).any()                            # the normal force still turns the body
+
+
+def test_a_swing_foot_and_a_frozen_robot_do_not_slide():
+    cfg, m = _standing(2, mu=0.0)
+    m.state[M.ROW_STATUS, 1] = 1.0
+    ls = STANCE4(2)
+    ls[0, 0] = CM.SWING
+    ft = np.tile(np.asarray(cfg.hip, dtype=np.float32).reshape(1, 12), (2, 1))
+    ft[:, 2::3] = np.float32(-0.4)
+    before = m.state.copy()
+    m.step_friction(_push(2, 3.0, 4.0, 10.0), ft, ls, 1)
+    assert (m.slip == 0.0).all()
+    assert m.state[M.ROW_STANCE, 0] == 0.0 and m.state[M.ROW_V, 0] == 0.0
+    assert m.state[:, 1].tobytes() == before[:, 1].tobytes()
+
+
+def test_on_a_grid_a_slid_foot_ends_at_the_grounds_height():
+    rng = np.random.default_rng(5)
+    ground = TM.Grid(rng.uniform(0.0, 0.05, (40, 40)), 0.05, (-1.0, -1.0))
+    cfg, m = _standing(3, ground, substeps=10, mu=np.array([0.2, 0.2, np.inf]), slip_gain=0.05)
+    before = m.state.copy()
+    g = _push(3, 30.0, 40.0, 10.0)
+    g[1, :2] = (-0.3, -0.4)                   # robot 1 sticks, robot 2 grips
+    m.step_friction(g, np.zeros((3, 12), np.float32), STANCE4(3), 0)
+    st = m.state
+    assert m.slip[0, 0] > 9e-3 and (m.slip[:, 1:] == 0.0).all() and (m.slip[1:, 0] == 0.0).all()
+    assert st[M.ROW_FOOT + 2, 0] == ground.height(st[M.ROW_FOOT, 0], st[M.ROW_FOOT + 1, 0]) != before[M.ROW_FOOT + 2, 0]
+    assert math.hypot(st[M.ROW_FOOT, 0] - before[M.ROW_FOOT, 0], st[M.ROW_FOOT + 1, 0] - before[M.ROW_FOOT + 1, 0]) > 9e-3
+    # a foot that did not slide keeps its height, bit for bit
+    assert st[M.ROW_FOOT:M.ROW_FOOT + 12, 1:].tobytes() == before[M.ROW_FOOT:M.ROW_FOOT + 12, 1:].tobytes()
+    assert st[M.ROW_FOOT + 3:M.ROW_FOOT + 12, 0].tobytes() == before[M.ROW_FOOT + 3:M.ROW_FOOT + 12, 0].tobytes()
+
+
+def test_a_nan_force_takes_the_slip_branch_and_the_robot_keeps_its_last_state():
+    cfg, m = _standing(2, mu=0.5)
+    before = m.state.copy()
+    g = _push(2, 1.0, 1.0, 10.0)
+    g[0, 1] = np.nan
+    m.step_friction(g, np.zeros((2, 12), np.float32), STANCE4(2), 1)
+    keep = [r for r in range(M.STATE_ROWS) if r != M.ROW_STATUS]
+    assert m.state[keep, 0].tobytes() == before[keep, 0].tobytes() and m.state[M.ROW_STATUS, 0] == 1.0
+    assert (m.slip[:, 0] == 0.0).all() and m.state[M.ROW_STATUS, 1] == 0.0 and m.state[M.ROW_STEPS, 1] == 1
+
+
+# ---- a robot that grips runs the tick without friction ---------------------------------------------------------------------
+
+GRIPS = (np.inf, np.nan, -1.0, -np.inf, -0.0 - 1e-300)
+
+
+@pytest.mark.parametrize("measured", [0, 1])
+@pytest.mark.parametrize("kind", FF.GROUNDS)
+def test_a_robot_that_grips_runs_the_tick_without_friction_bit_for_bit(kind, measured):
+    B = 19
+    cfg = MPCConfig.for_robot("ghost" if measured else "k3lso")
+    mu = np.array([GRIPS[b % len(GRIPS)] for b in range(B)])
+    rec = FF.run_model(cfg, B, 900 + FF.GROUNDS.index(kind) + 10 * measured, kind, measured, mu=mu)
+    assert rec.slipping == rec.sticking == 0 and all((s == 0.0).all() and not np.signbit(s).any() for s in rec.slips)
+    s = rec.s
+    m = (CM.ContactSRBModel if measured else TM.TerrainSRBModel)(B, cfg, rec.ground)
+    m.set_body(idx=rec.body_idx, mass=s["mass"][rec.body_idx], inertia=s["inertia"][:, rec.body_idx])
+    m.reset(xy=rec.start[0], yaw=rec.start[1], height=rec.start[2])
+    assert m.state.tobytes() == rec.states[0].tobytes()
+    for k, (g, ft, ls, ext) in enumerate(rec.inputs):
+        if k in rec.resets:
+            idx, xy, yaw, h = rec.resets[k]
+            m.reset(idx=idx, xy=xy, yaw=yaw, height=h)
+        if measured:
+            m.step_contact(g, ft, ls, ext)
+            assert (m.touch == rec.touches[k]).all(), k
+        else:
+            m.step(g, ft, ls, ext)
+            assert (rec.touches[k] == 0).all()
+        assert m.state.tobytes() == rec.states[k + 1].tobytes(), k
+        for name, want in rec.obs[k + 1].items():
+            assert m.obs[name].tobytes() == want.tobytes(), (k, name)
+    # the stream is the one described: someone fell, someone kept a state
+    assert rec.kept >= 1 and (rec.states[-1][M.ROW_STATUS] == 1).any() and (rec.states[-1][M.ROW_STATUS] == 0).any()
+
+
+def test_the_kernel_streams_slip_and_stick_in_like_numbers():
+    """The census the GPU test relies on, on the model's recordings: per ground and contact mode at least a quarter of the stance
+    leg-ticks of running robots with a coefficient slip and at least a quarter stick."""
+    for measured in (0, 1):
+        for g, kind in enumerate(FF.GROUNDS):
+            slip = stick = 0
+            for n, B in enumerate(FF.BATCHES):
+                rec = FF.run_model(MPCConfig.for_robot(FF.STREAM_ROBOT[B]), B, FF.stream_seed(g, n, measured), kind, measured)
+                slip, stick = slip + rec.slipping, stick + rec.sticking
+            print(kind, measured, "slipping", slip, "sticking", stick)
+            assert 4 * slip >= slip + stick and 4 * stick >= slip + stick and slip + stick > 1000, (kind, measured, slip, stick)
+    assert {np.inf, -1.0, 0.0, 0.05, 1.0} <= set(FF.stream_mu(67).tolist()) and np.isnan(FF.stream_mu(67)).any()
+
+
+# ---- the draw --------------------------------------------------------------------------------------------------------------
+
+def test_the_draw_lies_in_its_range_follows_the_key_and_leaves_the_rest():
+    B, seed, lo, hi = 300, 12345, 0.2, 0.9
+    rng = np.random.default_rng(3)
+    key = rng.integers(-1000, 1000, B).astype(np.float64)
+    draws = rng.integers(0, 50, B).astype(np.float64)
+    mask = (rng.uniform(size=B) < 0.6).astype(np.int32)
+    mu = np.full(B, -7.0)
+    FM.draw(mu, mask, key, draws, seed, lo, hi)
+    on = mask != 0
+    assert (mu[~on] == -7.0).all() and on.sum() > 100 and (~on).sum() > 50
+    assert (mu[on] >= lo).all() and (mu[on] <= hi).all() and mu[on].std() > 0.15
+    # by hand for two entries
+    for b in (int(np.nonzero(on)[0][0]), int(np.nonzero(on)[0][-1])):
+        assert mu[b] == lo + (hi - lo) * SM.uniform(seed, int(key[b]), int(draws[b]), 48, 0)
+    # the value follows the key and the draw count, not the position in the batch
+    perm = rng.permutation(B)
+    again = np.full(B, -7.0)
+    FM.draw(again, mask[perm], key[perm], draws[perm], seed, lo, hi)
+    assert again.tobytes() == mu[perm].tobytes()
+    # another draw count, another seed and another purpose give other values
+    other = np.full(B, -7.0)
+    FM.draw(other, mask, key, draws + 1.0, seed, lo, hi)
+    assert (other[on] != mu[on]).all()
+    assert SM.uniform(seed, 5, 0, 48, 0) != SM.uniform(seed, 5, 0, dr_abi.PURPOSE_MASS, 0) != SM.uniform(seed + 1, 5, 0, 48, 0)
+    # a degenerate range
+    flat = np.zeros(4)
+    FM.draw(flat, np.ones(4, np.int32), np.arange(4.0), np.zeros(4), 1, 0.5, 0.5)
+    assert (flat == 0.5).all()
+
+
+# ---- resources of rg_srb_friction.hip --------------------------------------------------------------------------------------
+
+KERNELS = {"rg_srb_friction_step_kernel", "rg_srb_friction_draw_kernel"}
+
+
+@pytest.fixture(scope="module")
+def remarks(tmp_path_factory):
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc here")
+    out = tmp_path_factory.mktemp("srb_friction") / "rg_srb_friction.s"
+    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
+                          "rg_srb_friction.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr[-4000:]
+    kernels, name = {}, None
+    for line in res.stderr.splitlines():
+        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
+        if not m:
+            continue
+        text = m.group(1).strip()
+        if text.startswith("Function Name:"):
+            mangled = text.split(":", 1)[1].strip()
+            k = re.search(r"(rg_srb_[a-z_]+_kernel)", mangled)
+            name = k.group(1) if k else mangled
+            kernels[name] = {}
+        elif name and ":" in text:
+            key, val = text.split(":", 1)
+            kernels[name][key.strip()] = val.strip()
+    return kernels
+
+
+def test_both_friction_kernels_are_reported_and_use_no_scratch_and_no_lds(remarks):
+    assert set(remarks) == KERNELS
+    for name in KERNELS:
+        r = remarks[name]
+        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
+        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
+        assert r["Dynamic Stack"] == "False", (name, r)
+        assert int(r["LDS Size [bytes/block]"]) == 0, (name, r)
+
+
+# What the device-only compile reports today (upper bounds): the step kernel where the contact step kernel is (256 + 34) -- the
+# friction rule adds a handful of live values inside the sub-step loop, and the third ground lookup sits outside it.
+REGISTERS = {"rg_srb_friction_step_kernel": dict(vgprs=256, agprs=34, waves=1), "rg_srb_friction_draw_kernel": dict(vgprs=12, agprs=0, waves=8)}
+
+
+def test_friction_register_use_is_pinned(remarks):
+    for name, want in REGISTERS.items():
+        r = remarks[name]
+        assert int(r["VGPRs"]) <= want["vgprs"], (name, r)
+        assert int(r["AGPRs"]) <= want["agprs"], (name, r)
+        assert int(r["Occupancy [waves/SIMD]"]) >= want["waves"], (name, r)
+
+
+def test_friction_source_keeps_contraction_off_and_both_library_targets_compile_it():
+    src = open(os.path.join(SRC, "rg_srb_friction.hip")).read()
+    assert src.index("#pragma clang fp contract(off)") < src.index('#include "rg_mpc_dev.h"') < src.index("__global__")
+    assert src.index("#pragma clang fp contract(off)") < src.index('#include "rg_srb_ground.inc"')
+    assert src.count("#pragma clang fp contract") == 1
+    code = re.sub(r"//.*", "", src)
+    assert "asm" not in code and "atomic" not in code and "__shared__" not in code and "fma(" not in code
+    makefile = open(os.path.join(SRC, "Makefile")).read()
+    assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_srb_friction\.hip", makefile)) == 2
+    # the existing simulator units are not touched by this one: it is a translation unit of its own
+    for other in ("rg_srb.hip", "rg_srb_terrain.hip", "rg_srb_contact.hip"):
+        assert "friction" not in open(os.path.join(SRC, other)).read(), other
+
+
+# ---- the CPU closed loop on floors of three coefficients -------------------------------------------------------------------
+
+GROUND_NAMES = ("plane", "reference")
+
+
+def _ground(name, n=32):
+    return TM.Flat() if name == "plane" else CF.reference_ground(n)
+
+
+@pytest.fixture(scope="module")
+def floors():
+    """{(robot, ground, mu): the loop after 400 ticks}: oracle plus friction model, the 32 cases."""
+    out = {}
+    for robot in F.ROBOTS:
+        for gname in GROUND_NAMES:
+            for mu in (FF.MU_GRIPS, FF.MU_SLIPPERY, FF.MU_ICE):
+                out[robot, gname, mu] = FF.run_cpu(robot, _ground(gname), mu)[1]
+    return out
+
+
+@pytest.mark.parametrize("gname", GROUND_NAMES)
+@pytest.mark.parametrize("robot", F.ROBOTS)
+def test_closed_loop_on_three_floors(robot, gname, floors):
+    assert tuple(MPCConfig.for_robot(robot).mu) == (FF.BELIEVED_MU,) * 4 and FF.MU_GRIPS > math.sqrt(2.0) * FF.BELIEVED_MU > FF.MU_SLIPPERY
+    grip, slippery, ice = (floors[robot, gname, mu] for mu in (FF.MU_GRIPS, FF.MU_SLIPPERY, FF.MU_ICE))
+    for name, loop in (("grip", grip), ("slippery", slippery), ("ice", ice)):
+        w = FF.worst_slid(loop.slid)
+        print(robot, gname, name, "fallen", int(loop.model.fallen().sum()), "robots that slid", int((w > 0).sum()), "worst slid", float(w.max()))
+    # the planner's pyramid allows |t| up to sqrt(2) mu n: a floor that holds more than that never slips
+    assert grip.slid.sum() == 0.0 and not grip.model.fallen().any()
+    assert (grip.model.state[M.ROW_STEPS] == 10 * F.TICKS).all()
+    # a moderately slippery floor: feet slide a centimetre and nobody falls
+    assert not slippery.model.fallen().any()
+    assert int((FF.worst_slid(slippery.slid) > 0).sum()) >= FF.SLIDERS
+    # ice: every robot falls
+    assert ice.model.fallen().all()
+
+
+def test_the_slid_band_is_twice_what_this_run_produces(floors):
+    for robot in F.ROBOTS:
+        worst = float(FF.worst_slid(floors[robot, "reference", FF.MU_SLIPPERY].slid).max())
+        print(robot, "measured worst slid", worst, "band", FF.SLID_BAND[robot])
+        assert abs(FF.SLID_BAND[robot] - 2 * worst) <= 0.01 * FF.SLID_BAND[robot], (robot, worst)

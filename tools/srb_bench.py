@@ -17,6 +17,13 @@ and a settle of the whole batch.
 schedule tick on the same terrain and the tick on the plane, in the same run, from the same state and on the same held
 controller outputs (the plane before and after, for the run-to-run spread).
 
+    python tools/srb_bench.py --friction [--batches 64,4096,32768] [--out profiles/srb_friction_tick.json]
+
+--friction times the tick with Coulomb friction (friction=, rg_srb_step_friction, measured contact) with every mu = +inf (every
+robot grips) and with every mu = 0.3 next to the measured-contact tick and the schedule tick, on the plane and on the random
+terrain, in the same run, from the same state and on the same held controller outputs.  No pass/fail ratio: these are
+launch-bound kernels of a few microseconds.
+
 Kernel statistics come from a run of their own:  rocprofv3 --kernel-trace --stats -d DIR -- python tools/srb_bench.py --batches 4096
 """
 import argparse
@@ -66,7 +73,8 @@ def srb_hash():
     h = hashlib.sha256()
     for rel in ("robot_gym_amd/csrc/rg_srb.hip", "robot_gym_amd/csrc/rg_srb_dev.inc", "robot_gym_amd/csrc/rg_srb_handle.h", "robot_gym_amd/csrc/rg_host.h",
                 "robot_gym_amd/csrc/rg_srb_terrain.hip", "robot_gym_amd/csrc/rg_srb_ground.inc", "robot_gym_amd/csrc/rg_stream_dev.inc",
-                "robot_gym_amd/csrc/rg_srb_contact.hip", "include/rg_srb.h", "include/rg_srb_terrain.h", "include/rg_srb_contact.h"):
+                "robot_gym_amd/csrc/rg_srb_contact.hip", "robot_gym_amd/csrc/rg_srb_friction.hip", "include/rg_srb.h", "include/rg_srb_terrain.h",
+                "include/rg_srb_contact.h", "include/rg_srb_friction.h"):
         h.update(open(os.path.join(ROOT, rel), "rb").read())
     return h.hexdigest()[:16]
 
@@ -139,12 +147,78 @@ def contact_rows(args, dev, cfg):
     return rows
 
 
+def friction_rows(args, dev, cfg):
+    """Per batch and ground (the plane, the random terrain): the friction tick with every mu = +inf, the friction tick with every
+    mu = 0.3, the measured-contact tick and the schedule tick, us per call; every measurement starts from the state the warm-up
+    (closed loop with measured contact and friction 0.3 on that ground) ended in, on the same held controller outputs."""
+    from robot_gym_amd.sim.terrain import RandomTerrain
+    rows = []
+    for B in [int(x) for x in args.batches.split(",")]:
+        for ground in ("plane", "random"):
+            rng = np.random.default_rng(B)
+            terrain = lambda: RandomTerrain() if ground == "random" else None
+            ctl = BatchedMPCController(B, cfg, device=dev)
+            schedule = BatchedSRBSim(B, cfg, device=dev, terrain=terrain())
+            contact = BatchedSRBSim(B, cfg, device=dev, terrain=terrain(), contact="measured")
+            grips = BatchedSRBSim(B, cfg, device=dev, terrain=terrain(), contact="measured", friction="inf")
+            slippery = BatchedSRBSim(B, cfg, device=dev, terrain=terrain(), contact="measured", friction=0.3)
+            sims = (schedule, contact, grips, slippery)
+            cmd = np.stack([rng.uniform(-0.35, 0.35, B), rng.uniform(-0.2, 0.2, B), rng.uniform(-0.4, 0.4, B)], 1).astype(np.float32)
+            hs = cfg.body_height * rng.uniform(0.9, 1.1, B)
+            for sim in sims:
+                sim.reset(height=hs)
+            ctl.reset()
+            ctl.update_controller_params(torch.as_tensor(cmd, device=dev))
+            slid = torch.zeros(B, dtype=torch.float64, device=dev)
+            rollout(ctl, slippery, None, args.warmup, on_tick=lambda k: slid.add_(slippery.slip.sum(0)))   # into the trot on the slippery floor
+            fallen, sliding = int(slippery.fallen().sum()), int((slid > 0).sum())
+            keep = slippery.state.clone()
+            out = {}
+            for name, sim in (("friction_inf_us", grips), ("friction_0p3_us", slippery), ("contact_us", contact), ("schedule_us", schedule),
+                              ("friction_inf_again_us", grips)):
+                sim.state.copy_(keep)
+                out[name], n = timed(lambda: sim.step(ctl), args.seconds)
+            rows.append(dict(batch=B, ground=ground, ticks=n, **{k: round(v, 2) for k, v in out.items()}, fallen_in_warmup=fallen,
+                             robots_that_slid_in_warmup=sliding))
+            print(json.dumps(rows[-1]), flush=True)
+            for h in (ctl,) + sims:
+                h.close()
+    return rows
+
+
+def closed_loop_slid(robot, dev, friction, ticks=400):
+    """The closed loop of tests/test_friction_gpu.py on a floor that holds twice what the planner believes: the 32 cases of
+    tests/srb_fixtures.py, measured contact on the reference's random terrain -> robots that slid at all and the worst distance a
+    robot's four feet slid, added up.  For the record: how closely the ADMM lane keeps the friction cone."""
+    from robot_gym_amd.sim.terrain import RandomTerrain
+    from tests import contact_fixtures as CF
+    from tests import srb_fixtures as F
+    cfg = MPCConfig.for_robot(robot)
+    cmd, hs = F.cases(robot)
+    B = len(hs)
+    ctl = BatchedMPCController(B, cfg, device=dev)
+    sim = BatchedSRBSim(B, cfg, device=dev, terrain=RandomTerrain(CF.AMPLITUDE, CF.CELL, CF.SEED), contact="measured", friction=friction)
+    sim.reset(height=cfg.body_height * hs)
+    ctl.reset()
+    ctl.set_raw_command(torch.as_tensor(np.ascontiguousarray(cmd.T), device=dev))
+    slid = torch.zeros(B, dtype=torch.float64, device=dev)
+    rollout(ctl, sim, None, ticks, on_tick=lambda k: slid.add_(sim.slip.sum(0)))
+    row = dict(robot=robot, friction=friction, ticks=ticks, robots=B, fallen=int(sim.fallen().sum()), robots_that_slid=int((slid > 0).sum()),
+               worst_slid_m=float(slid.max()))
+    print(json.dumps(row), flush=True)
+    ctl.close()
+    sim.close()
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--robot", default="ghost")
     ap.add_argument("--batches", default=None, help="default 1,1024,4096,32768 (--terrain: 1,64,1024,4096,32768)")
     ap.add_argument("--terrain", action="store_true", help="the tick on the random terrain next to the tick on the plane, and settle")
     ap.add_argument("--contact", action="store_true", help="the measured-contact tick next to the terrain tick and the plane tick (batch 4096)")
+    ap.add_argument("--friction", action="store_true", help="the friction tick (mu = +inf, mu = 0.3) next to the contact tick and the schedule tick "
+                                                            "(batch 64, 4096, 32768; the plane and the random terrain)")
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--out", default=None)
@@ -155,6 +229,21 @@ def main():
     args.batches_given = args.batches is not None
     args.batches = args.batches or ("1,64,1024,4096,32768" if args.terrain else "1,1024,4096,32768")
     rows = []
+    if args.friction:
+        args.batches = args.batches if args.batches_given else "64,4096,32768"
+        result = dict(what="simulator tick with Coulomb friction at the stance feet (measured contact; every mu = +inf, every mu = 0.3) next to the "
+                           "measured-contact tick and the schedule tick, on the plane and on the random terrain (amplitude 0.06, cell 0.05, one world "
+                           "per robot): same run, same start state, same held controller outputs; the +inf tick twice, for the run-to-run spread",
+                      robot=args.robot, commit=commit, dirty=dirty, source_hash=bench.source_hash(), srb_source_sha256=srb_hash(),
+                      device=torch.cuda.get_device_name(0), seconds_per_measurement=args.seconds, rows=friction_rows(args, dev, cfg))
+        result["closed_loop_friction_0p9"] = [closed_loop_slid(robot, dev, 0.9) for robot in ("ghost", "k3lso")]
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+        print(json.dumps(result))
+        return
     if args.contact:
         args.batches = args.batches if args.batches_given else "4096"
         result = dict(what="simulator tick with measured foot contact on the random terrain (amplitude 0.06, cell 0.05, one world per robot) next to "
