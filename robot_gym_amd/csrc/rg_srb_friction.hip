@@ -2,9 +2,9 @@
 // rg_srb_friction.h) and the per-episode draw of the coefficient (rg_srb_friction_draw).  Its own translation unit of
 // librg_mpc.so, so that rg_srb.hip, rg_srb_terrain.hip and rg_srb_contact.hip keep the code they have.
 //
-// Layout: that of rg_srb_contact.hip.  The step kernel is rg_srb_contact_step_kernel with step 1 chosen by `measured`
-// (wave-uniform) and the force rule in its third form: lane = (robot, leg), float64, no LDS, every lane guarded at its stores
-// only, lanes past the batch computing on the last robot, no branch around a cross-lane operation.  The friction rule is
+// Layout: that of rg_srb_contact.hip.  The step kernel stands on the shared body of a tick (rg_srb_tick.inc, where the
+// cross-lane operations and their invariants are stated) and owns step 1 chosen by `measured` (wave-uniform), the force rule in
+// its third form, the foot's slide and the touch and slip outputs: lane = (robot, leg), float64, no LDS.  The friction rule is
 // written with selects, so a robot that grips (mu +inf, NaN or negative) runs the operations of the tick without friction on
 // the values it had.  The ground is asked at the two points of the contact tick and, for a foot that slid, a third time under
 // the foot; one kernel serves all three ground kinds (kind is wave-uniform, the plane gives the literal 0).
@@ -36,20 +36,19 @@ namespace {
 
 constexpr int kBlock = kSrbBlock;
 
-// sum over the four lanes of a robot: (x_0 + x_1) + (x_2 + x_3) in every lane
-__device__ __forceinline__ double sum4(double x) {
-  x = x + __shfl_xor(x, 1);
-  return x + __shfl_xor(x, 2);
-}
+// sum4 and the tick_* functions, the body of a tick: shared with the other three step kernels
+#include "rg_srb_tick.inc"
 
 // kCoordBound, the stream (rg_stream_dev.inc) and Ground, h(x, y; robot) of rg_srb.h: shared with rg_srb_terrain.hip
 #include "rg_srb_ground.inc"
 
 static_assert(purposes_in_block(3, RG_SRB_FRICTION_PURPOSE_MU), "rg_stream.h: the friction unit owns purposes 48..63");
 
-// One control tick with friction on the ground g (kind 0: the plane).  rg_srb_contact_step_kernel with step 1 chosen by
-// `measured` and the force rule of rg_srb_friction.h, and otherwise its text, statement for statement.  touch, slip: [4][B]
-// or NULL.
+// One control tick with friction on the ground g (kind 0: the plane).  Its own: step 1 of rg_srb_contact_step_kernel or of
+// rg_srb_terrain_step_kernel, chosen by `measured`; the force rule of rg_srb_friction.h inside the sub-step loop, between the
+// force's rotation and the wrench, and the foot's slide between the body update and the quaternion update; a third ground query
+// under a foot that slid; and touch, slip: [4][B] or NULL.  The wrench and the body update of its sub-step are typed out here,
+// for speed (below); the loads, the quaternion update, the finite test and the stores are the shared ones.
 __global__ void __launch_bounds__(kBlock) rg_srb_friction_step_kernel(const DevCfg *__restrict__ kc, SrbCfg c, rg_srb_ground g,
                                                                        const double *__restrict__ body, double *__restrict__ state,
                                                                        const float *__restrict__ grf, const float *__restrict__ foot_target,
@@ -64,26 +63,11 @@ __global__ void __launch_bounds__(kBlock) rg_srb_friction_step_kernel(const DevC
   const bool in_batch = (t >> 2) < c.B;
   const int b = in_batch ? (t >> 2) : c.B - 1;   // lanes past the batch compute on the last robot and store nothing
   const size_t sB = (size_t)c.B;
-  double p[3], qt[4], v[3], w[3], foot[3], q[3];
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    p[i] = state[(RG_SRB_ROW_P + i) * sB + b];
-    v[i] = state[(RG_SRB_ROW_V + i) * sB + b];
-    w[i] = state[(RG_SRB_ROW_W + i) * sB + b];
-    foot[i] = state[(RG_SRB_ROW_FOOT + 3 * leg + i) * sB + b];
-    q[i] = state[(RG_SRB_ROW_Q + 3 * leg + i) * sB + b];
-  }
-#pragma unroll
-  for (int i = 0; i < 4; i++) qt[i] = state[(RG_SRB_ROW_QUAT + i) * sB + b];
-  double stance = state[(RG_SRB_ROW_STANCE + leg) * sB + b];
-  double steps = state[RG_SRB_ROW_STEPS * sB + b];
-  const bool running = state[RG_SRB_ROW_STATUS * sB + b] == 0.0;
-  const double mass = body[b];
+  double p[3], qt[4], v[3], w[3], foot[3], q[3], stance, steps, I[9], Iinv[9], eF[3], eT[3];
+  const bool running = tick_load_state(state, sB, b, leg, p, qt, v, w, foot, q, stance, steps);
+  const double mass = tick_load_body(body, sB, b, I, Iinv);
   const double mu = mu_row[b];
   const bool grips = !(mu >= 0.0 && mu < INFINITY);   // +inf, NaN, negative: the tick without friction
-  double I[9], Iinv[9];
-#pragma unroll
-  for (int i = 0; i < 9; i++) { I[i] = body[(1 + i) * sB + b]; Iinv[i] = body[(10 + i) * sB + b]; }
   double R[9];
   quat_rot(qt, R);
   // 1. feet: one ground evaluation per lane, at the swing target (measured) or under the foot
@@ -108,16 +92,12 @@ __global__ void __launch_bounds__(kBlock) rg_srb_friction_step_kernel(const DevC
 #pragma unroll
   for (int i = 0; i < 3; i++) fbody[i] = stance == 1.0 ? -(double)grf[(size_t)b * 12 + 3 * leg + i] : 0.0;
   const bool rubs = !grips && stance == 1.0;   // the lanes the friction rule applies to
-  double eF[3] = {0.0, 0.0, 0.0}, eT[3] = {0.0, 0.0, 0.0};
-  if (ext) {
-#pragma unroll
-    for (int i = 0; i < 3; i++) { eF[i] = ext[i * sB + b]; eT[i] = ext[(3 + i) * sB + b]; }
-  }
+  tick_load_ext(ext, sB, b, eF, eT);
   const double dt = c.dt, wz = mass * -c.g;
   double slid = 0.0;
   // 2. sub-steps
   for (int s = 0; s < c.substeps; s++) {
-    double f[3], r[3], tq[3];
+    double f[3], F[3], T[3];
     quat_rot(qt, R);
     rot(R, fbody, f);
     // friction: the ground does not pull, and holds at most mu times the normal force.  A NaN fails the comparison and slips.
@@ -130,11 +110,13 @@ __global__ void __launch_bounds__(kBlock) rg_srb_friction_step_kernel(const DevC
     f[0] = slips ? f[0] * sc : f[0];
     f[1] = slips ? f[1] * sc : f[1];
     f[2] = rubs ? fn : f[2];
+    // tick_wrench and tick_body of rg_srb_tick.inc, inline in this one kernel: on the calls its mu = 0.3 tick measured above the
+    // parent's range at batch 4096 on the plane, on this text every figure lies below it (profiles/srb_tick_identity.txt)
+    double r[3], tq[3];
     r[0] = foot[0] - p[0]; r[1] = foot[1] - p[1]; r[2] = foot[2] - p[2];
     tq[0] = r[1] * f[2] - r[2] * f[1];
     tq[1] = r[2] * f[0] - r[0] * f[2];
     tq[2] = r[0] * f[1] - r[1] * f[0];
-    double F[3], T[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) { F[i] = sum4(f[i]); T[i] = sum4(tq[i]); }
     F[0] = F[0] + eF[0]; F[1] = F[1] + eF[1]; F[2] = F[2] + wz + eF[2];
@@ -158,47 +140,15 @@ __global__ void __launch_bounds__(kBlock) rg_srb_friction_step_kernel(const DevC
     foot[0] = slips ? foot[0] - ux * d : foot[0];
     foot[1] = slips ? foot[1] - uy * d : foot[1];
     slid = slips ? slid + d : slid;
-    const double ax = 0.5 * dt * w[0], ay = 0.5 * dt * w[1], az = 0.5 * dt * w[2];
-    const double dx = ax * qt[3] + ay * qt[2] - az * qt[1];
-    const double dy = ay * qt[3] + az * qt[0] - ax * qt[2];
-    const double dz = az * qt[3] + ax * qt[1] - ay * qt[0];
-    const double dw = -(ax * qt[0]) - ay * qt[1] - az * qt[2];
-    qt[0] = qt[0] + dx; qt[1] = qt[1] + dy; qt[2] = qt[2] + dz; qt[3] = qt[3] + dw;
-    const double nrm = sqrt(qt[0] * qt[0] + qt[1] * qt[1] + qt[2] * qt[2] + qt[3] * qt[3]);
-    qt[0] = qt[0] / nrm; qt[1] = qt[1] / nrm; qt[2] = qt[2] / nrm; qt[3] = qt[3] / nrm;
+    tick_quat(dt, w, qt);
   }
   steps = steps + (double)c.substeps;
   // a foot that slid stands on the ground where it is now (no cross-lane operation inside the branch)
   if (!plane && slid > 0.0) foot[2] = ground(b, foot[0], foot[1]);
-  // 3. fall
-  int bad = 0;
-#pragma unroll
-  for (int i = 0; i < 3; i++) bad |= !isfinite(p[i]) || !isfinite(v[i]) || !isfinite(w[i]) || !isfinite(foot[i]);
-#pragma unroll
-  for (int i = 0; i < 4; i++) bad |= !isfinite(qt[i]);
-  bad |= __shfl_xor(bad, 1);
-  bad |= __shfl_xor(bad, 2);
+  // 3. fall, and the stores
+  const int bad = tick_bad(p, qt, v, w, foot);
   const double under = plane ? 0.0 : ground(b, p[0], p[1]);
-  const bool fallen = bad || p[2] - under < c.fall_z || (1 - 2 * (qt[0] * qt[0] + qt[1] * qt[1])) < c.cos_tilt;
-  const bool live = in_batch && running;
-  if (live && leg == 0) state[RG_SRB_ROW_STATUS * sB + b] = fallen ? 1.0 : 0.0;
-  const bool store = live && !bad;
-  if (store) {
-#pragma unroll
-    for (int i = 0; i < 3; i++) state[(RG_SRB_ROW_FOOT + 3 * leg + i) * sB + b] = foot[i];
-    state[(RG_SRB_ROW_STANCE + leg) * sB + b] = stance;
-    if (leg == 0) {
-#pragma unroll
-      for (int i = 0; i < 3; i++) {
-        state[(RG_SRB_ROW_P + i) * sB + b] = p[i];
-        state[(RG_SRB_ROW_V + i) * sB + b] = v[i];
-        state[(RG_SRB_ROW_W + i) * sB + b] = w[i];
-      }
-#pragma unroll
-      for (int i = 0; i < 4; i++) state[(RG_SRB_ROW_QUAT + i) * sB + b] = qt[i];
-      state[RG_SRB_ROW_STEPS * sB + b] = steps;
-    }
-  }
+  const bool store = tick_store(state, c, b, leg, in_batch && running, bad, p[2] - under, p, qt, v, w, foot, stance, steps);
   // touch and slip are this tick's: a robot that is frozen, or keeps its last state, touched nothing and slid nowhere
   if (touch && in_batch) touch[(size_t)leg * sB + b] = store && touches ? 1 : 0;
   if (slip && in_batch) slip[(size_t)leg * sB + b] = store ? slid : 0.0;

@@ -1,15 +1,16 @@
 """The float64 statement of the tick with Coulomb friction of include/rg_srb_friction.h in numpy: contact_model.
 ContactSRBModel with step_friction, which is its step_contact() (measured = 1) or terrain_model.TerrainSRBModel.step()
-(measured = 0) with the force rule in its third form and otherwise their text.  It restates
+(measured = 0) with the force rule in its third form, handed to the one tick of srb_model.SRBModel._tick.  It restates
 robot_gym_amd/csrc/rg_srb_friction.hip operation for operation: the friction rule by selects, so a robot that grips runs the
 operations of the tick without friction; np.fmax / np.fmin where the kernel has fmax / fmin (a NaN loses).  `mu` [B] float64
 is the coefficient of each robot, `slip` [4, B] float64 the metres each foot slid on the last tick.  draw() is
 rg_srb_friction_draw through stream_model.uniform, the one definition of the stream.
 """
+from types import SimpleNamespace
+
 import numpy as np
 
 from tests import contact_model as CM
-from tests import srb_model as M
 from tests import stream_model as SM
 from tests import terrain_model as TM   # noqa: F401 -- the grounds a model is built on
 
@@ -33,120 +34,48 @@ class FrictionSRBModel(CM.ContactSRBModel):
         self.slip = np.zeros((4, self.B))
 
     def step_friction(self, grf, foot_target, leg_state, measured=1, ext=None):
-        B, st, dt = self.B, self.state, self.dt
-        all_robots = np.arange(B)
-        plane = self.ground.kind == 0
-        grf = np.asarray(grf).astype(np.float64).reshape(B, 4, 3)
-        ft = np.asarray(foot_target).astype(np.float64).reshape(B, 4, 3)
-        ls = np.asarray(leg_state).reshape(B, 4)
-        swung = (ls == CM.SWING) | ((ls == CM.LOSE_CONTACT) if measured else np.zeros_like(ls, dtype=bool))
-        ext = np.zeros((6, B)) if ext is None else np.asarray(ext, dtype=np.float64)
-        running = st[M.ROW_STATUS] == 0.0
-        mu = self.mu
+        B, dt, mu, gain, vmax = self.B, self.dt, self.mu, self.slip_gain, self.slip_speed_max
+        height = self._height()
         with np.errstate(invalid="ignore"):
             grips = ~((mu >= 0.0) & (mu < np.inf))
-        gain, vmax = self.slip_gain, self.slip_speed_max
-        p = [st[M.ROW_P + i].copy() for i in range(3)]
-        qt = [st[M.ROW_QUAT + i].copy() for i in range(4)]
-        v = [st[M.ROW_V + i].copy() for i in range(3)]
-        w = [st[M.ROW_W + i].copy() for i in range(3)]
-        foot = [[st[M.ROW_FOOT + 3 * l + i].copy() for i in range(3)] for l in range(4)]
-        stance = [st[M.ROW_STANCE + l].copy() for l in range(4)]
-        mass, I, Iinv = self.mass, list(self.I), list(self.Iinv)
-        R = M.quat_rot(qt)
-        rot, rot_t = M.rot, M.rot_t
-        fbody, touches, rubs = [], [], []
-        slid = [np.zeros(B) for _ in range(4)]
-        with np.errstate(all="ignore"):
-            # 1. feet
-            for l in range(4):
-                sw = swung[:, l]
-                tested = sw if measured else np.zeros(B, dtype=bool)
-                r = rot(R, [ft[:, l, k] for k in range(3)])
-                c = [p[i] + r[i] for i in range(3)]
-                gh = self.ground.height(np.where(tested, c[0], foot[l][0]), np.where(tested, c[1], foot[l][1]), all_robots)
-                touch = tested & (c[2] <= gh)
-                land = ~sw & (stance[l] == 0.0)
-                foot[l][0] = np.where(sw, c[0], foot[l][0])
-                foot[l][1] = np.where(sw, c[1], foot[l][1])
-                foot[l][2] = np.where(sw, np.where(touch, gh, c[2]), np.where(land, gh, foot[l][2]))
-                stance[l] = np.where(sw, np.where(touch, 1.0, 0.0), 1.0)
-                touches.append(touch)
-                # the ground pushes only through a foot that is on it
-                fbody.append([np.where(stance[l] == 1.0, -grf[:, l, i], 0.0) for i in range(3)])
-                rubs.append(~grips & (stance[l] == 1.0))
-            wz = mass * -self.g
-            # 2. sub-steps
-            for _ in range(self.S):
-                R = M.quat_rot(qt)
-                f, tq, moves = [], [], []
-                for l in range(4):
-                    fl = rot(R, fbody[l])
-                    # friction: the ground does not pull, and holds at most mu times the normal force
-                    fn = np.fmax(fl[2], 0.0)
-                    t2 = fl[0] * fl[0] + fl[1] * fl[1]
-                    lim = mu * fn
-                    slips = rubs[l] & ~(t2 <= lim * lim)
-                    tn = np.sqrt(t2)
-                    sc, ux, uy = lim / tn, fl[0] / tn, fl[1] / tn
-                    d = dt * np.fmin(gain * (tn - lim), vmax)
-                    fl = [np.where(slips, fl[0] * sc, fl[0]), np.where(slips, fl[1] * sc, fl[1]), np.where(rubs[l], fn, fl[2])]
-                    moves.append((slips, ux, uy, d))
-                    r = [foot[l][i] - p[i] for i in range(3)]
-                    f.append(fl)
-                    tq.append([r[1] * fl[2] - r[2] * fl[1], r[2] * fl[0] - r[0] * fl[2], r[0] * fl[1] - r[1] * fl[0]])
-                F = [(f[0][i] + f[1][i]) + (f[2][i] + f[3][i]) for i in range(3)]
-                T = [(tq[0][i] + tq[1][i]) + (tq[2][i] + tq[3][i]) for i in range(3)]
-                F = [F[0] + ext[0], F[1] + ext[1], F[2] + wz + ext[2]]
-                T = [T[0] + ext[3], T[1] + ext[4], T[2] + ext[5]]
-                tb, wb = rot_t(R, T), rot_t(R, w)
-                Iw = rot(I, wb)
-                rhs = [tb[0] - (wb[1] * Iw[2] - wb[2] * Iw[1]), tb[1] - (wb[2] * Iw[0] - wb[0] * Iw[2]), tb[2] - (wb[0] * Iw[1] - wb[1] * Iw[0])]
-                aw = rot(R, rot(Iinv, rhs))
-                for i in range(3):
-                    w[i] = w[i] + dt * aw[i]
-                    v[i] = v[i] + dt * F[i] / mass
-                    p[i] = p[i] + dt * v[i]
-                # the slipping foot moves against the friction force
-                for l, (slips, ux, uy, d) in enumerate(moves):
-                    foot[l][0] = np.where(slips, foot[l][0] - ux * d, foot[l][0])
-                    foot[l][1] = np.where(slips, foot[l][1] - uy * d, foot[l][1])
-                    slid[l] = np.where(slips, slid[l] + d, slid[l])
-                ax, ay, az = 0.5 * dt * w[0], 0.5 * dt * w[1], 0.5 * dt * w[2]
-                dx = ax * qt[3] + ay * qt[2] - az * qt[1]
-                dy = ay * qt[3] + az * qt[0] - ax * qt[2]
-                dz = az * qt[3] + ax * qt[1] - ay * qt[0]
-                dw = -(ax * qt[0]) - ay * qt[1] - az * qt[2]
-                qt = [qt[0] + dx, qt[1] + dy, qt[2] + dz, qt[3] + dw]
-                nrm = np.sqrt(qt[0] * qt[0] + qt[1] * qt[1] + qt[2] * qt[2] + qt[3] * qt[3])
-                qt = [qt[i] / nrm for i in range(4)]
+        contact_feet = self._contact_feet(leg_state, height, measured)
+        rubs, moves, slid = [], [], [np.zeros(B) for _ in range(4)]
+
+        def feet(l, c, foot, stance, grf):
+            out = contact_feet(l, c, foot, stance, grf)
+            rubs.append(~grips & (out[1] == 1.0))
+            return out
+
+        def force(l, fl):
+            # friction: the ground does not pull, and holds at most mu times the normal force
+            fn = np.fmax(fl[2], 0.0)
+            t2 = fl[0] * fl[0] + fl[1] * fl[1]
+            lim = mu * fn
+            slips = rubs[l] & ~(t2 <= lim * lim)
+            tn = np.sqrt(t2)
+            sc, ux, uy = lim / tn, fl[0] / tn, fl[1] / tn
+            d = dt * np.fmin(gain * (tn - lim), vmax)
+            moves.append((slips, ux, uy, d))
+            return [np.where(slips, fl[0] * sc, fl[0]), np.where(slips, fl[1] * sc, fl[1]), np.where(rubs[l], fn, fl[2])]
+
+        def slide(foot):
+            # the slipping foot moves against the friction force
+            for l, (slips, ux, uy, d) in enumerate(moves):
+                foot[l][0] = np.where(slips, foot[l][0] - ux * d, foot[l][0])
+                foot[l][1] = np.where(slips, foot[l][1] - uy * d, foot[l][1])
+                slid[l] = np.where(slips, slid[l] + d, slid[l])
+            moves.clear()
+
+        def stand(foot):
             # a foot that slid stands on the ground where it is now
-            if not plane:
+            if self.ground.kind != 0:
                 for l in range(4):
                     moved = slid[l] > 0.0
                     if moved.any():
-                        foot[l][2] = np.where(moved, self.ground.height(foot[l][0], foot[l][1], all_robots), foot[l][2])
-            # 3. fall
-            finite = np.ones(B, dtype=bool)
-            for a in p + v + w + qt + [foot[l][i] for l in range(4) for i in range(3)]:
-                finite &= np.isfinite(a)
-            clearance = p[2] - self.ground.height(p[0], p[1], all_robots)
-            fallen = ~finite | (clearance < self.fall_z) | ((1 - 2 * (qt[0] * qt[0] + qt[1] * qt[1])) < self.cos_tilt)
-        st[M.ROW_STATUS] = np.where(running, np.where(fallen, 1.0, 0.0), st[M.ROW_STATUS])
-        store = running & finite
-        idx = np.nonzero(store)[0]
-        for i in range(3):
-            st[M.ROW_P + i, idx], st[M.ROW_V + i, idx], st[M.ROW_W + i, idx] = p[i][idx], v[i][idx], w[i][idx]
-        for i in range(4):
-            st[M.ROW_QUAT + i, idx] = qt[i][idx]
+                        foot[l][2] = np.where(moved, height(foot[l][0], foot[l][1]), foot[l][2])
+
+        store, touches = self._tick(grf, foot_target, ext, feet, height, SimpleNamespace(force=force, slide=slide, stand=stand))
+        # touch and slip are this tick's: a robot that is frozen, or keeps its last state, touched nothing and slid nowhere
         for l in range(4):
-            for i in range(3):
-                st[M.ROW_FOOT + 3 * l + i, idx] = foot[l][i][idx]
-            st[M.ROW_STANCE + l, idx] = stance[l][idx]
-            # touch and slip are this tick's: a robot that is frozen, or keeps its last state, touched nothing and slid nowhere
             self.touch[l] = (store & touches[l]).astype(np.int32)
             self.slip[l] = np.where(store, slid[l], 0.0)
-        st[M.ROW_STEPS, idx] = st[M.ROW_STEPS, idx] + float(self.S)
-        # 4. observation
-        if idx.size:
-            self._observe(idx, 1)

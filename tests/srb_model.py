@@ -259,12 +259,28 @@ class SRBModel:
         self._observe(idx, RESET_IK_PASSES, q0)
 
     # -- one control tick ------------------------------------------------------------------------
-    def step(self, grf, foot_target, desired_state, ext=None):
-        """grf [B,12], foot_target [B,12] (float32 values), desired_state [B,4] int, ext [6,B] float64 or None."""
+    def _schedule_feet(self, desired_state, height=None):
+        """Step 1 by the schedule: a swinging foot follows its target, a landing foot is put on the ground (height(x, y), or the
+        plane's literal 0), and the commanded force goes through every stance foot."""
+        swing = np.asarray(desired_state).reshape(self.B, 4) == SWING
+
+        def feet(l, c, foot, stance, grf):
+            sw = swing[:, l]
+            land = ~sw & (stance == 0.0)
+            foot = [np.where(sw, c[i], foot[i]) for i in range(3)]
+            foot[2] = np.where(land, 0.0 if height is None else height(foot[0], foot[1]), foot[2])
+            return foot, np.where(sw, 0.0, 1.0), [np.where(sw, 0.0, -grf[i]) for i in range(3)], None
+        return feet
+
+    def _tick(self, grf, foot_target, ext, feet, height=None, rule=None):
+        """The tick every entry shares (rg_srb_tick.inc and what the step kernels have in common): load, the sub-step loop, the
+        fall test, the stores and the observation.  What varies comes in: feet(l, c, foot, stance, grf) -> foot, stance, fbody,
+        touches is step 1 for leg l, c its swing target in the world; height(x, y) the ground, None for the plane's literal 0;
+        rule, optional, a force rule inside the sub-step loop: force(l, f) -> f on the leg's rotated force, slide(foot) after the
+        body update, stand(foot) after the loop.  -> store [B] bool, touches (4 arrays [B], or None where the rule has none)."""
         B, st, dt = self.B, self.state, self.dt
         grf = np.asarray(grf).astype(np.float64).reshape(B, 4, 3)
         ft = np.asarray(foot_target).astype(np.float64).reshape(B, 4, 3)
-        swing = np.asarray(desired_state).reshape(B, 4) == SWING
         ext = np.zeros((6, B)) if ext is None else np.asarray(ext, dtype=np.float64)
         running = st[ROW_STATUS] == 0.0
         p = [st[ROW_P + i].copy() for i in range(3)]
@@ -275,18 +291,15 @@ class SRBModel:
         stance = [st[ROW_STANCE + l].copy() for l in range(4)]
         mass, I, Iinv = self.mass, list(self.I), list(self.Iinv)
         R = quat_rot(qt)
-        fbody = []
+        fbody, touches = [], []
         with np.errstate(all="ignore"):
             # 1. feet
             for l in range(4):
-                sw = swing[:, l]
                 r = rot(R, [ft[:, l, k] for k in range(3)])
-                land = ~sw & (stance[l] == 0.0)
-                for i in range(3):
-                    foot[l][i] = np.where(sw, p[i] + r[i], foot[l][i])
-                foot[l][2] = np.where(land, 0.0, foot[l][2])
-                stance[l] = np.where(sw, 0.0, 1.0)
-                fbody.append([np.where(sw, 0.0, -grf[:, l, i]) for i in range(3)])
+                c = [p[i] + r[i] for i in range(3)]
+                foot[l], stance[l], fb, touch = feet(l, c, foot[l], stance[l], [grf[:, l, i] for i in range(3)])
+                fbody.append(fb)
+                touches.append(touch)
             wz = mass * -self.g
             # 2. sub-steps
             for _ in range(self.S):
@@ -294,6 +307,8 @@ class SRBModel:
                 f, tq = [], []
                 for l in range(4):
                     fl = rot(R, fbody[l])
+                    if rule is not None:
+                        fl = rule.force(l, fl)
                     r = [foot[l][i] - p[i] for i in range(3)]
                     f.append(fl)
                     tq.append([r[1] * fl[2] - r[2] * fl[1], r[2] * fl[0] - r[0] * fl[2], r[0] * fl[1] - r[1] * fl[0]])
@@ -309,6 +324,8 @@ class SRBModel:
                     w[i] = w[i] + dt * aw[i]
                     v[i] = v[i] + dt * F[i] / mass
                     p[i] = p[i] + dt * v[i]
+                if rule is not None:
+                    rule.slide(foot)
                 ax, ay, az = 0.5 * dt * w[0], 0.5 * dt * w[1], 0.5 * dt * w[2]
                 dx = ax * qt[3] + ay * qt[2] - az * qt[1]
                 dy = ay * qt[3] + az * qt[0] - ax * qt[2]
@@ -317,11 +334,14 @@ class SRBModel:
                 qt = [qt[0] + dx, qt[1] + dy, qt[2] + dz, qt[3] + dw]
                 nrm = np.sqrt(qt[0] * qt[0] + qt[1] * qt[1] + qt[2] * qt[2] + qt[3] * qt[3])
                 qt = [qt[i] / nrm for i in range(4)]
+            if rule is not None:
+                rule.stand(foot)
             # 3. fall
             finite = np.ones(B, dtype=bool)
             for a in p + v + w + qt + [foot[l][i] for l in range(4) for i in range(3)]:
                 finite &= np.isfinite(a)
-            fallen = ~finite | (p[2] < self.fall_z) | ((1 - 2 * (qt[0] * qt[0] + qt[1] * qt[1])) < self.cos_tilt)
+            clearance = p[2] if height is None else p[2] - height(p[0], p[1])
+            fallen = ~finite | (clearance < self.fall_z) | ((1 - 2 * (qt[0] * qt[0] + qt[1] * qt[1])) < self.cos_tilt)
         st[ROW_STATUS] = np.where(running, np.where(fallen, 1.0, 0.0), st[ROW_STATUS])
         store = running & finite
         idx = np.nonzero(store)[0]
@@ -337,6 +357,11 @@ class SRBModel:
         # 4. observation
         if idx.size:
             self._observe(idx, 1)
+        return store, touches
+
+    def step(self, grf, foot_target, desired_state, ext=None):
+        """grf [B,12], foot_target [B,12] (float32 values), desired_state [B,4] int, ext [6,B] float64 or None."""
+        self._tick(grf, foot_target, ext, self._schedule_feet(desired_state))
 
     def fallen(self):
         return self.state[ROW_STATUS] != 0

@@ -79,8 +79,8 @@ class Grid:
 
 
 class TerrainSRBModel(M.SRBModel):
-    """SRBModel on a ground (Flat, Random or Grid above).  step() is the parent's text with the two ground rules replaced;
-    reset() is the parent's followed by settle()."""
+    """SRBModel on a ground (Flat, Random or Grid above).  step() is the parent's tick with the ground in its two rules (where a
+    foot lands, the clearance of the fall test); reset() is the parent's followed by settle()."""
 
     def __init__(self, batch, cfg, ground=None, **kw):
         super().__init__(batch, cfg, **kw)
@@ -110,83 +110,11 @@ class TerrainSRBModel(M.SRBModel):
         if self.ground.kind != 0:
             self.settle(idx)
 
+    def _height(self):
+        """The ground under (x, y) of every robot, as SRBModel._tick and the feet rules ask it."""
+        all_robots = np.arange(self.B)
+        return lambda x, y: self.ground.height(x, y, all_robots)
+
     def step(self, grf, foot_target, desired_state, ext=None):
-        B, st, dt = self.B, self.state, self.dt
-        all_robots = np.arange(B)
-        grf = np.asarray(grf).astype(np.float64).reshape(B, 4, 3)
-        ft = np.asarray(foot_target).astype(np.float64).reshape(B, 4, 3)
-        swing = np.asarray(desired_state).reshape(B, 4) == M.SWING
-        ext = np.zeros((6, B)) if ext is None else np.asarray(ext, dtype=np.float64)
-        running = st[M.ROW_STATUS] == 0.0
-        p = [st[M.ROW_P + i].copy() for i in range(3)]
-        qt = [st[M.ROW_QUAT + i].copy() for i in range(4)]
-        v = [st[M.ROW_V + i].copy() for i in range(3)]
-        w = [st[M.ROW_W + i].copy() for i in range(3)]
-        foot = [[st[M.ROW_FOOT + 3 * l + i].copy() for i in range(3)] for l in range(4)]
-        stance = [st[M.ROW_STANCE + l].copy() for l in range(4)]
-        mass, I, Iinv = self.mass, list(self.I), list(self.Iinv)
-        R = M.quat_rot(qt)
-        rot, rot_t = M.rot, M.rot_t
-        fbody = []
-        with np.errstate(all="ignore"):
-            # 1. feet
-            for l in range(4):
-                sw = swing[:, l]
-                r = rot(R, [ft[:, l, k] for k in range(3)])
-                land = ~sw & (stance[l] == 0.0)
-                for i in range(3):
-                    foot[l][i] = np.where(sw, p[i] + r[i], foot[l][i])
-                foot[l][2] = np.where(land, self.ground.height(foot[l][0], foot[l][1], all_robots), foot[l][2])     # terrain rule 1
-                stance[l] = np.where(sw, 0.0, 1.0)
-                fbody.append([np.where(sw, 0.0, -grf[:, l, i]) for i in range(3)])
-            wz = mass * -self.g
-            # 2. sub-steps
-            for _ in range(self.S):
-                R = M.quat_rot(qt)
-                f, tq = [], []
-                for l in range(4):
-                    fl = rot(R, fbody[l])
-                    r = [foot[l][i] - p[i] for i in range(3)]
-                    f.append(fl)
-                    tq.append([r[1] * fl[2] - r[2] * fl[1], r[2] * fl[0] - r[0] * fl[2], r[0] * fl[1] - r[1] * fl[0]])
-                F = [(f[0][i] + f[1][i]) + (f[2][i] + f[3][i]) for i in range(3)]
-                T = [(tq[0][i] + tq[1][i]) + (tq[2][i] + tq[3][i]) for i in range(3)]
-                F = [F[0] + ext[0], F[1] + ext[1], F[2] + wz + ext[2]]
-                T = [T[0] + ext[3], T[1] + ext[4], T[2] + ext[5]]
-                tb, wb = rot_t(R, T), rot_t(R, w)
-                Iw = rot(I, wb)
-                rhs = [tb[0] - (wb[1] * Iw[2] - wb[2] * Iw[1]), tb[1] - (wb[2] * Iw[0] - wb[0] * Iw[2]), tb[2] - (wb[0] * Iw[1] - wb[1] * Iw[0])]
-                aw = rot(R, rot(Iinv, rhs))
-                for i in range(3):
-                    w[i] = w[i] + dt * aw[i]
-                    v[i] = v[i] + dt * F[i] / mass
-                    p[i] = p[i] + dt * v[i]
-                ax, ay, az = 0.5 * dt * w[0], 0.5 * dt * w[1], 0.5 * dt * w[2]
-                dx = ax * qt[3] + ay * qt[2] - az * qt[1]
-                dy = ay * qt[3] + az * qt[0] - ax * qt[2]
-                dz = az * qt[3] + ax * qt[1] - ay * qt[0]
-                dw = -(ax * qt[0]) - ay * qt[1] - az * qt[2]
-                qt = [qt[0] + dx, qt[1] + dy, qt[2] + dz, qt[3] + dw]
-                nrm = np.sqrt(qt[0] * qt[0] + qt[1] * qt[1] + qt[2] * qt[2] + qt[3] * qt[3])
-                qt = [qt[i] / nrm for i in range(4)]
-            # 3. fall
-            finite = np.ones(B, dtype=bool)
-            for a in p + v + w + qt + [foot[l][i] for l in range(4) for i in range(3)]:
-                finite &= np.isfinite(a)
-            clearance = p[2] - self.ground.height(p[0], p[1], all_robots)                                             # terrain rule 2
-            fallen = ~finite | (clearance < self.fall_z) | ((1 - 2 * (qt[0] * qt[0] + qt[1] * qt[1])) < self.cos_tilt)
-        st[M.ROW_STATUS] = np.where(running, np.where(fallen, 1.0, 0.0), st[M.ROW_STATUS])
-        store = running & finite
-        idx = np.nonzero(store)[0]
-        for i in range(3):
-            st[M.ROW_P + i, idx], st[M.ROW_V + i, idx], st[M.ROW_W + i, idx] = p[i][idx], v[i][idx], w[i][idx]
-        for i in range(4):
-            st[M.ROW_QUAT + i, idx] = qt[i][idx]
-        for l in range(4):
-            for i in range(3):
-                st[M.ROW_FOOT + 3 * l + i, idx] = foot[l][i][idx]
-            st[M.ROW_STANCE + l, idx] = stance[l][idx]
-        st[M.ROW_STEPS, idx] = st[M.ROW_STEPS, idx] + float(self.S)
-        # 4. observation
-        if idx.size:
-            self._observe(idx, 1)
+        height = self._height()
+        self._tick(grf, foot_target, ext, self._schedule_feet(desired_state, height), height)

@@ -286,8 +286,11 @@ def test_contact_source_keeps_contraction_off_and_both_library_targets_compile_i
     src = open(os.path.join(SRC, "rg_srb_contact.hip")).read()
     assert src.index("#pragma clang fp contract(off)") < src.index('#include "rg_mpc_dev.h"') < src.index("__global__")
     assert src.index("#pragma clang fp contract(off)") < src.index('#include "rg_srb_ground.inc"')
-    assert "asm" not in re.sub(r"//.*", "", src) and "atomic" not in src and "__shared__" not in src
-    assert "fma(" not in open(os.path.join(SRC, "rg_srb_ground.inc")).read()
+    assert src.index("#pragma clang fp contract(off)") < src.index('#include "rg_srb_tick.inc"') < src.index("__global__")
+    tick = open(os.path.join(SRC, "rg_srb_tick.inc")).read()
+    for text in (src, tick):
+        assert "asm" not in re.sub(r"//.*", "", text) and "atomic" not in text and "__shared__" not in text
+    assert "fma(" not in open(os.path.join(SRC, "rg_srb_ground.inc")).read() and "fma(" not in tick
     makefile = open(os.path.join(SRC, "Makefile")).read()
     assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_srb_contact\.hip", makefile)) == 2
 

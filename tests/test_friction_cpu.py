@@ -509,12 +509,16 @@ def test_friction_source_keeps_contraction_off_and_both_library_targets_compile_
     assert src.index("#pragma clang fp contract(off)") < src.index('#include "rg_mpc_dev.h"') < src.index("__global__")
     assert src.index("#pragma clang fp contract(off)") < src.index('#include "rg_srb_ground.inc"')
     assert src.count("#pragma clang fp contract") == 1
-    code = re.sub(r"//.*", "", src)
-    assert "asm" not in code and "atomic" not in code and "__shared__" not in code and "fma(" not in code
+    assert src.index("#pragma clang fp contract(off)") < src.index('#include "rg_srb_tick.inc"') < src.index("__global__")
+    tick = open(os.path.join(SRC, "rg_srb_tick.inc")).read()
+    assert "#pragma clang fp" not in re.sub(r"//.*", "", tick)
+    for text in (src, tick):
+        code = re.sub(r"//.*", "", text)
+        assert "asm" not in code and "atomic" not in code and "__shared__" not in code and "fma(" not in code
     makefile = open(os.path.join(SRC, "Makefile")).read()
     assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_srb_friction\.hip", makefile)) == 2
-    # the existing simulator units are not touched by this one: it is a translation unit of its own
-    for other in ("rg_srb.hip", "rg_srb_terrain.hip", "rg_srb_contact.hip"):
+    # the other simulator units, and the body of a tick they all share, know nothing of this one: its rule stays in its own file
+    for other in ("rg_srb.hip", "rg_srb_terrain.hip", "rg_srb_contact.hip", "rg_srb_tick.inc"):
         assert "friction" not in open(os.path.join(SRC, other)).read(), other
 
 

@@ -68,5 +68,21 @@ def test_register_use_is_pinned(remarks):
 
 def test_contraction_is_off_before_the_controller_header_is_included():
     src = open(os.path.join(SRC, "rg_srb.hip")).read()
-    assert src.index("#pragma clang fp contract(off)") < src.index('#include "rg_mpc_dev.h"')
-    assert "asm" not in re.sub(r"//.*", "", src) and "atomic" not in src and "__shared__" not in src
+    assert src.index("#pragma clang fp contract(off)") < src.index('#include "rg_mpc_dev.h"') < src.index('#include "rg_srb_tick.inc"')
+    assert src.index('#include "rg_srb_dev.inc"') < src.index('#include "rg_srb_tick.inc"') < src.index("__global__")
+    tick = open(os.path.join(SRC, "rg_srb_tick.inc")).read()
+    for text in (src, tick):
+        assert "asm" not in re.sub(r"//.*", "", text) and "atomic" not in text and "__shared__" not in text
+    # the shared body of a tick is under the including file's pragma and brings neither a pragma nor a fused operation of its own
+    code = re.sub(r"//.*", "", tick)
+    assert "#pragma clang fp" not in code and "fma(" not in tick and "#include" not in code
+
+
+def test_the_body_of_a_tick_is_typed_once():
+    """The four step kernels stand on rg_srb_tick.inc: the quaternion's renormalisation and sum4 are defined in one file."""
+    sources = {n: open(os.path.join(SRC, n)).read() for n in sorted(os.listdir(SRC)) if n.endswith((".hip", ".inc", ".h"))}
+    for text in ("double sum4(double", "qt[3] = qt[3] / nrm"):
+        assert [n for n, src in sources.items() if text in src] == ["rg_srb_tick.inc"], text
+    assert sources["rg_srb_tick.inc"].count("double sum4(double") == 1 and sources["rg_srb_tick.inc"].count("qt[3] = qt[3] / nrm") == 1
+    for n in ("rg_srb.hip", "rg_srb_terrain.hip", "rg_srb_contact.hip", "rg_srb_friction.hip"):
+        assert sources[n].count('#include "rg_srb_tick.inc"') == 1, n

@@ -340,6 +340,8 @@ def test_terrain_register_use_is_pinned(remarks):
 def test_terrain_source_keeps_contraction_off_and_both_library_targets_compile_it():
     src = open(os.path.join(SRC, "rg_srb_terrain.hip")).read()
     assert src.index("#pragma clang fp contract(off)") < src.index('#include "rg_mpc_dev.h"') < src.index("__global__")
-    assert "asm" not in re.sub(r"//.*", "", src) and "atomic" not in src and "__shared__" not in src
+    assert src.index("#pragma clang fp contract(off)") < src.index('#include "rg_srb_tick.inc"') < src.index("__global__")
+    for text in (src, open(os.path.join(SRC, "rg_srb_tick.inc")).read()):
+        assert "asm" not in re.sub(r"//.*", "", text) and "atomic" not in text and "__shared__" not in text
     makefile = open(os.path.join(SRC, "Makefile")).read()
     assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_srb_terrain\.hip", makefile)) == 2

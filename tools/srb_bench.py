@@ -71,7 +71,8 @@ def srb_hash():
     """sha256 (16 hex digits) over the simulator's own sources: bench.source_hash() covers the MPC kernels only."""
     import hashlib
     h = hashlib.sha256()
-    for rel in ("robot_gym_amd/csrc/rg_srb.hip", "robot_gym_amd/csrc/rg_srb_dev.inc", "robot_gym_amd/csrc/rg_srb_handle.h", "robot_gym_amd/csrc/rg_host.h",
+    for rel in ("robot_gym_amd/csrc/rg_srb.hip", "robot_gym_amd/csrc/rg_srb_dev.inc", "robot_gym_amd/csrc/rg_srb_tick.inc", "robot_gym_amd/csrc/rg_srb_handle.h",
+                "robot_gym_amd/csrc/rg_host.h",
                 "robot_gym_amd/csrc/rg_srb_terrain.hip", "robot_gym_amd/csrc/rg_srb_ground.inc", "robot_gym_amd/csrc/rg_stream_dev.inc",
                 "robot_gym_amd/csrc/rg_srb_contact.hip", "robot_gym_amd/csrc/rg_srb_friction.hip", "include/rg_srb.h", "include/rg_srb_terrain.h",
                 "include/rg_srb_contact.h", "include/rg_srb_friction.h"):
