@@ -8,7 +8,6 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,13 +17,13 @@ from robot_gym_amd.agents.ppo import DeviceRecurrentPPO, RecurrentGaussianPolicy
 from robot_gym_amd.core import bptt_abi, ppo_abi, rnn_abi
 from tests import bptt_cases as BC
 from tests import bptt_model as BM
+from tests import kernel_checks
 from tests import policy_model as PM
 from tests import rnn_model as RM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rg_bptt.h")
 SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 NAN, INF = float("nan"), float("inf")
 
 
@@ -372,28 +371,8 @@ KERNELS = {f"rg_bptt_{k}_kernel" for k in ("describe", "forward", "sample_kl", "
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc here")
-    out = tmp_path_factory.mktemp("bptt") / "rg_bptt.s"
-    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
-                          "rg_bptt.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            mangled = text.split(":", 1)[1].strip()
-            k = re.search(r"(rg_bptt_[a-z_]+_kernel)", mangled)
-            name = k.group(1) if k else mangled
-            kernels[name] = {}
-        elif name and ":" in text:
-            key, val = text.split(":", 1)
-            kernels[name][key.strip()] = val.strip()
-    return kernels
+def remarks():
+    return kernel_checks.remarks("rg_bptt.hip")
 
 
 def test_every_bptt_kernel_is_reported(remarks):
@@ -401,11 +380,7 @@ def test_every_bptt_kernel_is_reported(remarks):
 
 
 def test_no_bptt_kernel_uses_scratch_spills_or_a_dynamic_stack(remarks):
-    for name in KERNELS:
-        r = remarks[name]
-        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
-        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
-        assert r["Dynamic Stack"] == "False", (name, r)
+    kernel_checks.assert_lean(remarks, KERNELS)
 
 
 # The file's header comment, in floats of the header limits.  forward: two x buffers, h, r*h and u; delta: two dense delta
@@ -437,11 +412,7 @@ REGISTERS = {
 
 def test_register_use_is_pinned(remarks):
     assert set(REGISTERS) == KERNELS
-    for name, want in REGISTERS.items():
-        r = remarks[name]
-        assert int(r["VGPRs"]) <= want["vgprs"], (name, r)
-        assert int(r["AGPRs"]) <= want["agprs"], (name, r)
-        assert int(r["Occupancy [waves/SIMD]"]) >= want["occupancy"], (name, r)
+    kernel_checks.assert_registers(remarks, REGISTERS)
 
 
 def test_source_is_its_own_translation_unit_in_both_library_targets():
@@ -472,6 +443,4 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
     for other in sorted(os.listdir(SRC)):                                        # included from nowhere
         if other.endswith((".hip", ".inc", ".h")) and other != "rg_bptt.hip":
             assert "rg_bptt" not in open(os.path.join(SRC, other)).read(), other
-    makefile = open(os.path.join(SRC, "Makefile")).read()
-    assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_bptt\.hip", makefile)) == 2   # both library targets
-    assert len(re.findall(r"^librg_mpc\w*\.so:.*rg_bptt\.hip.*include/rg_bptt\.h", makefile, flags=re.M)) == 2
+    kernel_checks.assert_built_into_both("rg_bptt.hip", header="rg_bptt.h")

@@ -7,7 +7,6 @@ tests/contact_fixtures.py are twice what this run produces."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,13 +16,13 @@ from robot_gym_amd.core import srb_abi
 from robot_gym_amd.core.config import MPCConfig
 from tests import contact_fixtures as CF
 from tests import contact_model as CM
+from tests import kernel_checks
 from tests import srb_fixtures as F
 from tests import srb_model as M
 from tests import terrain_model as TM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 # ---- known answers ---------------------------------------------------------------------------------------------------
@@ -235,38 +234,13 @@ KERNELS = {"rg_srb_contact_step_kernel"}
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc here")
-    out = tmp_path_factory.mktemp("srb_contact") / "rg_srb_contact.s"
-    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
-                          "rg_srb_contact.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            mangled = text.split(":", 1)[1].strip()
-            k = re.search(r"(rg_srb_[a-z_]+_kernel)", mangled)
-            name = k.group(1) if k else mangled
-            kernels[name] = {}
-        elif name and ":" in text:
-            key, val = text.split(":", 1)
-            kernels[name][key.strip()] = val.strip()
-    return kernels
+def remarks():
+    return kernel_checks.remarks("rg_srb_contact.hip")
 
 
 def test_the_contact_kernel_is_reported_and_uses_no_scratch_and_no_lds(remarks):
     assert set(remarks) == KERNELS
-    for name in KERNELS:
-        r = remarks[name]
-        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
-        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
-        assert r["Dynamic Stack"] == "False", (name, r)
-        assert int(r["LDS Size [bytes/block]"]) == 0, (name, r)
+    kernel_checks.assert_lean(remarks, KERNELS, lds=0)
 
 
 # What the device-only compile reports today (upper bounds): where the terrain step kernel is (256 + 40), a few accumulation
@@ -275,11 +249,7 @@ REGISTERS = {"rg_srb_contact_step_kernel": dict(vgprs=256, agprs=34)}
 
 
 def test_contact_register_use_is_pinned(remarks):
-    for name, want in REGISTERS.items():
-        r = remarks[name]
-        assert int(r["VGPRs"]) <= want["vgprs"], (name, r)
-        assert int(r["AGPRs"]) <= want["agprs"], (name, r)
-        assert int(r["Occupancy [waves/SIMD]"]) >= 1, (name, r)
+    kernel_checks.assert_registers(remarks, REGISTERS)
 
 
 def test_contact_source_keeps_contraction_off_and_both_library_targets_compile_it():
@@ -291,8 +261,7 @@ def test_contact_source_keeps_contraction_off_and_both_library_targets_compile_i
     for text in (src, tick):
         assert "asm" not in re.sub(r"//.*", "", text) and "atomic" not in text and "__shared__" not in text
     assert "fma(" not in open(os.path.join(SRC, "rg_srb_ground.inc")).read() and "fma(" not in tick
-    makefile = open(os.path.join(SRC, "Makefile")).read()
-    assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_srb_contact\.hip", makefile)) == 2
+    kernel_checks.assert_built_into_both("rg_srb_contact.hip")
 
 
 # ---- the CPU closed loop with measured contact -----------------------------------------------------------------------------

@@ -1,12 +1,8 @@
 """State rows without a GPU: the layout the library reports matches the Python description, a row as a reset leaves it
 passes rg_mpc_state_check, every single corruption is refused naming the robot and the field, and the gather / scatter
 kernels (rg_mpc_state.hip) cross-compile for gfx950 without scratch."""
-import os
 import io
 import pickle
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,10 +10,7 @@ import pytest
 from robot_gym_amd.core import controller_state as CS
 from robot_gym_amd.core import mpc_abi
 from robot_gym_amd.core.config import MPCConfig
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import kernel_report  # noqa: E402
+from tests import kernel_checks
 
 
 def reset_rows(cfg, n, t0=0.25):
@@ -143,11 +136,7 @@ def test_truncated_buffer_and_duplicate_destinations_are_refused():
 
 
 def test_state_kernels_cross_compile_without_scratch():
-    src = os.path.join(ROOT, "robot_gym_amd", "csrc")
-    res = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", os.devnull,
-                          "rg_mpc_state.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=src, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-3000:]
-    rows = {re.search(r"rg_state_[a-z]+_kernel", r["mangled"]).group(0): r for r in kernel_report.parse_remarks(res.stderr)}
+    rows = kernel_checks.remarks("rg_mpc_state.hip")
     assert set(rows) == {"rg_state_gather_kernel", "rg_state_scatter_kernel"}, sorted(rows)
     for name, r in rows.items():
         assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)

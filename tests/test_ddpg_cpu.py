@@ -9,7 +9,6 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,12 +18,12 @@ from robot_gym_amd.agents.ddpg import BatchedDDPGAgent, collect
 from robot_gym_amd.core import ddpg_abi
 from tests import ddpg_cases as DC
 from tests import ddpg_model as DM
+from tests import kernel_checks
 from tests import policy_model as PM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rg_ddpg.h")
 SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 NAN, INF = float("nan"), float("inf")
 LOPSIDED = DC.CONFIGS["lopsided"]
 
@@ -411,28 +410,8 @@ SWEEPS = ("rg_ddpg_critic_sweep_kernel", "rg_ddpg_actor_sweep_kernel")
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc here")
-    out = tmp_path_factory.mktemp("ddpg") / "rg_ddpg.s"
-    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
-                          "rg_ddpg.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            mangled = text.split(":", 1)[1].strip()
-            k = re.search(r"(rg_ddpg_[a-z_]+_kernel)", mangled)
-            name = k.group(1) if k else mangled
-            kernels[name] = {}
-        elif name and ":" in text:
-            key, val = text.split(":", 1)
-            kernels[name][key.strip()] = val.strip()
-    return kernels
+def remarks():
+    return kernel_checks.remarks("rg_ddpg.hip")
 
 
 def test_every_ddpg_kernel_is_reported(remarks):
@@ -440,11 +419,7 @@ def test_every_ddpg_kernel_is_reported(remarks):
 
 
 def test_no_ddpg_kernel_uses_scratch_spills_or_a_dynamic_stack(remarks):
-    for name in KERNELS:
-        r = remarks[name]
-        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
-        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
-        assert r["Dynamic Stack"] == "False", (name, r)
+    kernel_checks.assert_lean(remarks, KERNELS)
 
 
 def test_lds_is_within_a_compute_units_160_kib(remarks):
@@ -480,9 +455,7 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
         assert "rg_ddpg" not in open(os.path.join(SRC, other)).read()                # the source hashes behind profiles/ do not move
     assert "__builtin_fmaf" in code and "mfma" not in code.lower()
     assert "static_assert(kMaxLds == 148032 && kMaxLds <= 160 * 1024" in code
-    makefile = open(os.path.join(SRC, "Makefile")).read()
-    assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_ddpg\.hip", makefile)) == 2   # both library targets
-    assert len(re.findall(r"^librg_mpc\w*\.so:.*rg_ddpg\.hip.*include/rg_ddpg\.h", makefile, flags=re.M)) == 2
+    kernel_checks.assert_built_into_both("rg_ddpg.hip", header="rg_ddpg.h")
 
 
 # ---- BatchedDDPGAgent's argument checks -----------------------------------------------------------------------------------

@@ -6,7 +6,6 @@ tests/test_dr_gpu.py."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,10 +13,10 @@ import pytest
 from robot_gym_amd.core import dr_abi
 from tests import dr_model as DM
 from tests import episode_model as EM
+from tests import kernel_checks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 # ---- the binding -------------------------------------------------------------------------------------------------------
@@ -328,28 +327,8 @@ KERNELS = {"rg_dr_reset_kernel", "rg_dr_apply_kernel", "rg_dr_push_kernel"}
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc here")
-    out = tmp_path_factory.mktemp("dr") / "rg_dr.s"
-    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
-                          "rg_dr.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            mangled = text.split(":", 1)[1].strip()
-            k = re.search(r"(rg_[a-z_]+_kernel)", mangled)
-            name = k.group(1) if k else mangled
-            kernels[name] = {}
-        elif name and ":" in text:
-            key, val = text.split(":", 1)
-            kernels[name][key.strip()] = val.strip()
-    return kernels
+def remarks():
+    return kernel_checks.remarks("rg_dr.hip")
 
 
 def test_exactly_the_three_kernels_are_reported(remarks):
@@ -357,12 +336,7 @@ def test_exactly_the_three_kernels_are_reported(remarks):
 
 
 def test_the_kernels_use_no_scratch_and_no_lds(remarks):
-    for name in KERNELS:
-        r = remarks[name]
-        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
-        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
-        assert r["Dynamic Stack"] == "False", (name, r)
-        assert int(r["LDS Size [bytes/block]"]) == 0, (name, r)
+    kernel_checks.assert_lean(remarks, KERNELS, lds=0)
 
 
 # What the device-only compile reports today (upper bounds): reset and apply hold a robot's 19 base values and their
@@ -372,11 +346,7 @@ REGISTERS = {"rg_dr_reset_kernel": dict(vgprs=50, agprs=0, occupancy=8), "rg_dr_
 
 
 def test_register_use_is_pinned(remarks):
-    for name, want in REGISTERS.items():
-        r = remarks[name]
-        assert int(r["VGPRs"]) <= want["vgprs"], (name, r)
-        assert int(r["AGPRs"]) <= want["agprs"], (name, r)
-        assert int(r["Occupancy [waves/SIMD]"]) >= want["occupancy"], (name, r)
+    kernel_checks.assert_registers(remarks, REGISTERS)
 
 
 def test_source_is_its_own_translation_unit_in_both_library_targets():
@@ -402,6 +372,4 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
     assert "#define RG_SRB_ABI_VERSION 1" in srb and "rg_dr" not in srb
     import bench
     assert not any("rg_dr" in rel for rel in bench.compiled_sources())           # the MPC hash behind profiles/ does not follow it
-    makefile = open(os.path.join(SRC, "Makefile")).read()
-    assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_dr\.hip", makefile)) == 2   # both library targets
-    assert len(re.findall(r"^librg_mpc\w*\.so:.*rg_dr\.hip.*include/rg_dr\.h", makefile, flags=re.M)) == 2
+    kernel_checks.assert_built_into_both("rg_dr.hip", header="rg_dr.h")

@@ -6,7 +6,6 @@ spills, within their LDS budget."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,11 +14,11 @@ from robot_gym_amd.core import episode_abi, goto_abi, mpc_abi, srb_abi
 from robot_gym_amd.core.config import MPCConfig
 from robot_gym_amd.gym import goto_path
 from tests import episode_model as EM
+from tests import kernel_checks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rg_episode.h")
 SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 NAN, INF = float("nan"), float("inf")
 
 
@@ -227,28 +226,8 @@ KERNELS = {"rg_episode_plan_kernel", "rg_episode_reset_kernel", "rg_episode_accu
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc here")
-    out = tmp_path_factory.mktemp("episode") / "rg_episode.s"
-    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
-                          "rg_episode.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            mangled = text.split(":", 1)[1].strip()
-            k = re.search(r"(rg_episode_[a-z_]+_kernel)", mangled)
-            name = k.group(1) if k else mangled
-            kernels[name] = {}
-        elif name and ":" in text:
-            key, val = text.split(":", 1)
-            kernels[name][key.strip()] = val.strip()
-    return kernels
+def remarks():
+    return kernel_checks.remarks("rg_episode.hip")
 
 
 def test_every_episode_kernel_is_reported(remarks):
@@ -256,11 +235,7 @@ def test_every_episode_kernel_is_reported(remarks):
 
 
 def test_no_episode_kernel_uses_scratch_spills_or_a_dynamic_stack(remarks):
-    for name in KERNELS:
-        r = remarks[name]
-        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
-        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
-        assert r["Dynamic Stack"] == "False", (name, r)
+    kernel_checks.assert_lean(remarks, KERNELS)
 
 
 # plan kernel: way points x / y / cumulative length (3 * 64 float64), obstacles x / y (2 * 16 float64), the last cells of the
@@ -281,11 +256,7 @@ REGISTERS = {"rg_episode_plan_kernel": dict(vgprs=52, agprs=0, occupancy=8), "rg
 
 
 def test_register_use_is_pinned(remarks):
-    for name, want in REGISTERS.items():
-        r = remarks[name]
-        assert int(r["VGPRs"]) <= want["vgprs"], (name, r)
-        assert int(r["AGPRs"]) <= want["agprs"], (name, r)
-        assert int(r["Occupancy [waves/SIMD]"]) >= want["occupancy"], (name, r)
+    kernel_checks.assert_registers(remarks, REGISTERS)
 
 
 def test_source_has_no_inline_assembly_no_atomics_and_contraction_off():
@@ -300,5 +271,4 @@ def test_source_has_no_inline_assembly_no_atomics_and_contraction_off():
         shared = open(os.path.join(SRC, inc)).read()
         assert "asm" not in re.sub(r"//.*", "", shared) and "atomic" not in shared.lower(), inc
     assert "atomic" not in open(os.path.join(SRC, "rg_goto.hip")).read().lower()
-    makefile = open(os.path.join(SRC, "Makefile")).read()
-    assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_episode\.hip", makefile)) == 2   # both library targets
+    kernel_checks.assert_built_into_both("rg_episode.hip")

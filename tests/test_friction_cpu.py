@@ -8,7 +8,6 @@ import glob
 import math
 import os
 import re
-import subprocess
 import types
 
 import numpy as np
@@ -21,6 +20,7 @@ from tests import contact_fixtures as CF
 from tests import contact_model as CM
 from tests import friction_fixtures as FF
 from tests import friction_model as FM
+from tests import kernel_checks
 from tests import srb_fixtures as F
 from tests import srb_model as M
 from tests import stream_model as SM
@@ -28,7 +28,6 @@ from tests import terrain_model as TM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 CPU = torch.device("cpu")
 
 
@@ -457,51 +456,22 @@ KERNELS = {"rg_srb_friction_step_kernel", "rg_srb_friction_draw_kernel"}
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc here")
-    out = tmp_path_factory.mktemp("srb_friction") / "rg_srb_friction.s"
-    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
-                          "rg_srb_friction.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            mangled = text.split(":", 1)[1].strip()
-            k = re.search(r"(rg_srb_[a-z_]+_kernel)", mangled)
-            name = k.group(1) if k else mangled
-            kernels[name] = {}
-        elif name and ":" in text:
-            key, val = text.split(":", 1)
-            kernels[name][key.strip()] = val.strip()
-    return kernels
+def remarks():
+    return kernel_checks.remarks("rg_srb_friction.hip")
 
 
 def test_both_friction_kernels_are_reported_and_use_no_scratch_and_no_lds(remarks):
     assert set(remarks) == KERNELS
-    for name in KERNELS:
-        r = remarks[name]
-        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
-        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
-        assert r["Dynamic Stack"] == "False", (name, r)
-        assert int(r["LDS Size [bytes/block]"]) == 0, (name, r)
+    kernel_checks.assert_lean(remarks, KERNELS, lds=0)
 
 
 # What the device-only compile reports today (upper bounds): the step kernel where the contact step kernel is (256 + 34) -- the
 # friction rule adds a handful of live values inside the sub-step loop, and the third ground lookup sits outside it.
-REGISTERS = {"rg_srb_friction_step_kernel": dict(vgprs=256, agprs=34, waves=1), "rg_srb_friction_draw_kernel": dict(vgprs=12, agprs=0, waves=8)}
+REGISTERS = {"rg_srb_friction_step_kernel": dict(vgprs=256, agprs=34, occupancy=1), "rg_srb_friction_draw_kernel": dict(vgprs=12, agprs=0, occupancy=8)}
 
 
 def test_friction_register_use_is_pinned(remarks):
-    for name, want in REGISTERS.items():
-        r = remarks[name]
-        assert int(r["VGPRs"]) <= want["vgprs"], (name, r)
-        assert int(r["AGPRs"]) <= want["agprs"], (name, r)
-        assert int(r["Occupancy [waves/SIMD]"]) >= want["waves"], (name, r)
+    kernel_checks.assert_registers(remarks, REGISTERS)
 
 
 def test_friction_source_keeps_contraction_off_and_both_library_targets_compile_it():
@@ -515,8 +485,7 @@ def test_friction_source_keeps_contraction_off_and_both_library_targets_compile_
     for text in (src, tick):
         code = re.sub(r"//.*", "", text)
         assert "asm" not in code and "atomic" not in code and "__shared__" not in code and "fma(" not in code
-    makefile = open(os.path.join(SRC, "Makefile")).read()
-    assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_srb_friction\.hip", makefile)) == 2
+    kernel_checks.assert_built_into_both("rg_srb_friction.hip")
     # the other simulator units, and the body of a tick they all share, know nothing of this one: its rule stays in its own file
     for other in ("rg_srb.hip", "rg_srb_terrain.hip", "rg_srb_contact.hip", "rg_srb_tick.inc"):
         assert "friction" not in open(os.path.join(SRC, other)).read(), other

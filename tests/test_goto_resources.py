@@ -1,41 +1,21 @@
 """The go-to-target kernels (robot_gym_amd/csrc/rg_goto.hip) compile for gfx950 without scratch and within their LDS budget:
-one device-only compile with the compiler's resource remarks, parsed here (no GPU needed).  The source must stay clear of
-what the kernels have no business with (atomics, inline assembly)."""
+one device-only compile with the compiler's resource remarks (tests/kernel_checks.py; no GPU needed).  The source must stay
+clear of what the kernels have no business with (atomics, inline assembly)."""
 import os
 import re
-import subprocess
 
 import pytest
 
+from tests import kernel_checks
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 KERNELS = {"rg_goto_post_kernel", "rg_goto_pre_kernel", "rg_goto_set_kernel"}
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc here")
-    out = tmp_path_factory.mktemp("goto") / "rg_goto.s"
-    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
-                          "rg_goto.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            mangled = text.split(":", 1)[1].strip()
-            k = re.search(r"(rg_goto_[a-z_]+_kernel)", mangled)
-            name = k.group(1) if k else mangled
-            kernels[name] = {}
-        elif name and ":" in text:
-            key, val = text.split(":", 1)
-            kernels[name][key.strip()] = val.strip()
-    return kernels
+def remarks():
+    return kernel_checks.remarks("rg_goto.hip")
 
 
 def test_every_goto_kernel_is_reported(remarks):
@@ -43,11 +23,7 @@ def test_every_goto_kernel_is_reported(remarks):
 
 
 def test_no_goto_kernel_uses_scratch(remarks):
-    for name in KERNELS:
-        r = remarks[name]
-        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
-        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
-        assert r["Dynamic Stack"] == "False", (name, r)
+    kernel_checks.assert_lean(remarks, KERNELS)
 
 
 # The tick kernel's budget: five arrays of RG_GOTO_MAX_VISIBLE float64 (visible x / y; chain x / y / cumulative length).
@@ -68,11 +44,7 @@ REGISTERS = {"rg_goto_post_kernel": dict(vgprs=71, occupancy=7), "rg_goto_pre_ke
 
 
 def test_register_use_is_pinned(remarks):
-    for name, want in REGISTERS.items():
-        r = remarks[name]
-        assert int(r["VGPRs"]) <= want["vgprs"], (name, r)
-        assert int(r["AGPRs"]) == 0, (name, r)
-        assert int(r["Occupancy [waves/SIMD]"]) >= want["occupancy"], (name, r)
+    kernel_checks.assert_registers(remarks, REGISTERS)     # no agprs in the table: none allowed
 
 
 def test_source_has_no_inline_assembly_no_atomics_and_contraction_off():

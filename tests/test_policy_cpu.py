@@ -8,7 +8,6 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,12 +15,12 @@ import torch
 
 from robot_gym_amd.agents.ppo import PPO, BatchedGaussianPolicy, RolloutBuffer
 from robot_gym_amd.core import policy_abi
+from tests import kernel_checks
 from tests import policy_model as PM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rg_policy.h")
 SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 NAN, INF = float("nan"), float("inf")
 
 
@@ -448,28 +447,8 @@ KERNELS = {"rg_policy_act_kernel", "rg_policy_record_first_kernel", "rg_policy_r
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc here")
-    out = tmp_path_factory.mktemp("policy") / "rg_policy.s"
-    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
-                          "rg_policy.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            mangled = text.split(":", 1)[1].strip()
-            k = re.search(r"(rg_policy_[a-z_]+_kernel)", mangled)
-            name = k.group(1) if k else mangled
-            kernels[name] = {}
-        elif name and ":" in text:
-            key, val = text.split(":", 1)
-            kernels[name][key.strip()] = val.strip()
-    return kernels
+def remarks():
+    return kernel_checks.remarks("rg_policy.hip")
 
 
 def test_every_policy_kernel_is_reported(remarks):
@@ -477,11 +456,7 @@ def test_every_policy_kernel_is_reported(remarks):
 
 
 def test_no_policy_kernel_uses_scratch_spills_or_a_dynamic_stack(remarks):
-    for name in KERNELS:
-        r = remarks[name]
-        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
-        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
-        assert r["Dynamic Stack"] == "False", (name, r)
+    kernel_checks.assert_lean(remarks, KERNELS)
 
 
 # act kernel: 2 networks * 2 buffers * 256 inputs * 8 robots float32, and 8 * 4 float32 of noise.
@@ -503,11 +478,7 @@ REGISTERS = {"rg_policy_act_kernel": dict(vgprs=100, agprs=0, occupancy=4), "rg_
 
 
 def test_register_use_is_pinned(remarks):
-    for name, want in REGISTERS.items():
-        r = remarks[name]
-        assert int(r["VGPRs"]) <= want["vgprs"], (name, r)
-        assert int(r["AGPRs"]) <= want["agprs"], (name, r)
-        assert int(r["Occupancy [waves/SIMD]"]) >= want["occupancy"], (name, r)
+    kernel_checks.assert_registers(remarks, REGISTERS)
 
 
 def test_source_is_its_own_translation_unit_in_both_library_targets():
@@ -525,6 +496,4 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
     import bench
     assert not any("rg_agent_" in rel or "rg_stream_" in rel or "rg_host" in rel for rel in bench.compiled_sources())     # the MPC hash behind profiles/ does not follow them
     assert "rg_policy" not in open(os.path.join(SRC, "rg_mpc.hip")).read()   # the source hash behind profiles/ does not move
-    makefile = open(os.path.join(SRC, "Makefile")).read()
-    assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_policy\.hip", makefile)) == 2   # both library targets
-    assert len(re.findall(r"^librg_mpc\w*\.so:.*rg_policy\.hip.*include/rg_policy\.h", makefile, flags=re.M)) == 2
+    kernel_checks.assert_built_into_both("rg_policy.hip", header="rg_policy.h")

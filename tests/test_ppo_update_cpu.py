@@ -8,7 +8,6 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,13 +15,13 @@ import torch
 
 from robot_gym_amd.agents.ppo import PPO, BatchedGaussianPolicy, DevicePPO, RolloutBuffer
 from robot_gym_amd.core import policy_abi, ppo_abi
+from tests import kernel_checks
 from tests import policy_model as PM
 from tests import ppo_update_model as UM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rg_ppo.h")
 SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 NAN, INF = float("nan"), float("inf")
 
 
@@ -328,28 +327,8 @@ SWEEPS = ("rg_ppo_policy_forward_kernel", "rg_ppo_policy_backward_kernel", "rg_p
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc here")
-    out = tmp_path_factory.mktemp("ppo") / "rg_ppo.s"
-    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
-                          "rg_ppo.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            mangled = text.split(":", 1)[1].strip()
-            k = re.search(r"(rg_ppo_[a-z_]+_kernel)", mangled)
-            name = k.group(1) if k else mangled
-            kernels[name] = {}
-        elif name and ":" in text:
-            key, val = text.split(":", 1)
-            kernels[name][key.strip()] = val.strip()
-    return kernels
+def remarks():
+    return kernel_checks.remarks("rg_ppo.hip")
 
 
 def test_every_ppo_kernel_is_reported(remarks):
@@ -357,11 +336,7 @@ def test_every_ppo_kernel_is_reported(remarks):
 
 
 def test_no_ppo_kernel_uses_scratch_spills_or_a_dynamic_stack(remarks):
-    for name in KERNELS:
-        r = remarks[name]
-        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
-        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
-        assert r["Dynamic Stack"] == "False", (name, r)
+    kernel_checks.assert_lean(remarks, KERNELS)
 
 
 def _sweep_lds(settings):
@@ -397,11 +372,7 @@ REGISTERS = {"rg_ppo_policy_forward_kernel": dict(vgprs=94, agprs=0, occupancy=5
 
 
 def test_register_use_is_pinned(remarks):
-    for name, want in REGISTERS.items():
-        r = remarks[name]
-        assert int(r["VGPRs"]) <= want["vgprs"], (name, r)
-        assert int(r["AGPRs"]) <= want["agprs"], (name, r)
-        assert int(r["Occupancy [waves/SIMD]"]) >= want["occupancy"], (name, r)
+    kernel_checks.assert_registers(remarks, REGISTERS)
 
 
 def test_source_is_its_own_translation_unit_in_both_library_targets():
@@ -429,9 +400,7 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
     for other in ("rg_mpc.hip", "rg_policy.hip"):
         assert "rg_ppo" not in open(os.path.join(SRC, other)).read()                # the source hashes behind profiles/ do not move
     assert "__builtin_fmaf" in code and "mfma" not in code.lower()
-    makefile = open(os.path.join(SRC, "Makefile")).read()
-    assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_ppo\.hip", makefile)) == 2   # both library targets
-    assert len(re.findall(r"^librg_mpc\w*\.so:.*rg_ppo\.hip.*include/rg_ppo\.h", makefile, flags=re.M)) == 2
+    kernel_checks.assert_built_into_both("rg_ppo.hip", header="rg_ppo.h")
 
 
 # ---- DevicePPO's argument checks ----------------------------------------------------------------------------------------

@@ -4,19 +4,18 @@ robot_gym_amd/csrc/rg_scan.hip from one device-only compile."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from robot_gym_amd.core import scan_abi, srb_abi
 from robot_gym_amd.core.config import MPCConfig
+from tests import kernel_checks
 from tests import scan_model as SM
 from tests import terrain_model as TM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 # ---- the binding -------------------------------------------------------------------------------------------------------
@@ -232,28 +231,8 @@ KERNELS = {"rg_scan_observe_kernel"}
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc here")
-    out = tmp_path_factory.mktemp("scan") / "rg_scan.s"
-    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
-                          "rg_scan.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            mangled = text.split(":", 1)[1].strip()
-            k = re.search(r"(rg_[a-z_]+_kernel)", mangled)
-            name = k.group(1) if k else mangled
-            kernels[name] = {}
-        elif name and ":" in text:
-            key, val = text.split(":", 1)
-            kernels[name][key.strip()] = val.strip()
-    return kernels
+def remarks():
+    return kernel_checks.remarks("rg_scan.hip")
 
 
 def test_exactly_the_scan_kernel_is_reported(remarks):
@@ -261,12 +240,7 @@ def test_exactly_the_scan_kernel_is_reported(remarks):
 
 
 def test_the_scan_kernel_uses_no_scratch_and_no_lds(remarks):
-    for name in KERNELS:
-        r = remarks[name]
-        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
-        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
-        assert r["Dynamic Stack"] == "False", (name, r)
-        assert int(r["LDS Size [bytes/block]"]) == 0, (name, r)
+    kernel_checks.assert_lean(remarks, KERNELS, lds=0)
 
 
 # What the device-only compile reports today (upper bounds): a lane's pose, heading and two hash prefixes, no more.
@@ -274,11 +248,7 @@ REGISTERS = {"rg_scan_observe_kernel": dict(vgprs=40, agprs=0, occupancy=8)}
 
 
 def test_scan_register_use_is_pinned(remarks):
-    for name, want in REGISTERS.items():
-        r = remarks[name]
-        assert int(r["VGPRs"]) <= want["vgprs"], (name, r)
-        assert int(r["AGPRs"]) <= want["agprs"], (name, r)
-        assert int(r["Occupancy [waves/SIMD]"]) >= want["occupancy"], (name, r)
+    kernel_checks.assert_registers(remarks, REGISTERS)
 
 
 def test_scan_source_is_its_own_translation_unit_in_both_library_targets():
@@ -296,6 +266,6 @@ def test_scan_source_is_its_own_translation_unit_in_both_library_targets():
             assert "rg_scan" not in open(os.path.join(SRC, other)).read(), other
     import bench
     assert not any("rg_scan" in rel for rel in bench.compiled_sources())         # the MPC hash behind profiles/ does not follow it
-    makefile = open(os.path.join(SRC, "Makefile")).read()
-    assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_bptt\.hip rg_scan\.hip", makefile)) == 2   # both library targets
-    assert len(re.findall(r"^librg_mpc\w*\.so:.*rg_bptt\.hip rg_scan\.hip.*include/rg_scan\.h$", makefile, flags=re.M)) == 2
+    kernel_checks.assert_built_into_both("rg_scan.hip", header="rg_scan.h")
+    for lib, t in kernel_checks.library_targets().items():                       # directly after the unit before it, the newest header last
+        assert t["sources"][t["sources"].index("rg_scan.hip") - 1] == "rg_bptt.hip" and t["prerequisites"][-1] == "../../include/rg_scan.h", (lib, t)

@@ -5,18 +5,17 @@ robot_gym_amd/csrc/rg_sensor.hip from one device-only compile."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from robot_gym_amd.core import sensor_abi
 from tests import episode_model as EM
+from tests import kernel_checks
 from tests import sensor_model as SM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 U = np.uint64
 
 
@@ -414,28 +413,8 @@ KERNELS = {"rg_sensor_reset_kernel", "rg_sensor_observe_kernel", "rg_sensor_act_
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc here")
-    out = tmp_path_factory.mktemp("sensor") / "rg_sensor.s"
-    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
-                          "rg_sensor.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            mangled = text.split(":", 1)[1].strip()
-            k = re.search(r"(rg_[a-z_]+_kernel)", mangled)
-            name = k.group(1) if k else mangled
-            kernels[name] = {}
-        elif name and ":" in text:
-            key, val = text.split(":", 1)
-            kernels[name][key.strip()] = val.strip()
-    return kernels
+def remarks():
+    return kernel_checks.remarks("rg_sensor.hip")
 
 
 def test_exactly_the_three_kernels_are_reported(remarks):
@@ -443,12 +422,7 @@ def test_exactly_the_three_kernels_are_reported(remarks):
 
 
 def test_the_kernels_use_no_scratch_no_spills_and_no_lds(remarks):
-    for name in KERNELS:
-        r = remarks[name]
-        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
-        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
-        assert r["Dynamic Stack"] == "False", (name, r)
-        assert int(r["LDS Size [bytes/block]"]) == 0, (name, r)
+    kernel_checks.assert_lean(remarks, KERNELS, lds=0)
 
 
 # What the device-only compile reports today (upper bounds).  reset and observe hold the settings of four groups in scalar
@@ -458,12 +432,7 @@ REGISTERS = {"rg_sensor_reset_kernel": dict(vgprs=36, sgprs=95, agprs=0, occupan
 
 
 def test_register_use_is_pinned(remarks):
-    for name, want in REGISTERS.items():
-        r = remarks[name]
-        assert int(r["VGPRs"]) <= want["vgprs"], (name, r)
-        assert int(r["TotalSGPRs"]) <= want["sgprs"], (name, r)
-        assert int(r["AGPRs"]) <= want["agprs"], (name, r)
-        assert int(r["Occupancy [waves/SIMD]"]) >= want["occupancy"], (name, r)
+    kernel_checks.assert_registers(remarks, REGISTERS)
 
 
 def test_source_is_its_own_translation_unit_in_both_library_targets():
@@ -490,9 +459,7 @@ def test_source_is_its_own_translation_unit_in_both_library_targets():
             assert "rg_sensor" not in open(os.path.join(SRC, other)).read(), other
     import bench
     assert not any("rg_sensor" in rel for rel in bench.compiled_sources())       # the MPC hash behind profiles/ does not follow it
-    makefile = open(os.path.join(SRC, "Makefile")).read()
-    assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_sensor\.hip", makefile)) == 2   # both library targets
-    assert len(re.findall(r"^librg_mpc\w*\.so:.*rg_sensor\.hip.*include/rg_sensor\.h", makefile, flags=re.M)) == 2
+    kernel_checks.assert_built_into_both("rg_sensor.hip", header="rg_sensor.h")
 
 
 def test_the_documents_no_longer_list_sensor_effects_as_missing():

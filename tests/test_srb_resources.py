@@ -1,41 +1,21 @@
 """The simulator kernels (robot_gym_amd/csrc/rg_srb.hip) compile for gfx950 without scratch: one device-only compile with
-the compiler's resource remarks, parsed here (no GPU needed).  Parity rests on float64 values kept in registers, and the
+the compiler's resource remarks (tests/kernel_checks.py; no GPU needed).  Parity rests on float64 values kept in registers, and the
 source must stay clear of what the kernels have no business with (LDS, atomics, inline assembly)."""
 import os
 import re
-import subprocess
 
 import pytest
 
+from tests import kernel_checks
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 KERNELS = {"rg_srb_step_kernel", "rg_srb_reset_kernel"}
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc here")
-    out = tmp_path_factory.mktemp("srb") / "rg_srb.s"
-    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
-                          "rg_srb.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            mangled = text.split(":", 1)[1].strip()
-            k = re.search(r"(rg_srb_[a-z_]+_kernel)", mangled)
-            name = k.group(1) if k else mangled
-            kernels[name] = {}
-        elif name and ":" in text:
-            key, val = text.split(":", 1)
-            kernels[name][key.strip()] = val.strip()
-    return kernels
+def remarks():
+    return kernel_checks.remarks("rg_srb.hip")
 
 
 def test_every_srb_kernel_is_reported(remarks):
@@ -43,12 +23,7 @@ def test_every_srb_kernel_is_reported(remarks):
 
 
 def test_no_srb_kernel_uses_scratch_or_lds(remarks):
-    for name in KERNELS:
-        r = remarks[name]
-        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
-        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
-        assert r["Dynamic Stack"] == "False", (name, r)
-        assert int(r["LDS Size [bytes/block]"]) == 0, (name, r)
+    kernel_checks.assert_lean(remarks, KERNELS, lds=0)
 
 
 # What the device-only compile reports today.  Both kernels fill the 256 architectural VGPRs a 256-lane workgroup may have
@@ -59,11 +34,7 @@ REGISTERS = {"rg_srb_step_kernel": dict(vgprs=256, agprs=40), "rg_srb_reset_kern
 
 
 def test_register_use_is_pinned(remarks):
-    for name, want in REGISTERS.items():
-        r = remarks[name]
-        assert int(r["VGPRs"]) <= want["vgprs"], (name, r)
-        assert int(r["AGPRs"]) <= want["agprs"], (name, r)
-        assert int(r["Occupancy [waves/SIMD]"]) >= 1, (name, r)
+    kernel_checks.assert_registers(remarks, REGISTERS)
 
 
 def test_contraction_is_off_before_the_controller_header_is_included():

@@ -5,12 +5,12 @@ what this run produces), and the resources of robot_gym_amd/csrc/rg_srb_terrain.
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from robot_gym_amd.core import srb_abi
+from tests import kernel_checks
 from tests import srb_fixtures as F
 from tests import terrain_fixtures as TF
 from tests import terrain_model as TM
@@ -18,7 +18,6 @@ from tests.episode_model import GOLDEN, M64, mix64
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 # ---- hash words ------------------------------------------------------------------------------------------------------
@@ -286,28 +285,8 @@ KERNELS = {"rg_srb_terrain_step_kernel", "rg_srb_terrain_settle_kernel", "rg_srb
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc here")
-    out = tmp_path_factory.mktemp("srb_terrain") / "rg_srb_terrain.s"
-    res = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(out),
-                          "rg_srb_terrain.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-4000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"remark: (?:\S+:\d+:\d+:\s+)?(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            mangled = text.split(":", 1)[1].strip()
-            k = re.search(r"(rg_srb_[a-z_]+_kernel)", mangled)
-            name = k.group(1) if k else mangled
-            kernels[name] = {}
-        elif name and ":" in text:
-            key, val = text.split(":", 1)
-            kernels[name][key.strip()] = val.strip()
-    return kernels
+def remarks():
+    return kernel_checks.remarks("rg_srb_terrain.hip")
 
 
 def test_every_terrain_kernel_is_reported(remarks):
@@ -315,12 +294,7 @@ def test_every_terrain_kernel_is_reported(remarks):
 
 
 def test_no_terrain_kernel_uses_scratch_or_lds(remarks):
-    for name in KERNELS:
-        r = remarks[name]
-        assert int(r["ScratchSize [bytes/lane]"]) == 0, (name, r)
-        assert int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
-        assert r["Dynamic Stack"] == "False", (name, r)
-        assert int(r["LDS Size [bytes/block]"]) == 0, (name, r)
+    kernel_checks.assert_lean(remarks, KERNELS, lds=0)
 
 
 # What the device-only compile reports today (upper bounds).  The step kernel is where the flat one is (256 + 40: the ground
@@ -330,11 +304,7 @@ REGISTERS = {"rg_srb_terrain_step_kernel": dict(vgprs=256, agprs=40), "rg_srb_te
 
 
 def test_terrain_register_use_is_pinned(remarks):
-    for name, want in REGISTERS.items():
-        r = remarks[name]
-        assert int(r["VGPRs"]) <= want["vgprs"], (name, r)
-        assert int(r["AGPRs"]) <= want["agprs"], (name, r)
-        assert int(r["Occupancy [waves/SIMD]"]) >= 1, (name, r)
+    kernel_checks.assert_registers(remarks, REGISTERS)
 
 
 def test_terrain_source_keeps_contraction_off_and_both_library_targets_compile_it():
@@ -343,5 +313,4 @@ def test_terrain_source_keeps_contraction_off_and_both_library_targets_compile_i
     assert src.index("#pragma clang fp contract(off)") < src.index('#include "rg_srb_tick.inc"') < src.index("__global__")
     for text in (src, open(os.path.join(SRC, "rg_srb_tick.inc")).read()):
         assert "asm" not in re.sub(r"//.*", "", text) and "atomic" not in text and "__shared__" not in text
-    makefile = open(os.path.join(SRC, "Makefile")).read()
-    assert len(re.findall(r"\$\(HIPCC\).*-shared.*rg_srb_terrain\.hip", makefile)) == 2
+    kernel_checks.assert_built_into_both("rg_srb_terrain.hip")

@@ -14,12 +14,13 @@ SRC = os.path.join(ROOT, "robot_gym_amd", "csrc")
 MIN_FMA = 12
 
 
-def compile_device(isa_path):
-    """hipcc -S --cuda-device-only with resource remarks -> stderr text (remarks); the ISA goes to isa_path."""
-    res = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", isa_path,
-                          "rg_mpc.hip", "-Rpass-analysis=kernel-resource-usage"], cwd=SRC, capture_output=True, text=True)
+def compile_device(isa_path, source="rg_mpc.hip"):
+    """One device-only compile of a csrc source for gfx950 with resource remarks -> stderr text (remarks); the ISA goes to isa_path.
+    The Makefile's resource-usage target does it, so the flags are the CXXFLAGS librg_mpc.so is built with."""
+    res = subprocess.run(["make", "-s", "resource-usage", "ARCH=gfx950", "UNIT=" + source, "ISA=" + os.path.abspath(isa_path)],
+                         cwd=SRC, capture_output=True, text=True)
     if res.returncode != 0:
-        raise RuntimeError("hipcc failed:\n" + res.stderr[-4000:])
+        raise RuntimeError(f"hipcc failed on {source}:\n" + res.stderr[-4000:])
     return res.stderr
 
 
