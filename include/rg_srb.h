@@ -7,7 +7,8 @@
  * loop.  It is for closed-loop validation of the controller, branched (cloned) rollouts and RL on the reduced model.
  *
  * Stated limits: feet that do not bounce and, in rg_srb_step and rg_srb_step_contact, do not slip; massless legs; first-order
- * (semi-implicit Euler) integration.  The ground is the plane z = 0 or a heightfield (rg_srb_set_terrain, below): kinematic
+ * (semi-implicit Euler) integration.  Every tick delivers the forces as they are planned unless a motor model stands in front of
+ * it (rg_srb_motor_apply, rg_srb_motor.h: a strength and a torque limit per motor).  The ground is the plane z = 0 or a heightfield (rg_srb_set_terrain, below): kinematic
  * feet.  In rg_srb_step touch-down
  * and lift-off follow the gait schedule (the controller's desired_state), not a measurement.  rg_srb_step_contact
  * (rg_srb_contact.h, which states its rule) measures ONE thing on either ground: the early touch-down of a swinging foot, which
@@ -210,5 +211,9 @@ int rg_srb_step(rg_srb_handle *h, double *state, const float *grf, const float *
 /* The tick with Coulomb friction at the stance feet (rg_srb_step_friction), the draw of its coefficient and the text of its
  * rule: part of this ABI, declared in its own file. */
 #include "rg_srb_friction.h"
+
+/* The motor model in front of any tick (rg_srb_motor_apply), the draw of its strengths and the text of its rule: part of this
+ * ABI, declared in its own file. */
+#include "rg_srb_motor.h"
 
 #endif /* RG_SRB_H */

@@ -41,7 +41,8 @@
  *      block 1  16..31   rg_sensor.h  16 observation delay, 17 action delay, 18 bias, 19 observation noise, 20 dropout, 21 action noise
  *      block 2  32..47   rg_est.h     32 bias, 33 noise, 34 contact miss, 35 contact ghost
  *      block 3  48..63   rg_srb_friction.h  48 friction coefficient
- *   A NEW USER TAKES THE NEXT FREE BLOCK OF 16 (block 4, 64..79); a user that needs a new purpose takes the next free one of its
+ *      block 4  64..79   rg_srb_motor.h     64 motor strength (the index word is the motor)
+ *   A NEW USER TAKES THE NEXT FREE BLOCK OF 16 (block 5, 80..95); a user that needs a new purpose takes the next free one of its
  *   own block.  Each unit asserts at compile time that its purposes lie in its block, and the test that their values are
  *   pairwise disjoint.
  *   Streams with words of their own, which have no purpose word (a different chain position by meaning; give them a seed of

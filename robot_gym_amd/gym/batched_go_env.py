@@ -64,7 +64,7 @@ class BatchedGoEnv:
 
     def __init__(self, batch, cfg: MPCConfig = None, targets=None, obstacles=None, seed=0, device=None, sim_settings=None, auto_reset=False,
                  episode_settings=None, terrain=None, contact="schedule", height_scan=None, randomizer=None, sensor_model=None, state_estimator=None,
-                 friction=None, **task):
+                 friction=None, motor_model=None, **task):
         # The default robot is ghost WITH ITS COMMAND OFFSETS ZEROED: vy_offset / wz_offset trim a drift of the reference's
         # PyBullet robot that the reduced model does not have, and with them a straight command walks a curve off the path.
         # A cfg passed in is taken as it is, offsets included.
@@ -79,7 +79,11 @@ class BatchedGoEnv:
         # friction: None (the feet grip) or the ground's friction coefficient (BatchedSRBSim: a float, one value per robot, or
         # "inf"); a DomainRandomizer(friction=(lo, hi)) draws it per episode.  An explicit keyword, not one of sim_settings, which
         # also feeds the episode handle.  A reset leaves a robot's coefficient as it is.
-        self.sim = BatchedSRBSim(B, self.cfg, device=dev, terrain=terrain, contact=contact, friction=friction, **(sim_settings or {}))
+        # motor_model: None (forces are delivered as planned) or a MotorModel (robot_gym_amd/sim/motor_model.py), passed on like
+        # friction; it lives in the simulator (env.sim.motors), so clone and the rollouts carry it with no argument of their own;
+        # a DomainRandomizer(motor_strength=(lo, hi)) draws its strengths per episode.  A reset leaves a robot's motors as they are.
+        self.sim = BatchedSRBSim(B, self.cfg, device=dev, terrain=terrain, contact=contact, friction=friction, motors=motor_model,
+                                 **(sim_settings or {}))
         task.setdefault("dt_sim", self.sim.dt_sim)
         task.setdefault("substeps", self.sim.substeps)
         self._handle = goto_abi.GotoHandle(B, self.cfg, dev, **task)

@@ -14,7 +14,8 @@ librg_mpc.so.
 
 The defaults are the identity: scales (1, 1), the world kept, no push, the friction kept.  Every magnitude is the caller's
 choice.  friction=(lo, hi) draws the ground's friction coefficient per episode into the mu row of a simulator built with
-friction= (include/rg_srb_friction.h); the planner keeps the friction it believes in (MPCConfig.mu).  Not covered:
+friction= (include/rg_srb_friction.h); the planner keeps the friction it believes in (MPCConfig.mu).  motor_strength=(lo, hi) draws the strength ratio of each of the twelve motors per
+episode into the strength rows of a simulator built with motors= (include/rg_srb_motor.h).  Not covered:
 per-axis inertia, offsets of the centre of mass.  Observation and action noise, dropout and
 latency are SensorModel's (robot_gym_amd/sim/sensor_model.py).
 
@@ -23,7 +24,7 @@ through DomainRandomizer.set_body, which forwards, captures the new base and sca
 """
 import torch
 
-from robot_gym_amd.core import dr_abi, friction_abi
+from robot_gym_amd.core import dr_abi, friction_abi, motor_abi
 from robot_gym_amd.sim.stream_state import copy_robot_columns, stream_state
 from robot_gym_amd.sim.terrain import RandomTerrain
 
@@ -45,11 +46,15 @@ class DomainRandomizer:
     (None without pushes)."""
 
     def __init__(self, mass_scale=(1.0, 1.0), inertia_scale=(1.0, 1.0), new_world_each_episode=False, seed=0, push_interval=0, push_ticks=0,
-                 push_probability=0.0, push_force_xy=0.0, push_force_z=0.0, push_torque_xy=0.0, push_torque_z=0.0, friction=None):
+                 push_probability=0.0, push_force_xy=0.0, push_force_z=0.0, push_torque_xy=0.0, push_torque_z=0.0, friction=None, motor_strength=None):
         (mlo, mhi), (ilo, ihi) = _range(mass_scale, "mass_scale"), _range(inertia_scale, "inertia_scale")
         # friction: None (nothing is drawn, nothing launched) or (lo, hi), the range of the friction coefficient each episode
         # draws (include/rg_srb_friction.h): 0 <= lo <= hi, finite; needs a simulator built with friction=
         self.friction = None if friction is None else friction_abi.checked_range(*_range(friction, "friction"), what="DomainRandomizer: friction")
+        # motor_strength: None (nothing is drawn, nothing launched) or (lo, hi), the range each motor's strength ratio is drawn
+        # from every episode (include/rg_srb_motor.h): 0 <= lo <= hi, finite; needs a simulator built with motors=
+        self.motor_strength = None if motor_strength is None else motor_abi.checked_range(*_range(motor_strength, "motor_strength"),
+                                                                                          what="DomainRandomizer: motor_strength")
         self.settings = dict(worlds=int(bool(new_world_each_episode)), seed=int(seed), mass_lo=mlo, mass_hi=mhi, inertia_lo=ilo, inertia_hi=ihi,
                              push_interval=int(push_interval), push_ticks=int(push_ticks), push_probability=float(push_probability),
                              push_force_xy=float(push_force_xy), push_force_z=float(push_force_z), push_torque_xy=float(push_torque_xy),
@@ -69,6 +74,9 @@ class DomainRandomizer:
         if self.friction is not None and getattr(sim, "mu", None) is None:
             raise ValueError("DomainRandomizer: friction=(lo, hi) needs a simulator built with friction (BatchedSRBSim(..., friction=...)): "
                              "its mu row is what the draw writes")
+        if self.motor_strength is not None and getattr(sim, "motors", None) is None:
+            raise ValueError("DomainRandomizer: motor_strength=(lo, hi) needs a simulator built with a motor model "
+                             "(BatchedSRBSim(..., motors=MotorModel())): its strength rows are what the draw writes")
         B, dev = sim.batch, sim.device
         self._handle = dr_abi.DrHandle(B, dev, substeps=sim.substeps, **self.settings)
         self.batch, self.device, self.sim = B, dev, sim
@@ -99,7 +107,7 @@ class DomainRandomizer:
         return self.state[dr_abi.ROW_MASS_SCALE:dr_abi.ROW_INERTIA_SCALE + 1]
 
     def on_reset(self, mask):
-        """A draw -- body scales, with new_world_each_episode a world, with friction=(lo, hi) a friction coefficient -- for the robots b with mask[b] != 0 (int32 [B]
+        """A draw -- body scales, with new_world_each_episode a world, with friction=(lo, hi) a friction coefficient, with motor_strength=(lo, hi) twelve motor strengths -- for the robots b with mask[b] != 0 (int32 [B]
         device tensor), BEFORE the simulator resets them, so that its settle stands them in the new world.  Enqueued on the
         current stream; nothing waits."""
         self._bound("on_reset")
@@ -108,6 +116,10 @@ class DomainRandomizer:
             # before rg_dr_reset, which counts the draw: both read the same draw count
             friction_abi.friction_draw(self.sim._handle, mask, self.state[dr_abi.ROW_KEY], self.state[dr_abi.ROW_DRAWS], self.settings["seed"],
                                        self.friction[0], self.friction[1], self.sim.mu)
+        if self.motor_strength is not None:
+            # next to the friction draw, and like it before rg_dr_reset
+            motor_abi.motor_draw(self.sim._handle, mask, self.state[dr_abi.ROW_KEY], self.state[dr_abi.ROW_DRAWS], self.settings["seed"],
+                                 self.motor_strength[0], self.motor_strength[1], self.sim.motors.strength)
         self._handle.reset(self.sim._handle, mask_ptr, self.state.data_ptr(), None if self._keys is None else self._keys.data_ptr())
 
     def pushes(self):

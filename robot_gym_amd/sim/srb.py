@@ -11,6 +11,8 @@ reach limit and body collision are not measured in either mode (a foot descendin
 CPU model fall: rg_srb_contact.h).  The feet grip whatever the force (friction=None, the default) or the ground has a Coulomb
 friction coefficient per robot (friction=, include/rg_srb_friction.h): a stance foot asked for more tangential force than mu
 times its normal force passes on that much, and slides; sim.slip holds the metres each foot slid on the last tick.
+The forces are delivered as planned (motors=None, the default) or pass through a motor model first (motors=MotorModel(...),
+robot_gym_amd/sim/motor_model.py, include/rg_srb_motor.h): a strength ratio and a torque limit per motor.
 PyTorch-ROCm is used only for device buffers and the current stream; all arithmetic
 happens in librg_mpc.so.
 
@@ -27,6 +29,7 @@ import torch
 from robot_gym_amd.controllers.mpc.batched import STATE_FIELDS
 from robot_gym_amd.core import friction_abi, srb_abi
 from robot_gym_amd.core.config import MPCConfig
+from robot_gym_amd.sim.motor_model import MotorModel
 
 CONTACT_MODES = ("schedule", "measured")
 CONTROLLER_OUTPUTS = (("grf", 12, torch.float32), ("foot_target", 12, torch.float32), ("desired_state", 4, torch.int32))
@@ -57,13 +60,20 @@ class BatchedSRBSim:
     device tensors in STATE_FIELDS order plus `t_robot`, accepted by BatchedMPCController.get_action as is."""
 
     def __init__(self, batch, cfg: MPCConfig = None, device=None, dt_sim=0.001, substeps=10, fall_height_scale=0.5, fall_tilt=1.0,
-                 terrain=None, contact="schedule", friction=None, slip_gain=friction_abi.SLIP_GAIN, slip_speed_max=friction_abi.SLIP_SPEED_MAX):
+                 terrain=None, contact="schedule", friction=None, slip_gain=friction_abi.SLIP_GAIN, slip_speed_max=friction_abi.SLIP_SPEED_MAX,
+                 motors=None):
         if contact not in CONTACT_MODES:
             raise ValueError(f"contact must be one of {CONTACT_MODES}, got {contact!r}")
         # friction: None (the feet grip: nothing is allocated and step dispatches as without it), or the coefficient of every
         # robot: a float, a (B,) array or tensor, or "inf" (the friction tick with every robot gripping)
         mu0 = None if friction is None else friction_values(friction, int(batch), "friction")
         self.slip_gain, self.slip_speed_max = friction_abi.checked_settings(slip_gain, slip_speed_max)
+        # motors: None (the forces are delivered as planned: nothing is allocated, nothing launched) or a MotorModel, which is bound
+        # to this simulator: step then applies it to the controller's grf and steps on the delivered force
+        if motors is not None and not isinstance(motors, MotorModel):
+            raise ValueError(f"motors must be a MotorModel or None, got {motors!r}")
+        if motors is not None:
+            motors.rows(batch)
         if not torch.cuda.is_available():
             raise RuntimeError("BatchedSRBSim needs a HIP device (no CPU fallback)")
         self.cfg = cfg or MPCConfig.for_robot("ghost")
@@ -95,6 +105,7 @@ class BatchedSRBSim:
         if mu0 is not None:
             self.mu = torch.as_tensor(mu0, device=self.device)
             self.slip = torch.zeros(4, B, dtype=torch.float64, device=self.device)
+        self.motors = None if motors is None else motors.bind(self)
 
     def set_terrain(self, terrain):
         """The ground: a RandomTerrain or GridTerrain of robot_gym_amd.sim.terrain (it is bound to this batch and device and
@@ -173,9 +184,15 @@ class BatchedSRBSim:
         dict with grf [B,12], foot_target [B,12] float32 and desired_state [B,4] int32; in measured mode leg_state [B,4] int32
         in place of desired_state (a ValueError names it when it is missing).  ext: float64 [6,B] world force and torque
         about the CoM, or None.  With friction the tick is rg_srb_step_friction in either mode, on the same outputs, and writes
-        self.slip.  Enqueued on the current stream; nothing waits."""
+        self.slip.  With a motor model the tick, whichever it is, runs on the force the motors deliver (self.motors.grf) in place of
+        grf.  Enqueued on the current stream; nothing waits."""
         out = getattr(ctl_or_outputs, "extra", ctl_or_outputs)
         get = lambda name: out.get(name) if hasattr(out, "get") else None
+        if self.motors is not None:
+            if get("grf") is None:
+                raise KeyError("step: controller output 'grf' missing (a BatchedMPCController needs extra_outputs=True)")
+            planned, delivered = out, self.motors.apply(get("grf"))
+            get = lambda name: delivered if name == "grf" else planned.get(name)
         if self.mu is not None:
             # the friction tick in either contact mode: it steps on leg_state (measured) or desired_state (schedule)
             measured = self.contact == "measured"
@@ -234,6 +251,8 @@ class BatchedSRBSim:
         self.state.index_copy_(1, dst, self.state.index_select(1, src))
         for t in list(self.obs.values()) + [self.touch] + ([] if self.mu is None else [self.mu, self.slip]):   # the floor a robot walks on goes with it
             t.index_copy_(t.dim() - 1, dst, t.index_select(t.dim() - 1, src))
+        if self.motors is not None:   # and so do its motors
+            self.motors.copy_columns(src, dst)
         keys = getattr(self.terrain, "keys", None)
         if keys is not None:   # the world a robot walks in goes with it
             keys.index_copy_(0, dst, keys.index_select(0, src))
