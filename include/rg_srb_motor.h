@@ -31,6 +31,21 @@
  *     floats, which the tick of rg_srb.h handles: the robot keeps its last state and is marked fallen.  So does a NaN in the
  *     force: its leg, and only its leg, delivers NaN, whatever the limit.
  *
+ * Settings the Python layer refuses and this entry takes as they are (nothing here is checked on the device; every case stays
+ * inside its leg, and what a leg delivers non-finite the tick of rg_srb.h handles for that robot alone):
+ *   strength 0: a_j = +-0, so a leg with force takes the solve on a zero right-hand side and delivers zero, each float with the
+ *     sign Cramer's sums give it; tau_out = +-0.
+ *   limit 0: c_j = +-0 for every a_j, and the leg delivers zero as under strength 0.
+ *   a NaN limit is no limit: fmin and fmax drop a NaN operand, so c_j = a_j, as under +inf.
+ *   a negative limit is not an interval: fmax(a_j, -limit) is at least -limit > limit, so c_j is the limit itself, a finite
+ *     negative torque, whatever a_j; the leg takes the solve.
+ *   +inf strength: a_j = +-inf where tau_j != 0, clipped to a finite limit like any torque; where tau_j == 0 (a swinging leg's
+ *     zero force among them) inf * 0 = NaN stays a NaN, and that leg, and only that leg, delivers NaN.
+ *   -0.0 and denormal floats in grf are widened exactly (nothing is flushed): a leg of -0.0 has tau_j = +-0 == c_j and passes
+ *     through with its signs, a denormal leg passes through by bits or is solved like any other.
+ *   an all-zero grf passes through by bits under every finite strength and every limit that is not negative, 0 and NaN
+ *     included: c_j = +-0 == tau_j.  Under a negative limit c_j is the limit, so there even a zero-force leg is solved.
+ *
  * Stated limits: the legs are massless, so swinging legs are not actuated by this rule (their grf is 0 and passes through);
  * there is no velocity-dependent limit, no back-EMF and no thermal model; near a singularity a bounded torque delivers an
  * unbounded force along the leg, as a rigid straight leg does; the angles read are the simulator's true ones, never a state

@@ -14,7 +14,7 @@ from robot_gym_amd.core.config import MPCConfig
 from tests import motor_model as MM
 from tests import srb_fixtures as F
 from tests import srb_model as M
-from tests.posctl_fixtures import REL_TOL
+from tests.posctl_fixtures import REL_TOL, within_ulp
 
 LIMIT_FRACTION = 0.8
 
@@ -119,4 +119,214 @@ def kernel_cases():
             assert (c["strength"] >= 0.5).all() and (c["strength"] <= 1.2).all() and np.isfinite(c["out"]).all()
         # between a fifth and four fifths of the legs saturate
         assert 0.2 * legs <= saturated <= 0.8 * legs, (robot, saturated, legs)
+    return out
+
+
+# ---- the delivered force of a tick against the model ----------------------------------------------------------------------
+
+def near_limit(strength, tau_cmd, limit):
+    """[4, B] bool: the legs with some |a_j| = |strength * tau_cmd| within REL_TOL * max(1, limit) of a finite limit.  Over a last
+    bit of the sine the kernel may clip such a joint where the model does not (or the reverse), and with it take the other of
+    pass-through and solve: a comparison leaves these legs out and counts them."""
+    with np.errstate(invalid="ignore"):
+        a, finite = np.abs(strength * tau_cmd), np.isfinite(limit)
+        lim = np.where(finite, limit, 1.0)
+        near = finite & (np.abs(a - lim) <= REL_TOL * np.maximum(1.0, lim))
+    return near.reshape(4, 3, -1).any(1)
+
+
+def delivered_mismatches(planned, want, got, skip=None):
+    """The rule of test_kernel_against_the_motor_model on one tick.  planned [B, 12] float32; want = motor_model.apply's (out,
+    tau_cmd, tau, sat); got = (grf, tau_cmd, tau) of the device; skip [4, B] bool: legs left out (near_limit).  The legs that
+    pass through keep the BITS of planned, the others are within one float32 ulp of the model's, the torques within REL_TOL *
+    max(1, |w|).  -> (["field (n differ)"], the largest |grf - model|, the largest torque deviation over max(1, |w|))."""
+    out, tau_cmd, tau, sat = want
+    g, g_cmd, g_tau = got
+    keep = np.ones(sat.shape, dtype=bool) if skip is None else ~skip
+    keep12, keep_rows = np.repeat(keep.T, 3, axis=1), np.repeat(keep, 3, axis=0)          # [B, 12] and [12, B]
+    passed = np.repeat(~sat.T, 3, axis=1) & keep12
+    solved = np.repeat(sat.T, 3, axis=1) & keep12
+    bad = []
+    if not (g[passed].tobytes() == planned[passed].tobytes() == out[passed].tobytes()):
+        bad.append(f"grf of the legs that pass through ({int((g[passed].view(np.int32) != planned[passed].view(np.int32)).sum())} differ)")
+    ok = within_ulp(g[solved], out[solved].astype(np.float64))
+    if not ok.all():
+        bad.append(f"grf of the legs the motors change ({int((~ok).sum())} beyond one ulp)")
+    worst_tau = 0.0
+    for name, a, w in (("tau_cmd", g_cmd, tau_cmd), ("tau", g_tau, tau)):
+        rel = np.abs(a - w)[keep_rows] / np.maximum(1.0, np.abs(w[keep_rows]))
+        worst_tau = max(worst_tau, float(rel.max(initial=0.0)))
+        if not (rel <= REL_TOL).all():
+            bad.append(f"{name} ({int((~(rel <= REL_TOL)).sum())} beyond the tolerance)")
+    worst = float(np.abs(g.astype(np.float64) - out)[keep12].max(initial=0.0))
+    return bad, worst, worst_tau
+
+
+# ---- non-identity motors in front of every tick ---------------------------------------------------------------------------
+
+TICK_B, TICK_T, TICK_MU = 17, 30, 0.3
+TICK_CONFIGS = ("plane_schedule", "terrain_schedule", "terrain_measured", "terrain_friction")
+
+
+def tick_motors(robot, B, identity_even=False):
+    """(strength, limit) [12, B] of the every-tick runs: every motor its own strength in 0.6 .. 1.1 (never 1: a leg with force
+    takes the solve), and limit rows mixed by (motor + robot) % 3: +inf, 0.7 of the motor's PEAK (binds), twice the PEAK (never
+    binds).  On the CPU loops (plane with schedule contact; reference terrain, measured contact, mu 0.3) nobody falls in 30 ticks at
+    0.7 and 236 / 272 motor-ticks clip; at 0.5 one robot of the 17 falls on the plane, its rates beyond float32 on the way.
+    identity_even: the even robots get strength 1 and +inf instead."""
+    rng = np.random.default_rng([B, F.ROBOTS.index(robot), 65])
+    strength = rng.uniform(0.6, 1.1, (12, B))
+    assert (strength != 1.0).all()
+    kind = (np.arange(12)[:, None] + np.arange(B)[None, :]) % 3
+    peak = np.asarray(PEAK[robot])[:, None]
+    limit = np.where(kind == 0, np.inf, np.where(kind == 1, 0.7 * peak, 2.0 * peak))
+    if identity_even:
+        strength[:, 0::2], limit[:, 0::2] = 1.0, np.inf
+    return np.ascontiguousarray(strength), np.ascontiguousarray(limit)
+
+
+def tick_model(name, cfg, B, ground):
+    """The numpy model of the tick the simulator runs in configuration `name` (ground: the terrain_model ground; None on the
+    plane) and step(model, grf, outputs): that tick on the controller's outputs with `grf` in place of theirs."""
+    from tests import contact_model as CM
+    from tests import friction_model as FM
+    from tests import terrain_model as TM
+    ft = lambda out: np.asarray(out["foot_target"], dtype=np.float32)
+    if name == "plane_schedule":
+        return M.SRBModel(B, cfg), lambda m, grf, out: m.step(grf, ft(out), out["desired_state"])
+    if name == "terrain_schedule":
+        return TM.TerrainSRBModel(B, cfg, ground), lambda m, grf, out: m.step(grf, ft(out), out["desired_state"])
+    if name == "terrain_measured":
+        return CM.ContactSRBModel(B, cfg, ground), lambda m, grf, out: m.step_contact(grf, ft(out), out["leg_state"])
+    if name == "terrain_friction":
+        return FM.FrictionSRBModel(B, cfg, ground, mu=TICK_MU), lambda m, grf, out: m.step_friction(grf, ft(out), out["leg_state"], 1)
+    raise ValueError(name)
+
+
+# ---- the singular leg -------------------------------------------------------------------------------------------------------
+
+def singular_cfg(robot):
+    """The robot's configuration with the toe of leg 0 (toe_xyz and toe_com) at zero: the foot lies on the knee axis, the knee
+    column of that leg's Jacobian is exactly zero at any q and det == 0.0 exactly.  The other three legs are the robot's."""
+    import dataclasses
+    cfg = MPCConfig.for_robot(robot)
+    flat = lambda v: (0.0,) * 3 + tuple(float(x) for x in v[3:])
+    return dataclasses.replace(cfg, toe_xyz=flat(cfg.toe_xyz), toe_com=flat(cfg.toe_com))
+
+
+def singular_case(robot, B=17):
+    """make_case's inputs on singular_cfg: a force on every leg, strengths that differ per joint in 0.5 .. 1.2, and one binding
+    limit, on joint 1 of leg 0 of the even robots at 0.3 of its torque (below every strength: it decides their scale).  Asserted
+    on the model: det == 0.0 exactly on leg 0 and nowhere else, all lanes of leg 0 take the uniform scale and the others the
+    solve, and leg 0's floats are (float)(k * g) with k the fmin chain over c_j / tau_j."""
+    cfg, regular = singular_cfg(robot), MPCConfig.for_robot(robot)
+    rng = np.random.default_rng([B, F.ROBOTS.index(robot), 66])
+    chain = M.Chain(cfg)
+    m = M.SRBModel(B, regular)
+    m.reset()
+    q = m.state[M.ROW_Q:M.ROW_Q + 12] + rng.uniform(-0.15, 0.15, (12, B))
+    g = rng.uniform(-40.0, 40.0, (B, 4, 3))
+    g[:, :, 2] = rng.uniform(-120.0, -10.0, (B, 4))
+    g = np.ascontiguousarray(g.reshape(B, 12)).astype(np.float32)
+    strength, limit = rng.uniform(0.5, 1.2, (12, B)), np.full((12, B), np.inf)
+    strength[0:2] = rng.uniform(0.5, 0.95, (2, B))          # the knee's ratio counts as 1 (tau_2 = 0): a weak hip, so that k < 1
+    _, tau0, _, _ = MM.apply(chain, q, g, np.ones((12, B)), limit)
+    limit[1, 0::2] = 0.3 * np.abs(tau0[1, 0::2])
+    out, tau_cmd, tau, sat = MM.apply(chain, q, g, strength, limit)
+    scaled = np.zeros((4, B), dtype=bool)
+    for l in range(4):
+        _, J = chain.fk(np.full(B, l), [q[3 * l + j] for j in range(3)])
+        _, det = MM.solve3([J[0], J[3], J[6], J[1], J[4], J[7], J[2], J[5], J[8]], [np.ones(B)] * 3)
+        assert ((det == 0.0) == (l == 0)).all(), (robot, l)
+        if l == 0:
+            assert all((J[3 * i + 2] == 0.0).all() for i in range(3))
+        _, _, _, solves, scales = MM.leg_rule([g[:, 3 * l + i] for i in range(3)], J, [chain.mdir[l, j] for j in range(3)],
+                                              [strength[3 * l + j] for j in range(3)], [limit[3 * l + j] for j in range(3)])
+        assert (scales == (l == 0)).all() and (solves == (l != 0)).all(), (robot, l)
+        scaled[l] = scales
+    assert sat.all() and (tau_cmd[2] == 0.0).all() and (tau_cmd[:2] != 0.0).all()
+    with np.errstate(all="ignore"):
+        k = np.fmin(np.fmin(tau[0] / tau_cmd[0], tau[1] / tau_cmd[1]), 1.0)
+    assert out[:, :3].tobytes() == (k[:, None] * g[:, :3].astype(np.float64)).astype(np.float32).tobytes()
+    assert (np.abs(k[0::2] - 0.3) < 1e-12).all() and (k[1::2] >= 0.5).all() and (k < 1.0).all()   # the limit decides where it binds
+    return dict(cfg=cfg, B=B, q=q, grf=g, strength=strength, limit=limit, out=out, tau_cmd=tau_cmd, tau=tau, sat=sat, scaled=scaled)
+
+
+# ---- settings only the C ABI accepts ----------------------------------------------------------------------------------------
+
+def abi_cases(robot="ghost", B=17):
+    """{name: inputs and what the model makes of them} for the settings MotorModel refuses and rg_srb_motor_apply accepts, on
+    make_case's angles and forces.  `exact` [B, 12] bool: the floats compared bit for bit with the model's (signs of zero
+    included); the others are held as in test_kernel_against_the_motor_model, a NaN to a NaN.  What each case is about is
+    asserted here, on the model alone."""
+    base = make_case(robot, B)
+    chain, q = M.Chain(base["cfg"]), base["q"]
+    stance = (base["grf"].reshape(B, 4, 3) != 0).any(2).T                                      # [4, B]
+    legs12 = lambda legs: np.repeat(legs.T, 3, axis=1)                                         # [4, B] -> [B, 12]
+    rows12 = lambda legs: np.repeat(legs, 3, axis=0)                                           # [4, B] -> [12, B]
+    every = np.ones((B, 12), dtype=bool)
+    out = {}
+
+    def case(name, grf, strength, limit, exact):
+        grf = np.ascontiguousarray(grf, dtype=np.float32)
+        o, tau_cmd, tau, sat = MM.apply(chain, q, grf, strength, limit)
+        c = out[name] = dict(cfg=base["cfg"], B=B, q=q, grf=grf, strength=np.ascontiguousarray(strength), limit=np.ascontiguousarray(limit), out=o,
+                             tau_cmd=tau_cmd, tau=tau, sat=sat, exact=exact)
+        return c
+
+    # strength 0 on the even robots: a stance leg delivers zero, and the zeros' signs are the model's
+    s = base["strength"].copy()
+    s[:, 0::2] = 0.0
+    dead = stance.copy()
+    dead[:, 1::2] = False
+    c = case("strength_zero", base["grf"], s, base["limit"], legs12(dead))
+    assert dead.sum() > 2 * B // 2 and (c["out"][legs12(dead)] == 0.0).all() and (c["tau"][rows12(dead)] == 0.0).all() and c["sat"][dead].all()
+    # limit 0 on every motor of the even robots: nothing is delivered either
+    lim = base["limit"].copy()
+    lim[:, 0::2] = 0.0
+    c = case("limit_zero", base["grf"], base["strength"], lim, np.zeros((B, 12), dtype=bool))
+    assert (c["out"][legs12(dead)] == 0.0).all() and (c["tau"][rows12(dead)] == 0.0).all() and c["sat"][dead].all()
+    # a NaN limit is no limit: with strength 1 every leg passes through by bits, with another strength the torque is a_j unclipped
+    lim = np.full((12, B), np.nan)
+    s = np.ones((12, B))
+    s[:, 1::2] = base["strength"][:, 1::2]
+    c = case("limit_nan", base["grf"], s, lim, legs12(np.repeat((np.arange(B) % 2 == 0)[None, :], 4, 0)))
+    assert not c["sat"][:, 0::2].any() and c["out"][0::2].tobytes() == base["grf"][0::2].tobytes() and (c["tau"] == s * c["tau_cmd"]).all()
+    assert np.isfinite(c["out"]).all()
+    # a negative limit is no interval: fmin(fmax(a, -limit), limit) is the limit itself whatever a_j, a finite torque
+    lim = np.full((12, B), np.inf)
+    lim[:, 0::2] = -3.0
+    c = case("limit_negative", base["grf"], np.ones((12, B)), lim, legs12(np.repeat((np.arange(B) % 2 == 1)[None, :], 4, 0)))
+    assert (c["tau"][:, 0::2] == -3.0).all() and c["sat"][:, 0::2].all() and not c["sat"][:, 1::2].any() and np.isfinite(c["out"]).all()
+    # +inf strength on a zero-force leg: inf * 0 = NaN lands on that leg, and on no other
+    g = base["grf"].copy()
+    g[:, 3:6] = 0.0
+    s = base["strength"].copy()
+    s[3:6, 0::2] = np.inf
+    c = case("strength_inf_on_a_swinging_leg", g, s, base["limit"], np.zeros((B, 12), dtype=bool))
+    hit = np.zeros((B, 12), dtype=bool)
+    hit[0::2, 3:6] = True
+    assert np.isnan(c["out"][hit]).all() and np.isfinite(c["out"][~hit]).all() and np.isnan(c["tau"][3:6, 0::2]).all()
+    assert np.isfinite(np.delete(c["tau"], [3, 4, 5], 0)).all() and (c["tau_cmd"][3:6] == 0.0).all()
+    # -0.0 and denormal force components: a leg of -0.0 passes through with its signs under any strength and limit; a leg of
+    # float32 denormals passes through by bits under strength 1 (leg 1) and is halved by the solve under strength 0.5 (leg 2)
+    g = base["grf"].copy()
+    g[:, 0:3] = np.float32(-0.0)
+    tiny = np.array([1e-40, -3e-41, -7e-39], dtype=np.float32)
+    assert (tiny != 0).all() and (np.abs(tiny) < np.finfo(np.float32).tiny).all()
+    g[:, 3:6], g[:, 6:9] = tiny, tiny
+    s, lim = base["strength"].copy(), base["limit"].copy()
+    s[0:3], lim[0:3] = 0.5, 3.0
+    s[3:6], lim[3:6] = 1.0, np.inf
+    s[6:9], lim[6:9] = 0.5, np.inf
+    exact = np.zeros((B, 12), dtype=bool)
+    exact[:, 0:6] = True
+    c = case("negative_zero_and_denormal_force", g, s, lim, exact)
+    assert not c["sat"][:2].any() and c["sat"][2].all() and c["out"][:, :6].tobytes() == g[:, :6].tobytes() and np.signbit(c["out"][:, :3]).all()
+    assert within_ulp(c["out"][:, 6:9], 0.5 * g[:, 6:9].astype(np.float64)).all() and (c["out"][:, 6:9] != 0).all()
+    # an all-zero grf: every float passes through by bits, whatever the strength and the limit
+    lim = base["limit"].copy()
+    lim[:, 0::3] = 0.0
+    c = case("all_zero_force", np.zeros((B, 12), np.float32), base["strength"], lim, every)
+    assert not c["sat"].any() and (c["tau_cmd"] == 0.0).all() and (c["tau"] == 0.0).all() and c["out"].tobytes() == bytes(4 * 12 * B)
     return out

@@ -1,6 +1,7 @@
 """The composed env's test helpers without a GPU (tests/env_stack.py): the reach of the stack's settings from the models alone,
 the plan status of the targets the hand-made resets use, and that Replay reports, with the unit's name, each error of ordering it
-is there to notice -- on records the models make themselves, one change at a time."""
+is there to notice -- on records the models make themselves, one change at a time.  For STACK_FULL: its settings against the
+originals, the errors of the floor, the motors and the plant, and the oracle-driven CPU loop its ranges and limits are chosen on."""
 import numpy as np
 import pytest
 
@@ -64,8 +65,10 @@ class ModelEnv:
     """The stack made of the numpy models, called in BatchedGoEnv's order, over a simulator that is a random walk with a step
     count: what it records is what the env would.  mutate: one deliberate error of ordering (MUTATIONS)."""
 
-    def __init__(self, mutate=None, seed=0):
-        self.m = ES.Replay(B, ES.base_body(ES.default_cfg(), B))      # its buffers and settings; the ORDER is this class's
+    episode_ticks = ES.EPISODE_TICKS
+
+    def __init__(self, mutate=None, seed=0, stack=ES.STACK):
+        self.m = ES.Replay(B, ES.base_body(ES.default_cfg(), B), stack=stack)      # its buffers and settings; the ORDER is this class's
         self.mutate, self.rng, self.tick = mutate, np.random.default_rng(seed), 0
         self.sim_state = np.zeros((43, B))
         self.true, self.true_final = (np.zeros((ES.PATH_ROWS + ES.SCAN_ROWS, B), dtype=np.float32) for _ in range(2))
@@ -88,36 +91,47 @@ class ModelEnv:
                     obs=m.sensor["obs_out"].copy(), final_obs=m.final.copy(), applied=self.applied.copy(), sensor_state=m.sensor["state"].copy(),
                     obs_ring=m.sensor["obs_ring"].copy(), act_ring=m.sensor["act_ring"].copy(), est_obs=self.est_obs, est_state=m.est_state.copy())
 
+    # what a stack with a plant of its own replaces: the draw of a reset, the simulator's tick and its observation
+    def _draw(self, on):
+        m = self.m
+        DM.reset(m.dr_cfg, on, m.dr_state, m.base, m.body, m.keys)
+
+    def _advance(self):
+        self.sim_state[0:2] += self.rng.uniform(-0.03, 0.03, (2, B))
+        self.sim_state[DM.STEPS_ROW] += 10.0
+
+    def _observe_sim(self):
+        return EM.random_obs(self.rng, B, self.m.chain)
+
     def reset(self):
         m, on = self.m, np.ones(B, dtype=bool)
-        DM.reset(m.dr_cfg, on, m.dr_state, m.base, m.body, m.keys)
+        self._draw(on)
         self._stand(on)
         EM.reset(on, m.est_state)
         self._path(on)
         self.true[ES.PATH_ROWS:] = m.scan(self.sim_state)
         SM.reset(m.sensor_cfg, on, m.sensor, self.true)
-        self.sim_obs = EM.random_obs(self.rng, B, m.chain)
+        self.sim_obs = self._observe_sim()
 
     def step(self, action):
         m = self.m
         self.tick += 1
-        ends = self.sim_state[DM.STEPS_ROW] >= 10.0 * (ES.EPISODE_TICKS - 1)              # the robots this tick resets
+        ends = self.sim_state[DM.STEPS_ROW] >= 10.0 * (self.episode_ticks - 1)            # the robots this tick resets
         rec = dict(action=action, sim_state0=self.sim_state.copy(), sim_obs0={n: v.copy() for n, v in self.sim_obs.items()})
         self.applied = SM.act(m.sensor_cfg, m.sensor, action)
         if self.mutate == "estimator reset one tick early":
             EM.reset(ends, m.est_state)
         self.est_obs = EM.estimate(m.est_cfg, m.chain, m.est_state, self.sim_obs)
         self.ext = DM.push(m.dr_cfg, self.sim_state, m.dr_state)
-        self.sim_state[0:2] += self.rng.uniform(-0.03, 0.03, (2, B))
-        self.sim_state[DM.STEPS_ROW] += 10.0
-        self.sim_obs = EM.random_obs(self.rng, B, m.chain)
+        self._advance()
+        self.sim_obs = self._observe_sim()
         self._path(np.ones(B, dtype=bool))
         self.true[ES.PATH_ROWS:] = m.scan(self.sim_state)
         SM.observe(m.sensor_cfg, m.sensor, self.true)
         # the reset on the device, for the robots that ended
         self.true_final[:, ends] = self.true[:, ends]
         self._path(ends)
-        DM.reset(m.dr_cfg, ends, m.dr_state, m.base, m.body, m.keys)
+        self._draw(ends)
         if self.mutate != "estimator reset one tick early":
             EM.reset(ends, m.est_state)
         self._stand(ends)
@@ -168,3 +182,187 @@ def test_replay_names_the_unit_of_each_error_of_ordering_and_reports_nothing_wit
         assert reports[0][0] == ES.EPISODE_TICKS                                           # the first tick with a reset
     if mutate == "sensor reset before the scan":
         assert any("obs_ring" in f for f in fields) and any("obs " in f for f in fields)
+
+
+# ================================================================================================================================
+# STACK_FULL: the floor, the motors and the plant (tests/env_stack.py)
+# ================================================================================================================================
+
+def test_the_full_stack_is_the_stack_plus_a_floor_and_motors_and_restates_the_originals():
+    from robot_gym_amd.core import friction_abi, motor_abi
+    from robot_gym_amd.sim.motor_model import MotorModel
+    from tests import friction_model as FM
+    from tests import motor_fixtures as MF
+    from tests import motor_model as MM
+    full = ES.STACK_FULL
+    for k in ("terrain", "height_scan", "sensor_model", "state_estimator"):
+        assert full[k] == ES.STACK[k], k
+    assert {k: v for k, v in full["env"].items() if k != "friction"} == dict(ES.STACK["env"], max_time=0.95)
+    assert {k: v for k, v in full["randomizer"].items() if k not in ("friction", "motor_strength")} == ES.STACK["randomizer"]
+    assert ES.STACK["env"]["max_time"] == 0.45 and "friction" not in ES.STACK["env"] and "motors" not in ES.STACK      # STACK itself is as it was
+    # 95 sub-steps at ten a tick: the time limit ends every episode on tick 10 (the friction env test's setting)
+    assert ES.EPISODE_TICKS_FULL == 10 == -(-95 // 10) and full["env"]["max_time"] == 0.95
+    # the ranges are ones the library takes, and the two purposes are the headers', apart from every purpose STACK uses
+    assert friction_abi.checked_range(*ES.FRICTION_RANGE) == ES.FRICTION_RANGE == full["randomizer"]["friction"]
+    assert motor_abi.checked_range(*ES.STRENGTH_RANGE) == ES.STRENGTH_RANGE == full["randomizer"]["motor_strength"]
+    assert (FM.PURPOSE_MU, MM.PURPOSE_STRENGTH) == (friction_abi.PURPOSE_MU, motor_abi.PURPOSE_STRENGTH) == (48, 64)
+    used = set(range(DM.MASS, DM.PUSH_GATE + 1)) | set(range(SM.OBS_DELAY, SM.ACT_NOISE + 1)) | set(range(EM.BIAS, EM.GHOST + 1))
+    assert not used & {48, 64}
+    # the limits: +inf for the robots 0 mod 3, a share of the env's robot's PEAK for the others, and what MotorModel accepts
+    assert ES.default_cfg().robot == "ghost" and ES.LIMIT_FRACTIONS[0] is None and all(0.0 < f <= 1.0 for f in ES.LIMIT_FRACTIONS[1:])
+    for batch in (32, 64, 67):
+        rows = ES.limit_rows(batch)
+        assert rows.shape == (12, batch) and np.isinf(rows[:, 0::3]).all() and np.isfinite(rows[:, 1::3]).all() and np.isfinite(rows[:, 2::3]).all()
+        assert (rows[:, 1] == ES.LIMIT_FRACTIONS[1] * np.asarray(MF.PEAK["ghost"])).all() and (rows[:, 2] == ES.LIMIT_FRACTIONS[2] * np.asarray(MF.PEAK["ghost"])).all()
+        s, lim = MotorModel(strength=full["motors"]["strength"], torque_limit=rows).rows(batch)
+        assert lim.tobytes() == rows.tobytes() and (s == 1.0).all()
+    r = ES.Replay(B, ES.base_body(ES.default_cfg(), B), stack=full)
+    assert r.full and (r.mu == ES.FRICTION_START).all() and (r.strength == 1.0).all() and r.limit.tobytes() == ES.limit_rows(B).tobytes()
+    assert not ES.Replay(B, ES.base_body(ES.default_cfg(), B)).full
+    # a clone keeps its limits apart from its source's: dst = src + 32 has another fraction
+    assert all(ES.LIMIT_FRACTIONS[b % 3] != ES.LIMIT_FRACTIONS[(b + 32) % 3] for b in range(32))
+
+
+class FullModelEnv(ModelEnv):
+    """ModelEnv over STACK_FULL.  The simulator is the friction model itself on the random terrain with measured contact, driven
+    without a controller by the streams of tests/contact_fixtures.py (forces that hold the robot up, drawn leg states and swing
+    targets); the motors stand in front of it; the draws of a reset are DomainRandomizer.on_reset's: friction, motors, then the
+    randomizer's own, which counts the draw.  mutate: one deliberate error (FULL_MUTATIONS)."""
+    episode_ticks = ES.EPISODE_TICKS_FULL
+
+    def __init__(self, mutate=None, seed=0, ticks=12):
+        from tests import contact_fixtures as CF
+        from tests import friction_model as FM
+        from tests import terrain_model as TM
+        super().__init__(mutate, seed, stack=ES.STACK_FULL)
+        m = self.m
+        self.plant = FM.FrictionSRBModel(B, m.cfg, TM.Random(m.terrain["amplitude"], m.terrain["cell"], m.terrain["seed"], m.keys))   # m.keys: the worlds, in place
+        self.sim_state = self.plant.state
+        self.s = CF.contact_streams(m.cfg, B, ticks, 5 + seed)
+        self.s["fall"][:] = False
+        self.tick_out = dict(delivered=np.zeros((B, 12), np.float32), tau_cmd=np.zeros((12, B)), tau=np.zeros((12, B)))
+
+    def _body_into_the_plant(self, body):
+        p = self.plant
+        p.mass, p.I, p.Iinv = body[0].copy(), body[1:10].copy(), body[10:19].copy()
+
+    def _draw(self, on):
+        from tests import friction_model as FM
+        from tests import motor_model as MM
+        m = self.m
+        seed = m.dr_cfg["seed"]
+        if self.mutate == "the friction draw after the count":
+            MM.draw(m.strength, on, m.dr_state[DM.ROW_KEY], m.dr_state[DM.ROW_DRAWS].copy(), seed, *m.motor_strength)
+            DM.reset(m.dr_cfg, on, m.dr_state, m.base, m.body, m.keys)
+            FM.draw(m.mu, on, m.dr_state[DM.ROW_KEY], m.dr_state[DM.ROW_DRAWS].copy(), seed, *m.friction)
+            return
+        swapped = self.mutate == "purposes 48 and 64 swapped"
+        was = FM.PURPOSE_MU, MM.PURPOSE_STRENGTH
+        try:
+            if swapped:
+                FM.PURPOSE_MU, MM.PURPOSE_STRENGTH = was[1], was[0]
+            FM.draw(m.mu, on, m.dr_state[DM.ROW_KEY], m.dr_state[DM.ROW_DRAWS].copy(), seed, *m.friction)
+            MM.draw(m.strength, on, m.dr_state[DM.ROW_KEY], m.dr_state[DM.ROW_DRAWS].copy(), seed, *m.motor_strength)
+        finally:
+            FM.PURPOSE_MU, MM.PURPOSE_STRENGTH = was
+        DM.reset(m.dr_cfg, on, m.dr_state, m.base, m.body, m.keys)
+        if self.mutate == "a limit changed by a reset":
+            m.limit[:, on] = 0.5 * m.limit[:, on]
+
+    def _stand(self, on):
+        idx = np.nonzero(on)[0]
+        if idx.size:
+            self.plant.reset(idx=idx, xy=self.rng.uniform(-2.0, 2.0, (idx.size, 2)), yaw=self.rng.uniform(-3.0, 3.0, idx.size))   # settles in the world just drawn
+
+    def _observe_sim(self):
+        return {n: v.copy() for n, v in self.plant.obs.items()}
+
+    def _advance(self):
+        from tests import motor_model as MM
+        from tests import terrain_fixtures as TF
+        m, p, k = self.m, self.plant, self.tick - 1
+        self.s["mass"] = m.body[0].copy()
+        planned = TF.stream_grf(p, m.cfg, self.s, k)
+        delivered, tau_cmd, tau, _ = MM.apply(m.chain, p.state[ES.M.ROW_Q:ES.M.ROW_Q + 12], planned, m.strength, m.limit)
+        body = m.body
+        if self.mutate == "the body taken after the reset":
+            # the body of the NEXT draw: what a tick reads when the randomizer's reset has run ahead of it.  (Taken after this
+            # step's own reset it would differ only for the robots the reset stands up anew, whose tick nobody can see.)
+            st, body, keys = m.dr_state.copy(), m.body.copy(), m.keys.copy()
+            DM.reset(m.dr_cfg, np.ones(B, dtype=bool), st, m.base, body, keys)
+        self._body_into_the_plant(body)
+        p.mu[:] = m.mu
+        ft, ls = self.s["foot_target"][k].copy(), self.s["leg_state"][k].copy()
+        p.step_friction(planned if self.mutate == "the planned force handed to the plant" else delivered, ft, ls, 1, self.ext)
+        self.tick_out = dict(grf=planned, foot_target=ft, leg_state=ls, delivered=delivered, tau_cmd=tau_cmd, tau=tau)
+        self.touch, self.slip = p.touch.copy(), p.slip.copy()
+
+    def step(self, action):
+        rec = super().step(action)
+        rec.update({k: self.tick_out[k] for k in ("grf", "foot_target", "leg_state", "delivered")})
+        return rec
+
+    def got(self):
+        m, out = self.m, self.tick_out
+        return dict(super().got(), mu=m.mu.copy(), strength=m.strength.copy(), torque_limit=m.limit.copy(), delivered=out["delivered"], tau_cmd=out["tau_cmd"],
+                    tau=out["tau"], sim_state=self.sim_state.copy(), sim_obs=self._observe_sim(), touch=getattr(self, "touch", None), slip=getattr(self, "slip", None))
+
+
+# mutation: (the units Replay must name on the first call it reports anything, a word every report of that call holds)
+FULL_MUTATIONS = {None: None,
+                  "the friction draw after the count": ({"floor"}, "mu"),
+                  "purposes 48 and 64 swapped": ({"floor", "motors"}, ""),
+                  "the planned force handed to the plant": ({"plant"}, "plant: "),
+                  "the body taken after the reset": ({"plant"}, "plant: "),
+                  "a limit changed by a reset": ({"motors"}, "torque_limit")}
+
+
+@pytest.mark.parametrize("mutate", list(FULL_MUTATIONS), ids=lambda m: str(m).replace(" ", "_"))
+def test_replay_names_floor_motors_or_plant_for_each_error_and_reports_nothing_without_one(mutate):
+    T = 12                                                                                 # the resets of the time limit fall on tick 10
+    env = FullModelEnv(mutate, ticks=T)
+    replay = ES.Replay(B, ES.base_body(ES.default_cfg(), B), stack=ES.STACK_FULL)
+    env.reset()
+    reports = [(0, f) for f in replay.mismatches(replay.host_reset(None, env.sim_state, env.true), env.got())]
+    rng = np.random.default_rng(1)
+    resets = 0
+    for t in range(T):
+        rec = env.step(rng.uniform(-0.3, 0.4, (B, 2)).astype(np.float32))
+        resets += int(rec["reset_mask"].sum())
+        found = replay.mismatches(replay.step(rec), env.got())
+        if found and not reports:
+            reports = [(t + 1, f) for f in found]
+    print(mutate, reports, replay.count)
+    c = replay.count
+    assert resets == B and c["resets"] == B and c["compared"] == T * B - B                 # only the robots of a reset were left out
+    if mutate is None:
+        assert reports == [] and (replay.draws() == 2).all() and c["force_legs"] > 0 and c["solved"] == c["force_legs"]
+        assert 0 < c["pushed"] < T * B and c["clipped"] > 0
+        return
+    units, word = FULL_MUTATIONS[mutate]
+    assert reports and {f.split(":")[0] for _, f in reports} == units, reports
+    assert all(word in f for _, f in reports), reports
+    if mutate == "purposes 48 and 64 swapped":
+        assert sorted(f.split(":")[1].split()[0] for _, f in reports) == ["mu", "strength"], reports
+    if mutate in ("the friction draw after the count", "purposes 48 and 64 swapped"):
+        assert reports[0][0] == 0                                                          # at reset() already: its draw is a draw like any other
+    elif mutate == "a limit changed by a reset":
+        assert reports[0][0] == 0 and len(reports) == 1
+    else:
+        assert reports[0][0] == 1 and any("sim_state.state" in f for _, f in reports)      # on the first tick, the integrated rows among it
+
+
+# ---- the CPU loop the ranges and the limit fractions are chosen on ------------------------------------------------------------
+
+def test_the_settings_of_the_full_stack_slide_clip_and_keep_everybody_up_on_the_cpu_loop():
+    """friction_fixtures.FrictionCpuLoop with motor_model.MotorSRBModel in front, the 32 srb_fixtures.cases on the reference's
+    random terrain with measured contact, 100 ticks, under the ranges and limits of STACK_FULL: legs slide, legs clip, nobody
+    falls, and under 1 % of the stance legs lie so near a limit that the device may take the other branch (the share the GPU
+    test leaves out of its comparison).  The figures are the ones env_stack.full_cpu_loop's docstring records."""
+    loop = ES.full_cpu_loop()
+    got = dict(loop.count, fallen=int(loop.model.fallen().sum()))
+    print("full CPU loop:", got, "robots that slid", int((loop.slid.sum(0) > 0).sum()))
+    assert got["sliding"] > 0 and got["clipped"] > 0 and got["fallen"] == 0
+    assert got["near_limit"] < 0.01 * got["force_legs"]
+    assert got == ES.FULL_LOOP_MEASURED["ghost"]
+    assert all(str(v) in ES.full_cpu_loop.__doc__ for v in got.values())

@@ -2,7 +2,11 @@
 scan, a DomainRandomizer, a SensorModel and a StateEstimator under ONE seed -- held tick by tick to the four numpy models through
 env_stack.Replay: the whole stack under auto-reset, the sensor model's transparency to the plant, the three defaults together as
 the identity, a partial host reset, a device reset by hand with plans that fail and the frozen ticks after it, and a clone.
-Everything bit for bit but the estimator's quat, rpy, foot_pos and jac (one float32 ulp, the rule of tests/test_est_gpu.py)."""
+Everything bit for bit but the estimator's quat, rpy, foot_pos and jac (one float32 ulp, the rule of tests/test_est_gpu.py).
+
+Then the same with a floor and motors on (tests/env_stack.py: STACK_FULL -- friction, a MotorModel with torque limits, a randomizer
+that draws mu and the strengths): the full stack replayed with the plant itself held to the friction model on every tick, the
+defaults of all five together as the identity, a partial host reset, and a clone."""
 import time
 
 import numpy as np
@@ -44,11 +48,12 @@ def _bits(t):
     return (t.view(torch.int32) if t.element_size() == 4 else t.view(torch.int64)).cpu()
 
 
-def _replay(env):
+def _replay(env, stack=ES.STACK):
     """A Replay of a freshly built env (before its first reset: the body on the device is the base)."""
     t = env.sim.terrain
     assert env.sensor_model.bound_groups == [(0, ES.PATH_ROWS, ES.SENSOR["path"]), (ES.PATH_ROWS, ES.PATH_ROWS + ES.SCAN_ROWS, ES.SENSOR["scan"])]
-    return ES.Replay(env.batch, _np(env.randomizer.body()), cfg=env.cfg, terrain=dict(amplitude=t.amplitude, cell=t.cell, seed=t.seed), substeps=env.sim.substeps)
+    return ES.Replay(env.batch, _np(env.randomizer.body()), cfg=env.cfg, stack=stack, terrain=dict(amplitude=t.amplitude, cell=t.cell, seed=t.seed),
+                     substeps=env.sim.substeps)
 
 
 def _before(env, action):
@@ -320,4 +325,183 @@ def test_a_clone_under_the_whole_stack_continues_as_its_source():
             assert torch.equal(_bits(v[..., src]), _bits(v[..., dst])), (t, n)
         pushed += int((dr.ext[:, dst] != 0).any(0).sum())
     assert int(env.episode_count[dst].min()) >= 6 and pushed > 0 and len(torch.unique(keys[src])) == 16
+    env.close()
+
+
+# ================================================================================================================================
+# STACK_FULL: the same stack with a floor that has friction and motors between the controller and the body (tests/env_stack.py)
+# ================================================================================================================================
+
+def _stack_full(batch, **env_kw):
+    """The env of ES.STACK_FULL: STACK's plus friction=, a MotorModel with the limits of ES.limit_rows, and a randomizer that draws mu
+    and the strengths; env_kw over STACK_FULL's."""
+    from robot_gym_amd.gym.batched_go_env import BatchedGoEnv
+    from robot_gym_amd.sim import DomainRandomizer, MotorModel, RandomTerrain, SensorModel, StateEstimator
+    from robot_gym_amd.sim.height_scan import HeightScan
+    full = ES.STACK_FULL
+    motors = MotorModel(strength=full["motors"]["strength"], torque_limit=torch.as_tensor(ES.limit_rows(batch)))
+    return BatchedGoEnv(batch, device=DEV, terrain=RandomTerrain(**full["terrain"]), height_scan=HeightScan(**full["height_scan"]),
+                        randomizer=DomainRandomizer(**full["randomizer"]), sensor_model=SensorModel(**full["sensor_model"]),
+                        state_estimator=StateEstimator(**_grouped(full["state_estimator"])), motor_model=motors, **{**full["env"], **env_kw})
+
+
+def _after_full(env, auto_reset=True):
+    """_after plus the controller's outputs of the tick and the force the motors delivered."""
+    out = env.ctl.extra
+    return dict(_after(env, auto_reset), grf=_np(out["grf"]), foot_target=_np(out["foot_target"]), leg_state=_np(out["leg_state"]),
+                delivered=_np(env.sim.motors.grf))
+
+
+def _got_full(env):
+    sim, mot = env.sim, env.sim.motors
+    return dict(_got(env), mu=_np(sim.mu), strength=_np(mot.strength), torque_limit=_np(mot.torque_limit), delivered=_np(mot.grf), tau_cmd=_np(mot.tau_cmd),
+                tau=_np(mot.tau), sim_state=_np(sim.state), sim_obs={n: _np(sim.obs[n]) for n in srb_abi.OBS_FIELDS}, touch=_np(sim.touch), slip=_np(sim.slip))
+
+
+def _full_tensors(env):
+    """_model_tensors plus the floor's and the motors' rows."""
+    sim, mot = env.sim, env.sim.motors
+    return dict(_model_tensors(env), mu=sim.mu, slip=sim.slip, strength=mot.strength, torque_limit=mot.torque_limit)
+
+
+# ---- a. the full stack replayed ----------------------------------------------------------------------------------------------
+
+def test_the_full_stack_is_its_seven_units_on_every_tick():
+    """B = 67 (four waves and three robots), reset(), then 60 ticks with resets on the device on ticks 10, 20, ...: after every call
+    the four units of STACK and mu, the strengths and the limits (bit for bit), the delivered force and the two torque tables (the
+    rule of test_kernel_against_the_motor_model, on the recorded angles and the controller's recorded grf) and the simulator's
+    state, observation, touch and slip (the friction model over the random terrain with measured contact, stepped once from the
+    recorded state on the body, mu and world held before the step's reset, the model's push and the DEVICE's delivered force) are
+    what env_stack.Replay makes of the record.  Only the robots of a step's reset_mask are left out of the plant's comparison.
+    resets >= 5 B follows from the time limit of 10 ticks; the other counts are asserted non-zero only, nobody having measured
+    them before this run (figures: LAB_NOTES.md, "Composed env").  The share of stance legs left out of the motors' comparison
+    for lying near a limit is at most 1 %."""
+    t0 = time.perf_counter()
+    T, batch = 60, 67
+    env = _stack_full(batch)
+    replay = _replay(env, ES.STACK_FULL)
+    assert replay.full and _np(env.sim.motors.torque_limit).tobytes() == replay.limit.tobytes()
+    env.reset()
+    assert replay.mismatches(replay.host_reset(None, _np(env.sim.state), _np(env.true_obs.t())), _got_full(env)) == []
+    assert bool((_draw_rows(env) == 1).all())
+    assert bool((env.sim.mu != ES.FRICTION_START).all()) and bool((env.sim.motors.strength != 1.0).all())       # the first draw is in
+    actions = _actions(T, batch)
+    for t in range(T):
+        rec = _before(env, actions[t])
+        env.step(actions[t])
+        rec.update(_after_full(env))
+        assert replay.mismatches(replay.step(rec), _got_full(env)) == [], t
+        assert bool((_draw_rows(env) == (1 + env.episode_count)[None, :]).all()), t
+    c = replay.count
+    share = c["near_limit"] / max(c["force_legs"], 1)
+    print("full stack replay: ulp", {n: round(v, 3) for n, v in replay.worst.items()}, "plant", replay.cmp.worst, "tick", replay.worst_tick, "counts", c,
+          "of", T * batch, "robot-ticks; near-limit share", share, "seconds", round(time.perf_counter() - t0, 2))
+    assert c["resets"] >= 5 * batch
+    assert c["compared"] == T * batch - c["resets"]                                         # nothing else was skipped
+    assert c["sliding"] > 0 and c["clipped"] > 0
+    assert 0 < c["pushed"] < T * batch
+    assert c["force_legs"] > 0 and c["solved"] == c["force_legs"]                          # strength != 1: every leg with a force took the solve
+    assert share <= 0.01
+    assert set(replay.worst) == set(ES.ROUNDED)
+    env.close()
+
+
+# ---- b. the defaults ---------------------------------------------------------------------------------------------------------
+
+def test_the_defaults_of_floor_motors_and_models_together_change_nothing():
+    """friction="inf" (the friction tick with every robot gripping), MotorModel() and the three default models against the bare env,
+    both with terrain, measured contact, the scan and the time limit on: bit-identical over 40 ticks under auto-reset."""
+    from robot_gym_amd.gym.batched_go_env import BatchedGoEnv
+    from robot_gym_amd.sim import DomainRandomizer, MotorModel, RandomTerrain, SensorModel, StateEstimator
+    from robot_gym_amd.sim.height_scan import HeightScan
+    T = 40
+    kw0 = {k: v for k, v in ES.STACK_FULL["env"].items() if k != "friction"}              # measured contact, auto-reset, ten ticks an episode
+    make = lambda **kw: BatchedGoEnv(B, device=DEV, terrain=RandomTerrain(), height_scan=HeightScan(), **kw0, **kw)   # noqa: E731
+    plain = make()
+    env = make(friction="inf", motor_model=MotorModel(), randomizer=DomainRandomizer(), sensor_model=SensorModel(), state_estimator=StateEstimator())
+    assert plain.sim.mu is None and plain.sim.motors is None and env.sim.mu is not None and env.sim.motors is not None
+    assert torch.equal(_bits(plain.reset()), _bits(env.reset())) and torch.equal(_bits(plain.sim.state), _bits(env.sim.state))
+    actions = _actions(T)
+    for t in range(T):
+        p, e = plain.step(actions[t]), env.step(actions[t])
+        for x, y in zip(p, e):                                                             # obs, reward, done
+            assert torch.equal(_bits(x), _bits(y)), t
+        assert torch.equal(_bits(plain.sim.state), _bits(env.sim.state)) and torch.equal(plain.sim.touch, env.sim.touch), t
+        assert torch.equal(plain.reset_mask, env.reset_mask) and torch.equal(_bits(plain.final_obs), _bits(env.final_obs)), t
+        assert torch.equal(_bits(env.sim.motors.grf), _bits(env.ctl.extra["grf"])) and bool((env.sim.slip == 0).all()), t
+    assert int(env.episode_count.sum()) >= (T // ES.EPISODE_TICKS_FULL) * B
+    plain.close()
+    env.close()
+
+
+# ---- c. a partial host reset -------------------------------------------------------------------------------------------------
+
+def test_a_partial_host_reset_draws_floor_and_motors_for_its_robots_at_their_own_draw_counts():
+    """Two partial resets, of every second robot and then of every third: a robot of both draws at draw count 2 while its neighbours
+    draw at 1.  The robots of a reset hold the model's mu and strengths; for the others every byte of mu, slip, strength and
+    torque_limit (and of the three models) stays; torque_limit stays for everybody."""
+    env = _stack_full(B, auto_reset=False)
+    replay = _replay(env, ES.STACK_FULL)
+    env.reset()
+    assert replay.mismatches(replay.host_reset(None, _np(env.sim.state), _np(env.true_obs.t())), _got_full(env)) == []
+    limit0 = env.sim.motors.torque_limit.clone()
+    actions = _actions(6)
+    t = 0
+    for every in (2, 3):
+        for _ in range(3):
+            rec = _before(env, actions[t])
+            env.step(actions[t])
+            rec.update(_after_full(env, auto_reset=False))
+            assert replay.mismatches(replay.step(rec), _got_full(env)) == [], t
+            t += 1
+        idx = np.arange(0, B, every)
+        inside = torch.zeros(B, dtype=torch.bool, device=DEV)
+        inside[torch.as_tensor(idx, device=DEV)] = True
+        before, draws0 = _snapshot(_full_tensors(env)), _draw_rows(env)
+        env.reset(idx, targets=[ES.OK_TARGETS[k % len(ES.OK_TARGETS)] for k in range(len(idx))])
+        assert replay.mismatches(replay.host_reset(idx, _np(env.sim.state), _np(env.true_obs.t())), _got_full(env)) == []
+        assert torch.equal(_draw_rows(env), draws0 + inside.to(torch.int64)[None, :])
+        after = _full_tensors(env)
+        _unchanged(before, after, ~inside, f"outside every {every}")
+        assert bool((after["mu"][inside] != before["mu"][inside]).all()) and bool((after["strength"][:, inside] != before["strength"][:, inside]).all())
+        assert torch.equal(_bits(env.sim.motors.torque_limit), _bits(limit0))
+    assert set(_draw_rows(env)[0].tolist()) == {1, 2, 3}                                   # reset(): 1; one partial reset: 2; both: 3
+    env.close()
+
+
+# ---- d. a clone under the full stack -----------------------------------------------------------------------------------------
+
+def test_a_clone_under_the_full_stack_takes_floor_and_motors_along():
+    """dst = src + 32 (dst = src modulo 16), taken on tick 3 of an episode: mu, slip, strength, torque_limit, tau and the delivered
+    grf go with the robot; for 30 ticks, across the resets on ticks 10, 20, 30, the clone's state, touch, slip and delivered force are
+    its source's bit for bit, and at every reset the clone draws the mu and the strengths its source draws."""
+    env = _stack_full(B)
+    env.reset()
+    actions = _actions(33, B, seed=2)
+    for t in range(3):
+        env.step(actions[t])
+    src = np.arange(32)
+    dst = src + 32
+    sim, mot = env.sim, env.sim.motors
+    rows = lambda: dict(mu=sim.mu, slip=sim.slip, strength=mot.strength, torque_limit=mot.torque_limit, tau=mot.tau, tau_cmd=mot.tau_cmd, grf=mot.grf.t())   # noqa: E731
+    for n in ("mu", "strength", "torque_limit", "tau", "grf"):
+        assert not torch.equal(rows()[n][..., src], rows()[n][..., dst]), n                # they differ before
+    env.clone(src, dst)
+    for n, v in rows().items():
+        assert torch.equal(_bits(v[..., src]), _bits(v[..., dst])), n
+    assert _np(mot.torque_limit)[:, :32].tobytes() == np.ascontiguousarray(ES.limit_rows(B)[:, :32]).tobytes()
+    mu0, strength0 = sim.mu.clone(), mot.strength.clone()
+    slid = clipped = 0
+    for t in range(3, 33):
+        a = actions[t].clone()
+        a[dst] = a[src]
+        env.step(a)
+        pairs = dict(rows(), sim_state=sim.state, touch=sim.touch, reset_mask=env.reset_mask, obs=env.obs.t())
+        for n, v in pairs.items():
+            assert torch.equal(_bits(v[..., src]), _bits(v[..., dst])), (t, n)
+        slid += int((sim.slip[:, dst] > 0).sum())
+        clipped += int((mot.tau[:, dst] != mot.tau_cmd[:, dst] * mot.strength[:, dst]).sum())
+    assert int(env.episode_count[dst].min()) >= 3
+    assert bool((sim.mu != mu0).all()) and bool((mot.strength != strength0).all())         # drawn again since, the same for both
+    assert len(torch.unique(sim.mu[src])) == 32 and slid > 0 and clipped > 0
     env.close()

@@ -3,7 +3,9 @@ tests/motor_model.py at batches around a wave and a workgroup for both robots, w
 its tau_cmd against the controller's own tau_stance in the closed loop; the default model bit-identical to no model in three
 simulator configurations and in the go-to env; the closed loop under the torque limit of the CPU reference loop inside that
 loop's band (tests/motor_fixtures.py); a clone; rg_srb_motor_draw against the model bit for bit, and the randomiser's draws under
-auto_reset replayed into the model.
+auto_reset replayed into the model; non-identity motors in front of each of the four ticks BatchedSRBSim.step dispatches to, the
+delivered force and the tick both held to their models; the kernel's singular branch on a configuration with a foot on its knee
+axis; and the settings only the C ABI accepts (strength 0 and +inf, limit 0, NaN and negative, -0.0 and denormal forces).
 
 Every model run is made before the GPU is opened (`dev` depends on `cases`)."""
 import numpy as np
@@ -371,3 +373,156 @@ def test_the_randomiser_draws_the_models_strengths_at_every_reset(dev):
     with pytest.raises(ValueError, match="needs a simulator built with a motor model"):
         DomainRandomizer(motor_strength=(lo, hi)).bind(plain)
     plain.close()
+
+
+# ---- 4. non-identity motors in front of every tick ---------------------------------------------------------------------------
+
+def _tick_sim_kw(name):
+    from robot_gym_amd.sim.terrain import RandomTerrain
+    terrain = lambda: RandomTerrain(CF.AMPLITUDE, CF.CELL, CF.SEED)
+    return dict(plane_schedule=lambda: dict(), terrain_schedule=lambda: dict(terrain=terrain()),
+                terrain_measured=lambda: dict(terrain=terrain(), contact="measured"),
+                terrain_friction=lambda: dict(terrain=terrain(), contact="measured", friction=MF.TICK_MU))[name]()
+
+
+def _tick_run(name, robot, dev, rows, model=False):
+    """MF.TICK_T closed-loop ticks of MF.TICK_B robots in configuration `name`.  rows: (strength, limit) or None (motors=None).
+    model: hold every tick to the numpy models, resynchronised at the start of the tick: motors.grf to motor_model.apply on the
+    controller's grf and the angles before the tick, the tick to the configuration's model stepped on motors.grf.
+    -> (the snapshots after every tick, figures of the run)."""
+    from robot_gym_amd.sim import MotorModel
+    from tests import terrain_model as TM
+    B = MF.TICK_B
+    cmd, hs = F.tiled_cases(robot, B)
+    motors = None if rows is None else MotorModel(strength=rows[0], torque_limit=torch.as_tensor(rows[1]))
+    cfg, ctl, sim = _pair(robot, B, dev, motors=motors, **_tick_sim_kw(name))
+    _start(ctl, sim, cmd, hs)
+    host = lambda t: t.cpu().numpy()
+    if model:
+        t = sim.terrain
+        ground = None if t is None else TM.Random(t.amplitude, t.cell, t.seed, host(t.keys))
+        m, step = MF.tick_model(name, cfg, B, ground)
+        chain, cmp = M.Chain(cfg), S.Comparison()
+    fig = dict(worst_grf=0.0, worst_tau=0.0, worst_slip=0.0, changed=0, clipped=0, slid=0, touched=0)
+    snaps = []
+    for k in range(MF.TICK_T):
+        state0, obs0 = host(sim.state), {n: host(v) for n, v in sim.obs.items()}
+        ctl.get_action(0.0, sim.obs)
+        sim.step(ctl)
+        snaps.append(_snap(sim))
+        if not model:
+            continue
+        out = {n: host(ctl.extra[n]) for n in ("grf", "foot_target", "desired_state", "leg_state")}
+        mot = sim.motors
+        planned, delivered = out["grf"], host(mot.grf)
+        want = MM.apply(chain, state0[M.ROW_Q:M.ROW_Q + 12], planned, rows[0], rows[1])
+        bad, worst, worst_tau = MF.delivered_mismatches(planned, want, (delivered, host(mot.tau_cmd), host(mot.tau)))
+        assert bad == [], (name, k, bad)
+        fig["worst_grf"], fig["worst_tau"] = max(fig["worst_grf"], worst), max(fig["worst_tau"], worst_tau)
+        changed = (delivered.view(np.int32) != planned.view(np.int32)).reshape(B, 4, 3).any(2)
+        assert changed.any(), (name, k)                          # delivered != planned on some leg of every tick
+        fig["changed"] += int(changed.sum())
+        fig["clipped"] += int((np.abs(want[2]) == rows[1]).sum())
+        # the tick, from the simulator's state and observation before it, on the DELIVERED force
+        m.state[:] = state0
+        for n in m.obs:
+            m.obs[n][...] = obs0[n]
+        step(m, delivered, out)
+        cmp.check(host(sim.state), {n: host(v) for n, v in sim.obs.items()}, m.state, m.obs)
+        assert cmp.clean(), (name, k, cmp.bad, cmp.worst)
+        if hasattr(m, "touch"):
+            assert (host(sim.touch) == m.touch).all(), (name, k)
+            fig["touched"] += int(m.touch.sum())
+        else:
+            assert not bool(sim.touch.any()), (name, k)
+        if hasattr(m, "slip"):
+            got, w = host(sim.slip), m.slip
+            rel = np.abs(got - w) / np.maximum(1.0, np.abs(w))
+            fig["worst_slip"] = max(fig["worst_slip"], float(rel.max()))
+            assert (rel <= S.REL_TOL).all(), (name, k, fig["worst_slip"])
+            fig["slid"] += int((w > 0).sum())
+        else:
+            assert sim.slip is None
+    if model:
+        fig.update(cmp.worst)
+    fig["fallen"] = int(sim.fallen().sum())
+    ctl.close()
+    sim.close()
+    return snaps, fig
+
+
+@pytest.mark.parametrize("name", MF.TICK_CONFIGS)
+def test_non_identity_motors_stand_in_front_of_every_tick(name, dev):
+    """Each of the four ticks BatchedSRBSim.step dispatches to, with every motor at its own strength and mixed limits: the force
+    the tick integrates is the DELIVERED one (a tick handed the planned force fails the state comparison on its first tick), the
+    delivered force is the model's, and it differs from the planned one on every tick.  Then even robots at strength 1 without a
+    limit in the same batch walk bit for bit as in a run without motors."""
+    robot = "ghost"
+    _, fig = _tick_run(name, robot, dev, MF.tick_motors(robot, MF.TICK_B), model=True)
+    print(name, fig)
+    assert fig["changed"] > 0 and fig["clipped"] > 0 and fig["fallen"] == 0
+    assert name != "terrain_friction" or fig["slid"] > 0
+    mixed, _ = _tick_run(name, robot, dev, MF.tick_motors(robot, MF.TICK_B, identity_even=True))
+    free, _ = _tick_run(name, robot, dev, None)
+    cols = lambda snap, sl: [t[..., sl] for t in snap]
+    for k, (a, b) in enumerate(zip(mixed, free)):
+        assert _same(cols(a, slice(0, None, 2)), cols(b, slice(0, None, 2))), (name, k)
+    assert not _same(cols(mixed[-1], slice(1, None, 2)), cols(free[-1], slice(1, None, 2)))
+
+
+# ---- 5. the kernel's singular branch and the settings only the C ABI accepts ------------------------------------------------
+
+@pytest.fixture(scope="module")
+def edge_cases(cases):
+    return dict(singular={robot: MF.singular_case(robot) for robot in F.ROBOTS}, abi=MF.abi_cases())
+
+
+def _run_case(c, dev):
+    """rg_srb_motor_apply on a case's raw tensors, guarded -> (grf_out, tau_cmd, tau_out) as numpy."""
+    B = c["B"]
+    handle = srb_abi.SrbHandle(c["cfg"], B, dev)
+    guard = Guarded(dev)
+    state = np.zeros((M.STATE_ROWS, B))
+    state[M.ROW_Q:M.ROW_Q + 12] = c["q"]
+    st, grf, strength, limit = guard(state), guard(c["grf"]), guard(c["strength"]), guard(c["limit"])
+    out, tau_cmd, tau = guard(np.full((B, 12), -5.0, np.float32)), guard(np.full((12, B), -5.0)), guard(np.full((12, B), -5.0))
+    motor_abi.motor_apply(handle, st, grf, strength, limit, out, tau_cmd, tau)
+    got = out.cpu().numpy(), tau_cmd.cpu().numpy(), tau.cpu().numpy()
+    assert guard.intact()
+    handle.close()
+    return got
+
+
+@pytest.mark.parametrize("robot", F.ROBOTS)
+def test_a_leg_with_its_foot_on_the_knee_axis_takes_the_uniform_scale_on_the_device(robot, edge_cases, dev):
+    """The `!solve3(...)` branch of the kernel: leg 0's floats are (float)(k * g), bit for bit with the model, which takes its fmin
+    chain in the kernel's order; the other three legs take the solve and are held as in the regular test."""
+    c = edge_cases["singular"][robot]
+    got, got_cmd, got_tau = _run_case(c, dev)
+    assert got[:, :3].tobytes() == c["out"][:, :3].tobytes()
+    assert (got[:, :3] != c["grf"][:, :3]).all() and np.isfinite(got).all()
+    assert (got_cmd[2] == 0.0).all() and (got_tau[2] == 0.0).all()                          # the knee moves nothing
+    bad, worst, worst_tau = MF.delivered_mismatches(c["grf"], (c["out"], c["tau_cmd"], c["tau"], c["sat"]), (got, got_cmd, got_tau))
+    print(robot, "singular leg: largest |grf_out - model|", worst, "largest torque deviation", worst_tau)
+    assert bad == []
+
+
+@pytest.mark.parametrize("name", ["strength_zero", "limit_zero", "limit_nan", "limit_negative", "strength_inf_on_a_swinging_leg",
+                                  "negative_zero_and_denormal_force", "all_zero_force"])
+def test_settings_only_the_c_abi_accepts_are_the_models(name, edge_cases, dev):
+    """What MotorModel refuses and rg_srb_motor_apply takes, each held to the model (what the case is about is asserted on the
+    model in motor_fixtures.abi_cases, and stated in rg_srb_motor.h): a NaN where the model has one and nowhere else, the floats
+    of `exact` by bits, the rest within one ulp, the torques within the tolerance."""
+    c = edge_cases["abi"][name]
+    got, got_cmd, got_tau = _run_case(c, dev)
+    want = c["out"]
+    assert (np.isnan(got) == np.isnan(want)).all(), np.argwhere(np.isnan(got) != np.isnan(want))[:5]
+    exact = c["exact"]
+    assert got[exact].tobytes() == want[exact].tobytes(), np.argwhere((got.view(np.int32) != want.view(np.int32)) & exact)[:5]
+    rest = ~exact & ~np.isnan(want)
+    assert within_ulp(got[rest], want[rest].astype(np.float64)).all()
+    for g, w in ((got_cmd, c["tau_cmd"]), (got_tau, c["tau"])):
+        assert (np.isnan(g) == np.isnan(w)).all()
+        ok = ~np.isnan(w)
+        assert (np.abs(g[ok] - w[ok]) <= REL_TOL * np.maximum(1.0, np.abs(w[ok]))).all(), float(np.abs(g[ok] - w[ok]).max())
+    assert exact.any() or np.isnan(want).any() or name == "limit_zero"
