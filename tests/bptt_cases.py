@@ -48,6 +48,17 @@ CONFIGS = {      # "default", "lopsided", "limits" and the two-dense configurati
     "two dense": dict(obs_dim=5, act_dim=2, policy_layers=(7, 4), gru_units=3, value_layers=(6,)),
     "limits": dict(obs_dim=64, act_dim=4, policy_layers=(256, 256), gru_units=128, value_layers=(256, 256, 256)),
 }
+# The configurations of tests/rnn_edges.py.  net() and case() seed a configuration of CONFIGS from its place in sorted(CONFIGS), so
+# a new key there would redraw every case above: these have their own table and explicit seeds (EDGE_SEEDS: net, case).
+EDGE_CONFIGS = {
+    "wave63": dict(obs_dim=16, act_dim=2, policy_layers=(65,), gru_units=63, value_layers=(65,)),       # 2H = 126
+    "wave64": dict(obs_dim=15, act_dim=1, policy_layers=(64,), gru_units=64, value_layers=(65,)),       # 2H = 128; 15 inputs: the bias closes the row tile
+    "wave65": dict(obs_dim=1, act_dim=4, policy_layers=(63, 65), gru_units=65, value_layers=(65,)),     # 2H = 130: three waves; two dense layers
+    "unit1": dict(obs_dim=16, act_dim=2, policy_layers=(65,), gru_units=1, value_layers=(65,)),         # H = 1
+    "rows15": dict(obs_dim=15, act_dim=3, policy_layers=(31,), gru_units=16, value_layers=(65,)),       # blocks of 15, 47, 47 and 16 input rows
+}
+EDGE_SEEDS = {"wave63": (4101, 5101), "wave64": (4102, 5102), "wave65": (4103, 5103), "unit1": (4104, 5104), "rows15": (4105, 5105)}
+assert not set(EDGE_CONFIGS) & set(CONFIGS) and set(EDGE_SEEDS) == set(EDGE_CONFIGS)
 # one robot; below a tile; one robot past a tile; five tiles with a ragged one; 519 chunks: every group of the W phase folds
 # more than one chunk and the last chunk is short
 SHAPES = [(1, 1), (3, 5), (2, 9), (5, 37), (8, 1037)]
@@ -62,8 +73,8 @@ MODEL_KW = dict(penalty=0.7, kl_target=1e-2, kl_cutoff_factor=2.0, kl_cutoff_coe
 def net(name):
     """(cfg, layout, policy_params, value_params, norm_state, centre, spread) of a configuration: weights within the Glorot
     limit, non-zero biases, a distinct logstd per component, a normaliser state with non-trivial statistics."""
-    cfg = CONFIGS[name]
-    rng = np.random.default_rng(1900 + sorted(CONFIGS).index(name))
+    cfg = CONFIGS[name] if name in CONFIGS else EDGE_CONFIGS[name]
+    rng = np.random.default_rng(1900 + sorted(CONFIGS).index(name) if name in CONFIGS else EDGE_SEEDS[name][0])
     lay = RM.layout(cfg["obs_dim"], cfg["act_dim"], cfg["policy_layers"], cfg["gru_units"], cfg["value_layers"])
     pp = np.zeros(lay["policy_count"], dtype=np.float32)
     for i, o, w, b in RM.blocks(lay):
@@ -104,17 +115,34 @@ def resets(T, B, rng):
     return reset
 
 
+def saturate(pp, lay, gates):
+    """A copy of the policy buffer with the gates' biases moved to where float32 saturates: "hold": the u half of b_ru at +100
+    (u == 1.0f, the cell holds its state); "shut": all of b_ru at -100 (expf overflows: r == u == 0.0f, h' = c); None: pp itself."""
+    if gates is None:
+        return pp
+    H, b = lay["gru_units"], lay["w_ru"][3]
+    out = np.array(pp)
+    if gates == "hold":
+        out[b + H:b + 2 * H] = 100.0
+    else:
+        assert gates == "shut"
+        out[b:b + 2 * H] = -100.0
+    return out
+
+
 @functools.lru_cache(maxsize=None)
-def case(name, T, B, mask_kind="some", cutoff=True):
+def case(name, T, B, mask_kind="some", cutoff=True, gates=None):
     """The rollout of (configuration, T, B) and the model's answers, once: inputs as float32 / int32 arrays, the float64 model,
     the float32 model's deviations and the bounds.  Every third robot lies off the behaviour policy by OFF_POLICY
     standard deviations (its KL is above the cutoff), the others by a hundredth.  mask "some": zeros in the mask and, where
-    B > 1, the last robot masked throughout; "none": an all-zero mask.  cutoff=False: kl_cutoff_coef = 0 (c["ppo_kw"], c["model_kw"]
-    are the settings of the case)."""
+    B > 1, the last robot masked throughout; "last": the first robot masked throughout and the last one valid at every tick (the
+    last robot of a batch is the one a tile's slots past the batch mirror); "none": an all-zero mask.  cutoff=False: kl_cutoff_coef = 0 (c["ppo_kw"], c["model_kw"]
+    are the settings of the case).  gates: saturate() applied to the configuration's parameters before anything is drawn from them."""
     MODEL_KW = dict(globals()["MODEL_KW"], kl_cutoff_coef=1000.0 if cutoff else 0.0)
     cfg, lay, pp, vp, state, centre, spread = net(name)
+    pp = saturate(pp, lay, gates)
     d, A, H = cfg["obs_dim"], cfg["act_dim"], cfg["gru_units"]
-    rng = np.random.default_rng(2000 * T + B + 7 * sorted(CONFIGS).index(name))
+    rng = np.random.default_rng(2000 * T + B + (7 * sorted(CONFIGS).index(name) if name in CONFIGS else EDGE_SEEDS[name][1]))
     obs = (centre[None, :, None] + spread[None, :, None] * rng.normal(size=(T, d, B)) * 2.5).astype(np.float32)
     margins, redrawn = None, np.zeros(T * B, dtype=bool)
     for _ in range(50):                                   # keep every dense pre-activation away from 0 (module docstring)
@@ -140,6 +168,8 @@ def case(name, T, B, mask_kind="some", cutoff=True):
     logstd0 = (logstd + rng.normal(0.0, 0.01, A)).astype(np.float32)
     off = 0.01 * rng.normal(size=(T, B, A))
     off[:, ::3] += OFF_POLICY * np.exp(logstd)
+    if mask_kind == "last" and (B - 1) % 3 != 0:          # the last robot above the cutoff too: it carries a large part of every tensor
+        off[:, B - 1] += OFF_POLICY * np.exp(logstd)
     mean0 = (mu + off).astype(np.float32)
     action = (mean0 + np.exp(logstd0) * rng.normal(size=(T, B, A))).astype(np.float32)
     adv = rng.normal(0.5, 2.0, size=(T, B)).astype(np.float32)
@@ -151,6 +181,8 @@ def case(name, T, B, mask_kind="some", cutoff=True):
         mask[0, 0] = 1
         if B > 1:
             mask[:, B - 1] = 0
+        if mask_kind == "last" and B > 1:                 # the first robot masked throughout instead, the last one valid at every tick
+            mask[:, 0], mask[:, B - 1] = 0, 1
     c = dict(name=name, T=T, B=B, cfg=cfg, lay=lay, pp=pp, vp=vp, state=state, obs=obs, action=action, mean=mean0, logstd=logstd0, adv=adv, ret=ret,
              mask=mask, reset=reset, h0=h0, x=x, redrawn=float(redrawn.mean()), model_kw=MODEL_KW,
              ppo_kw=dict(PPO_KW, kl_cutoff_coef=MODEL_KW["kl_cutoff_coef"]))

@@ -117,7 +117,7 @@ def forward(x, layers, head, dtype=np.float64):
             for i in range(W.shape[0]):
                 y += x[:, i:i + 1] * W[i][None, :]
             y = y + b
-        x = (np.tanh(y) if head == "tanh" else y) if k == len(layers) - 1 else np.maximum(y, dtype(0))
+        x = (np.tanh(y) if head == "tanh" else y) if k == len(layers) - 1 else np.where(y > 0, y, dtype(0))   # the kernels' v > 0 ? v : 0: a NaN gives 0
     return x
 
 

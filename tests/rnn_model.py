@@ -57,7 +57,8 @@ def tick(x0, h, reset, policy_params, lay, dtype=np.float64):
     (W_ru, b_ru), (W_c, b_c), (W_h, b_h) = PM.split(policy_params, [lay["w_ru"], lay["w_c"], lay["head"]], dtype)
     x = np.asarray(x0, dtype=dtype)
     for W, b in PM.split(policy_params, lay["dense"], dtype):
-        x = np.maximum(_affine([x], W, b, dtype), dtype(0))
+        y = _affine([x], W, b, dtype)
+        x = np.where(y > 0, y, dtype(0))           # rg_bptt.h, F: relu as v > 0 ? v : 0 (a NaN gives 0), as bptt_model.dense_forward
     h = np.asarray(h, dtype=dtype)
     if reset is not None:
         h = np.where(np.asarray(reset)[:, None] != 0, dtype(0), h)
